@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpix/s of SIFT extraction on synthetic 1920x1080 grayscale (BASELINE.json config 2 / 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  Started WITHOUT a torch.distributed environment and with --gpus N > 1, this script starts its
@@ -68,7 +68,12 @@ def parse():
                                                  "(3840x2160: BASELINE.json config 3)")
     ap.add_argument("--threshold", type=float, default=None,
                     help="tuning runs (--quick): Config threshold of the timed loop (0.17: the keypoint-sparse regime)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop computed in its last step (rank 0's images) as DIR/*.npy: see dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -124,6 +129,9 @@ class Workers:
         self.next = self.end = 0
         self.feats = [0] * self.n
         self.descs = [0] * self.n
+        # keep(ctx, i, counts): called by a worker after each launch of the LAST step of a run with the launch's first image
+        # index i within the step and its [(features, descriptors)] per image, while the results are still in the context
+        self.keep = None
         self.threads = [threading.Thread(target=self._loop, args=(i,), daemon=True) for i in range(self.n)]
         for t in self.threads:
             t.start()
@@ -154,14 +162,15 @@ class Workers:
                 mine = [self.ptrs[k % n] for k in range(*t)]
                 if self.lb == 1:
                     ctx.submit_dev(mine[0], self.w, self.h, self.w)
-                    nf, nd = ctx.wait()
-                    f += nf
-                    d += nd
+                    counts = [ctx.wait()]
                 else:
                     ctx.submit_batch_dev(mine, self.w, self.h, self.w)
-                    for nf, nd in ctx.wait_batch():
-                        f += nf
-                        d += nd
+                    counts = ctx.wait_batch()
+                for nf, nd in counts:
+                    f += nf
+                    d += nd
+                if self.keep is not None and t[0] >= self.end - n:
+                    self.keep(ctx, t[0] % n, counts)
             self.feats[i], self.descs[i] = f, d
             self.done.wait()
 
@@ -249,6 +258,91 @@ def other_config(hip, torch, np, synth, device, w, h, seed, params_kw, contexts,
             "in_flight_pipeline_frac_of_8TBps": round(bytes_alg * n / dt / 1e9 / HBM_PEAK_GBPS, 4)}
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+DUMP_SEED = 1234        # ... and samples the features of every image with this seed (and the image's index)
+
+
+class _DevBytes:
+    """n bytes of device memory at ptr, for torch.as_tensor (__cuda_array_interface__): a view, no copy"""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class OutputKeeper:
+    """Workers.keep for --dump-outputs: a device-to-device copy of every result slot of the last step, on a stream of the
+    worker's own, before the context's next launch overwrites it.  The timed loop leaves its results device resident;
+    reading them to the host here would put PCIe traffic into the timed region.  saved: image index -> (feature bytes,
+    descriptor bytes), uint8 tensors on the device."""
+
+    def __init__(self, hip, torch, device, ctxs):
+        self.hip, self.torch, self.device = hip, torch, device
+        self.streams = {id(c): torch.cuda.Stream(device) for c in ctxs}
+        self.saved = {}
+        self.error = None       # raised by main() after the timed region: a worker that raised would never reach its barrier
+        self.lock = threading.Lock()
+
+    def _copy(self, ptr, n):
+        if n == 0:
+            return self.torch.empty(0, dtype=self.torch.uint8, device=self.device)
+        return self.torch.as_tensor(_DevBytes(ptr, n), device=self.device).clone()
+
+    def __call__(self, ctx, first, counts):
+        import ctypes as C
+        torch, lib = self.torch, self.hip.lib()
+        s = self.streams[id(ctx)]
+        out = {}
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(s):
+                for k, (nf, nd) in enumerate(counts):
+                    fp, dp = C.c_void_p(), C.c_void_p()
+                    ctx._chk(lib.popsift_hip_results_dev_item(ctx._h, k, C.byref(fp), C.byref(dp)),
+                             "popsift_hip_results_dev_item")
+                    out[first + k] = (self._copy(fp.value, nf * self.hip.FEATURE_DTYPE.itemsize),
+                                      self._copy(dp.value, nd * 128 * 4))
+            s.synchronize()
+        except Exception as e:
+            self.error = e
+        with self.lock:
+            self.saved.update(out)
+
+
+def dump_outputs(path, saved, image_seeds, hip, np):
+    """--dump-outputs: what a caller of the timed loop received for every image j of its last step, as float arrays that do
+    not depend on the device's compaction order (features sorted by octave, y, x, sigma, num_ori, first orientation;
+    descriptors in the order of their features and orientations):
+      image_stats.npy  float64 (B, 9): input seed, features, descriptors, and over ALL of the image's results the sums of
+                       x, y, sigma, the orientations in use, the descriptor values and their squares
+      features.npy     float32 (N, 10): a seeded sample of each image's sorted features -- j, octave, x, y, sigma, num_ori,
+                       orientation[0..3] (slots beyond num_ori 0)
+      descriptors.npy  float32 (M, 128): the descriptors of the sampled features, num_ori rows per feature
+    The sample size per image keeps the three files under DUMP_BYTES whatever the number of orientations."""
+    B = len(image_seeds)
+    per_image = max(1, (DUMP_BYTES - B * 9 * 8) // (B * (10 * 4 + 4 * 128 * 4)))
+    stats, frows, drows = [], [], []
+    for j in range(B):
+        fb, db = saved[j]
+        f = np.frombuffer(fb.cpu().numpy().tobytes(), hip.FEATURE_DTYPE)
+        d = db.cpu().numpy().view(np.float32).reshape(-1, 128)
+        f = f[np.lexsort((f["orientation"][:, 0], f["num_ori"], f["sigma"], f["xpos"], f["ypos"], f["debug_octave"]))]
+        used = np.arange(hip.ORI_MAX)[None, :] < f["num_ori"][:, None]
+        ori = np.where(used, f["orientation"], 0.0).astype(np.float32)
+        d = d[f["desc_idx"][used]]              # row-major: feature by feature, orientation by orientation
+        d64 = d.astype(np.float64)
+        stats.append([image_seeds[j], len(f), len(d), f["xpos"].astype(np.float64).sum(), f["ypos"].astype(np.float64).sum(),
+                      f["sigma"].astype(np.float64).sum(), ori.astype(np.float64).sum(), d64.sum(), (d64 * d64).sum()])
+        rng = np.random.default_rng([DUMP_SEED, j])
+        pick = np.sort(rng.choice(len(f), size=min(per_image, len(f)), replace=False))
+        frows.append(np.column_stack([np.full(len(pick), j), f["debug_octave"][pick], f["xpos"][pick], f["ypos"][pick],
+                                      f["sigma"][pick], f["num_ori"][pick], ori[pick]]).astype(np.float32))
+        first = np.concatenate([[0], np.cumsum(f["num_ori"])])   # the sorted features' first rows in d
+        drows.append(d[np.concatenate([np.arange(first[i], first[i + 1]) for i in pick] + [np.zeros(0, np.int64)])])
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image_stats.npy"), np.array(stats, np.float64))
+    np.save(os.path.join(path, "features.npy"), np.concatenate(frows))
+    np.save(os.path.join(path, "descriptors.npy"), np.concatenate(drows).astype(np.float32))
+
+
 def main():
     global W, H
     args = parse()
@@ -334,6 +428,9 @@ def main():
     leg("setup")
     if args.warmup:
         workers.run(args.warmup)
+    keeper = None
+    if args.dump_outputs and rank == 0:
+        keeper = workers.keep = OutputKeeper(hip, torch, local_rank, ctxs)
     barrier()
     leg("warmup")
     t0 = time.perf_counter()
@@ -343,6 +440,12 @@ def main():
     barrier()
     leg("timed")
     workers.close()
+    if keeper is not None:
+        if keeper.error is not None:
+            raise keeper.error
+        dump_outputs(args.dump_outputs, keeper.saved, [seeds[j % U] for j in range(B)], hip, np)
+        keeper = None
+        leg("dump_outputs")
 
     # MAX over ranks of the time, SUM of the counters (popsift_amd/shard.py)
     elapsed, (feats_step, descs_step) = reduce_stats(dist if world > 1 else None, elapsed,
