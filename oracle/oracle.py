@@ -96,6 +96,7 @@ def lib():
         for n in ("oracle_run_u8", "oracle_run_f32", "oracle_build_pyramid_u8", "oracle_build_pyramid_f32"):
             getattr(L, n).argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
         L.oracle_run_keypoint_stages.argtypes = [vp]
+        L.oracle_keypoint_stages_from.argtypes = [vp, vp, C.c_int]
         L.oracle_num_octaves.argtypes = [vp]
         L.oracle_octave_dims.argtypes = [vp, C.c_int, ip, ip]
         L.oracle_plane_mut.restype = fp
@@ -167,6 +168,18 @@ class Oracle:
     def run_keypoint_stages(self):
         if lib().oracle_run_keypoint_stages(self._h):
             raise RuntimeError("keypoint stages failed")
+        return self
+
+    def run_from_extrema(self, ext):
+        """Orientation and descriptors of the given extrema (an EXTREMUM_DTYPE array, the layout Context.extrema()
+        returns) on the planes this oracle holds -- run(img, keypoints=False) builds them -- in place of its own extrema
+        search and grid filter.  The list must be grouped by ascending octave with at most max_extrema entries per
+        octave; anything else raises ValueError and leaves the oracle as it was."""
+        ext = np.ascontiguousarray(ext)
+        if ext.dtype != EXTREMUM_DTYPE or ext.ndim != 1:
+            raise TypeError("a 1-D array of EXTREMUM_DTYPE expected, got %s %s" % (ext.dtype, ext.shape))
+        if lib().oracle_keypoint_stages_from(self._h, ext.ctypes.data if len(ext) else None, len(ext)):
+            raise ValueError("oracle_keypoint_stages_from rejected the extremum list (%d entries)" % len(ext))
         return self
 
     @property

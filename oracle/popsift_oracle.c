@@ -1561,11 +1561,10 @@ static void all_descriptors(oracle_ctx* c)
     }
 }
 
-static int keypoint_stages(oracle_ctx* c)
+/* orientation, ori_prefix_sum and descriptors of the extrema currently listed (Pyramid::orientation and
+ * Pyramid::descriptors after the extrema / filter stages) */
+static int orient_and_describe(oracle_ctx* c)
 {
-    if (c->n_oct <= 0) return -1;
-    if (find_extrema(c)) return -1;
-    if (filter_grid(c)) return -1;
     const int n = c->ext_total;
 #pragma omp parallel for schedule(dynamic, 16) num_threads(c->threads) if (c->threads > 1)
     for (int i = 0; i < n; i++) orientation_one(c, &c->ext[i]);
@@ -1587,6 +1586,56 @@ static int keypoint_stages(oracle_ctx* c)
     }
     all_descriptors(c);
     return 0;
+}
+
+static int keypoint_stages(oracle_ctx* c)
+{
+    if (c->n_oct <= 0) return -1;
+    if (find_extrema(c)) return -1;
+    if (filter_grid(c)) return -1;
+    return orient_and_describe(c);
+}
+
+/* Test hook: the keypoint stages on an extremum list from elsewhere (the HIP path's, whose capped subset depends on
+ * arrival order) instead of the oracle's own: find_extrema and filter_grid are skipped -- the list is taken as already
+ * capped and filtered -- and orientation, prefix sum and descriptors run on the planes held, as in keypoint_stages.
+ * The list must be grouped by ascending octave (it is not sorted here: a list that is not is rejected), every octave
+ * in [0, n_oct) with at most max_extrema entries, every position finite and inside its octave's plane and every sigma
+ * finite and positive.  A rejected list leaves the context as it was. */
+int oracle_keypoint_stages_from(oracle_ctx* c, const popsift_hip_extremum* ext, int n)
+{
+    if (!c || c->n_oct <= 0 || n < 0 || (n > 0 && !ext)) return -1;
+    int ct[MAXO] = {0};
+    for (int i = 0; i < n; i++) {
+        const popsift_hip_extremum* e = &ext[i];
+        if (e->octave < 0 || e->octave >= c->n_oct) return -1;
+        if (i > 0 && e->octave < ext[i - 1].octave) return -1;
+        if (++ct[e->octave] > c->max_extrema) return -1;
+        const oct_t* oc = &c->oct[e->octave];
+        if (!(e->xpos >= 0.0f && e->xpos <= (float)(oc->w - 1) && e->ypos >= 0.0f && e->ypos <= (float)(oc->h - 1)))
+            return -1;
+        if (!(e->sigma > 0.0f && isfinite(e->sigma))) return -1;
+    }
+    if (n > c->ext_cap) {
+        ext_t* nb = (ext_t*)realloc(c->ext, sizeof(ext_t) * (size_t)n);
+        if (!nb) return -1;
+        c->ext = nb;
+        c->ext_cap = n;
+    }
+    for (int i = 0; i < n; i++) {
+        ext_t* e = &c->ext[i];
+        e->xpos = ext[i].xpos;
+        e->ypos = ext[i].ypos;
+        e->lpos = ext[i].lpos;
+        e->sigma = ext[i].sigma;
+        e->octave = ext[i].octave;
+        e->cell = ext[i].cell;
+        e->num_ori = 0;
+        e->idx_ori = 0;
+    }
+    c->ext_total = n;
+    for (int o = 0; o < MAXO; o++) c->ext_ct[o] = ct[o];
+    return orient_and_describe(c);
 }
 
 /* Test hook: the descriptors again, in OTHER frames -- orientations `ori` (4 floats per extremum, in the order of

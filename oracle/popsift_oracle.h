@@ -39,6 +39,9 @@ int oracle_run_f32(oracle_ctx* c, const float* img, int w, int h, int pitch);
 int oracle_build_pyramid_u8(oracle_ctx* c, const uint8_t* img, int w, int h, int pitch);
 int oracle_build_pyramid_f32(oracle_ctx* c, const float* img, int w, int h, int pitch);
 int oracle_run_keypoint_stages(oracle_ctx* c); /* on the planes currently held */
+/* test hook: orientation and descriptors of the extrema `ext` (grouped by ascending octave, <= max_extrema per octave)
+ * on the planes currently held, in place of the oracle's own extrema; no extremum search, no grid filter */
+int oracle_keypoint_stages_from(oracle_ctx* c, const popsift_hip_extremum* ext, int n);
 
 int          oracle_num_octaves(const oracle_ctx* c);
 int          oracle_octave_dims(const oracle_ctx* c, int octave, int* w, int* h);

@@ -67,6 +67,23 @@ static int run_case(const char* name, popsift_hip_params p, int w, int h, int as
                 if (m[i].best < 0 || m[i].best >= nd) bad = 1;
             free(m);
         }
+        /* the keypoint stages again on the oracle's own list (oracle_keypoint_stages_from): the same counts; the list
+         * reversed is no longer grouped by ascending octave and must be rejected */
+        popsift_hip_extremum* e = (popsift_hip_extremum*)calloc((size_t)nf + 1, sizeof(*e));
+        oracle_fetch_extrema(c, e);
+        int nf2 = -1, nd2 = -1;
+        if (oracle_keypoint_stages_from(c, e, nf)) bad = 1;
+        oracle_counts(c, &nf2, &nd2);
+        if (nf2 != nf || nd2 != nd) bad = 1;
+        if (nf >= 2 && e[0].octave != e[nf - 1].octave) {
+            for (int i = 0; i < nf / 2; i++) {
+                const popsift_hip_extremum t = e[i];
+                e[i] = e[nf - 1 - i];
+                e[nf - 1 - i] = t;
+            }
+            if (oracle_keypoint_stages_from(c, e, nf) == 0) bad = 1;
+        }
+        free(e);
         free(f);
         free(d);
     }

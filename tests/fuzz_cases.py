@@ -6,7 +6,7 @@ import time
 import numpy as np
 
 from popsift_amd.synth import synth
-from util import bits, feature_parity
+from util import bits, capped_parity, feature_parity
 
 
 def random_case(rng, case, max_w=700, max_h=500):
@@ -20,7 +20,7 @@ def random_case(rng, case, max_w=700, max_h=500):
               max_extrema=int(rng.choice([100000, 100000, 300])))
     if rng.random() < 0.3:
         kw["octaves"] = int(rng.integers(1, 6))
-    if rng.random() < 0.25 and kw["max_extrema"] != 300:   # a binding cap keeps an arrival-order subset: not comparable
+    if rng.random() < 0.25 and kw["max_extrema"] != 300:   # filter and cap together: tests/test_gpu_cap.py
         kw.update(filter_max_extrema=int(rng.integers(50, 600)), filter_sorting=int(rng.integers(1, 3)),
                   filter_grid_size=int(rng.integers(1, 6)))
     img = synth(1000 + case, w, h)
@@ -64,7 +64,27 @@ def check_case(O, hip, kw, img, threads=16, debug=()):
             else:
                 msg = "EXTREMA DIFFER %d vs %d" % (len(eo), len(eh))
         else:
-            msg = "capped"
+            # a binding cap keeps an arrival-order subset: the cap's counts, the survivors' identity in the uncapped set
+            # and their parity with the oracle's keypoint stages on the same list (util.capped_parity)
+            lifted = dict(kw, max_extrema=100000)
+            full = O.Oracle(O.default_params(**lifted), threads=threads).run(img)
+            counts = full.ext_counts()
+            full_ctx = hip.Context(hip.default_params(**lifted))
+            for what, value in debug:
+                full_ctx.debug_set(what, value)
+            full_dev = full_ctx.submit(img).fetch()
+            full_ext = full_ctx.extrema()       # the identity set: the device's sigma is the oracle's within 1e-5 (powf)
+            full_ctx.close()
+            try:
+                assert max(counts) < 100000, counts
+                assert orc.ext_counts() == [min(c, 300) for c in counts], (orc.ext_counts(), counts)
+                key = lambda e: sorted(zip(e["octave"].tolist(), e["lpos"].tolist(), e["xpos"].tolist(), e["ypos"].tolist()))
+                assert key(full.extrema()) == key(full_ext), "uncapped extrema differ: %d vs %d" % (len(full.extrema()), len(full_ext))
+                capped_parity(full_ext, 300, ctx, kw["upscale_factor"], orc=orc, full_dev=full_dev,
+                              grid_mode=kw["desc_mode"] == 2)
+                msg = "capped %s of %s" % (ctx.report().ext_total, sum(counts))
+            except AssertionError as e:
+                ok, msg = False, "CAPPED: %s" % (e,)
         ctx.close()
     except Exception as e:  # noqa: BLE001 -- a crash in either side is a failed case, with its parameters printed
         ok, planes_ok, msg = False, False, "EXCEPTION %r" % (e,)

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from popsift_amd.synth import gaussian_blob, synth
-from util import bits, compare_features, descriptor_parity, feature_parity, sorted_features
+from util import bits, capped_parity, compare_features, descriptor_parity, feature_parity, sorted_features
 
 pytestmark = pytest.mark.gpu
 
@@ -220,10 +220,15 @@ def test_max_extrema_cap_and_buffer_growth(oracle_mod, gpu_hip):
     n2 = (desc.astype(np.float64) ** 2).sum(1)
     np.testing.assert_allclose(n2, 1.0, rtol=1e-4)
     # the kept extrema are a subset of the uncapped run's
-    full = gpu_hip.Context().submit(img).extrema()
+    full_ctx = gpu_hip.Context().submit(img)
+    full = full_ctx.extrema()
     capped = ctx.extrema()
     allk = set(zip(full["octave"].tolist(), full["xpos"].tolist(), full["ypos"].tolist()))
     assert all(k in allk for k in zip(capped["octave"].tolist(), capped["xpos"].tolist(), capped["ypos"].tolist()))
+    # and exactly what the cap must leave: per-octave counts, survivors bit for bit, their parity with the oracle's
+    # keypoint stages on the same list and with the uncapped run keypoint by keypoint (util.capped_parity)
+    orc = oracle_mod.Oracle(oracle_mod.default_params(max_extrema=300), threads=8).run(img, keypoints=False)
+    capped_parity(full, 300, ctx, 1.0, orc=orc, full_dev=full_ctx.fetch())
 
 
 def test_candidate_and_histogram_buffers_regrow(gpu_hip):

@@ -187,3 +187,177 @@ def test_interpolated_descriptor_modes(oracle_mod):
     r = rel(res[0][1], res[1][1])
     cos = np.sum(res[0][1] * res[1][1], axis=1)
     assert 1e-4 < np.median(r) < 0.05 and np.median(cos) > 0.999 and cos.min() > 0.6
+
+
+# ---- the keypoint stages on a given extremum list (oracle_keypoint_stages_from): what the capped-run checks stand on ----
+
+FROM_CONFIGS = [dict(desc_mode=0), dict(desc_mode=2), dict(desc_mode=4), dict(sift_mode=1, desc_mode=0, norm_mode=1),
+                dict(desc_mode=0, max_extrema=200)]
+
+
+@pytest.mark.parametrize("kw", FROM_CONFIGS, ids=["loop", "grid", "notile", "opencv", "loop-capped"])
+def test_keypoint_stages_from_own_extrema_are_bit_identical(oracle_mod, kw):
+    """The oracle's own extrema fed into a pyramid-only oracle: the same features and descriptors, bit for bit."""
+    O = oracle_mod
+    img = synth(8, 200, 150)
+    full = O.Oracle(O.default_params(**kw), threads=4).run(img)
+    fa, da = full.fetch()
+    ext = full.extrema()
+    assert len(ext) > 100
+    if "max_extrema" in kw:
+        assert max(full.ext_counts()) == kw["max_extrema"]
+    fresh = O.Oracle(O.default_params(**kw), threads=4).run(img, keypoints=False)
+    assert fresh.counts() == (0, 0)
+    fb, db = fresh.run_from_extrema(ext).fetch()
+    assert fresh.ext_counts() == full.ext_counts()
+    assert np.array_equal(fa.view(np.uint8), fb.view(np.uint8))
+    assert np.array_equal(da.view(np.uint32), db.view(np.uint32))
+    assert np.array_equal(fresh.extrema().view(np.uint8), ext.view(np.uint8))
+
+
+@pytest.mark.parametrize("desc_mode", [0, 2])
+def test_keypoint_stages_from_a_shuffled_subset(oracle_mod, desc_mode):
+    """A subset shuffled within each octave (arrival order): every keypoint keeps its own orientations and
+    descriptors, bit for bit, and the features come out in the order of the list."""
+    O = oracle_mod
+    img = synth(9, 180, 140)
+    p = O.default_params(desc_mode=desc_mode)
+    full = O.Oracle(p, threads=4).run(img)
+    fa, da = full.fetch()
+    ext = full.extrema()
+    rng = np.random.default_rng(5)
+    pick = np.sort(rng.choice(len(ext), size=len(ext) * 3 // 5, replace=False))
+    pick = np.concatenate([rng.permutation(pick[ext["octave"][pick] == o]) for o in range(full.num_octaves)])
+    assert np.all(np.diff(ext["octave"][pick]) >= 0) and not np.all(np.diff(pick) > 0)
+    sub = O.Oracle(p, threads=4).run(img, keypoints=False).run_from_extrema(ext[pick])
+    fb, db = sub.fetch()
+    assert len(fb) == len(pick)
+    assert sub.ext_counts() == np.bincount(ext["octave"][pick], minlength=full.num_octaves).tolist()
+    for i, j in enumerate(pick):
+        a, b = fa[j], fb[i]
+        for f in ("debug_octave", "xpos", "ypos", "sigma", "num_ori"):
+            assert a[f] == b[f], (i, j, f)
+        n = int(a["num_ori"])
+        assert np.array_equal(a["orientation"][:n].view(np.uint32), b["orientation"][:n].view(np.uint32)), (i, j)
+        assert np.array_equal(da[a["desc_idx"][:n]].view(np.uint32), db[b["desc_idx"][:n]].view(np.uint32)), (i, j)
+    # descriptors are laid out feature by feature in the list's order (s_orientation.cu:303-345)
+    idx = np.concatenate([f["desc_idx"][:int(f["num_ori"])] for f in fb])
+    assert np.array_equal(idx, np.arange(len(db)))
+
+
+def test_keypoint_stages_from_rejects_malformed_lists(oracle_mod):
+    O = oracle_mod
+    img = synth(8, 200, 150)
+    p = O.default_params(max_extrema=120)
+    full = O.Oracle(O.default_params(), threads=4).run(img)
+    ext = full.extrema()
+    n_oct = full.num_octaves
+    o0 = ext[ext["octave"] == 0]
+    assert len(o0) > 120
+    ok = ext[np.concatenate([np.nonzero(ext["octave"] == o)[0][:120] for o in range(n_oct)])]
+
+    cases = {}
+    e = ok.copy(); e["octave"][-1] = n_oct; cases["octave past the last"] = e
+    e = ok.copy(); e["octave"][0] = -1; cases["negative octave"] = e
+    cases["not grouped by ascending octave"] = ok[::-1].copy()
+    cases["more than max_extrema in an octave"] = np.concatenate([o0[:121], ok[ok["octave"] > 0]])
+    e = ok.copy(); e["xpos"][3] = full.octave_dims(0)[0]; cases["x outside the plane"] = e
+    e = ok.copy(); e["ypos"][3] = -0.5; cases["y outside the plane"] = e
+    e = ok.copy(); e["xpos"][3] = np.nan; cases["NaN position"] = e
+    e = ok.copy(); e["sigma"][3] = 0.0; cases["zero sigma"] = e
+    e = ok.copy(); e["sigma"][3] = np.inf; cases["infinite sigma"] = e
+    orc = O.Oracle(p, threads=4).run(img, keypoints=False)
+    for what, e in cases.items():
+        with pytest.raises(ValueError):
+            orc.run_from_extrema(e)
+        assert orc.counts() == (0, 0), what          # rejected: nothing computed, nothing replaced
+    with pytest.raises(TypeError):
+        orc.run_from_extrema(np.zeros(3, O.FEATURE_DTYPE))
+    with pytest.raises(ValueError):                  # no planes yet
+        O.Oracle(p).run_from_extrema(ok[:5])
+    # the well-formed list is accepted, and a rejected one after it leaves its results in place
+    orc.run_from_extrema(ok)
+    before = orc.fetch()
+    with pytest.raises(ValueError):
+        orc.run_from_extrema(cases["not grouped by ascending octave"])
+    after = orc.fetch()
+    assert np.array_equal(before[0].view(np.uint8), after[0].view(np.uint8))
+    assert np.array_equal(before[1].view(np.uint32), after[1].view(np.uint32))
+    # an empty list: no features
+    assert orc.run_from_extrema(ok[:0]).counts() == (0, 0)
+
+
+def test_capped_parity_passes_a_capped_oracle_run_and_catches_defects(oracle_mod):
+    """util.capped_parity on a capped oracle run (raster-order survivors) standing in for a batch item, then on
+    copies with the defects it exists to catch: each must raise, naming what is wrong."""
+    from util import capped_parity
+    O = oracle_mod
+    img = synth(21, 200, 150)
+    cap = 150
+    full = O.Oracle(O.default_params(max_extrema=100000), threads=4).run(img)
+    capped = O.Oracle(O.default_params(max_extrema=cap), threads=4).run(img)
+    counts = full.ext_counts()
+    assert counts[0] > cap and counts[1] < cap
+    assert capped.ext_counts() == [min(c, cap) for c in counts]
+    fc, dc = capped.fetch()
+    pyr = lambda: O.Oracle(O.default_params(max_extrema=cap), threads=4).run(img, keypoints=False)
+    capped_parity(full.extrema(), cap, (fc, dc), 1.0, orc=pyr(), full_dev=full.fetch())
+
+    def expect(msg, f, d):
+        with pytest.raises(AssertionError, match=msg):
+            capped_parity(full.extrema(), cap, (f, d), 1.0, orc=pyr(), full_dev=full.fetch())
+
+    i = int(np.nonzero(fc["debug_octave"] == 0)[0][-1])
+    f = fc.copy(); f["sigma"][i] = np.nextafter(f["sigma"][i], np.float32(0)); expect("not uncapped extrema", f, dc)
+    expect("per-octave counts", fc[np.arange(len(fc)) != i], dc)                     # one survivor short
+    f = fc.copy(); f[i] = f[i - 1]; expect("repeated", f, dc)                          # a survivor twice
+    f = fc.copy(); f["debug_octave"][i] = 1; expect("per-octave counts", f, dc)       # in the next octave's region
+    d = dc.copy(); d[fc["desc_idx"][i][0]] *= 1.0001
+    with pytest.raises(AssertionError, match="not bit-identical"):
+        capped_parity(full.extrema(), cap, (fc, d), 1.0, full_dev=full.fetch())
+    f = fc.copy(); f["orientation"][i][0] = np.nextafter(f["orientation"][i][0], np.float32(9))
+    with pytest.raises(AssertionError, match="not bit-identical"):
+        capped_parity(full.extrema(), cap, (f, dc), 1.0, full_dev=full.fetch())
+    d = dc.copy(); d[fc["desc_idx"][i][0]] = np.roll(d[fc["desc_idx"][i][0]], 8)   # another keypoint's frame, in effect
+    expect("oracle", fc, d)
+
+
+class _OracleAsContext:
+    """The three calls capped_parity makes on a device Context, answered by a capped oracle run."""
+
+    def __init__(self, O, orc):
+        self._o, self._O = orc, O
+        self.ext_ct = orc.ext_counts() + [0] * (O.MAX_OCTAVES - orc.num_octaves)
+        self.num_octaves, self.ext_total = orc.num_octaves, orc.counts()[0]
+
+    def fetch(self):
+        return self._o.fetch()
+
+    def extrema(self):
+        return self._o.extrema()
+
+    def report(self):
+        return self
+
+
+def test_capped_parity_on_a_context(oracle_mod):
+    """The Context form of util.capped_parity (report counts, extrema() identity with lpos, features against the list)."""
+    from util import capped_parity
+    O = oracle_mod
+    img = synth(22, 200, 150)
+    cap = 97
+    full = O.Oracle(O.default_params(), threads=4).run(img)
+    capped = O.Oracle(O.default_params(max_extrema=cap), threads=4).run(img)
+    assert full.ext_counts()[0] > cap
+    pyr = lambda: O.Oracle(O.default_params(max_extrema=cap), threads=4).run(img, keypoints=False)
+    stub = _OracleAsContext(O, capped)
+    capped_parity(full.extrema(), cap, stub, 1.0, orc=pyr(), full_dev=full.fetch())
+    stub.ext_ct[0] -= 1
+    with pytest.raises(AssertionError, match="report"):
+        capped_parity(full.extrema(), cap, stub, 1.0)
+    stub = _OracleAsContext(O, capped)
+    e = capped.extrema()
+    e["lpos"][5] += 1
+    stub.extrema = lambda: e
+    with pytest.raises(AssertionError, match="extrema\\(\\) entries"):
+        capped_parity(full.extrema(), cap, stub, 1.0)

@@ -77,8 +77,8 @@ def compare_features(fa, da, fb, db, tol_desc=1e-3, tol_ang=1e-3):
                 # A descriptor is computed in the frame of its keypoint orientation: when the two sides' orientations differ
                 # by dth (the orientation comes out of a HARD-binned histogram, s_orientation.cu:129, where an ulp of atan2
                 # moves a sample to the neighbouring bin), the descriptors differ by a few times dth although each is right
-                # for its frame.  Such an offender is "explained"; one whose orientations agree is not.
-                explained = rel <= EXPLAIN_FACTOR * dth + tol_desc
+                # for its frame.  Such an offender is "explained"; one whose orientations agree (within tol_ang) is not.
+                explained = dth > tol_ang and rel <= EXPLAIN_FACTOR * dth + tol_desc
                 if not explained:
                     st["unexplained"] += 1
                 st["offenders"].append(dict(octave=int(a["debug_octave"]), x=float(a["xpos"]), y=float(a["ypos"]), k=k,
@@ -99,14 +99,20 @@ def descriptor_parity(st):
         explanation itself (8 x the angle difference + 1e-3), and an angle difference is at most half a histogram bin
         (0.087 rad: beyond that compare_features counts a different SELECTION of peaks, with num_ori_diff).  Round 3
         capped both at 3e-2 from what 1 900 cases had shown; 500 more (seed 70707) brought 3.01e-2 and 3.07e-2;
-      - no unexplained descriptor beyond 3e-2.
+      - no unexplained descriptor beyond 3e-2;
+      - an explained offender's angle difference and descriptor difference both below 5e-2 (the largest of either seen
+        in 17 400 fuzz cases is 3.07e-2, profiles/r04_fuzz_parity.txt).
     The GRID descriptor is held to the same bars, compared in the same frame: see feature_parity."""
     n = max(st["n_desc"], 1)
     expl = st["desc_bad"] - st["unexplained"]
     worst_unexplained = max([o["d_desc"] for o in st["offenders"] if not o["explained"]] + [0.0])
-    ok = st["unexplained"] <= max(1, n // 5000) and expl <= max(2, n // 2000) and worst_unexplained < 3e-2
+    worst_expl_ang = max([o["d_angle"] for o in st["offenders"] if o["explained"]] + [0.0])
+    worst_expl_desc = max([o["d_desc"] for o in st["offenders"] if o["explained"]] + [0.0])
+    ok = st["unexplained"] <= max(1, n // 5000) and expl <= max(2, n // 2000) and worst_unexplained < 3e-2 and \
+        worst_expl_ang < 5e-2 and worst_expl_desc < 5e-2
     msg = "%d of %d descriptors outside 1e-3 (%d with agreeing orientation, %d explained by an orientation difference), max %.2e; " \
-          "angles: %d outside 1e-3 rad, max %.2e" % (st["desc_bad"], n, st["unexplained"], expl, st["max_desc"], st["ang_bad"], st["max_ang"])
+          "angles: %d outside 1e-3 rad, max %.2e; explained offenders: angle up to %.2e, descriptor up to %.2e" % (
+              st["desc_bad"], n, st["unexplained"], expl, st["max_desc"], st["ang_bad"], st["max_ang"], worst_expl_ang, worst_expl_desc)
     for o in st["offenders"][:20]:
         msg += "\n    octave %d (%.3f, %.3f) sigma %.3f ori %d: d_angle %.2e d_desc %.2e %s" % (
             o["octave"], o["x"], o["y"], o["sigma"], o["k"], o["d_angle"], o["d_desc"],
@@ -183,3 +189,143 @@ def sorted_features(feats, desc):
             rows.append(desc[r["desc_idx"][k]])
     d = np.array(rows, np.float32).reshape(-1, 128)
     return f, d
+
+
+def _feature_frame(ext, upscale_factor):
+    """Extrema (octave units) -> the (octave, x, y, sigma) of their features: prep_features multiplies by
+    2^(octave - int(upscale)), a power of two, so the float32 products are exact on both sides."""
+    sc = np.exp2(ext["octave"].astype(np.float64) - int(upscale_factor)).astype(np.float32)
+    return (ext["octave"].astype(np.int32), (ext["xpos"] * sc).astype(np.float32), (ext["ypos"] * sc).astype(np.float32),
+            (ext["sigma"] * sc).astype(np.float32))
+
+
+def _keys(octave, *floats):
+    return list(zip(np.asarray(octave).tolist(), *[bits(f).tolist() for f in floats]))
+
+
+def _fkeys(feats):
+    return _keys(feats["debug_octave"], feats["xpos"], feats["ypos"], feats["sigma"])
+
+
+def _fail(what, rows):
+    raise AssertionError("%s: %d offender(s)\n    %s" % (what, len(rows), "\n    ".join(rows[:20])))
+
+
+def _kp(o, x, y, s):
+    return "octave %d keypoint (%.9g, %.9g) sigma %.9g" % (o, x, y, s)
+
+
+def capped_parity(full_ext, cap, capped, upscale_factor, orc=None, full_dev=None, grid_mode=False, filtered=False):
+    """What a binding max_extrema cap must leave, whichever extrema arrive first (s_extrema.cu:541,558: atomicAdd, a
+    guarded store, a clamp).  Raises AssertionError naming the octave and keypoint of every offender.
+
+    full_ext: the UNCAPPED, unfiltered extrema of the image (EXTREMUM_DTYPE, cap lifted): the device's, whose sigma the
+    survivors must match bit for bit (the oracle's sigma differs in the last bits: the device's powf);
+    cap: the max_extrema of the capped run; capped: the capped device Context after its submit, or a (features,
+    descriptors) pair (a batch item: counts come from debug_octave); upscale_factor: of the params (features are in
+    image units); orc: an Oracle holding the image's planes under the capped run's params -- its extrema are replaced
+    by the survivors; full_dev: (features, descriptors) of an uncapped device run of the image; filtered: the capped run
+    had the grid filter on, so its list is post-filter (counts bounded instead of equal).
+
+    1. counts: every octave's count is min(uncapped count, cap) -- with the filter, at most that and at most
+       sum(min(count, cap)) in all -- and report().ext_total, the extrema and the features agree;
+    2. identity: every survivor is, bit for bit, an extremum of the uncapped set (octave, lpos, x, y, sigma for the
+       Context's list, octave, x, y, sigma for features), none more often than the uncapped set holds it; the
+       features are the extrema's;
+    3. parity: the oracle's keypoint stages on the survivors (run_from_extrema) against the device's features under
+       feature_parity (grid descriptors in the device's frame);
+    4. with full_dev: each survivor's num_ori, orientations and descriptors bit-identical to the uncapped run's."""
+    from collections import Counter
+    is_ctx = not isinstance(capped, tuple)
+    if is_ctx:
+        feats, desc = capped.fetch()
+        ext = capped.extrema()
+        rep = capped.report()
+    else:
+        feats, desc = capped
+        ext, rep = None, None
+    n_oct = max([int(full_ext["octave"].max()) + 1 if len(full_ext) else 0,
+                 int(feats["debug_octave"].max()) + 1 if len(feats) else 0] + ([rep.num_octaves] if rep else []))
+    full_ct = np.bincount(full_ext["octave"], minlength=n_oct)[:n_oct]
+    want = np.minimum(full_ct, cap)
+    feat_ct = np.bincount(feats["debug_octave"], minlength=n_oct)[:n_oct] if len(feats) else np.zeros(n_oct, np.int64)
+
+    # 1. counts
+    sources = [("features", feat_ct)]
+    if is_ctx:
+        sources.append(("report().ext_ct", np.array(rep.ext_ct[:n_oct])))
+        sources.append(("extrema()", np.bincount(ext["octave"], minlength=n_oct)[:n_oct] if len(ext) else np.zeros(n_oct)))
+        if list(rep.ext_ct[n_oct:]) != [0] * (len(rep.ext_ct) - n_oct):
+            _fail("report().ext_ct beyond the %d octaves" % n_oct, [str(list(rep.ext_ct))])
+    for name, ct in sources:
+        bad = ["octave %d: %s %d, uncapped %d, cap %d, want %s%d" % (o, name, ct[o], full_ct[o], cap,
+                                                                         "<= " if filtered else "", want[o])
+               for o in range(n_oct) if (ct[o] > want[o] if filtered else ct[o] != want[o])]
+        if bad:
+            _fail("per-octave counts (%s)" % name, bad)
+    if filtered and len(feats) > int(want.sum()):
+        _fail("filtered total", ["%d features, sum of min(count, cap) %d" % (len(feats), want.sum())])
+    if is_ctx and not (rep.ext_total == len(ext) == len(feats) == int(sum(rep.ext_ct[:n_oct]))):
+        _fail("totals", ["report().ext_total %d, extrema() %d, features %d, sum(ext_ct) %d" % (
+            rep.ext_total, len(ext), len(feats), sum(rep.ext_ct[:n_oct]))])
+
+    # 2. identity: a multiset inclusion, bit for bit
+    full_fkeys = _keys(*_feature_frame(full_ext, upscale_factor))
+    full_count = Counter(full_fkeys)
+    surv = Counter(_fkeys(feats))
+    bad = ["%s: %d times, %d in the uncapped set" % (_kp(k[0], *np.array(k[1:], np.uint32).view(np.float32)), n,
+                                                       full_count.get(k, 0))
+           for k, n in surv.items() if n > full_count.get(k, 0)]
+    if bad:
+        _fail("survivors that are not uncapped extrema (or are repeated)", bad)
+    if is_ctx:
+        full_ekeys = Counter(_keys(full_ext["octave"], full_ext["lpos"].view(np.float32), full_ext["xpos"], full_ext["ypos"],
+                                   full_ext["sigma"]))
+        bad = ["octave %d lpos %d (%.9g, %.9g) sigma %.9g: %d times, %d in the uncapped set" % (
+                   k[0], k[1], *np.array(k[2:], np.uint32).view(np.float32), n, full_ekeys.get(k, 0))
+               for k, n in Counter(_keys(ext["octave"], ext["lpos"].view(np.float32), ext["xpos"], ext["ypos"],
+                                         ext["sigma"])).items() if n > full_ekeys.get(k, 0)]
+        if bad:
+            _fail("extrema() entries that are not uncapped extrema (or are repeated)", bad)
+        if Counter(_keys(*_feature_frame(ext, upscale_factor))) != surv:
+            _fail("features that are not the extrema() list's", ["%d features, %d extrema" % (len(feats), len(ext))])
+
+    # 3. parity of the survivors with the oracle's keypoint stages on the same list
+    if orc is not None:
+        if is_ctx:
+            lst = ext
+        else:
+            first = {}
+            for i, k in enumerate(full_fkeys):
+                first.setdefault(k, i)
+            lst = full_ext[np.array([first[k] for k in _fkeys(feats)], np.int64)] if len(feats) else full_ext[:0]
+            lst = lst[np.argsort(lst["octave"], kind="stable")]
+        orc.run_from_extrema(lst)
+        ok, msg, _ = feature_parity(orc, feats, desc, grid_mode=grid_mode)
+        assert ok, "survivors against the oracle's keypoint stages on the same list: " + msg
+
+    # 4. bit-identity with the uncapped device run, keypoint by keypoint
+    if full_dev is not None:
+        ff, fd = full_dev
+        at = {}
+        for i, k in enumerate(_fkeys(ff)):
+            at.setdefault(k, i)
+        j = np.array([at.get(k, -1) for k in _fkeys(feats)], np.int64)
+        if (j < 0).any():
+            _fail("survivors missing in the uncapped device run",
+                  [_kp(f["debug_octave"], f["xpos"], f["ypos"], f["sigma"]) for f in feats[j < 0]])
+        g = ff[j]
+        bad_ori = feats["num_ori"] != g["num_ori"]
+        k = np.arange(4)[None, :]
+        live = (k < feats["num_ori"][:, None]) & ~bad_ori[:, None]   # descriptors where the number of orientations agrees
+        bad_ori |= ((bits(feats["orientation"]) != bits(g["orientation"])) & live).any(1)
+        di, gi = feats["desc_idx"][live], g["desc_idx"][live]
+        bad_desc_rows = (bits(desc[di]) != bits(fd[gi])).any(1)
+        bad_desc = np.zeros(len(feats), bool)
+        bad_desc[np.nonzero(live)[0][bad_desc_rows]] = True
+        bad = ["%s: num_ori %d / %d, orientations %s / %s%s" % (
+                   _kp(f["debug_octave"], f["xpos"], f["ypos"], f["sigma"]), f["num_ori"], h["num_ori"],
+                   f["orientation"][:f["num_ori"]], h["orientation"][:h["num_ori"]], ", descriptors differ" if bd else "")
+               for f, h, bd in zip(feats[bad_ori | bad_desc], g[bad_ori | bad_desc], bad_desc[bad_ori | bad_desc])]
+        if bad:
+            _fail("survivors not bit-identical to the uncapped device run (capped / uncapped)", bad)
