@@ -173,6 +173,11 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* ctx);
  * filter[(levels+3) * 32], span[levels+3], sigma[levels+3]. */
 int popsift_hip_get_gauss_table(const popsift_hip_ctx* ctx, float* filter, int* span, float* sigma,
                                 int* n_levels);
+/* The abs_o0 table of the vlfeat-direct Gauss mode (POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL, gauss_filter.cu:190-199):
+ * octave 0's level l is blurred straight from the input image with row l.  Same layout as above; ERR_STATE in the other
+ * modes. */
+int popsift_hip_get_gauss_table_abs0(const popsift_hip_ctx* ctx, float* filter, int* span, float* sigma,
+                                     int* n_levels);
 
 /* Replaces Image::load + Pyramid::step1 + step2 (s_image.cu:71-79,
  * sift_pyramid.cu:226-239): upload one host image and enqueue the whole
@@ -314,11 +319,13 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * wherever they apply, also on small planes (results do not depend on it: every path is bit-identical; the tests run
  * their small images through 2); BLUR_SEG = rows per segment of the march kernels (a multiple of 32; 0 = chosen from the
  * plane and the batch); PYR_TAIL = 0: the smallest octaves -- from the first whose plane fits one workgroup's LDS -- are
- * built by one launch (default), 1: by level launches like the others (results do not depend on it). */
+ * built by one launch (default), 1: by level launches like the others (results do not depend on it); DIRECT_PATH (Gauss
+ * mode vlfeat-direct only) = 0: octave 0's levels by one fused launch (default), 1: by one level-0 launch per level
+ * (results do not depend on it). */
 enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_HIP_DEBUG_OHIST_CAP = 3,
        POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, POPSIFT_HIP_DEBUG_PYR_ORDER = 6,
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
-       POPSIFT_HIP_DEBUG_PYR_TAIL = 10 };
+       POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

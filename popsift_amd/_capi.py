@@ -88,6 +88,7 @@ SYMBOLS = [
     ("popsift_hip_ctx_create", C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(_vp)]),
     ("popsift_hip_ctx_destroy", C.c_int, [_vp]),
     ("popsift_hip_get_gauss_table", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
+    ("popsift_hip_get_gauss_table_abs0", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
     ("popsift_hip_submit_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_f32", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_dev_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
@@ -127,7 +128,7 @@ SYMBOLS = [
 MATCH_AUTO, MATCH_EXACT, MATCH_SCREEN = 0, 1, 2
 STAGES = ("pyramid", "detect", "refine", "orientation", "scan", "descriptor")
 DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_PYR_ORDER, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 6, 7
-DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL = 8, 9, 10
+DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL, DEBUG_DIRECT_PATH = 8, 9, 10, 11
 MAX_BATCH = 16
 IMG_HOST_U8, IMG_HOST_F32, IMG_DEV_U8, IMG_DEV_F32, IMG_PINNED_U8, IMG_PINNED_F32 = range(6)
 
@@ -321,14 +322,16 @@ class Context:
         if rc != OK:
             raise PopsiftHipError(rc, where, lib().popsift_hip_last_error(self._h).decode())
 
-    def gauss_table(self):
+    def gauss_table(self, abs0=False):
+        """(filter[L, 32], span[L], sigma[L]): the incremental table, or with abs0=True the abs_o0 table of the
+        vlfeat-direct Gauss mode (octave 0's levels straight from the input image)"""
+        get = lib().popsift_hip_get_gauss_table_abs0 if abs0 else lib().popsift_hip_get_gauss_table
         n = C.c_int()
-        self._chk(lib().popsift_hip_get_gauss_table(self._h, None, None, None, C.byref(n)), "get_gauss_table")
+        self._chk(get(self._h, None, None, None, C.byref(n)), "get_gauss_table")
         f = np.zeros((n.value, 32), np.float32)
         s = np.zeros(n.value, np.int32)
         g = np.zeros(n.value, np.float32)
-        self._chk(lib().popsift_hip_get_gauss_table(self._h, f.ctypes.data, s.ctypes.data, g.ctypes.data,
-                                                    C.byref(n)), "get_gauss_table")
+        self._chk(get(self._h, f.ctypes.data, s.ctypes.data, g.ctypes.data, C.byref(n)), "get_gauss_table")
         return f, s, g
 
     def submit(self, img):

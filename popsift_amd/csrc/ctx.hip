@@ -94,6 +94,9 @@ struct popsift_hip_ctx {
     popsift_hip_params p{};
     int                levels = 3, L = 6;
     HostTables         tab{};
+    HostTables         abs0{};           /* vlfeat-direct (gauss_mode 2): abs_o0, octave 0's levels from the input image */
+    float*             d_abs0 = nullptr; /* abs0.filter on the device (the fused kernel's taps), gauss_mode 2 only */
+    int                direct_path = 0;  /* DIRECT_PATH debug switch: 0 fused octave-0 kernel, 1 one level-0 launch per level */
     SiftConsts         sc{};
     hipStream_t        stream = nullptr;
     hipEvent_t         ev_begin = nullptr, ev_end = nullptr;
@@ -193,6 +196,26 @@ int span_for(int gauss_mode, float sigma)
     return std::min<int>(ceilf(4.0f * sigma) + 1, PS_GA - 1);
 }
 
+/* GaussTable::computeBlurTable (gauss_filter.cu:340-372): spans and normalised half filters of t.sigma */
+void compute_filters(HostTables& t, int gauss_mode)
+{
+    for (int level = 0; level < POPSIFT_HIP_MAX_LEVELS; level++) {
+        t.span[level] = std::min(span_for(gauss_mode, t.sigma[level]), PS_GA - 1);
+        const float sig = t.sigma[level];
+        const int   spn = t.span[level];
+        float*      f = &t.filter[level * PS_GA];
+        double      sum = 1.0;
+        f[0] = 1.0f;
+        for (int x = 1; x < spn; x++) {
+            const float val = (float)exp(-0.5 * (pow(double(x) / sig, 2.0)));
+            f[x] = val;
+            sum += 2.0f * val;
+        }
+        for (int x = 0; x < spn; x++) f[x] = (float)(f[x] / sum);
+        for (int x = spn; x < PS_GA; x++) f[x] = 0.0f;
+    }
+}
+
 /* init_filter (inc table; dd[0] is identical to inc[0]) gauss_filter.cu:163-181,340-372
  * and init_constants sift_constants.cu:22-31 */
 void init_tables(popsift_hip_ctx* c)
@@ -209,20 +232,18 @@ void init_tables(popsift_hip_ctx* c)
         const float sigmaS = sigma0 * powf(2.0f, (float)(lvl) / (float)levels);
         t.sigma[lvl] = sqrtf(sigmaS * sigmaS - sigmaP * sigmaP);
     }
-    for (int level = 0; level < POPSIFT_HIP_MAX_LEVELS; level++) {
-        t.span[level] = std::min(span_for(p.gauss_mode, t.sigma[level]), PS_GA - 1);
-        const float sig = t.sigma[level];
-        const int   spn = t.span[level];
-        float*      f = &t.filter[level * PS_GA];
-        double      sum = 1.0;
-        f[0] = 1.0f;
-        for (int x = 1; x < spn; x++) {
-            const float val = (float)exp(-0.5 * (pow(double(x) / sig, 2.0)));
-            f[x] = val;
-            sum += 2.0f * val;
+    compute_filters(t, p.gauss_mode);
+    /* abs_o0 (gauss_filter.cu:190-199): octave 0's level l straight from the input image, sigma relative to the assumed
+     * blur of the input; spans by the VLFeat rule (GaussInfo::getSpan for VLFeat_Relative_All).  abs0.sigma[0] equals
+     * tab.sigma[0] (sqrt(RN(s * s)) == s), so level 0 is the default mode's level 0. */
+    HostTables& a0 = c->abs0;
+    memset(&a0, 0, sizeof(a0));
+    if (p.gauss_mode == POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL) {
+        for (int lvl = 0; lvl < c->L; lvl++) {
+            const float sigmaS = sigma0 * powf(2.0f, (float)lvl / (float)levels);
+            a0.sigma[lvl] = sqrtf(fabsf(sigmaS * sigmaS - initial_blur * initial_blur));
         }
-        for (int x = 0; x < spn; x++) f[x] = (float)(f[x] / sum);
-        for (int x = spn; x < PS_GA; x++) f[x] = 0.0f;
+        compute_filters(a0, p.gauss_mode);
     }
     SiftConsts& sc = c->sc;
     sc.sigma0 = sigma0;
@@ -541,6 +562,124 @@ BlurArgs level_args(const popsift_hip_ctx* c, int o, int level)
     return a;
 }
 
+/* the shift of the upscale from the input image (s_pyramid_build.cu:109-114) */
+float input_shift(const popsift_hip_ctx* c)
+{
+    if (c->p.sift_mode == POPSIFT_HIP_SIFT_POPSIFT || c->p.sift_mode == POPSIFT_HIP_SIFT_VLFEAT)
+        return 0.5f * powf(2.0f, c->p.upscale_factor - 0);
+    return 0.5f;
+}
+
+/* profile mode 1 brackets PROFILE_REPS back-to-back launches with one event pair (see blur_launch); every launch of
+ * the octave-0 paths below is idempotent */
+template <typename F>
+int timed_launch(popsift_hip_ctx* c, double alg_bytes, const char* what, F launch)
+{
+    if (c->profile == 1) {
+        if (c->blur_events_used == c->blur_events.size()) {
+            EventPair ep;
+            HIP_TRY(c, hipEventCreate(&ep.a));
+            HIP_TRY(c, hipEventCreate(&ep.b));
+            c->blur_events.push_back(ep);
+        }
+        EventPair& ep = c->blur_events[c->blur_events_used++];
+        ep.bytes = alg_bytes * c->nb;
+        ep.big = false;
+        HIP_TRY(c, hipEventRecord(ep.a, c->stream));
+        for (int rep = 0; rep < PROFILE_REPS; rep++) HIP_TRY(c, launch());
+        HIP_TRY(c, hipEventRecord(ep.b, c->stream));
+    } else {
+        HIP_TRY(c, launch());
+        SYNC_CHK(c, what);
+    }
+    (void)what;
+    return 0;
+}
+
+/*
+ * Octave 0 of the vlfeat-direct Gauss mode (Pyramid::build_pyramid, s_pyramid_build.cu:545-548): every level l is the
+ * input image upscaled and blurred with the abs_o0[l] taps, horizontally (normalizedSource::horiz_all) then vertically
+ * (absoluteSource::vert_all_abs0).  Writes the L Gaussian planes, the L-1 DoG planes when they are stored, level 0 of
+ * octave 1 (every second pixel of level L-3) and clears the images' counters, like the default mode's octave-0
+ * launches.  DIRECT_PATH 0: one fused launch (pyr_direct.hip); 1: the level-0 kernel once per level with the abs_o0
+ * taps, then the DoG planes and octave 1's level 0 by launches of their own (the in-tree yardstick of the fused one).
+ */
+int enqueue_direct_octave0(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
+{
+    const PyrDesc& pd = c->pd;
+    const OctDesc& od = pd.o[0];
+    const int      L = pd.L;
+    const int      zero_words = (int)(sizeof(Counters) / sizeof(int));
+    const int64_t  next0_off = pd.n_oct > 1 ? pd.o[1].data_off : -1;
+    const double   in_bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1);
+    const double   px = (double)od.w * od.h;
+    if (c->direct_path == 0) {
+        DirectArgs a{};
+        a.dst_off = od.data_off;
+        a.dog_off = pd.dog_fly ? -1 : od.dog_off;
+        a.plane_stride = od.plane_stride;
+        a.next0_off = next0_off;
+        a.taps = c->d_abs0;
+        a.w = od.w;
+        a.h = od.h;
+        a.pitch = od.pitch;
+        a.next_pitch = pd.n_oct > 1 ? pd.o[1].pitch : 0;
+        a.tiles_x = (od.w + blur_tile_w() - 1) / blur_tile_w();
+        a.tiles_y = (od.h + pyr_direct_tile_h() - 1) / pyr_direct_tile_h();
+        a.in_w = c->in_w;
+        a.in_h = c->in_h;
+        a.in_pitch = pitch;
+        a.shift = input_shift(c);
+        a.L = L;
+        for (int l = 0; l < L; l++) a.halo[l] = c->abs0.span[l] - 1;
+        a.zero_words = zero_words;
+        const double bytes = in_bytes + 4.0 * px * (L + (pd.dog_fly ? 0 : L - 1)) + (next0_off >= 0 ? px : 0.0);
+        return timed_launch(c, bytes, "k_pyr_direct", [&] { return launch_pyr_direct(a, c->bd, c->nb, is_f32, c->stream); });
+    }
+    const int thd = blur_tile_h(od.w, od.h), twd = blur_tile_w();
+    for (int l = 0; l < L; l++) {
+        BlurArgs a{};
+        a.w = od.w;
+        a.h = od.h;
+        a.pitch = od.pitch;
+        a.tiles_x = (od.w + twd - 1) / twd;
+        a.tiles_y = (od.h + thd - 1) / thd;
+        memcpy(a.taps.g, &c->abs0.filter[l * PS_GA], sizeof(a.taps.g));
+        a.dst_off = od.data_off + l * od.plane_stride;
+        a.src_off = 0;
+        a.dog_off = -1;
+        a.next0_off = -1;
+        a.in_w = c->in_w;
+        a.in_h = c->in_h;
+        a.in_pitch = pitch;
+        a.shift = input_shift(c);
+        /* the level-0 kernel's exact-2x paths, as in the default mode's level-0 launch */
+        a.fast2x = (c->p.upscale_factor == 1.0f && a.shift == 1.0f && od.w == 2 * c->in_w && od.h == 2 * c->in_h) ? 1 : 0;
+        if (a.fast2x && !is_f32 && aligned4) a.fast2x = 2;
+        a.zero_words = l == 0 ? zero_words : 0;
+        const int span = c->abs0.span[l];
+        if (int rc = timed_launch(c, in_bytes + 4.0 * px, "k_blur_tile (direct level)",
+                                  [&] { return launch_blur(a, c->bd, c->nb, is_f32 ? 2 : 1, span, thd, c->stream, c->blur_tune); }))
+            return rc;
+    }
+    if (!pd.dog_fly)
+        for (int l = 0; l + 1 < L; l++) {
+            const int64_t lo = od.data_off + l * od.plane_stride, up = lo + od.plane_stride, dg = od.dog_off + l * od.plane_stride;
+            if (int rc = timed_launch(c, 12.0 * px, "k_dog_batch",
+                                      [&] { return launch_dog_batch(lo, up, dg, od.plane_stride, c->bd, c->nb, c->stream); }))
+                return rc;
+        }
+    if (next0_off >= 0) {
+        const OctDesc& o1 = pd.o[1];
+        const int64_t  src = od.data_off + (L - 3) * od.plane_stride;
+        if (int rc = timed_launch(c, 8.0 * o1.w * o1.h, "k_pick_every_second", [&] {
+                return launch_pick_every_second(src, od.w, od.h, od.pitch, o1.data_off, o1.w, o1.h, o1.pitch, c->bd, c->nb, c->stream);
+            }))
+            return rc;
+    }
+    return 0;
+}
+
 /*
  * Pyramid::build_pyramid default branch (s_pyramid_build.cu:549-588), one stream, every launch for all images of the
  * batch (gridDim.y).  Launch order:
@@ -561,7 +700,10 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
         /* read plane l-1 once, write plane l (and DoG l-1 when it is stored) once: 8 (12) B / pixel */
         return blur_launch(c, a, 0, c->tab.span[level], blur_tile_h(pd.o[o].w, pd.o[o].h), (pd.dog_fly ? 8.0 : 12.0) * px);
     };
-    {
+    const bool direct = c->p.gauss_mode == POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL;
+    if (direct) {
+        if (int rc = enqueue_direct_octave0(c, is_f32, pitch, aligned4)) return rc;
+    } else {
         /* horiz_from_input_image, s_pyramid_build.cu:96-126 */
         const OctDesc& od = pd.o[0];
         BlurArgs       a{};
@@ -621,8 +763,10 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
             }
         }
     }
-    const bool early1 = c->pyr_order == 1 && n_front >= 2 && L - 3 >= 1;
-    for (int level = 1; level < L; level++) {
+    /* vlfeat-direct: octave 0 is complete, octave 1's level 0 included, so "early" is any time from here on and the
+     * octave loop below takes level 1 of octave 1 in its place */
+    const bool early1 = !direct && c->pyr_order == 1 && n_front >= 2 && L - 3 >= 1;
+    for (int level = 1; level < L && !direct; level++) {
         if (int rc = single(0, level)) return rc;
         if (early1 && level == L - 3)
             if (int rc = single(1, 1)) return rc;
@@ -1017,7 +1161,8 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
     /* gauss_filter.cu:131-144: sigma > 2 or too many levels is fatal in the reference */
     if (!(p->sigma > 0.0f) || p->sigma > 2.0f) return POPSIFT_HIP_ERR_INVALID;
     if (p->levels > POPSIFT_HIP_MAX_LEVELS - 3) return POPSIFT_HIP_ERR_INVALID;
-    if (p->gauss_mode != POPSIFT_HIP_GAUSS_VLFEAT_COMPUTE && p->gauss_mode != POPSIFT_HIP_GAUSS_OPENCV_COMPUTE)
+    if (p->gauss_mode != POPSIFT_HIP_GAUSS_VLFEAT_COMPUTE && p->gauss_mode != POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL &&
+        p->gauss_mode != POPSIFT_HIP_GAUSS_OPENCV_COMPUTE)
         return POPSIFT_HIP_ERR_INVALID;
     if (p->desc_mode < POPSIFT_HIP_DESC_LOOP || p->desc_mode > POPSIFT_HIP_DESC_NOTILE) return POPSIFT_HIP_ERR_INVALID;
     if (p->sift_mode < 0 || p->sift_mode > 2 || p->norm_mode < 0 || p->norm_mode > 1) return POPSIFT_HIP_ERR_INVALID;
@@ -1053,6 +1198,11 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
         HIP_TRY(c, hipHostMalloc((void**)&c->h_pd, sizeof(PyrDesc), hipHostMallocDefault));
         HIP_TRY(c, hipHostMalloc((void**)&c->h_ct, sizeof(Counters) * PS_MAX_BATCH, hipHostMallocDefault));
         memset(c->h_ct, 0, sizeof(Counters) * PS_MAX_BATCH);
+        if (c->p.gauss_mode == POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL) {
+            const size_t bytes = sizeof(float) * (size_t)c->L * PS_GA;
+            HIP_TRY(c, hipMalloc((void**)&c->d_abs0, bytes));
+            HIP_TRY(c, hipMemcpy(c->d_abs0, c->abs0.filter, bytes, hipMemcpyHostToDevice));
+        }
         return 0;
     }();
     if (rc) {
@@ -1100,6 +1250,7 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
     }
     if (c->d_ct) (void)hipFree(c->d_ct);
     if (c->d_pd) (void)hipFree(c->d_pd);
+    if (c->d_abs0) (void)hipFree(c->d_abs0);
     if (c->h_pd) (void)hipHostFree(c->h_pd);
     if (c->h_ct) (void)hipHostFree(c->h_ct);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1114,6 +1265,18 @@ int popsift_hip_get_gauss_table(const popsift_hip_ctx* c, float* filter, int* sp
     if (filter) memcpy(filter, c->tab.filter, sizeof(float) * (size_t)c->L * PS_GA);
     if (span) memcpy(span, c->tab.span, sizeof(int) * (size_t)c->L);
     if (sigma) memcpy(sigma, c->tab.sigma, sizeof(float) * (size_t)c->L);
+    if (n_levels) *n_levels = c->L;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_get_gauss_table_abs0(const popsift_hip_ctx* c, float* filter, int* span, float* sigma, int* n_levels)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (c->p.gauss_mode != POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL)
+        return fail(const_cast<popsift_hip_ctx*>(c), POPSIFT_HIP_ERR_STATE, "the abs_o0 table exists in the vlfeat-direct Gauss mode only");
+    if (filter) memcpy(filter, c->abs0.filter, sizeof(float) * (size_t)c->L * PS_GA);
+    if (span) memcpy(span, c->abs0.span, sizeof(int) * (size_t)c->L);
+    if (sigma) memcpy(sigma, c->abs0.sigma, sizeof(float) * (size_t)c->L);
     if (n_levels) *n_levels = c->L;
     return POPSIFT_HIP_OK;
 }
@@ -1636,6 +1799,10 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_DESC_ROWS:
         c->desc_rows = c->sc.desc_rows = std::max(value, 4);
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_DIRECT_PATH:
+        if (value < 0 || value > 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "DIRECT_PATH: 0 or 1");
+        c->direct_path = value;
         return POPSIFT_HIP_OK;
     }
     return fail(c, POPSIFT_HIP_ERR_INVALID, "unknown debug switch %d", what);

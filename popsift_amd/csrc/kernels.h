@@ -68,6 +68,30 @@ struct TailArgs {
 bool       pyr_tail_fits(int w, int h);
 hipError_t launch_pyr_tail(const TailArgs& a, const BatchDesc& bd, int nb, hipStream_t s);
 
+/* pyr_direct.hip: octave 0 of the vlfeat-direct Gauss mode (every level blurred straight from the input image), all
+ * L Gaussian planes (+ the L-1 DoG planes) in one launch */
+struct DirectArgs {
+    int64_t      dst_off;      /* plane 0 of octave 0; plane l at dst_off + l * plane_stride */
+    int64_t      dog_off;      /* DoG plane 0 of octave 0, < 0: not stored */
+    int64_t      plane_stride; /* floats */
+    int64_t      next0_off;    /* level 0 of octave 1 = every second pixel of level L-3, < 0: no octave 1 */
+    const float* taps;         /* L x PS_GA abs_o0 taps, zero beyond each level's span (device memory of the context) */
+    int          w, h, pitch, next_pitch;
+    int          tiles_x, tiles_y;
+    int          in_w, in_h, in_pitch;
+    float        shift;
+    int          L;
+    int          halo[PS_MAX_PLANES]; /* span - 1 of level l */
+    int          zero_words;          /* words of the slot's Counters the launch clears */
+};
+int        pyr_direct_tile_h();
+hipError_t launch_pyr_direct(const DirectArgs& a, const BatchDesc& bd, int nb, int is_f32, hipStream_t s);
+/* the per-level path of the same mode (popsift_hip_debug_set DIRECT_PATH 1): octave 1's level 0 and the DoG planes */
+hipError_t launch_pick_every_second(int64_t src_off, int w, int h, int pitch, int64_t dst_off, int nw, int nh, int npitch,
+                                    const BatchDesc& bd, int nb, hipStream_t s);
+hipError_t launch_dog_batch(int64_t lower_off, int64_t upper_off, int64_t dog_off, int64_t n, const BatchDesc& bd, int nb,
+                            hipStream_t s);
+
 /* extrema.hip */
 hipError_t launch_dog_plane(float* dog, const float* upper, const float* lower, size_t n, hipStream_t s); /* debug / test downloads */
 int        extrema_units(int w, int h); /* wave-sized work units of the detection kernel */

@@ -267,8 +267,9 @@ bool PopSift::configure(const popsift::Config& config, bool /*force*/)
     if (_config.sigma > 2.0f) DIE("Sigma > 2.0 is not supported.");
     if (_config.levels > GAUSS_LEVELS - 3) DIE("More than 9 levels are not supported.");
     if (_config.getGaussMode() != popsift::Config::VLFeat_Compute &&
+        _config.getGaussMode() != popsift::Config::VLFeat_Relative_All &&
         _config.getGaussMode() != popsift::Config::OpenCV_Compute)
-        DIE("this build implements the Gauss modes 'vlfeat' and 'opencv' only");
+        DIE("this build implements the Gauss modes 'vlfeat', 'vlfeat-direct' and 'opencv' only");
     if (_config.getScalingMode() != popsift::Config::ScaleDefault) DIE("ScaleDirect is not supported");
     if (_config.getFilterMaxExtrema() > 0 && (_config.getFilterGridSize() < 1 || _config.getFilterGridSize() > 64))
         DIE("the grid filter supports grid sizes 1..64");
