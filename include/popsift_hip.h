@@ -321,11 +321,13 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * plane and the batch); PYR_TAIL = 0: the smallest octaves -- from the first whose plane fits one workgroup's LDS -- are
  * built by one launch (default), 1: by level launches like the others (results do not depend on it); DIRECT_PATH (Gauss
  * mode vlfeat-direct only) = 0: octave 0's levels by one fused launch (default), 1: by one level-0 launch per level
- * (results do not depend on it). */
+ * (results do not depend on it); DESC_CAP = initial capacity of the descriptor buffer, in descriptors (0 = the default,
+ * 2 * max_extrema: small values exercise the grow-and-rerun path of popsift_hip_wait for descriptors). */
 enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_HIP_DEBUG_OHIST_CAP = 3,
        POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, POPSIFT_HIP_DEBUG_PYR_ORDER = 6,
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
-       POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11 };
+       POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
+       POPSIFT_HIP_DEBUG_DESC_CAP = 12 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

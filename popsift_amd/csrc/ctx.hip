@@ -122,6 +122,7 @@ struct popsift_hip_ctx {
     int       cand_cap_init = 1 << 20;
     bool      cand_cap_user = false;
     int       ohist_cap_init = 0;
+    int       desc_cap_init = 0; /* DESC_CAP debug switch: initial descriptor capacity (0 = 2 * max_extrema) */
     size_t    ext_cap = 0; /* entries every one of d_iext/d_ext/d_feats(/d_iext2) of the sized slots holds */
     /* capacities the kernels are told: the smallest over the slots of the batch (refresh_caps) */
     int       cand_cap = 0, desc_cap = 0;
@@ -477,7 +478,9 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
         }
         if (int rc = grow(c, &s.d_partial, &s.partial_cap, (need_ext / scan_chunk() + 2) * scan_partials_per_chunk())) return rc;
         /* sift_pyramid.cu:149: max(2*max_extrema, max_orientations) descriptors to start with */
-        if (int rc = slot_desc_cap(c, s, std::max(std::max(2 * c->sc.max_extrema, c->sc.max_extrema + c->sc.max_extrema / 4), c->desc_cap)))
+        const int desc0 = c->desc_cap_init > 0 ? c->desc_cap_init
+                                               : std::max(2 * c->sc.max_extrema, c->sc.max_extrema + c->sc.max_extrema / 4);
+        if (int rc = slot_desc_cap(c, s, std::max(desc0, c->desc_cap)))
             return rc;
         /* candidates: 64 region slices of one buffer (extrema.hip); a default-sized buffer grows with the pyramid, so that
          * the first image of a 4K stream does not overflow a slice and re-run (a test's explicit CAND_CAP is taken as is) */
@@ -1777,6 +1780,9 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_OHIST_CAP:
         c->ohist_cap_init = std::max(value, 1);
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_DESC_CAP:
+        c->desc_cap_init = std::max(value, 0);
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_FAIL_ALLOC:
         c->fail_alloc_in = std::max(value, 0);

@@ -1,0 +1,98 @@
+"""The contract of tests/planted.py, checked on the oracle without a GPU: the keypoint stages run on the planted planes
+find EXACTLY the requested number of extrema in every octave, each at its planted centre and level."""
+import numpy as np
+import pytest
+
+import planted as P
+
+W, H, OCT = 480, 480, 4
+
+
+def _run(O, request, seed=0, sift_mode=0, w=W, h=H, octaves=OCT, **kw):
+    dims = P.octave_dims(O, w, h, octaves, sift_mode=sift_mode, **kw)
+    pl = P.Planted(dims, request, seed=seed, sift_mode=sift_mode)
+    orc = O.Oracle(O.default_params(**P.params_kw(octaves, sift_mode=sift_mode, **kw)), threads=4)
+    orc.run(np.zeros((h, w), np.uint8), keypoints=False)
+    pl.load_oracle(orc)
+    return pl, orc
+
+
+def _check(pl, orc):
+    assert orc.ext_counts() == pl.counts
+    e = orc.extrema()
+    for o, bt in enumerate(pl.bumps):
+        eo = e[e["octave"] == o]
+        assert len(eo) == len(bt)
+        if not len(eo):
+            continue
+        # each extremum at its own bump's centre (one to one), on the bump's search level
+        d = np.hypot(eo["xpos"][:, None] - bt["xc"][None, :], eo["ypos"][:, None] - bt["yc"][None, :])
+        j = d.argmin(1)
+        assert len(set(j.tolist())) == len(bt), "octave %d: two extrema at one bump" % o
+        assert d[np.arange(len(eo)), j].max() <= 2e-3, "octave %d: found and planted centres differ" % o
+        assert np.array_equal(eo["lpos"], bt["z"][j]), "octave %d: lpos differs from the planted level" % o
+        zc = bt["zc"][j]
+        assert np.allclose(eo["sigma"], 1.6 * 2.0 ** (zc / P.LEVELS), rtol=1e-5), o
+
+
+@pytest.mark.parametrize("sift_mode", [0, 1, 2])
+@pytest.mark.parametrize("request_", [{}, {0: 1}, {0: 63, 1: 2}, {0: 255, 1: 3}, {0: 40, 2: 40}, {1: 10, 2: 10, 3: 5},
+                                      {3: 20}, {0: 2049}, {0: 1000, 1: 500, 2: 120, 3: 20}],
+                         ids=lambda r: "-".join("%d:%d" % kv for kv in sorted(r.items())) or "empty")
+def test_oracle_finds_exactly_the_planted_extrema(oracle_mod, sift_mode, request_):
+    pl, orc = _run(oracle_mod, request_, seed=len(request_) + sift_mode, sift_mode=sift_mode)
+    _check(pl, orc)
+
+
+def test_planted_regions_and_sub_queues(oracle_mod):
+    """bumps confined to one detection sub-queue's cell land there, and only there"""
+    dims = P.octave_dims(oracle_mod, W, H, OCT)
+    w, h = dims[0]
+    rect = P.subq_rect(w, h, 9)
+    n = P.capacity(w, h, rect=rect)
+    assert n >= 20
+    pl, orc = _run(oracle_mod, {0: (n, rect)})
+    _check(pl, orc)
+    x0, y0, x1, y1 = rect
+    bt = pl.bumps[0]
+    assert ((bt["x"] >= x0) & (bt["x"] < x1) & (bt["y"] >= y0) & (bt["y"] < y1)).all()
+    # every pixel of the octave belongs to exactly one sub-queue cell
+    cover = np.zeros((h, w), np.int32)
+    for q in range(P.DET_SUBQ):
+        a, b, c, d = P.subq_rect(w, h, q)
+        cover[b:d, a:c] += 1
+    assert (cover[1:h - 1, 1:w - 1] == 1).all()
+    yy, xx = np.mgrid[0:h, 0:w]
+    q = np.full((h, w), -1)
+    q[1:h - 1, 1:w - 1] = P.subq_of(w, h, xx, yy)[1:h - 1, 1:w - 1]
+    for k in range(P.DET_SUBQ):
+        a, b, c, d = P.subq_rect(w, h, k)
+        inner = q[max(b, 1):min(d, h - 1), max(a, 1):min(c, w - 1)]
+        assert inner.size and (inner == k).all(), k
+
+
+def test_planted_geometry_covers_the_edges(oracle_mod):
+    """the first / last detectable rows and columns, both ends of the search range, minima and maxima, the smallest
+    octave, and orientations of more than one peak: the cases where clipping and indexing go wrong"""
+    for mode in (0, 1):
+        pl, orc = _run(oracle_mod, {0: 300, 1: 100, 2: 40, 3: 12}, seed=5, sift_mode=mode)
+        _check(pl, orc)
+        b = P.border(mode)
+        for o, bt in enumerate(pl.bumps):
+            w, h = pl.dims[o]
+            assert (bt["x"] == b).any() and (bt["x"] == w - 1 - b).any(), o
+            assert (bt["y"] == b).any() and (bt["y"] == h - 1 - b).any(), o
+            assert set(bt["z"]) == {1, 2, 3}, o
+            assert set(bt["sign"]) == {-1, 1}, o
+        f, _ = orc.fetch()
+        assert (f["num_ori"] > 1).sum() >= 5
+    # the orientations are not mirror-symmetric: no two peaks of one keypoint tie (a set comparison is not needed)
+    for r in f[f["num_ori"] > 1]:
+        v = r["orientation"][:r["num_ori"]]
+        assert len(set(v.tolist())) == len(v)
+
+
+def test_request_beyond_the_lattice_is_refused(oracle_mod):
+    dims = P.octave_dims(oracle_mod, 64, 64, 2)
+    with pytest.raises(ValueError):
+        P.Planted(dims, {1: P.capacity(*dims[1]) + 1})
