@@ -27,6 +27,17 @@
 
 struct popsift_hip_ctx;
 
+namespace popsift {
+/** Extension: a caller-supplied keypoint for PopSift::enqueue(w, h, img, frames), the layout of popsift_hip_frame
+ *  (include/popsift_hip.h, where the octave / level rule and the validity rules are written down).  Position and sigma in
+ *  input-image units, as Feature reports them; orientation in radians, used when the job does not compute orientations. */
+struct Frame {
+    float xpos, ypos, sigma, orientation;
+    int   octave = -1; /* -1: derived from sigma */
+    int   level = -1;  /* -1: derived from sigma */
+};
+}  // namespace popsift
+
 class SiftJob {
     std::promise<popsift::FeaturesBase*> _p;
     std::future<popsift::FeaturesBase*>  _f;
@@ -57,6 +68,22 @@ public:
     const unsigned char* getImageData() const { return _imageData; }
     /** extension: the job's image copy is page-locked (the worker then uploads it without a staging copy) */
     bool                 isPinned() const { return _pinned; }
+
+    /** extension: a describe job (PopSift::enqueue with frames) and its frames, copied at enqueue */
+    void setFrames(const std::vector<popsift::Frame>& frames, bool computeOrientation)
+    {
+        _frames = frames;
+        _describe = true;
+        _compute_ori = computeOrientation;
+    }
+    bool                               isDescribe() const { return _describe; }
+    bool                               computesOrientation() const { return _compute_ori; }
+    const std::vector<popsift::Frame>& getFrames() const { return _frames; }
+
+private:
+    std::vector<popsift::Frame> _frames;
+    bool                        _describe = false;
+    bool                        _compute_ori = true;
 };
 
 namespace popsift {
@@ -85,6 +112,16 @@ public:
     SiftJob* enqueue(int w, int h, const unsigned char* imageData);
     /** float image, values 0..1 */
     SiftJob* enqueue(int w, int h, const float* imageData);
+
+    /** Extension (vl_sift 'frames', OpenCV SIFT::compute): descriptors of caller-supplied keypoints instead of detected
+     *  ones.  job->get() holds one Feature per frame, in the caller's order; computeOrientation = false describes each
+     *  valid frame once, in frame.orientation.  Invalid frames (popsift_hip.h) come back with num_ori = 0.  The frames are
+     *  copied before the call returns.  With POPSIFT_BATCH > 1 a worker batches describe jobs only with describe jobs of
+     *  the same size, type and orientation mode. */
+    SiftJob* enqueue(int w, int h, const unsigned char* imageData, const std::vector<popsift::Frame>& frames,
+                     bool computeOrientation = true);
+    SiftJob* enqueue(int w, int h, const float* imageData, const std::vector<popsift::Frame>& frames,
+                     bool computeOrientation = true);
 
     /** deprecated blocking interface */
     inline void uninit(int /*pipe*/) { uninit(); }
@@ -121,7 +158,8 @@ private:
         cpu_set_t        cpus;
     };
 
-    void start_workers(int w, int h);
+    void     start_workers(int w, int h);
+    SiftJob* push(SiftJob* job, int w, int h);
     void worker_loop(Worker* me);
 
     std::vector<Worker*>    _workers;

@@ -219,6 +219,51 @@ int popsift_hip_results_dev_item(popsift_hip_ctx* ctx, int k, const void** d_fea
 int popsift_hip_fetch_begin_item(popsift_hip_ctx* ctx, int k, popsift_hip_feature* feats, size_t feats_cap, float* desc,
                                  size_t desc_cap);
 
+/*
+ * Describe caller-supplied keypoints (vl_sift's 'frames' / 'orientations' options, OpenCV's SIFT::compute): the pyramid
+ * of each image is built as for extraction, detection and refinement do not run, and every frame is described where the
+ * caller put it.  Results come back through the same calls as an extraction's -- wait / wait_batch, fetch(_item),
+ * fetch_begin(_item), results_dev(_item), clone_results -- with n_features[k] == n_frames[k] and feature i belonging to
+ * frame i (caller order); desc_idx points into the image's descriptor array as usual, and the reverse map of a cloned
+ * set names caller-order feature indices.
+ *
+ * A frame goes into octave o at x_oct = ldexpf(xpos, up - o) (likewise ypos and sigma), up = (int)upscale_factor, so the
+ * feature it gets back reports the frame's own xpos / ypos / sigma.  With octave / level = -1 both are derived from sigma:
+ *     t    = log2f(sigma / sigma0) + up
+ *     o    = clamp(floor(t - 0.5f / levels), 0, n_oct - 1)
+ *     lpos = clamp(roundf(levels * log2f(sigma_oct / sigma0)), 0, L - 1)          (L = levels + 3 Gaussian planes)
+ * which inverts refinement's sigma = sigma0 * 2^(sn / levels), lpos = roundf(sn), for sn in [0.5, levels + 0.5).
+ *
+ * An INVALID frame gets a record with num_ori = 0, desc_idx all -1, debug_octave = -1 and its position and scale echoed;
+ * it takes no list slot.  A frame is invalid when a coordinate or sigma is not finite, sigma <= 0, x_oct is outside
+ * [0, w_o - 1] or y_oct outside [0, h_o - 1], an octave / level hint is out of range (octave < -1 or >= n_oct, level < -1
+ * or >= L), the orientation is not finite (POPSIFT_HIP_ORI_GIVEN), or sigma_oct > POPSIFT_HIP_FRAME_SIGMA_MAX.
+ *
+ * ori_mode POPSIFT_HIP_ORI_COMPUTE: up to four orientations per frame, exactly as extraction computes them;
+ * POPSIFT_HIP_ORI_GIVEN: one orientation (frame.orientation, radians, used as given) and one descriptor per valid frame.
+ * n_frames[k] <= params.max_extrema (else ERR_INVALID); 0 is allowed.  Frames are host memory and are copied before the
+ * call returns.  The grid filter (filter_max_extrema) does not apply.  download_extrema afterwards returns the resolved
+ * frames (ascending octave, caller order within an octave, cell = frame index), get_report their counts,
+ * rerun_keypoint_stages re-runs these stages.
+ */
+typedef struct popsift_hip_frame {   /* 24 bytes */
+    float   xpos, ypos;   /* input-image coordinates, as popsift_hip_feature reports them                     */
+    float   sigma;        /* input-image units, as popsift_hip_feature::sigma                                  */
+    float   orientation;  /* radians, used as given; read only with POPSIFT_HIP_ORI_GIVEN                      */
+    int32_t octave;       /* -1: derived from sigma; else the octave to sample (not checked against sigma)     */
+    int32_t level;        /* -1: derived from sigma; else the Gaussian level (plane) to sample                 */
+} popsift_hip_frame;
+enum { POPSIFT_HIP_ORI_COMPUTE = 0, POPSIFT_HIP_ORI_GIVEN = 1 };
+/* Largest accepted scale in octave units.  The loop descriptor walks a patch in passes of at most 128 rows whose samples
+ * are numbered in signed 16-bit fields (T <= 128 * (5 * sqrt(2) * 3 * sigma + 1) < 2^15 needs sigma < 12.0), and 8 is
+ * the largest scale extraction itself produces (sigma0 = 2 at two levels, refinement's sn = levels + 2: the 173-row
+ * patches the multi-pass walk was built for).  Orientation's window (4.5 sigma, clipped to the plane) has no tighter
+ * limit. */
+#define POPSIFT_HIP_FRAME_SIGMA_MAX 8.0f
+/* image k of n (one size, kind = POPSIFT_HIP_IMG_*) with its own n_frames[k] frames; a single image is n = 1 */
+int popsift_hip_describe_batch(popsift_hip_ctx* ctx, const void* const* imgs, const popsift_hip_frame* const* frames,
+                               const int* n_frames, int n, int kind, int w, int h, int pitch, int ori_mode);
+
 /* Replaces the counter read-back of Pyramid::get_descriptors
  * (sift_pyramid.cu:281-294): blocks until the submitted image is finished and
  * returns the feature / descriptor counts. */

@@ -74,6 +74,13 @@ EXTREMUM_DTYPE = np.dtype([
     ("xpos", np.float32), ("ypos", np.float32), ("lpos", np.int32),
     ("sigma", np.float32), ("octave", np.int32), ("cell", np.int32),
 ])
+# popsift_hip_frame: a caller-supplied keypoint for Context.describe (octave / level -1: derived from sigma)
+FRAME_DTYPE = np.dtype([
+    ("xpos", np.float32), ("ypos", np.float32), ("sigma", np.float32), ("orientation", np.float32),
+    ("octave", np.int32), ("level", np.int32),
+])
+ORI_COMPUTE, ORI_GIVEN = 0, 1
+FRAME_SIGMA_MAX = np.float32(8.0)  # POPSIFT_HIP_FRAME_SIGMA_MAX: the largest accepted scale in octave units
 
 # every symbol include/popsift_hip.h declares: (name, restype, argtypes)
 _vp, _ip = C.c_void_p, C.POINTER(C.c_int)
@@ -96,6 +103,8 @@ SYMBOLS = [
     ("popsift_hip_submit_pinned_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_pinned_f32", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_batch", C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("popsift_hip_describe_batch", C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_wait_batch", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("popsift_hip_fetch_item", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("popsift_hip_results_dev_item", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
@@ -381,6 +390,42 @@ class Context:
         self._chk(lib().popsift_hip_submit_batch(self._h, arr, len(ptrs), IMG_DEV_F32 if is_f32 else IMG_DEV_U8, w, h, pitch),
                   "popsift_hip_submit_batch")
         return self
+
+    def describe_batch_async(self, imgs, frame_lists, orientation="compute"):
+        """popsift_hip_describe_batch: host images of one size and dtype, each with its own FRAME_DTYPE frames; results as
+        for submit_batch (wait_batch / fetch_item), one feature per frame in caller order"""
+        if orientation not in ("compute", "given"):
+            raise ValueError("orientation: 'compute' or 'given'")
+        imgs = [np.ascontiguousarray(im) for im in imgs]
+        if len(frame_lists) != len(imgs):
+            raise ValueError("one frame list per image")
+        h, w = imgs[0].shape
+        if any(im.ndim != 2 or im.shape != (h, w) or im.dtype != imgs[0].dtype for im in imgs):
+            raise ValueError("the images of a batch share one size and dtype")
+        if imgs[0].dtype == np.uint8:
+            kind = IMG_HOST_U8
+        elif imgs[0].dtype == np.float32:
+            kind = IMG_HOST_F32
+        else:
+            raise TypeError("uint8 or float32 images expected, got %s" % imgs[0].dtype)
+        frs = [np.ascontiguousarray(f, FRAME_DTYPE) for f in frame_lists]
+        arr = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
+        farr = (C.c_void_p * len(imgs))(*[f.ctypes.data if len(f) else None for f in frs])
+        nfr = (C.c_int * len(imgs))(*[len(f) for f in frs])
+        self._chk(lib().popsift_hip_describe_batch(self._h, arr, farr, nfr, len(imgs), kind, w, h, w,
+                                                   ORI_GIVEN if orientation == "given" else ORI_COMPUTE),
+                  "popsift_hip_describe_batch")
+        return self
+
+    def describe(self, img, frames, orientation="compute"):
+        """descriptors of caller-supplied keypoints (FRAME_DTYPE) -> (feats, desc), feature i for frame i.
+        orientation="compute": up to four orientations per frame as extraction finds them; "given": frames["orientation"]"""
+        return self.describe_batch_async([img], [frames], orientation).fetch_item(0)
+
+    def describe_batch(self, imgs, frame_lists, orientation="compute"):
+        """-> [(feats, desc)] per image, as describe() gives them"""
+        self.describe_batch_async(imgs, frame_lists, orientation)
+        return [self.fetch_item(k) for k in range(len(imgs))]
 
     def wait_batch(self):
         """-> [(features, descriptors)] per image of the batch"""

@@ -87,6 +87,19 @@ struct ImageSlot {
     float*   alt_desc = nullptr;
     int      alt_desc_cap = 0;
     bool     moved = false; /* the finished image's results went to fetch_begin: the current slab is stale */
+    /* describe (popsift_hip_describe_batch) only, grown on the first describe: the frames (device copy and pinned staging),
+     * the per-chunk counts of the partition, list position <-> frame, k_scan_apply's records in list order */
+    popsift_hip_frame*   d_frames = nullptr;
+    popsift_hip_frame*   h_frames = nullptr;
+    size_t               frames_cap = 0, h_frames_cap = 0;
+    int*                 d_fcounts = nullptr;
+    size_t               fcounts_cap = 0;
+    int*                 d_perm = nullptr;
+    int*                 d_inv = nullptr;
+    size_t               perm_cap = 0, inv_cap = 0;
+    popsift_hip_feature* d_lfeats = nullptr;
+    size_t               lfeats_cap = 0;
+    int                  n_frames = 0; /* frames of the described image */
 };
 
 struct popsift_hip_ctx {
@@ -108,6 +121,9 @@ struct popsift_hip_ctx {
     bool have_image = false, finished = false;
     bool batch_ok = false; /* the last submit enqueued everything it had to: there are (or will be) results to wait for */
     int  nb = 1; /* images of the submitted batch */
+    bool describe = false;  /* the batch in the context is a describe (popsift_hip_describe_batch), not an extraction */
+    int  ori_given = 0;     /* ... with POPSIFT_HIP_ORI_GIVEN */
+    int  frames_max = 0;    /* ... and the most frames of one of its images */
 
     /* one slot per image of a batch; a plain submit uses slot 0 */
     ImageSlot slot[PS_MAX_BATCH];
@@ -804,7 +820,10 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
 }
 
 /* Pyramid::step2 + prep_features: extrema -> orientation -> scan -> descriptors -> features */
-InitExt* final_iext(popsift_hip_ctx* c, int k = 0) { return c->sc.filter_max > 0 ? c->slot[k].d_iext2 : c->slot[k].d_iext; }
+InitExt* final_iext(popsift_hip_ctx* c, int k = 0)
+{
+    return c->sc.filter_max > 0 && !c->describe ? c->slot[k].d_iext2 : c->slot[k].d_iext; /* frames are not grid-filtered */
+}
 
 /* counters_cleared: the level-0 launch of this batch has zeroed the counters (submit); re-runs clear them here */
 int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
@@ -838,8 +857,82 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     return 0;
 }
 
+/* The keypoint stages of a describe (describe.hip): the frames instead of detection and refinement, then orientation (or
+ * the given angles) -> scan -> descriptors as for extraction, then the records in caller order.  Re-runs clear the
+ * counters here, as enqueue_keypoint_stages does. */
+int enqueue_describe_stages(popsift_hip_ctx* c, bool counters_cleared = false)
+{
+    POPSIFT_RANGE("popsift_hip: describe stages");
+    const bool stages = (c->profile == 2);
+    auto       mark = [&](int k) -> hipError_t { return stages ? hipEventRecord(c->ev_stage[k], c->stream) : hipSuccess; };
+    FrameBatch fb{};
+    BatchDesc  lb = c->bd; /* k_scan_apply writes its feature records in list order, k_frame_out moves them */
+    for (int k = 0; k < c->nb; k++) {
+        const ImageSlot& sl = c->slot[k];
+        fb.s[k].frames = sl.d_frames;
+        fb.s[k].counts = sl.d_fcounts;
+        fb.s[k].perm = sl.d_perm;
+        fb.s[k].inv = sl.d_inv;
+        fb.s[k].lfeats = sl.d_lfeats;
+        fb.s[k].n = sl.n_frames;
+        lb.s[k].feats = sl.d_lfeats;
+    }
+    if (!counters_cleared) HIP_TRY(c, hipMemsetAsync(c->d_ct, 0, sizeof(Counters) * (size_t)c->nb, c->stream));
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DETECT));
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_REFINE)); /* no detection: the resolve-and-partition launches take refinement's place */
+    HIP_TRY(c, launch_frame_count(c->d_pd, fb, c->nb, c->sc, c->ori_given, c->frames_max, c->stream));
+    SYNC_CHK(c, "k_frame_count");
+    HIP_TRY(c, launch_frame_place(c->d_pd, c->bd, fb, c->nb, c->sc, c->ori_given, c->frames_max, c->stream));
+    SYNC_CHK(c, "k_frame_place");
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_ORIENTATION));
+    if (!c->ori_given) {
+        HIP_TRY(c, launch_orientation(c->d_pd, c->bd, c->nb, c->sc, false, (int)c->ohist_cap, c->kp_waves, c->stream));
+        SYNC_CHK(c, "k_orientation");
+    }
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_SCAN));
+    const int n_chunks = std::max((int)(((size_t)c->pd.n_oct * c->sc.max_extrema + scan_chunk() - 1) / scan_chunk()), 1);
+    if (!c->ori_given)
+        HIP_TRY(c, launch_scan(c->d_pd, lb, c->nb, c->sc, false, (int)c->ohist_cap, n_chunks, c->desc_cap, c->stream));
+    else
+        HIP_TRY(c, launch_scan_apply(c->d_pd, lb, c->nb, c->sc, n_chunks, c->desc_cap, c->stream));
+    SYNC_CHK(c, "k_scan_local / k_scan_apply");
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DESCRIPTOR));
+    HIP_TRY(c, launch_descriptors(c->d_pd, c->bd, c->nb, c->sc, c->desc_cap, c->kp_waves, c->stream));
+    SYNC_CHK(c, "descriptor kernel");
+    /* after the descriptor kernel: k_descriptor_grid / _notile read ext + map[d] with the list positions */
+    HIP_TRY(c, launch_frame_out(c->bd, fb, c->nb, c->desc_cap, c->frames_max, c->stream));
+    SYNC_CHK(c, "k_frame_out");
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_COUNT));
+    HIP_TRY(c, hipMemcpyAsync(c->h_ct, c->d_ct, sizeof(Counters) * (size_t)c->nb, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+/* the frames of a describe (popsift_hip_describe_batch); null for an extraction */
+struct DescribeArgs {
+    const popsift_hip_frame* const* frames;
+    const int*                      n_frames;
+    int                             ori_mode;
+};
+
+/* per-slot buffers of a describe, grown on first use (the extraction path allocates none of them) */
+int prepare_frames(popsift_hip_ctx* c, ImageSlot& s)
+{
+    const size_t n = (size_t)c->sc.max_extrema;
+    if (int rc = grow(c, &s.d_frames, &s.frames_cap, n)) return rc;
+    if (int rc = grow(c, &s.d_fcounts, &s.fcounts_cap, (size_t)PS_MAX_OCT * frame_chunks(c->sc.max_extrema))) return rc;
+    if (int rc = grow(c, &s.d_perm, &s.perm_cap, n)) return rc;
+    if (int rc = grow(c, &s.d_inv, &s.inv_cap, n)) return rc;
+    if (int rc = grow(c, &s.d_lfeats, &s.lfeats_cap, n)) return rc;
+    if (!s.h_frames) {
+        HIP_TRY(c, hipHostMalloc((void**)&s.h_frames, n * sizeof(popsift_hip_frame), hipHostMallocDefault));
+        s.h_frames_cap = n;
+    }
+    return 0;
+}
+
 /* where the images of a batch lie: kind = POPSIFT_HIP_IMG_* */
-int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind, int w, int h, int pitch)
+int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind, int w, int h, int pitch,
+                  const DescribeArgs* da = nullptr)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     POPSIFT_RANGE("popsift_hip: submit");
@@ -901,11 +994,26 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
         dpitch = w;
     }
     if (where != 1) aligned4 = (dpitch & 3) == 0; /* hipMalloc'd buffers are aligned */
+    c->describe = da != nullptr;
+    c->ori_given = da && da->ori_mode == POPSIFT_HIP_ORI_GIVEN;
+    c->frames_max = 0;
+    for (int k = 0; k < nb && da; k++) {
+        /* like the images, the caller's frames are copied into pinned memory before this call returns */
+        ImageSlot& s = c->slot[k];
+        if (int rc = prepare_frames(c, s)) return rc;
+        const int nf = da->n_frames[k];
+        s.n_frames = nf;
+        c->frames_max = std::max(c->frames_max, nf);
+        if (nf > 0) {
+            memcpy(s.h_frames, da->frames[k], (size_t)nf * sizeof(popsift_hip_frame));
+            HIP_TRY(c, hipMemcpyAsync(s.d_frames, s.h_frames, (size_t)nf * sizeof(popsift_hip_frame), hipMemcpyHostToDevice, c->stream));
+        }
+    }
     c->blur_events_used = 0;
     HIP_TRY(c, hipEventRecord(c->ev_begin, c->stream));
     if (c->profile == 2) HIP_TRY(c, hipEventRecord(c->ev_stage[POPSIFT_HIP_STAGE_PYRAMID], c->stream));
     if (int rc = enqueue_pyramid(c, is_f32, dpitch, aligned4)) return rc;
-    if (int rc = enqueue_keypoint_stages(c, true)) return rc;
+    if (int rc = da ? enqueue_describe_stages(c, true) : enqueue_keypoint_stages(c, true)) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_end, c->stream));
     c->have_image = true;
     c->finished = false;
@@ -937,7 +1045,7 @@ int finish(popsift_hip_ctx* c)
         }
         const bool desc_short = ori_max > c->desc_cap;
         const bool cand_short = qmax > c->cand_cap / DET_SUBQ;
-        const bool hist_short = (size_t)ext_max > c->ohist_cap;
+        const bool hist_short = (size_t)ext_max > c->ohist_cap && !c->ori_given; /* given angles need no histograms */
         if (!desc_short && !cand_short && !hist_short) {
             fits = true;
             break;
@@ -950,7 +1058,7 @@ int finish(popsift_hip_ctx* c)
             if (int rc = ensure_cand_cap(c, DET_SUBQ * (qmax + qmax / 8 + 64))) return rc;
         if (hist_short)
             if (int rc = ensure_ohist_cap(c, (size_t)ext_max + (size_t)ext_max / 8 + 1024)) return rc;
-        if (int rc = enqueue_keypoint_stages(c)) return rc;
+        if (int rc = c->describe ? enqueue_describe_stages(c) : enqueue_keypoint_stages(c)) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_end, c->stream));
         rerun = true;
     }
@@ -959,7 +1067,7 @@ int finish(popsift_hip_ctx* c)
     if (!fits) return fail(c, POPSIFT_HIP_ERR_DEVICE, "the keypoint buffers still do not fit after 8 grow-and-rerun rounds");
     popsift_hip_report& r = c->rep;
     for (int k = 0; k < c->nb; k++) {
-        c->n_feat[k] = c->h_ct[k].ext_total;
+        c->n_feat[k] = c->describe ? c->slot[k].n_frames : c->h_ct[k].ext_total; /* describe: one record per frame */
         c->n_desc[k] = std::min(c->h_ct[k].ori_total, c->desc_cap);
     }
     /* the report describes image 0 of the batch: per-octave descriptor counts from the octave start offsets the scan
@@ -979,7 +1087,7 @@ int finish(popsift_hip_ctx* c)
         r.ext_ct[o] = h0.ext_ct[o];
         r.ori_ct[o] = h0.ori_ct[o];
     }
-    r.ext_total = c->n_feat[0];
+    r.ext_total = c->h_ct[0].ext_total; /* describe: the valid frames */
     r.ori_total = c->n_desc[0];
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, c->ev_begin, c->ev_end) == hipSuccess) r.ms_device = ms;
@@ -1250,6 +1358,12 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
         if (sl.d_ovf) (void)hipFree(sl.d_ovf);
         if (sl.alt_feats) (void)hipFree(sl.alt_feats);
         if (sl.alt_desc) (void)hipFree(sl.alt_desc);
+        if (sl.d_frames) (void)hipFree(sl.d_frames);
+        if (sl.h_frames) (void)hipHostFree(sl.h_frames);
+        if (sl.d_fcounts) (void)hipFree(sl.d_fcounts);
+        if (sl.d_perm) (void)hipFree(sl.d_perm);
+        if (sl.d_inv) (void)hipFree(sl.d_inv);
+        if (sl.d_lfeats) (void)hipFree(sl.d_lfeats);
     }
     if (c->d_ct) (void)hipFree(c->d_ct);
     if (c->d_pd) (void)hipFree(c->d_pd);
@@ -1317,6 +1431,24 @@ int popsift_hip_submit_batch(popsift_hip_ctx* c, const void* const* imgs, int n,
     return submit_common(c, imgs, n, kind, w, h, pitch);
 }
 
+int popsift_hip_describe_batch(popsift_hip_ctx* c, const void* const* imgs, const popsift_hip_frame* const* frames,
+                               const int* n_frames, int n, int kind, int w, int h, int pitch, int ori_mode)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (n < 1 || n > PS_MAX_BATCH || !n_frames || !frames) return fail(c, POPSIFT_HIP_ERR_INVALID, "bad frame arguments");
+    if (ori_mode != POPSIFT_HIP_ORI_COMPUTE && ori_mode != POPSIFT_HIP_ORI_GIVEN)
+        return fail(c, POPSIFT_HIP_ERR_INVALID, "ori_mode: POPSIFT_HIP_ORI_COMPUTE or POPSIFT_HIP_ORI_GIVEN");
+    for (int k = 0; k < n; k++) {
+        if (n_frames[k] < 0 || (n_frames[k] > 0 && !frames[k])) return fail(c, POPSIFT_HIP_ERR_INVALID, "bad frame list %d", k);
+        /* so that no octave's list can overflow */
+        if (n_frames[k] > c->sc.max_extrema)
+            return fail(c, POPSIFT_HIP_ERR_INVALID, "%d frames for image %d: more than max_extrema (%d)", n_frames[k], k,
+                        c->sc.max_extrema);
+    }
+    const DescribeArgs da{frames, n_frames, ori_mode};
+    return submit_common(c, imgs, n, kind, w, h, pitch, &da);
+}
+
 int popsift_hip_wait_batch(popsift_hip_ctx* c, int* n_images, int* n_features, int* n_descriptors)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
@@ -1358,7 +1490,7 @@ int popsift_hip_wait(popsift_hip_ctx* c, int* n_features, int* n_descriptors)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = finish(c)) return rc;
-    if (n_features) *n_features = c->rep.ext_total;
+    if (n_features) *n_features = c->n_feat[0];
     if (n_descriptors) *n_descriptors = c->rep.ori_total;
     return POPSIFT_HIP_OK;
 }
@@ -1368,7 +1500,7 @@ int popsift_hip_fetch(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t fea
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch");
-    const size_t nf = (size_t)c->rep.ext_total, nd = (size_t)c->rep.ori_total;
+    const size_t nf = (size_t)c->n_feat[0], nd = (size_t)c->rep.ori_total;
     if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
     if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1452,7 +1584,7 @@ int popsift_hip_clone_results(popsift_hip_ctx* c, popsift_hip_devfeatures** out)
     popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
     if (!f) return fail(c, POPSIFT_HIP_ERR_OOM, "out of host memory");
     f->device = c->device;
-    f->n_feat = c->rep.ext_total;
+    f->n_feat = c->n_feat[0];
     f->n_desc = c->rep.ori_total;
     int rc = [&]() -> int {
         /* allocations of at least one element keep the pointers valid for empty results */
@@ -1825,7 +1957,7 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* c)
     if (int rc = drain_copy(c)) return rc;
     c->blur_events_used = 0;
     HIP_TRY(c, hipEventRecord(c->ev_begin, c->stream));
-    if (int rc = enqueue_keypoint_stages(c)) return rc;
+    if (int rc = c->describe ? enqueue_describe_stages(c) : enqueue_keypoint_stages(c)) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_end, c->stream));
     c->finished = false;
     for (ImageSlot& sl : c->slot) sl.moved = false;

@@ -111,6 +111,22 @@ hipError_t launch_scan(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const S
 hipError_t launch_descriptors(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
                               hipStream_t s);
 
+/* k_scan_apply alone, for lists whose Ext records and local partial sums were written elsewhere (k_frame_place) */
+hipError_t launch_scan_apply(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
+                             hipStream_t s);
+
+/* describe.hip: caller-supplied frames (popsift_hip_describe_batch).  n_max: the most frames of an image of the batch.
+ * frame_count + frame_place resolve each frame to (octave, level) and partition the frames stably by octave into the
+ * InitExt lists (ext_ct, perm / inv; with `given` also the Ext records and k_scan_local's partial sums); frame_out, after
+ * the descriptor kernel, moves the feature records to caller order and rewrites the descriptor -> feature map. */
+constexpr int FRAME_CHUNK = 256;
+int        frame_chunks(int n_max);
+hipError_t launch_frame_count(const PyrDesc* d_pd, const FrameBatch& fb, int nb, const SiftConsts& sc, int given, int n_max,
+                              hipStream_t s);
+hipError_t launch_frame_place(const PyrDesc* d_pd, const BatchDesc& bd, const FrameBatch& fb, int nb, const SiftConsts& sc,
+                              int given, int n_max, hipStream_t s);
+hipError_t launch_frame_out(const BatchDesc& bd, const FrameBatch& fb, int nb, int desc_cap, int n_max, hipStream_t s);
+
 /* filter.hip: grid filter between refinement and orientation (s_filtergrid.cu:109-322) */
 bool       filter_supported(int n_oct, int max_extrema, int grid_size);
 size_t     filter_hist_bytes(int grid_size);

@@ -1541,6 +1541,14 @@ hipError_t launch_scan(const PyrDesc* pd, const BatchDesc& bd, int nb, const Sif
     return hipGetLastError();
 }
 
+hipError_t launch_scan_apply(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
+                             hipStream_t s)
+{
+    hipLaunchKernelGGL(k_scan_apply, dim3(std::min(n_chunks, 1024), nb), dim3(256), 0, s, pd, sc, bd,
+                       sc.desc_mode == POPSIFT_HIP_DESC_LOOP ? 1 : 0, desc_cap);
+    return hipGetLastError();
+}
+
 int scan_chunk() { return SCAN_CHUNK; }
 int scan_partials_per_chunk() { return SCAN_SUB; }
 

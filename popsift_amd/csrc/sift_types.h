@@ -158,3 +158,19 @@ struct FilterState {
     int                cell_mode[FILTER_MAX_CELLS]; /* 0 select, 1 keep all, 2 keep none */
     unsigned long long prefix[FILTER_MAX_CELLS];    /* radix select: digits chosen so far */
 };
+
+/* Describe (popsift_hip_describe_batch, describe.hip): what the frame kernels need of an image beyond its Slot.  A table
+ * of its own, passed by value next to BatchDesc to the new kernels only, so that the extraction kernels' argument block
+ * keeps its size. */
+struct FrameSlot {
+    const popsift_hip_frame* frames; /* the caller's frames, device copy                                          */
+    int*                     counts; /* valid frames per (octave, chunk of FRAME_CHUNK frames), octave-major     */
+    int*                     perm;   /* list position (all octaves, ascending) -> frame                          */
+    int*                     inv;    /* frame -> list position, -1: invalid frame                                */
+    popsift_hip_feature*     lfeats; /* k_scan_apply's feature records, in list order                            */
+    int                      n;      /* frames of this image                                                     */
+    int                      pad_;
+};
+struct FrameBatch {
+    FrameSlot s[PS_MAX_BATCH];
+};

@@ -338,6 +338,13 @@ static void convert_features(const popsift_hip_feature* pod, int nf, popsift::Fe
     }
 }
 
+static_assert(sizeof(popsift::Frame) == sizeof(popsift_hip_frame) && offsetof(popsift::Frame, level) == offsetof(popsift_hip_frame, level),
+              "popsift::Frame mirrors popsift_hip_frame");
+static const popsift_hip_frame* frame_ptr(const SiftJob* job)
+{
+    return job->getFrames().empty() ? nullptr : reinterpret_cast<const popsift_hip_frame*>(job->getFrames().data());
+}
+
 /* One worker = one context.  Where the reference's extractDownloadLoop (popsift.cpp:187-213) downloads image i before
  * it looks at image i+1, this loop starts the download (popsift_hip_fetch_begin: copy stream, second result slab) and
  * submits image i+1 first -- its kernels run under the PCIe transfer and under the host-side conversion of image i.
@@ -396,6 +403,8 @@ void PopSift::worker_loop(Worker* me)
                     while ((int)more.size() + 1 < max_batch && !_queue.empty() && _queue.front() != 0 &&
                            _queue.front()->getWidth() == job->getWidth() && _queue.front()->getHeight() == job->getHeight() &&
                            _queue.front()->isFloat() == job->isFloat() && _proc_mode != popsift::Config::MatchingMode &&
+                           _queue.front()->isDescribe() == job->isDescribe() &&
+                           _queue.front()->computesOrientation() == job->computesOrientation() &&
                            _config.getLogMode() != popsift::Config::All) {
                         more.push_back(_queue.front());
                         _queue.pop();
@@ -421,7 +430,19 @@ void PopSift::worker_loop(Worker* me)
             for (size_t k = 0; k < jobs.size(); k++) imgs[k] = jobs[k]->getImageData();
             const int kind = job->isFloat() ? (pinned ? POPSIFT_HIP_IMG_PINNED_F32 : POPSIFT_HIP_IMG_HOST_F32)
                                             : (pinned ? POPSIFT_HIP_IMG_PINNED_U8 : POPSIFT_HIP_IMG_HOST_U8);
-            int rc = popsift_hip_submit_batch(me->ctx, imgs, (int)jobs.size(), kind, job->getWidth(), job->getHeight(), job->getWidth());
+            int rc;
+            if (job->isDescribe()) {
+                const popsift_hip_frame* frs[POPSIFT_HIP_MAX_BATCH];
+                int                      nfr[POPSIFT_HIP_MAX_BATCH];
+                for (size_t k = 0; k < jobs.size(); k++) {
+                    frs[k] = frame_ptr(jobs[k]);
+                    nfr[k] = (int)jobs[k]->getFrames().size();
+                }
+                rc = popsift_hip_describe_batch(me->ctx, imgs, frs, nfr, (int)jobs.size(), kind, job->getWidth(), job->getHeight(),
+                                                job->getWidth(), job->computesOrientation() ? POPSIFT_HIP_ORI_COMPUTE : POPSIFT_HIP_ORI_GIVEN);
+            } else {
+                rc = popsift_hip_submit_batch(me->ctx, imgs, (int)jobs.size(), kind, job->getWidth(), job->getHeight(), job->getWidth());
+            }
             if (rc != POPSIFT_HIP_OK) DIE(string("extraction failed: ") + popsift_hip_last_error(me->ctx));
             complete_pending(); /* the previous jobs' downloads and conversion, under this batch's kernels */
             int n = 0, nfs[POPSIFT_HIP_MAX_BATCH], nds[POPSIFT_HIP_MAX_BATCH];
@@ -450,7 +471,15 @@ void PopSift::worker_loop(Worker* me)
         POPSIFT_RANGE("PopSift job (submit, wait, fetch)");
         int rc;
         /* the job's block stays untouched until the job is deleted, i.e. beyond popsift_hip_wait below */
-        if (job->isFloat())
+        if (job->isDescribe()) {
+            const void*              img = job->getImageData();
+            const popsift_hip_frame* frs = frame_ptr(job);
+            const int                nfr = (int)job->getFrames().size();
+            const int kind = job->isFloat() ? (job->isPinned() ? POPSIFT_HIP_IMG_PINNED_F32 : POPSIFT_HIP_IMG_HOST_F32)
+                                            : (job->isPinned() ? POPSIFT_HIP_IMG_PINNED_U8 : POPSIFT_HIP_IMG_HOST_U8);
+            rc = popsift_hip_describe_batch(me->ctx, &img, &frs, &nfr, 1, kind, job->getWidth(), job->getHeight(), job->getWidth(),
+                                            job->computesOrientation() ? POPSIFT_HIP_ORI_COMPUTE : POPSIFT_HIP_ORI_GIVEN);
+        } else if (job->isFloat())
             rc = (job->isPinned() ? popsift_hip_submit_pinned_f32 : popsift_hip_submit_f32)(
                 me->ctx, (const float*)job->getImageData(), job->getWidth(), job->getHeight(), job->getWidth());
         else
@@ -527,22 +556,37 @@ SiftJob* PopSift::enqueue(int w, int h, const unsigned char* imageData)
 {
     if (_image_mode != ByteImages)
         DIE("Image mode error: cannot load byte images into a PopSift pipeline configured for float images");
-    SiftJob* job = new SiftJob(w, h, imageData);
-    {
-        std::lock_guard<std::mutex> lk(_mtx);
-        if (_stopped) DIE("enqueue() after uninit()");
-        if (!_started) start_workers(w, h);
-        _queue.push(job);
-    }
-    _cv.notify_one();
-    return job;
+    return push(new SiftJob(w, h, imageData), w, h);
 }
 
 SiftJob* PopSift::enqueue(int w, int h, const float* imageData)
 {
     if (_image_mode != FloatImages)
         DIE("Image mode error: cannot load float images into a PopSift pipeline configured for byte images");
+    return push(new SiftJob(w, h, imageData), w, h);
+}
+
+SiftJob* PopSift::enqueue(int w, int h, const unsigned char* imageData, const std::vector<popsift::Frame>& frames,
+                          bool computeOrientation)
+{
+    if (_image_mode != ByteImages)
+        DIE("Image mode error: cannot load byte images into a PopSift pipeline configured for float images");
     SiftJob* job = new SiftJob(w, h, imageData);
+    job->setFrames(frames, computeOrientation);
+    return push(job, w, h);
+}
+
+SiftJob* PopSift::enqueue(int w, int h, const float* imageData, const std::vector<popsift::Frame>& frames, bool computeOrientation)
+{
+    if (_image_mode != FloatImages)
+        DIE("Image mode error: cannot load float images into a PopSift pipeline configured for byte images");
+    SiftJob* job = new SiftJob(w, h, imageData);
+    job->setFrames(frames, computeOrientation);
+    return push(job, w, h);
+}
+
+SiftJob* PopSift::push(SiftJob* job, int w, int h)
+{
     {
         std::lock_guard<std::mutex> lk(_mtx);
         if (_stopped) DIE("enqueue() after uninit()");
