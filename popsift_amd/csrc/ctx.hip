@@ -791,8 +791,9 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
             if (int rc = single(1, 1)) return rc;
     }
     for (int o = 1; o < n_front; o++) {
-        /* per-launch profiling keeps one kernel per event pair */
-        const bool pair = c->profile != 1 && o >= 2 && blur_tile_h(pd.o[o].w, pd.o[o].h) == 32 &&
+        /* per-launch profiling keeps one kernel per event pair; BLUR_PATH = 2 sends every plane-to-plane level through
+         * the march kernels, so no level of it is paired into k_blur_duo */
+        const bool pair = c->profile != 1 && c->blur_tune.path != 2 && o >= 2 && blur_tile_h(pd.o[o].w, pd.o[o].h) == 32 &&
                           blur_tile_h(pd.o[o - 1].w, pd.o[o - 1].h) == 32;
         for (int level = 1; level <= L - 3; level++) {
             if (early1 && o == 1 && level == 1) continue; /* launched behind level L-3 of octave 0 */

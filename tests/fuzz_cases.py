@@ -9,12 +9,18 @@ from popsift_amd.synth import synth
 from util import bits, capped_parity, feature_parity
 
 
-def random_case(rng, case, max_w=700, max_h=500):
+def random_case(rng, case, max_w=700, max_h=500, wide=False):
+    """wide: draw from the whole accepted range -- levels 0 .. 9, sigma 0.4 .. 2, upscale -2 .. 2 -- instead of the
+    window the fixed-seed slices were cut from (levels 2 .. 6, sigma 1 .. 2, upscale -1 .. 1).  Either way the case
+    consumes the same number of draws, so the default stream is what it was before the option existed."""
     w = int(rng.integers(9, max_w))
     h = int(rng.integers(9, max_h))
-    kw = dict(levels=int(rng.integers(2, 7)), sigma=float(np.float32(rng.uniform(1.0, 2.0))),
+    levels = int(rng.integers(0, 10)) if wide else int(rng.integers(2, 7))
+    sigma = float(np.float32(rng.uniform(0.4, 2.0) if wide else rng.uniform(1.0, 2.0)))
+    upscales = [-2.0, -1.0, 0.0, 1.0, 2.0] if wide else [1.0, 1.0, 0.0, -1.0]
+    kw = dict(levels=levels, sigma=sigma,
               sift_mode=int(rng.integers(0, 3)), gauss_mode=int(rng.choice([0, 3])),
-              upscale_factor=float(rng.choice([1.0, 1.0, 0.0, -1.0])), norm_mode=int(rng.integers(0, 2)),
+              upscale_factor=float(rng.choice(upscales)), norm_mode=int(rng.integers(0, 2)),
               norm_multi=int(rng.choice([0, 0, 9])), desc_mode=int(rng.choice([0, 0, 0, 1, 2, 3, 4])),
               edge_limit=float(np.float32(rng.uniform(5, 15))), threshold=float(np.float32(rng.uniform(0.02, 0.08))),
               max_extrema=int(rng.choice([100000, 100000, 300])))

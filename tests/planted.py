@@ -15,7 +15,9 @@ one by one), different at every level.
 
 The lattice spans the detectable area: its first and last rows and columns are the first and last rows and columns the
 detection examines (1 and w - 2, or 5 and w - 6 in OpenCV mode), so orientation windows and descriptor patches there are
-clipped by the plane border.  The levels cycle through the whole search range 1 .. levels.
+clipped by the plane border.  The levels cycle through the whole search range 1 .. levels (`levels` of Planted, the
+params' levels: 3 by default, up to 9); with pin_z the first bump on level 1 is centred at zc = 0.7 and the first on the top
+search level at zc = levels + 0.3, the outermost sub-level centres refinement accepts.
 """
 import numpy as np
 
@@ -78,10 +80,12 @@ def subq_of(w, h, x, y):
 class Planted:
     """dims: [(w, h)] per octave; request: {octave: n} or {octave: (n, rect)}; sites are drawn from the octave's lattice
     (inside rect) by a seeded permutation that puts the four corners and the edges first.  Attributes: dog[o][z],
-    gauss[o][z] (float32 planes), bumps[o] (structured: x, y, z pixel and level, xc, yc, zc centre, sign), counts."""
+    gauss[o][z] (float32 planes), bumps[o] (structured: x, y, z pixel and level, xc, yc, zc centre, sign), counts.
+    levels: DoG search levels (levels + 2 DoG, levels + 3 Gaussian planes per octave); pin_z: see the module's notes."""
 
-    def __init__(self, dims, request, seed=0, sift_mode=0, minima=True):
+    def __init__(self, dims, request, seed=0, sift_mode=0, minima=True, levels=LEVELS, pin_z=False):
         rng = np.random.default_rng(seed)
+        self.levels = levels
         self.dims = list(dims)
         self.counts = [0] * len(self.dims)
         self.bumps, self.dog, self.gauss = [], [], []
@@ -100,14 +104,19 @@ class Planted:
             bt = np.zeros(n, [("x", np.int32), ("y", np.int32), ("z", np.int32), ("xc", np.float64), ("yc", np.float64),
                               ("zc", np.float64), ("sign", np.int32)])
             bt["x"], bt["y"] = pick[:, 0], pick[:, 1]
-            bt["z"] = 1 + (rng.permutation(n) % LEVELS)
+            bt["z"] = 1 + (rng.permutation(n) % levels)
             off = rng.uniform(0.05, 0.3, (n, 3)) * rng.choice([-1.0, 1.0], (n, 3))
+            if pin_z:
+                for z, dz in ((1, -0.3), (levels, 0.3)):
+                    at = np.nonzero(bt["z"] == z)[0]
+                    if len(at):
+                        off[at[0], 2] = dz
             bt["xc"], bt["yc"], bt["zc"] = bt["x"] + off[:, 0], bt["y"] + off[:, 1], bt["z"] + off[:, 2]
             bt["sign"] = rng.choice([-1, 1], n) if minima else 1
             self.bumps.append(bt)
             self.counts[o] = n
-            self.dog.append(dog_planes(w, h, bt))
-            self.gauss.append(gauss_planes(w, h, rng))
+            self.dog.append(dog_planes(w, h, bt, levels + 2))
+            self.gauss.append(gauss_planes(w, h, rng, planes=levels + 3))
 
     @property
     def total(self):
@@ -139,28 +148,28 @@ class Planted:
             raise ValueError("planted for octaves %s, the target has %s" % (self.dims, got))
 
 
-def dog_planes(w, h, bumps):
-    out = np.zeros((DOG_PLANES, h, w), np.float64)
+def dog_planes(w, h, bumps, n_planes=DOG_PLANES):
+    out = np.zeros((n_planes, h, w), np.float64)
     r = int(np.ceil(np.sqrt(A / CURV))) + 1
     for b in bumps:
         x0, x1 = max(b["x"] - r, 0), min(b["x"] + r + 1, w)
         y0, y1 = max(b["y"] - r, 0), min(b["y"] + r + 1, h)
         yy, xx = np.mgrid[y0:y1, x0:x1].astype(np.float64)
         d2 = (xx - b["xc"]) ** 2 + (yy - b["yc"]) ** 2
-        for z in range(DOG_PLANES):
+        for z in range(n_planes):
             v = np.maximum(A - CURV * d2 - ZCURV * (z - b["zc"]) ** 2, 0.0)
             out[z, y0:y1, x0:x1] += b["sign"] * v
     return [p.astype(np.float32) for p in out]
 
 
-def gauss_planes(w, h, rng, terms=5):
+def gauss_planes(w, h, rng, terms=5, planes=GAUSS_PLANES):
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
     out = []
     ramp = rng.uniform(-0.05, 0.05, 2)
     th = rng.uniform(0, 2 * np.pi, terms)
     fr = rng.uniform(0.05, 0.35, terms)
     am = rng.uniform(4.0, 12.0, terms)
-    for z in range(GAUSS_PLANES):
+    for z in range(planes):
         g = 100.0 + ramp[0] * xx + ramp[1] * yy
         for k in range(terms):
             ph = rng.uniform(0, 2 * np.pi)
@@ -170,7 +179,8 @@ def gauss_planes(w, h, rng, terms=5):
 
 
 def params_kw(octaves, **kw):
-    """the params of a planted case: no upscaling (octave 0 is the image), `octaves` octaves, the default levels"""
+    """the params of a planted case: no upscaling (octave 0 is the image), `octaves` octaves, the default levels unless
+    kw names others"""
     d = dict(upscale_factor=0.0, octaves=octaves, levels=LEVELS)
     d.update(kw)
     return d

@@ -50,6 +50,7 @@ ROUND_TRIP = [
     dict(norm_mode=1),
     dict(sift_mode=1), dict(sift_mode=2, desc_mode=4),
     dict(upscale_factor=0.0), dict(upscale_factor=-1.0, desc_mode=2),
+    dict(levels=9), dict(levels=9, sigma=2.0),    # 12 Gaussian planes: level hints and derived lpos up to L - 1 = 11
 ]
 
 

@@ -64,7 +64,12 @@ CASES = [
     ("tiny_17x13", dict(), (17, 13), "u8"),
     ("thin_300x9", dict(), (300, 9), "u8"),
     ("thin_9x300", dict(), (9, 300), "u8"),
+    ("levels7_200x150", dict(levels=7), (200, 150), "u8"),                # L = 10
+    ("levels9_180x140", dict(levels=9), (180, 140), "u8"),                # L = 12, the largest the library takes
+    ("sigma0p5_190x150", dict(sigma=0.5), (190, 150), "u8"),              # abs_o0 level 3 has sigma 0: a one-tap filter
+    ("levels9_sigma0p5_odd_161x117", dict(levels=9, sigma=0.5), (161, 117), "u8"),
 ]
+EDGE_CASES = [c for c in CASES if c[0].startswith(("levels7_", "levels9_", "sigma0p5_"))]
 
 
 @pytest.mark.gpu
@@ -101,6 +106,22 @@ def test_planes_bit_identical_to_restatement(gpu_hip, ref, name, kw, shape, kind
         assert not np.array_equal(d.plane(0, 0, 2), want[0][2])
         d.close()
     ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,kw,shape,kind", EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
+def test_per_level_path_at_the_range_edges(gpu_hip, ref, name, kw, shape, kind):
+    """DIRECT_PATH = 1 (one level-0 launch per level of octave 0) at L = 10 and 12 and at sigma 0.5: the restatement's
+    planes too, and the fused launch's results bit for bit"""
+    img = synth(90 + len(name), *shape)
+    res = []
+    for path in (0, 1):
+        ctx = _ctx(gpu_hip, path=path, **kw).submit(img)
+        ctx.wait()
+        _check_pyramid(ctx, ref, img, ctx.params, "%s DIRECT_PATH %d" % (name, path))
+        res.append(_canon(*ctx.fetch()))
+        ctx.close()
+    assert _same(res[0], res[1]), name
 
 
 @pytest.mark.gpu

@@ -157,10 +157,16 @@ def test_flat_image_gives_valid_empty_result(gpu_hip):
 
 
 def test_gauss_tables_match(oracle_mod, gpu_hip):
-    for kw in (dict(), dict(gauss_mode=3), dict(levels=4, sigma=1.3)):
-        fo, so, go = oracle_mod.Oracle(oracle_mod.default_params(**kw)).gauss_table()
+    # levels 0 and 1 are clamped to 2; sigma 0.5 at upscale +1 takes level 0's sigma through fabsf (0.25 - 1 < 0);
+    # vlfeat-direct's incremental table is the default mode's (its abs_o0 table: tests/test_gpu_gauss_direct.py)
+    for kw in (dict(), dict(gauss_mode=3), dict(levels=4, sigma=1.3), dict(levels=0), dict(levels=1), dict(levels=9),
+               dict(levels=9, gauss_mode=3), dict(sigma=0.5), dict(levels=9, sigma=0.5), dict(upscale_factor=2.0),
+               dict(upscale_factor=-2.0), dict(levels=9, gauss_mode=2)):
+        okw = dict(kw, gauss_mode=0) if kw.get("gauss_mode") == 2 else kw
+        fo, so, go = oracle_mod.Oracle(oracle_mod.default_params(**okw)).gauss_table()
         fh, sh, gh = gpu_hip.Context(gpu_hip.default_params(**kw)).gauss_table()
-        assert np.array_equal(so, sh) and np.array_equal(bits(fo), bits(fh)) and np.array_equal(bits(go), bits(gh))
+        assert np.array_equal(so, sh) and np.array_equal(bits(fo), bits(fh)) and np.array_equal(bits(go), bits(gh)), kw
+        assert len(sh) == max(2, kw.get("levels", 3)) + 3, kw
 
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))

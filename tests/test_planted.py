@@ -1,5 +1,7 @@
 """The contract of tests/planted.py, checked on the oracle without a GPU: the keypoint stages run on the planted planes
 find EXACTLY the requested number of extrema in every octave, each at its planted centre and level."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -8,9 +10,9 @@ import planted as P
 W, H, OCT = 480, 480, 4
 
 
-def _run(O, request, seed=0, sift_mode=0, w=W, h=H, octaves=OCT, **kw):
+def _run(O, request, seed=0, sift_mode=0, w=W, h=H, octaves=OCT, pin_z=False, **kw):
     dims = P.octave_dims(O, w, h, octaves, sift_mode=sift_mode, **kw)
-    pl = P.Planted(dims, request, seed=seed, sift_mode=sift_mode)
+    pl = P.Planted(dims, request, seed=seed, sift_mode=sift_mode, levels=kw.get("levels", P.LEVELS), pin_z=pin_z)
     orc = O.Oracle(O.default_params(**P.params_kw(octaves, sift_mode=sift_mode, **kw)), threads=4)
     orc.run(np.zeros((h, w), np.uint8), keypoints=False)
     pl.load_oracle(orc)
@@ -32,7 +34,7 @@ def _check(pl, orc):
         assert d[np.arange(len(eo)), j].max() <= 2e-3, "octave %d: found and planted centres differ" % o
         assert np.array_equal(eo["lpos"], bt["z"][j]), "octave %d: lpos differs from the planted level" % o
         zc = bt["zc"][j]
-        assert np.allclose(eo["sigma"], 1.6 * 2.0 ** (zc / P.LEVELS), rtol=1e-5), o
+        assert np.allclose(eo["sigma"], 1.6 * 2.0 ** (zc / pl.levels), rtol=1e-5), o
 
 
 @pytest.mark.parametrize("sift_mode", [0, 1, 2])
@@ -96,3 +98,33 @@ def test_request_beyond_the_lattice_is_refused(oracle_mod):
     dims = P.octave_dims(oracle_mod, 64, 64, 2)
     with pytest.raises(ValueError):
         P.Planted(dims, {1: P.capacity(*dims[1]) + 1})
+
+
+def _digest(pl):
+    h = hashlib.sha256()
+    for o in range(len(pl.dims)):
+        h.update(pl.bumps[o].tobytes())
+        for p in pl.dog[o] + pl.gauss[o]:
+            h.update(p.tobytes())
+    return h.hexdigest()[:16]
+
+
+def test_default_levels_generate_the_same_planes():
+    """levels became a parameter of Planted: its default (3) draws and writes exactly what the generator did before,
+    so the planted cases of tests/test_gpu_count_edges.py are the ones they were (digests of bumps and planes)"""
+    assert _digest(P.Planted([(120, 90), (60, 45), (30, 22)], {0: 40, 1: (10, (0, 0, 40, 40)), 2: 3}, seed=5)) == \
+        "40855fb0a8573ebb"
+    assert _digest(P.Planted([(100, 80), (50, 40)], {0: 30, 1: 8}, seed=1, sift_mode=1, minima=False)) == "baa3a62b1667e03d"
+    assert _digest(P.Planted([(100, 80), (50, 40)], {0: 30, 1: 8}, seed=1, sift_mode=1, minima=False, levels=3)) == \
+        "baa3a62b1667e03d"
+
+
+@pytest.mark.parametrize("sift_mode", [0, 1, 2])
+def test_oracle_finds_exactly_the_planted_extrema_at_levels_9(oracle_mod, sift_mode):
+    """nine search levels (12 Gaussian planes): bumps on every level 1 .. 9, centres down to zc = 0.7 and up to 9.3"""
+    pl, orc = _run(oracle_mod, {0: 300, 1: 100, 2: 40, 3: 12}, seed=9 + sift_mode, sift_mode=sift_mode, levels=9, pin_z=True)
+    _check(pl, orc)
+    for o, bt in enumerate(pl.bumps):
+        assert len(pl.dog[o]) == 11 and len(pl.gauss[o]) == 12
+        assert set(bt["z"]) == set(range(1, 10)), o
+        assert np.isclose(bt["zc"].min(), 0.7) and np.isclose(bt["zc"].max(), 9.3), o
