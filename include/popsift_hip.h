@@ -71,7 +71,11 @@ typedef struct popsift_hip_params {
     int32_t filter_sorting;      /* POPSIFT_HIP_FILTER_*                         */
     int32_t store_dog;           /* 0 (default): DoG planes are formed on the fly by their consumers (bit-identical);
                                   * 1: stored as the reference does (s_pyramid_build.cu:74-92), for stage tests     */
-    int32_t reserved[2];
+    int32_t scale_direct;        /* Config::ScalingMode: 0 (default) ScaleDefault, level 0 of octave o >= 1 is every second
+                                  * pixel of level L-3 of octave o-1; 1 ScaleDirect, every octave's level 0 is blurred
+                                  * straight from the input image (popsift_hip_get_gauss_table_dd).  Not Config's enum
+                                  * values: a zeroed struct keeps the default.  ScaleDirect takes Gauss modes 0, 2, 3. */
+    int32_t reserved[1];
 } popsift_hip_params;
 
 /* POD mirror of popsift::Feature (features.h:22-34): the four Descriptor*
@@ -178,6 +182,12 @@ int popsift_hip_get_gauss_table(const popsift_hip_ctx* ctx, float* filter, int* 
  * modes. */
 int popsift_hip_get_gauss_table_abs0(const popsift_hip_ctx* ctx, float* filter, int* span, float* sigma,
                                      int* n_levels);
+/* The dd table of the ScaleDirect scaling mode (params.scale_direct = 1, gauss_filter.cu:217-236): octave o's level 0 is
+ * the input image sampled at octave o's size, blurred horizontally with row o and vertically with row 0 of the
+ * incremental table; row 0 equals that row.  Same layout as above with one row per octave of the context (fixed by
+ * params.octaves or the first image; POPSIFT_HIP_MAX_OCTAVES rows before that); ERR_STATE with scale_direct = 0. */
+int popsift_hip_get_gauss_table_dd(const popsift_hip_ctx* ctx, float* filter, int* span, float* sigma,
+                                   int* n_octaves);
 
 /* Replaces Image::load + Pyramid::step1 + step2 (s_image.cu:71-79,
  * sift_pyramid.cu:226-239): upload one host image and enqueue the whole
@@ -366,13 +376,15 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * plane and the batch); PYR_TAIL = 0: the smallest octaves -- from the first whose plane fits one workgroup's LDS -- are
  * built by one launch (default), 1: by level launches like the others (results do not depend on it); DIRECT_PATH (Gauss
  * mode vlfeat-direct only) = 0: octave 0's levels by one fused launch (default), 1: by one level-0 launch per level
- * (results do not depend on it); DESC_CAP = initial capacity of the descriptor buffer, in descriptors (0 = the default,
+ * (results do not depend on it); SCALE_PATH (ScaleDirect only) = 0: level 0 of every octave by one launch and each
+ * level of every octave by one launch (default), 1: one level-0 launch per octave and the default mode's level launches
+ * per octave (results do not depend on it); DESC_CAP = initial capacity of the descriptor buffer, in descriptors (0 = the default,
  * 2 * max_extrema: small values exercise the grow-and-rerun path of popsift_hip_wait for descriptors). */
 enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_HIP_DEBUG_OHIST_CAP = 3,
        POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, POPSIFT_HIP_DEBUG_PYR_ORDER = 6,
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
        POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
-       POPSIFT_HIP_DEBUG_DESC_CAP = 12 };
+       POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

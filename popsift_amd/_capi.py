@@ -24,6 +24,7 @@ GAUSS_VLFEAT_COMPUTE, GAUSS_VLFEAT_RELATIVE, GAUSS_VLFEAT_RELATIVE_ALL = 0, 1, 2
 GAUSS_OPENCV_COMPUTE, GAUSS_FIXED9, GAUSS_FIXED15 = 3, 4, 5
 DESC_LOOP, DESC_ILOOP, DESC_GRID, DESC_IGRID, DESC_NOTILE = 0, 1, 2, 3, 4
 NORM_ROOTSIFT, NORM_CLASSIC = 0, 1
+SCALE_DEFAULT, SCALE_DIRECT = 0, 1  # params.scale_direct (not Config::ScalingMode's enum values)
 
 
 class Params(C.Structure):
@@ -35,7 +36,7 @@ class Params(C.Structure):
         ("norm_mode", C.c_int32), ("norm_multi", C.c_int32), ("max_extrema", C.c_int32),
         ("assume_initial_blur", C.c_int32), ("initial_blur", C.c_float),
         ("filter_grid_size", C.c_int32), ("filter_max_extrema", C.c_int32), ("filter_sorting", C.c_int32),
-        ("store_dog", C.c_int32), ("reserved", C.c_int32 * 2),
+        ("store_dog", C.c_int32), ("scale_direct", C.c_int32), ("reserved", C.c_int32 * 1),
     ]
 
 
@@ -96,6 +97,7 @@ SYMBOLS = [
     ("popsift_hip_ctx_destroy", C.c_int, [_vp]),
     ("popsift_hip_get_gauss_table", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
     ("popsift_hip_get_gauss_table_abs0", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
+    ("popsift_hip_get_gauss_table_dd", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
     ("popsift_hip_submit_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_f32", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_dev_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
@@ -138,6 +140,7 @@ MATCH_AUTO, MATCH_EXACT, MATCH_SCREEN = 0, 1, 2
 STAGES = ("pyramid", "detect", "refine", "orientation", "scan", "descriptor")
 DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_PYR_ORDER, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 6, 7
 DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL, DEBUG_DIRECT_PATH, DEBUG_DESC_CAP = 8, 9, 10, 11, 12
+DEBUG_SCALE_PATH = 13
 MAX_BATCH = 16
 IMG_HOST_U8, IMG_HOST_F32, IMG_DEV_U8, IMG_DEV_F32, IMG_PINNED_U8, IMG_PINNED_F32 = range(6)
 
@@ -331,10 +334,14 @@ class Context:
         if rc != OK:
             raise PopsiftHipError(rc, where, lib().popsift_hip_last_error(self._h).decode())
 
-    def gauss_table(self, abs0=False):
+    def gauss_table(self, abs0=False, dd=False):
         """(filter[L, 32], span[L], sigma[L]): the incremental table, or with abs0=True the abs_o0 table of the
-        vlfeat-direct Gauss mode (octave 0's levels straight from the input image)"""
-        get = lib().popsift_hip_get_gauss_table_abs0 if abs0 else lib().popsift_hip_get_gauss_table
+        vlfeat-direct Gauss mode (octave 0's levels straight from the input image), or with dd=True the dd table of the
+        ScaleDirect scaling mode (one row per octave: each octave's level 0 straight from the input image)"""
+        if abs0 and dd:
+            raise ValueError("abs0 or dd, not both")
+        get = (lib().popsift_hip_get_gauss_table_abs0 if abs0 else
+               lib().popsift_hip_get_gauss_table_dd if dd else lib().popsift_hip_get_gauss_table)
         n = C.c_int()
         self._chk(get(self._h, None, None, None, C.byref(n)), "get_gauss_table")
         f = np.zeros((n.value, 32), np.float32)

@@ -43,6 +43,13 @@ struct HostTables {
     float sigma[POPSIFT_HIP_MAX_LEVELS];
 };
 
+/* the dd table of the ScaleDirect scaling mode: row o blurs octave o's level 0 straight from the input image */
+struct DdTables {
+    float filter[POPSIFT_HIP_MAX_OCTAVES * PS_GA];
+    int   span[POPSIFT_HIP_MAX_OCTAVES];
+    float sigma[POPSIFT_HIP_MAX_OCTAVES];
+};
+
 struct EventPair {
     hipEvent_t a, b;
     double     bytes;
@@ -110,6 +117,9 @@ struct popsift_hip_ctx {
     HostTables         abs0{};           /* vlfeat-direct (gauss_mode 2): abs_o0, octave 0's levels from the input image */
     float*             d_abs0 = nullptr; /* abs0.filter on the device (the fused kernel's taps), gauss_mode 2 only */
     int                direct_path = 0;  /* DIRECT_PATH debug switch: 0 fused octave-0 kernel, 1 one level-0 launch per level */
+    DdTables           dd{};             /* ScaleDirect (params.scale_direct = 1): dd, every octave's level 0 from the input */
+    float*             d_dd = nullptr;   /* dd.filter on the device (the level-0 launch's horizontal taps), ScaleDirect only */
+    int                scale_path = 0;   /* SCALE_PATH debug switch: 0 all-octave launches, 1 per-octave launches */
     SiftConsts         sc{};
     hipStream_t        stream = nullptr;
     hipEvent_t         ev_begin = nullptr, ev_end = nullptr;
@@ -213,14 +223,14 @@ int span_for(int gauss_mode, float sigma)
     return std::min<int>(ceilf(4.0f * sigma) + 1, PS_GA - 1);
 }
 
-/* GaussTable::computeBlurTable (gauss_filter.cu:340-372): spans and normalised half filters of t.sigma */
-void compute_filters(HostTables& t, int gauss_mode)
+/* GaussTable::computeBlurTable (gauss_filter.cu:340-372): spans and normalised half filters of the n rows of sigma */
+void compute_filter_rows(float* filter, int* span, const float* sigma, int n, int gauss_mode)
 {
-    for (int level = 0; level < POPSIFT_HIP_MAX_LEVELS; level++) {
-        t.span[level] = std::min(span_for(gauss_mode, t.sigma[level]), PS_GA - 1);
-        const float sig = t.sigma[level];
-        const int   spn = t.span[level];
-        float*      f = &t.filter[level * PS_GA];
+    for (int level = 0; level < n; level++) {
+        span[level] = std::min(span_for(gauss_mode, sigma[level]), PS_GA - 1);
+        const float sig = sigma[level];
+        const int   spn = span[level];
+        float*      f = &filter[level * PS_GA];
         double      sum = 1.0;
         f[0] = 1.0f;
         for (int x = 1; x < spn; x++) {
@@ -232,6 +242,8 @@ void compute_filters(HostTables& t, int gauss_mode)
         for (int x = spn; x < PS_GA; x++) f[x] = 0.0f;
     }
 }
+
+void compute_filters(HostTables& t, int gauss_mode) { compute_filter_rows(t.filter, t.span, t.sigma, POPSIFT_HIP_MAX_LEVELS, gauss_mode); }
 
 /* init_filter (inc table; dd[0] is identical to inc[0]) gauss_filter.cu:163-181,340-372
  * and init_constants sift_constants.cu:22-31 */
@@ -262,6 +274,17 @@ void init_tables(popsift_hip_ctx* c)
         }
         compute_filters(a0, p.gauss_mode);
     }
+    /* dd (gauss_filter.cu:217-236): octave o's level 0 blurred straight from the input image; the blur is sigma0 * 2^o
+     * less the assumed blur of the input, in octave-o pixels.  dd.sigma[0] equals tab.sigma[0], so octave 0 is the
+     * default mode's octave 0. */
+    DdTables& dd = c->dd;
+    memset(&dd, 0, sizeof(dd));
+    for (int oct = 0; oct < POPSIFT_HIP_MAX_OCTAVES; oct++) {
+        const float oct_sigma = ldexpf(sigma0, oct);
+        const float b = sqrtf(fabsf(oct_sigma * oct_sigma - initial_blur * initial_blur));
+        dd.sigma[oct] = ldexpf(b, -oct);
+    }
+    compute_filter_rows(dd.filter, dd.span, dd.sigma, POPSIFT_HIP_MAX_OCTAVES, p.gauss_mode);
     SiftConsts& sc = c->sc;
     sc.sigma0 = sigma0;
     sc.sigma_k = powf(2.0f, 1.0f / levels);
@@ -700,6 +723,87 @@ int enqueue_direct_octave0(popsift_hip_ctx* c, int is_f32, int pitch, bool align
 }
 
 /*
+ * The ScaleDirect scaling mode (Pyramid::build_pyramid, s_pyramid_build.cu:499-516), taken before the vlfeat-direct
+ * branch, so also for Gauss mode 2: octave o's level 0 is the input image sampled at octave o's size, blurred
+ * horizontally with dd[o] and vertically with inc[0]; levels 1 .. L-1 are incremental as in the default mode; no
+ * octave's level 0 comes from the octave before.  The octaves are independent, so SCALE_PATH 0 builds the pyramid in
+ * L launches for the whole batch: level 0 of every octave (k_pyr_level0_octaves, which also clears the counters), then
+ * one launch per level l covering every octave (k_blur_octaves).  SCALE_PATH 1, the yardstick: level 0 of each octave
+ * by a launch of its own, then each octave's levels by the default mode's level launches, without next0, duo or tail.
+ */
+int enqueue_scale_direct(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
+{
+    const PyrDesc& pd = c->pd;
+    const int      L = pd.L;
+    const int      zero_words = (int)(sizeof(Counters) / sizeof(int));
+    const double   in_bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1);
+    Taps           vt;
+    memcpy(vt.g, &c->tab.filter[0], sizeof(vt.g)); /* inc[0]: every octave's vertical pass of level 0 */
+    int halo0 = c->tab.span[0] - 1;
+    for (int o = 0; o < pd.n_oct; o++) halo0 = std::max(halo0, c->dd.span[o] - 1);
+    /* level 0: the input image and octave 0's sampling */
+    BlurArgs a0{};
+    a0.src_off = 0;
+    a0.dog_off = -1;
+    a0.next0_off = -1;
+    a0.in_w = c->in_w;
+    a0.in_h = c->in_h;
+    a0.in_pitch = pitch;
+    a0.shift = input_shift(c);
+    const OctDesc& od0 = pd.o[0];
+    a0.fast2x = (c->p.upscale_factor == 1.0f && a0.shift == 1.0f && od0.w == 2 * c->in_w && od0.h == 2 * c->in_h) ? 1 : 0;
+    if (a0.fast2x && !is_f32 && aligned4) a0.fast2x = 2;
+    a0.zero_words = zero_words;
+    double px_all = 0.0;
+    for (int o = 0; o < pd.n_oct; o++) px_all += (double)pd.o[o].w * pd.o[o].h;
+    const double lvl_bpp = pd.dog_fly ? 8.0 : 12.0; /* read plane l-1, write plane l (and DoG l-1) */
+    if (c->scale_path == 0) {
+        if (int rc = timed_launch(c, in_bytes + 4.0 * px_all, "k_pyr_level0_octaves", [&] {
+                return launch_pyr_level0_octaves(a0, vt, c->d_dd, c->d_pd, pd, c->bd, c->nb, halo0, is_f32, c->stream);
+            }))
+            return rc;
+        for (int l = 1; l < L; l++) {
+            BlurArgs a{};
+            memcpy(a.taps.g, &c->tab.filter[l * PS_GA], sizeof(a.taps.g));
+            const int halo = c->tab.span[l] - 1;
+            if (int rc = timed_launch(c, lvl_bpp * px_all, "k_blur_octaves", [&] {
+                    return launch_blur_octaves(a, l, c->d_pd, pd, c->bd, c->nb, halo, c->stream);
+                }))
+                return rc;
+        }
+        return 0;
+    }
+    for (int o = 0; o < pd.n_oct; o++) {
+        const OctDesc& od = pd.o[o];
+        BlurArgs       a = a0;
+        a.w = od.w;
+        a.h = od.h;
+        a.pitch = od.pitch;
+        a.tiles_x = (od.w + blur_tile_w() - 1) / blur_tile_w();
+        a.tiles_y = (od.h + scale_tile_h() - 1) / scale_tile_h();
+        a.dst_off = od.data_off;
+        memcpy(a.taps.g, &c->dd.filter[o * PS_GA], sizeof(a.taps.g));
+        if (o > 0) {
+            a.shift = 0.5f; /* s_pyramid_build.cu:109-114: octave 0's shift only */
+            a.fast2x = 0;
+            a.zero_words = 0;
+        }
+        const int halo = std::max(c->tab.span[0], c->dd.span[o]) - 1;
+        if (int rc = timed_launch(c, in_bytes + 4.0 * od.w * od.h, "k_blur_tile_sep",
+                                  [&] { return launch_blur_level0_sep(a, vt, c->bd, c->nb, halo, is_f32, c->stream); }))
+            return rc;
+    }
+    for (int o = 0; o < pd.n_oct; o++)
+        for (int l = 1; l < L; l++) {
+            BlurArgs a = level_args(c, o, l);
+            a.next0_off = -1;
+            if (int rc = blur_launch(c, a, 0, c->tab.span[l], blur_tile_h(pd.o[o].w, pd.o[o].h), lvl_bpp * pd.o[o].w * pd.o[o].h))
+                return rc;
+        }
+    return 0;
+}
+
+/*
  * Pyramid::build_pyramid default branch (s_pyramid_build.cu:549-588), one stream, every launch for all images of the
  * batch (gridDim.y).  Launch order:
  *   octave 0: level 0 (from the input image), levels 1 .. L-1;
@@ -711,6 +815,7 @@ int enqueue_direct_octave0(popsift_hip_ctx* c, int is_f32, int pitch, bool align
 int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
 {
     POPSIFT_RANGE("popsift_hip: pyramid");
+    if (c->p.scale_direct) return enqueue_scale_direct(c, is_f32, pitch, aligned4);
     const PyrDesc& pd = c->pd;
     const int      L = pd.L;
     auto single = [&](int o, int level) -> int {
@@ -1282,6 +1387,7 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
     if (p->filter_max_extrema > 0 &&
         (p->filter_grid_size < 1 || p->filter_grid_size > 64 || p->filter_sorting < 0 || p->filter_sorting > 2))
         return POPSIFT_HIP_ERR_INVALID;
+    if (p->scale_direct != 0 && p->scale_direct != 1) return POPSIFT_HIP_ERR_INVALID;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
     if (device < 0 || device >= n) return POPSIFT_HIP_ERR_INVALID;
@@ -1314,6 +1420,10 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
             const size_t bytes = sizeof(float) * (size_t)c->L * PS_GA;
             HIP_TRY(c, hipMalloc((void**)&c->d_abs0, bytes));
             HIP_TRY(c, hipMemcpy(c->d_abs0, c->abs0.filter, bytes, hipMemcpyHostToDevice));
+        }
+        if (c->p.scale_direct) {
+            HIP_TRY(c, hipMalloc((void**)&c->d_dd, sizeof(c->dd.filter)));
+            HIP_TRY(c, hipMemcpy(c->d_dd, c->dd.filter, sizeof(c->dd.filter), hipMemcpyHostToDevice));
         }
         return 0;
     }();
@@ -1369,6 +1479,7 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
     if (c->d_ct) (void)hipFree(c->d_ct);
     if (c->d_pd) (void)hipFree(c->d_pd);
     if (c->d_abs0) (void)hipFree(c->d_abs0);
+    if (c->d_dd) (void)hipFree(c->d_dd);
     if (c->h_pd) (void)hipHostFree(c->h_pd);
     if (c->h_ct) (void)hipHostFree(c->h_ct);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1396,6 +1507,20 @@ int popsift_hip_get_gauss_table_abs0(const popsift_hip_ctx* c, float* filter, in
     if (span) memcpy(span, c->abs0.span, sizeof(int) * (size_t)c->L);
     if (sigma) memcpy(sigma, c->abs0.sigma, sizeof(float) * (size_t)c->L);
     if (n_levels) *n_levels = c->L;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_get_gauss_table_dd(const popsift_hip_ctx* c, float* filter, int* span, float* sigma, int* n_octaves)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (!c->p.scale_direct)
+        return fail(const_cast<popsift_hip_ctx*>(c), POPSIFT_HIP_ERR_STATE, "the dd table exists in the ScaleDirect scaling mode only");
+    /* the octaves of the context: fixed by params.octaves or by the first image; all MAX_OCTAVES rows before that */
+    const int n = c->frozen_octaves > 0 ? std::min(c->frozen_octaves, (int)POPSIFT_HIP_MAX_OCTAVES) : POPSIFT_HIP_MAX_OCTAVES;
+    if (filter) memcpy(filter, c->dd.filter, sizeof(float) * (size_t)n * PS_GA);
+    if (span) memcpy(span, c->dd.span, sizeof(int) * (size_t)n);
+    if (sigma) memcpy(sigma, c->dd.sigma, sizeof(float) * (size_t)n);
+    if (n_octaves) *n_octaves = n;
     return POPSIFT_HIP_OK;
 }
 
@@ -1942,6 +2067,10 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
     case POPSIFT_HIP_DEBUG_DIRECT_PATH:
         if (value < 0 || value > 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "DIRECT_PATH: 0 or 1");
         c->direct_path = value;
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_SCALE_PATH:
+        if (value < 0 || value > 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "SCALE_PATH: 0 or 1");
+        c->scale_path = value;
         return POPSIFT_HIP_OK;
     }
     return fail(c, POPSIFT_HIP_ERR_INVALID, "unknown debug switch %d", what);

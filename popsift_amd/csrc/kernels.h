@@ -92,6 +92,19 @@ hipError_t launch_pick_every_second(int64_t src_off, int w, int h, int pitch, in
 hipError_t launch_dog_batch(int64_t lower_off, int64_t upper_off, int64_t dog_off, int64_t n, const BatchDesc& bd, int nb,
                             hipStream_t s);
 
+/* pyramid.hip, the ScaleDirect scaling mode (every octave's level 0 straight from the input image): */
+/* level 0 of every octave of the batch in one launch, horizontal taps dd[o] (d_dd: PS_MAX_OCT x PS_GA floats of the
+ * context), vertical taps vt (inc[0]); base: the input image, octave 0's shift / fast2x, zero_words, taps ignored */
+hipError_t launch_pyr_level0_octaves(const BlurArgs& base, const Taps& vt, const float* d_dd, const PyrDesc* d_pd,
+                                     const PyrDesc& pd, const BatchDesc& bd, int nb, int halo, int is_f32, hipStream_t s);
+/* level `level` >= 1 of every octave of the batch in one launch (base: the taps inc[level]; DoG when stored) */
+hipError_t launch_blur_octaves(const BlurArgs& base, int level, const PyrDesc* d_pd, const PyrDesc& pd, const BatchDesc& bd,
+                               int nb, int halo, hipStream_t s);
+/* level 0 of one octave with separate vertical taps (the yardstick path, popsift_hip_debug_set SCALE_PATH 1) */
+hipError_t launch_blur_level0_sep(const BlurArgs& a, const Taps& vt, const BatchDesc& bd, int nb, int halo, int is_f32,
+                                  hipStream_t s);
+int        scale_tile_h(); /* rows of the tiles of the three launches above */
+
 /* extrema.hip */
 hipError_t launch_dog_plane(float* dog, const float* upper, const float* lower, size_t n, hipStream_t s); /* debug / test downloads */
 int        extrema_units(int w, int h); /* wave-sized work units of the detection kernel */

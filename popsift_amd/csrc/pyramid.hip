@@ -86,8 +86,10 @@ constexpr int blur_lds_floats()
  * and take as long as the instruction stream of ONE lane: the staged rows of the horizontal pass are dealt evenly to
  * all NT / 32 half-waves and each block's four output rows of the vertical pass to LP lanes, so a lane executes about
  * 1 / LP of the instructions (the values and their order per output do not change). */
-template <int HALO, int MODE, int TH, int NT, int LP = 1>
-__device__ __forceinline__ void blur_tile_body(const BlurArgs& a, const BatchDesc& bd, int block, float* __restrict__ s_t)
+/* SEPV (ScaleDirect level 0 only): the vertical pass takes the taps `vt`, the horizontal pass those of `a` */
+template <int HALO, int MODE, int TH, int NT, int LP = 1, bool SEPV = false>
+__device__ __forceinline__ void blur_tile_body(const BlurArgs& a, const BatchDesc& bd, int block, float* __restrict__ s_t,
+                                               const Taps& vt = Taps{})
 {
     /* this image's planes (the slot of blockIdx.y) */
     float* const       arena = bd.s[blockIdx.y].arena;
@@ -468,14 +470,16 @@ __device__ __forceinline__ void blur_tile_body(const BlurArgs& a, const BatchDes
                 v2f alo = {0.0f, 0.0f}, ahi = {0.0f, 0.0f};
 #pragma unroll
                 for (int k = HALO; k > 0; k--) {
-                    const v2f gk = {a.taps.g[k], a.taps.g[k]};
+                    const float gv = SEPV ? vt.g[k] : a.taps.g[k];
+                    const v2f   gk = {gv, gv};
                     alo = __builtin_elementwise_fma(win[cpos - k].lo, gk, alo);
                     ahi = __builtin_elementwise_fma(win[cpos - k].hi, gk, ahi);
                     alo = __builtin_elementwise_fma(win[cpos + k].lo, gk, alo);
                     ahi = __builtin_elementwise_fma(win[cpos + k].hi, gk, ahi);
                 }
                 {
-                    const v2f g0 = {a.taps.g[0], a.taps.g[0]};
+                    const float gv = SEPV ? vt.g[0] : a.taps.g[0];
+                    const v2f   g0 = {gv, gv};
                     alo = __builtin_elementwise_fma(win[cpos].lo, g0, alo);
                     ahi = __builtin_elementwise_fma(win[cpos].hi, g0, ahi);
                 }
@@ -546,6 +550,112 @@ __global__ __launch_bounds__(256 * LP) void k_blur_small(BlurArgs a, BatchDesc b
 {
     __shared__ __attribute__((aligned(16))) float s_t[blur_lds_floats<HALO, 32>()];
     blur_tile_body<HALO, 0, 32, 256 * LP, LP>(a, bd, blockIdx.x, s_t);
+}
+
+/*
+ * ScaleDirect (Pyramid::build_pyramid's ScaleDirect branch, s_pyramid_build.cu:499-516): every octave's level 0 comes
+ * from the input image, so the octaves do not depend on one another and one launch can cover a level of ALL of them.
+ * Both kernels below walk a flat table of 128 x 32 tiles over the octaves of the PyrDesc, octave 0 (the largest)
+ * first; the octave geometry is read from the context's device copy of the PyrDesc and the level-0 taps from its dd
+ * table, through the constant address space (uniform addresses: s_load, the values sit in SGPRs).
+ */
+typedef const __attribute__((address_space(4))) PyrDesc* cpd_t;
+constexpr int SD_TH = 32, SD_NT = 256;
+
+/* the octave of workgroup `block` and its first workgroup */
+__device__ __forceinline__ int sd_octave(cpd_t pd, int n_oct, int block, int& begin)
+{
+    int o = 0, b = 0;
+    for (; o < n_oct - 1; o++) {
+        const int tiles = ((pd->o[o].w + TW - 1) / TW) * ((pd->o[o].h + SD_TH - 1) / SD_TH);
+        if (block < b + tiles) break;
+        b += tiles;
+    }
+    begin = b;
+    return o;
+}
+
+/* the geometry of octave o into a; returns its plane offsets (data_off, dog_off, plane_stride) */
+struct SdOct {
+    int64_t data_off, dog_off, plane_stride;
+};
+__device__ __forceinline__ SdOct sd_geometry(BlurArgs& a, cpd_t pd, int o)
+{
+    a.w = pd->o[o].w;
+    a.h = pd->o[o].h;
+    a.pitch = pd->o[o].pitch;
+    a.tiles_x = (a.w + TW - 1) / TW;
+    a.tiles_y = (a.h + SD_TH - 1) / SD_TH;
+    return SdOct{pd->o[o].data_off, pd->o[o].dog_off, pd->o[o].plane_stride};
+}
+
+/*
+ * Level 0 of every octave of every image of the batch, one launch.  Octave o samples the input bilinearly at
+ * ((X + shift) / w_o, (Y + shift) / h_o) of its own size (normalizedSource::horiz, s_pyramid_build_ra.cu:17-55), blurs
+ * horizontally with dd[o] (outermost tap first, centre last, x 255) and vertically with inc[0] (absoluteSource::vert,
+ * s_pyramid_build_aa.cu:54-91; `vt`).  shift and the exact-2x paths (fast2x) are octave 0's; the other octaves take
+ * shift 0.5 (s_pyramid_build.cu:109-114).  Octaves coarser than the input touch more source texels per tile than the
+ * staging buffer holds and take the gather path of the level-0 body.  The last workgroup clears the slots' Counters.
+ */
+template <int HALO, int MODE>
+__global__ __launch_bounds__(SD_NT) void k_pyr_level0_octaves(BlurArgs base, Taps vt, const float* dd, const PyrDesc* pd,
+                                                              int n_oct, BatchDesc bd)
+{
+    __shared__ __attribute__((aligned(16))) float s_t[blur_lds_floats<HALO, SD_TH>()];
+    if (base.zero_words > 0 && blockIdx.x == gridDim.x - 1) {
+        int* zero = (int*)bd.s[blockIdx.y].ct;
+        for (int i = threadIdx.x; i < base.zero_words; i += SD_NT) zero[i] = 0;
+    }
+    const cpd_t cpd = (cpd_t)pd;
+    int         begin;
+    const int   o = sd_octave(cpd, n_oct, blockIdx.x, begin);
+    BlurArgs    a = base;
+    a.dst_off = sd_geometry(a, cpd, o).data_off;
+    if (o > 0) {
+        a.shift = 0.5f;
+        a.fast2x = 0;
+    }
+    const __attribute__((address_space(4))) float* g = (const __attribute__((address_space(4))) float*)(dd + o * PS_GA);
+#pragma unroll
+    for (int k = 0; k < PS_GA; k++) a.taps.g[k] = g[k];
+    blur_tile_body<HALO, MODE, SD_TH, SD_NT, 1, true>(a, bd, blockIdx.x - begin, s_t, vt);
+}
+
+/* Level `level` >= 1 of the octaves [0, n_oct) of every image, one launch: plane l-1 -> plane l (+ DoG l-1 when the
+ * DoG planes are stored), taps inc[level] (base.taps), no next octave's level 0 */
+template <int HALO>
+__global__ __launch_bounds__(SD_NT) void k_blur_octaves(BlurArgs base, int level, const PyrDesc* pd, int n_oct, BatchDesc bd)
+{
+    __shared__ __attribute__((aligned(16))) float s_t[blur_lds_floats<HALO, SD_TH>()];
+    const cpd_t cpd = (cpd_t)pd;
+    int         begin;
+    const int   o = sd_octave(cpd, n_oct, blockIdx.x, begin);
+    BlurArgs    a = base;
+    const SdOct od = sd_geometry(a, cpd, o);
+    a.src_off = od.data_off + (int64_t)(level - 1) * od.plane_stride;
+    a.dst_off = od.data_off + (int64_t)level * od.plane_stride;
+    a.dog_off = cpd->dog_fly ? -1 : od.dog_off + (int64_t)(level - 1) * od.plane_stride;
+    a.next0_off = -1;
+    blur_tile_body<HALO, 0, SD_TH, SD_NT>(a, bd, blockIdx.x - begin, s_t);
+}
+
+/* level 0 of ONE octave with separate vertical taps (the ScaleDirect yardstick path, SCALE_PATH 1) */
+template <int HALO, int MODE>
+__global__ __launch_bounds__(SD_NT) void k_blur_tile_sep(BlurArgs a, Taps vt, BatchDesc bd)
+{
+    __shared__ __attribute__((aligned(16))) float s_t[blur_lds_floats<HALO, SD_TH>()];
+    if (a.zero_words > 0 && blockIdx.x == gridDim.x - 1) {
+        int* zero = (int*)bd.s[blockIdx.y].ct;
+        for (int i = threadIdx.x; i < a.zero_words; i += SD_NT) zero[i] = 0;
+    }
+    blur_tile_body<HALO, MODE, SD_TH, SD_NT, 1, true>(a, bd, blockIdx.x, s_t, vt);
+}
+
+int sd_tiles(const PyrDesc& pd, int n_oct)
+{
+    int t = 0;
+    for (int o = 0; o < n_oct; o++) t += ((pd.o[o].w + TW - 1) / TW) * ((pd.o[o].h + SD_TH - 1) / SD_TH);
+    return t;
 }
 
 /* get_by_2_pick_every_second (s_pyramid_build.cu:50-71) */
@@ -713,6 +823,86 @@ hipError_t launch_blur(const BlurArgs& a, const BatchDesc& bd, int nb, int mode,
         case 2: return launch_blur_mode<2, 32, 256>(a, bd, nb, halo, s);
         }
     }
+    return hipErrorInvalidValue;
+}
+
+
+int scale_tile_h() { return SD_TH; }
+
+hipError_t launch_pyr_level0_octaves(const BlurArgs& base, const Taps& vt, const float* d_dd, const PyrDesc* d_pd,
+                                     const PyrDesc& pd, const BatchDesc& bd, int nb, int halo, int is_f32, hipStream_t s)
+{
+    if (!d_dd || !d_pd || pd.n_oct < 1 || pd.n_oct > PS_MAX_OCT) return hipErrorInvalidValue;
+    const dim3 grid(sd_tiles(pd, pd.n_oct), nb), block(SD_NT);
+#define PS_CASE(H)                                                                                                  \
+    if (halo <= H) {                                                                                                \
+        if (is_f32)                                                                                                 \
+            hipLaunchKernelGGL((k_pyr_level0_octaves<H, 2>), grid, block, 0, s, base, vt, d_dd, d_pd, pd.n_oct, bd); \
+        else                                                                                                        \
+            hipLaunchKernelGGL((k_pyr_level0_octaves<H, 1>), grid, block, 0, s, base, vt, d_dd, d_pd, pd.n_oct, bd); \
+        return hipGetLastError();                                                                                   \
+    }
+    if (halo < 0) return hipErrorInvalidValue;
+    PS_CASE(4)
+    PS_CASE(5)
+    PS_CASE(6)
+    PS_CASE(7)
+    PS_CASE(8)
+    PS_CASE(10)
+    PS_CASE(13)
+    PS_CASE(16)
+    PS_CASE(22)
+    PS_CASE(30)
+#undef PS_CASE
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_blur_octaves(const BlurArgs& base, int level, const PyrDesc* d_pd, const PyrDesc& pd, const BatchDesc& bd,
+                               int nb, int halo, hipStream_t s)
+{
+    if (!d_pd || pd.n_oct < 1 || pd.n_oct > PS_MAX_OCT || level < 1 || level >= pd.L) return hipErrorInvalidValue;
+    const dim3 grid(sd_tiles(pd, pd.n_oct), nb), block(SD_NT);
+#define PS_CASE(H)                                                                              \
+    if (halo <= H) {                                                                            \
+        hipLaunchKernelGGL((k_blur_octaves<H>), grid, block, 0, s, base, level, d_pd, pd.n_oct, bd); \
+        return hipGetLastError();                                                               \
+    }
+    if (halo < 0) return hipErrorInvalidValue;
+    PS_CASE(4)
+    PS_CASE(5)
+    PS_CASE(6)
+    PS_CASE(7)
+    PS_CASE(8)
+    PS_CASE(10)
+    PS_CASE(13)
+    PS_CASE(16)
+    PS_CASE(22)
+    PS_CASE(30)
+#undef PS_CASE
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_blur_level0_sep(const BlurArgs& a, const Taps& vt, const BatchDesc& bd, int nb, int halo, int is_f32,
+                                  hipStream_t s)
+{
+    const dim3 grid(a.tiles_x * a.tiles_y, nb), block(SD_NT);
+#define PS_CASE(H)                                                                         \
+    if (halo <= H) {                                                                       \
+        if (is_f32)                                                                        \
+            hipLaunchKernelGGL((k_blur_tile_sep<H, 2>), grid, block, 0, s, a, vt, bd);     \
+        else                                                                               \
+            hipLaunchKernelGGL((k_blur_tile_sep<H, 1>), grid, block, 0, s, a, vt, bd);     \
+        return hipGetLastError();                                                          \
+    }
+    if (halo < 0) return hipErrorInvalidValue;
+    PS_CASE(4)
+    PS_CASE(8)
+    PS_CASE(10)
+    PS_CASE(13)
+    PS_CASE(16)
+    PS_CASE(22)
+    PS_CASE(30)
+#undef PS_CASE
     return hipErrorInvalidValue;
 }
 

@@ -64,6 +64,7 @@ popsift_hip_params to_params(const popsift::Config& c)
     p.filter_grid_size = c.getFilterGridSize();
     p.filter_max_extrema = c.getFilterMaxExtrema();
     p.filter_sorting = (int)c.getFilterSorting(); /* RandomScale, LargestScaleFirst, SmallestScaleFirst */
+    p.scale_direct = c.getScalingMode() == popsift::Config::ScaleDirect ? 1 : 0;
     return p;
 }
 
@@ -270,7 +271,6 @@ bool PopSift::configure(const popsift::Config& config, bool /*force*/)
         _config.getGaussMode() != popsift::Config::VLFeat_Relative_All &&
         _config.getGaussMode() != popsift::Config::OpenCV_Compute)
         DIE("this build implements the Gauss modes 'vlfeat', 'vlfeat-direct' and 'opencv' only");
-    if (_config.getScalingMode() != popsift::Config::ScaleDefault) DIE("ScaleDirect is not supported");
     if (_config.getFilterMaxExtrema() > 0 && (_config.getFilterGridSize() < 1 || _config.getFilterGridSize() > 64))
         DIE("the grid filter supports grid sizes 1..64");
     _shadow_config = _config;
