@@ -48,8 +48,10 @@ public:
 };
 
 class FeaturesHost : public FeaturesBase {
-    Feature*    _ext;
-    Descriptor* _ori;
+    Feature*         _ext;
+    Descriptor*      _ori;
+    unsigned char*   _bytes = 0;   /* byte format: num_ori x 128 bytes, a pinned block like the others */
+    std::vector<int> _desc_idx;    /* byte format: ORIENTATION_MAX_COUNT descriptor indices per feature, -1 = none */
 
 public:
     FeaturesHost();
@@ -72,9 +74,21 @@ public:
     void unpin() {}
 
     inline Feature*    getFeatures() { return _ext; }
-    inline Descriptor* getDescriptors() { return _ori; }
+    inline Descriptor* getDescriptors() { return _ori; } /* null in the byte format */
 
-    /* one line per (feature, orientation): x y 1/s^2 0 1/s^2 d0 .. d127 */
+    /* Extension, Config::ByteDescriptors: (re)allocates num_ext features and num_ori descriptors of 128 bytes each (no
+     * float descriptors: getDescriptors() and every Feature::desc[k] are null) */
+    void resetBytes(int num_ext, int num_ori);
+    bool hasDescriptorBytes() const { return _bytes != 0; }
+    /* num_ori x 128 bytes (null in the float format); the D2H copy lands here */
+    inline unsigned char* getDescriptorBytes() { return _bytes; }
+    /* the 128 bytes of orientation `ori` of feature `feature`; null when ori >= num_ori (or in the float format) */
+    const unsigned char* descriptorBytes(int feature, int ori) const;
+    /* ORIENTATION_MAX_COUNT descriptor indices per feature (byte format; filled by PopSift's workers) */
+    inline int* getDescriptorIndices() { return _desc_idx.data(); }
+
+    /* one line per (feature, orientation): x y 1/s^2 0 1/s^2 d0 .. d127; the byte format writes the bytes as
+     * integers (the layout of write_as_uchar) */
     void print(std::ostream& ostr, bool write_as_uchar) const;
 };
 

@@ -76,6 +76,9 @@ public:
         _describe = true;
         _compute_ori = computeOrientation;
     }
+    /** extension: the job's descriptors come back as bytes (Config::ByteDescriptors when it was enqueued) */
+    void                               setDescriptorBytes(bool on) { _desc_bytes = on; }
+    bool                               wantsDescriptorBytes() const { return _desc_bytes; }
     bool                               isDescribe() const { return _describe; }
     bool                               computesOrientation() const { return _compute_ori; }
     const std::vector<popsift::Frame>& getFrames() const { return _frames; }
@@ -84,6 +87,7 @@ private:
     std::vector<popsift::Frame> _frames;
     bool                        _describe = false;
     bool                        _compute_ori = true;
+    bool                        _desc_bytes = false;
 };
 
 namespace popsift {

@@ -47,6 +47,13 @@ struct Config {
      * MatchingMode: features stay on the GPU (FeaturesDev, SiftJob::getDev()) for FeaturesDev::match. */
     enum ProcessingMode { ExtractingMode, MatchingMode };
 
+    /* Extension: how FeaturesHost returns descriptors.  FloatDescriptors (default): 128 floats each, Feature::desc[k].
+     * ByteDescriptors: 128 bytes each, quantized on the GPU (include/popsift_hip.h, popsift_hip_fetch_item_u8), so that a
+     * quarter of the data crosses PCIe; FeaturesHost::descriptorBytes(i, k), and desc[k] / getDescriptors() are null.
+     * Scale first: setNormalizationMultiplier(9) gives VLFeat-style bytes (with the default 0 every byte is 0 or 1).
+     * A job takes the format the configuration has when it is enqueued.  MatchingMode ignores it (FeaturesDev is float). */
+    enum DescriptorFormat { FloatDescriptors, ByteDescriptors };
+
     /* ---- setters (sift_conf.cu:51-258) -------------------------------------- */
     void setGaussMode(const std::string& m);
     void setGaussMode(GaussMode m) { _gauss_mode = m; }
@@ -80,6 +87,7 @@ struct Config {
     void setNormMode(const std::string& m);
     DEPRECATED(void setUseRootSift(bool on));
     void setNormalizationMultiplier(int mul) { _normalization_multiplier = mul; }
+    void setDescriptorFormat(DescriptorFormat f) { _descriptor_format = f; }
 
     /* ---- getters ------------------------------------------------------------- */
     bool  hasInitialBlur() const { return _assume_initial_blur; }
@@ -106,8 +114,10 @@ struct Config {
     GridFilterMode getFilterSorting() const { return _grid_filter_mode; }
     ScalingMode    getScalingMode() const { return _scaling_mode; }
     DescMode       getDescMode() const { return _desc_mode; }
+    DescriptorFormat getDescriptorFormat() const { return _descriptor_format; }
 
-    /* compares the 14 fields that decide whether tables must be rebuilt (sift_conf.cu:285-303) */
+    /* compares the 14 fields that decide whether tables must be rebuilt (sift_conf.cu:285-303), and the descriptor
+     * format */
     bool equal(const Config& other) const;
 
     /* ---- public data members, as in the reference ------------------------------ */
@@ -134,6 +144,7 @@ private:
     NormMode       _normalization_mode;
     int            _normalization_multiplier;
     bool           _print_gauss_tables;
+    DescriptorFormat _descriptor_format;
 };
 
 inline bool operator==(const Config& l, const Config& r) { return l.equal(r); }

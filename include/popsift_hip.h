@@ -300,6 +300,35 @@ int popsift_hip_fetch_end(popsift_hip_ctx* ctx);
  * stay valid until the next submit on this context. */
 int popsift_hip_results_dev(popsift_hip_ctx* ctx, const void** d_feats, const void** d_desc);
 
+/*
+ * Descriptors as bytes (VLFeat's and OpenCV's byte formats, the demo's --write-as-uchar): the GPU quantizes, and only
+ * 128 bytes per descriptor cross the link instead of 512.  For each element d of the float descriptor, exactly as the
+ * float calls return it (2^norm_multi applied):
+ *     q(d) = 0                    if d is NaN or d <= 0      (-0.0 included)
+ *            255                  if d >= 255                (+inf included)
+ *            (uint8_t) roundf(d)  otherwise                  (ties away from zero, as Feature::print(.., true) rounds)
+ * Useful bytes need a scale: norm_multi = 9 (x 512) gives VLFeat-style bytes; with the default 0 every byte is 0 or 1.
+ * The float path can hold NaN (the normalisation of a patch without gradient, e.g. a caller frame on a flat region):
+ * such elements become 0.
+ *
+ * Same rules and errors as the float calls above (desc_cap counted in BYTES, >= n_descriptors * 128).  Extraction and
+ * describe results alike; clone_results and matching stay float.  The float results are untouched: a context that never
+ * asks for bytes allocates and launches nothing more.  The pass (desc_bytes.hip) writes a byte buffer of the image's
+ * slot, allocated on the first byte request.  It runs on the context's stream; fetch_begin*_u8 enqueues it there before
+ * it returns (ahead of the next submit's kernels) and its byte copy on the copy stream waits for it (protocol as above:
+ * begin for every image, submit the next batch, one fetch_end).  Every call that writes the buffer first waits for a
+ * pending fetch_begin*_u8 download that still reads it.
+ * results_dev*_u8: the byte pointer stays valid until the next submit or byte request for that image.
+ */
+int popsift_hip_fetch_item_u8(popsift_hip_ctx* ctx, int k, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
+                              size_t desc_cap);
+int popsift_hip_fetch_u8(popsift_hip_ctx* ctx, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc, size_t desc_cap);
+int popsift_hip_fetch_begin_item_u8(popsift_hip_ctx* ctx, int k, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
+                                    size_t desc_cap);
+int popsift_hip_fetch_begin_u8(popsift_hip_ctx* ctx, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
+                               size_t desc_cap);
+int popsift_hip_results_dev_item_u8(popsift_hip_ctx* ctx, int k, const void** d_feats, const void** d_desc_u8);
+
 /* Pinned (page-locked) host memory for result buffers: a D2H copy into it runs at PCIe speed
  * without staging.  Replaces FeaturesHost::pin/unpin (cudaHostRegister per image,
  * features.cu:84-109).  Returns NULL on failure / when no GPU runtime is usable. */
@@ -324,6 +353,8 @@ int popsift_hip_devfeatures_alloc(int device, int n_features, int n_descriptors,
 int popsift_hip_devfeatures_from_host(int device, const float* desc, int n_descriptors, popsift_hip_devfeatures** out);
 /* Host copies (tests, printing): desc n_descriptors*128 floats, rev n_descriptors ints; either may be NULL. */
 int popsift_hip_devfeatures_download(const popsift_hip_devfeatures* f, float* desc, int32_t* rev);
+/* The set's descriptors as bytes (n_descriptors * 128, the rule of popsift_hip_fetch_item_u8), quantized on its GPU */
+int popsift_hip_devfeatures_download_u8(const popsift_hip_devfeatures* f, uint8_t* desc);
 
 /* One row of the reference's match_matrix (int3, features.cu:178-220) plus the two squared distances. */
 typedef struct popsift_hip_match {

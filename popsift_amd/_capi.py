@@ -116,6 +116,11 @@ SYMBOLS = [
     ("popsift_hip_fetch_begin", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("popsift_hip_fetch_end", C.c_int, [_vp]),
     ("popsift_hip_results_dev", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    ("popsift_hip_fetch_item_u8", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]),
+    ("popsift_hip_fetch_u8", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    ("popsift_hip_fetch_begin_item_u8", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]),
+    ("popsift_hip_fetch_begin_u8", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
+    ("popsift_hip_results_dev_item_u8", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("popsift_hip_host_alloc", _vp, [C.c_size_t]),
     ("popsift_hip_host_free", None, [_vp]),
     ("popsift_hip_clone_results", C.c_int, [_vp, C.POINTER(_vp)]),
@@ -125,6 +130,7 @@ SYMBOLS = [
     ("popsift_hip_devfeatures_alloc", C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     ("popsift_hip_devfeatures_from_host", C.c_int, [C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
     ("popsift_hip_devfeatures_download", C.c_int, [_vp, _vp, _vp]),
+    ("popsift_hip_devfeatures_download_u8", C.c_int, [_vp, _vp]),
     ("popsift_hip_match_sets", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_set_path", C.c_int, [C.c_int]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
@@ -145,6 +151,29 @@ MAX_BATCH = 16
 IMG_HOST_U8, IMG_HOST_F32, IMG_DEV_U8, IMG_DEV_F32, IMG_PINNED_U8, IMG_PINNED_F32 = range(6)
 
 _lib = None
+
+
+def _desc_type(fmt):
+    """numpy element type of a descriptor format: "f32" (the default) or "u8" (popsift_hip_fetch*_u8)"""
+    if fmt == "f32":
+        return np.float32
+    if fmt == "u8":
+        return np.uint8
+    raise ValueError("fmt: 'f32' or 'u8', got %r" % (fmt,))
+
+
+def quantize_u8(desc):
+    """The byte rule of popsift_hip_fetch_item_u8 on the host (the reference the tests hold the GPU pass to):
+    0 for NaN and d <= 0, 255 for d >= 255, else roundf(d) -- ties away from zero -- as a byte."""
+    d = np.asarray(desc, np.float32)
+    with np.errstate(invalid="ignore"):
+        pos = d > 0
+        t = np.trunc(d)
+        # roundf: |d - trunc(d)| >= 0.5 moves one away from zero (exact in float32 below 2^23)
+        r = np.where(np.abs(d - t) >= np.float32(0.5), t + np.float32(1.0), t)
+        r = np.where(d >= np.float32(255.0), np.float32(255.0), r)
+        r = np.where(pos, r, np.float32(0.0))
+    return r.astype(np.uint8)
 
 
 class PopsiftHipError(RuntimeError):
@@ -226,6 +255,15 @@ class DevFeatures:
             raise PopsiftHipError(rc, "popsift_hip_devfeatures_download")
         return desc, rev
 
+    def download_u8(self):
+        """the set's descriptors as bytes (n, 128), quantized on its GPU (popsift_hip_devfeatures_download_u8)"""
+        _, _, nd = self.info()
+        desc = np.zeros((nd, 128), np.uint8)
+        rc = lib().popsift_hip_devfeatures_download_u8(self._h, desc.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_devfeatures_download_u8")
+        return desc
+
     def match(self, other):
         _, _, nd = self.info()
         out = np.zeros(nd, MATCH_DTYPE)
@@ -249,9 +287,10 @@ class DevFeatures:
 class PendingFetch:
     """A download started by Context.fetch_begin; result() waits for it (popsift_hip_fetch_end)."""
 
-    def __init__(self, ctx, nf, nd, pinned):
+    def __init__(self, ctx, nf, nd, pinned, k=None, fmt="f32"):
         self._ctx, self._done = ctx, False
-        self._fbytes, self._dbytes = max(nf, 1) * FEATURE_DTYPE.itemsize, max(nd, 1) * 512
+        dt = np.dtype(_desc_type(fmt))
+        self._fbytes, self._dbytes = max(nf, 1) * FEATURE_DTYPE.itemsize, max(nd, 1) * 128 * dt.itemsize
         self._pin = []
         if pinned:
             for n in (self._fbytes, self._dbytes):
@@ -263,13 +302,19 @@ class PendingFetch:
             fb = (C.c_char * self._fbytes).from_address(self._pin[0])
             db = (C.c_char * self._dbytes).from_address(self._pin[1])
             self._feats = np.frombuffer(fb, FEATURE_DTYPE, nf)
-            self._desc = np.frombuffer(db, np.float32, nd * 128).reshape(nd, 128)
+            self._desc = np.frombuffer(db, dt, nd * 128).reshape(nd, 128)
         else:
             self._feats = np.zeros(nf, FEATURE_DTYPE)
-            self._desc = np.zeros((nd, 128), np.float32)
+            self._desc = np.zeros((nd, 128), dt)
         try:
-            ctx._chk(lib().popsift_hip_fetch_begin(ctx._h, self._feats.ctypes.data, nf, self._desc.ctypes.data, nd * 128),
-                     "popsift_hip_fetch_begin")
+            f, d = self._feats.ctypes.data, self._desc.ctypes.data
+            if k is None:
+                fn = lib().popsift_hip_fetch_begin_u8 if fmt == "u8" else lib().popsift_hip_fetch_begin
+                rc = fn(ctx._h, f, nf, d, nd * 128)
+            else:
+                fn = lib().popsift_hip_fetch_begin_item_u8 if fmt == "u8" else lib().popsift_hip_fetch_begin_item
+                rc = fn(ctx._h, k, f, nf, d, nd * 128)
+            ctx._chk(rc, "popsift_hip_fetch_begin")
         except Exception:
             self._release()
             raise
@@ -442,33 +487,49 @@ class Context:
         self._chk(lib().popsift_hip_wait_batch(self._h, C.byref(n), nf, nd), "popsift_hip_wait_batch")
         return [(nf[k], nd[k]) for k in range(n.value)]
 
-    def fetch_item(self, k):
+    def fetch_item(self, k, fmt="f32"):
+        """(feats, desc) of image k of the finished batch; fmt="u8": descriptors as bytes, quantized on the GPU"""
         nf, nd = self.wait_batch()[k]
         feats = np.zeros(nf, FEATURE_DTYPE)
-        desc = np.zeros((nd, 128), np.float32)
-        self._chk(lib().popsift_hip_fetch_item(self._h, k, feats.ctypes.data, nf, desc.ctypes.data, nd * 128),
-                  "popsift_hip_fetch_item")
+        desc = np.zeros((nd, 128), _desc_type(fmt))
+        fn = lib().popsift_hip_fetch_item_u8 if fmt == "u8" else lib().popsift_hip_fetch_item
+        self._chk(fn(self._h, k, feats.ctypes.data, nf, desc.ctypes.data, nd * 128), "popsift_hip_fetch_item")
         return feats, desc
+
+    def fetch_begin_item(self, k, pinned=True, fmt="f32"):
+        """fetch_begin for image k of the finished batch (call it for every image, submit the next batch, then result()
+        of any one handle -- one popsift_hip_fetch_end -- completes them all)"""
+        nf, nd = self.wait_batch()[k]
+        return PendingFetch(self, nf, nd, pinned, k=k, fmt=fmt)
+
+    def results_dev_item(self, k, fmt="f32"):
+        """(device address of the features, of the descriptors) of image k; fmt="u8": the byte descriptors"""
+        fp, dp = C.c_void_p(), C.c_void_p()
+        fn = lib().popsift_hip_results_dev_item_u8 if fmt == "u8" else lib().popsift_hip_results_dev_item
+        self._chk(fn(self._h, k, C.byref(fp), C.byref(dp)), "popsift_hip_results_dev_item")
+        return fp.value, dp.value
 
     def wait(self):
         a, b = C.c_int(), C.c_int()
         self._chk(lib().popsift_hip_wait(self._h, C.byref(a), C.byref(b)), "popsift_hip_wait")
         return a.value, b.value
 
-    def fetch(self):
+    def fetch(self, fmt="f32"):
+        """(feats, desc) of the finished image; fmt="u8": descriptors as bytes, quantized on the GPU"""
         nf, nd = self.wait()
         feats = np.zeros(nf, FEATURE_DTYPE)
-        desc = np.zeros((nd, 128), np.float32)
-        self._chk(lib().popsift_hip_fetch(self._h, feats.ctypes.data, nf, desc.ctypes.data, nd * 128),
-                  "popsift_hip_fetch")
+        desc = np.zeros((nd, 128), _desc_type(fmt))
+        fn = lib().popsift_hip_fetch_u8 if fmt == "u8" else lib().popsift_hip_fetch
+        self._chk(fn(self._h, feats.ctypes.data, nf, desc.ctypes.data, nd * 128), "popsift_hip_fetch")
         return feats, desc
 
-    def fetch_begin(self, pinned=True):
+    def fetch_begin(self, pinned=True, fmt="f32"):
         """Start the download of the finished image and return a handle; the context is free for the next submit.
-        handle.result() (popsift_hip_fetch_end) -> (feats, desc).  pinned: page-locked targets (asynchronous copy)."""
+        handle.result() (popsift_hip_fetch_end) -> (feats, desc).  pinned: page-locked targets (asynchronous copy).
+        fmt="u8": descriptors as bytes, quantized on the GPU."""
         nf, nd = self.wait()
         prev = getattr(self, "_pending", None)
-        self._pending = PendingFetch(self, nf, nd, pinned)   # the C call waits for an earlier pending download first
+        self._pending = PendingFetch(self, nf, nd, pinned, fmt=fmt)   # the C call waits for an earlier pending download first
         if prev is not None and not prev._done:
             prev._landed()
         return self._pending

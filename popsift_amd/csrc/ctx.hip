@@ -94,6 +94,11 @@ struct ImageSlot {
     float*   alt_desc = nullptr;
     int      alt_desc_cap = 0;
     bool     moved = false; /* the finished image's results went to fetch_begin: the current slab is stale */
+    /* descriptors as bytes (popsift_hip_fetch*_u8), allocated on the first byte request and grown with the slab: desc_cap
+     * descriptors of 128 bytes.  One buffer, not swapped: every path that writes it waits for a pending download first */
+    uint8_t* d_desc_u8 = nullptr;
+    int      desc_u8_cap = 0;
+    bool     u8_read = false; /* a popsift_hip_fetch_begin*_u8 download reads d_desc_u8 (until copy_stream is waited for) */
     /* describe (popsift_hip_describe_batch) only, grown on the first describe: the frames (device copy and pinned staging),
      * the per-chunk counts of the partition, list position <-> frame, k_scan_apply's records in list order */
     popsift_hip_frame*   d_frames = nullptr;
@@ -154,6 +159,7 @@ struct popsift_hip_ctx {
     int       cand_cap = 0, desc_cap = 0;
     size_t    ohist_cap = 0;
     hipStream_t copy_stream = nullptr;
+    hipEvent_t  ev_u8 = nullptr;    /* the byte pass of a fetch_begin*_u8 on `stream` -> its copies on copy_stream */
     bool     copy_pending = false;  /* fetch_begin downloads have not been waited for */
     unsigned long submit_seq = 0, copy_seq = 0; /* the batch now in the context / the batch whose downloads are pending */
     Counters* d_ct = nullptr; /* PS_MAX_BATCH counter blocks, one per slot */
@@ -1248,6 +1254,94 @@ int results_here(popsift_hip_ctx* c, int k = 0)
     return 0;
 }
 
+/* The byte buffer of a slot, sized for its slab.  Writers call this first: it waits for a pending fetch_begin*_u8 download
+ * that still reads the buffer (the state of that download is left as it is: fetch_end still completes it). */
+int slot_u8_ready(popsift_hip_ctx* c, ImageSlot& sl)
+{
+    if (sl.u8_read && c->copy_pending) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+    sl.u8_read = false;
+    if (sl.desc_u8_cap >= sl.desc_cap && sl.d_desc_u8) return 0;
+    if (sl.d_desc_u8) HIP_TRY(c, hipFree(sl.d_desc_u8));
+    sl.d_desc_u8 = nullptr;
+    sl.desc_u8_cap = 0;
+    HIP_TRY(c, ctx_malloc(c, (void**)&sl.d_desc_u8, (size_t)std::max(sl.desc_cap, 1) * 128));
+    sl.desc_u8_cap = sl.desc_cap;
+    return 0;
+}
+
+/* image k's results into caller memory, descriptors as floats (u8 = false) or as bytes, on the compute stream */
+int fetch_sync(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap,
+               size_t nd, bool u8)
+{
+    const size_t nf = (size_t)c->n_feat[k];
+    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
+    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    ImageSlot& sl = c->slot[k];
+    if (u8 && nd) {
+        if (int rc = slot_u8_ready(c, sl)) return rc;
+        HIP_TRY(c, launch_desc_bytes(sl.d_desc, (int)nd, sl.d_desc_u8, c->stream));
+        SYNC_CHK(c, "k_desc_bytes");
+    }
+    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
+    if (nd && u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc_u8, nd * 128, hipMemcpyDeviceToHost, c->stream));
+    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+/* popsift_hip_fetch_begin_item(_u8) */
+int fetch_begin(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap, bool u8)
+{
+    const size_t nf = (size_t)c->n_feat[k], nd = (size_t)c->n_desc[k];
+    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
+    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    /* the other slabs may still be the source of the downloads of the batch before this one */
+    if (c->copy_pending && c->copy_seq != c->submit_seq)
+        if (int rc = drain_copy(c)) return rc;
+    /* The copy stream is made on first use: the runtime deals its few hardware queues to streams in the order they
+     * are created, so a second stream in EVERY context -- used or not -- takes queues from the streams that do the work
+     * (four active contexts next to sixteen idle ones: 7.8 -> 6.5 Gpix/s on the sparse workload). */
+    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    /* nothing has been issued or swapped yet: a failed allocation leaves the results where they are (plain fetch works) */
+    ImageSlot& sl = c->slot[k];
+    if (int rc = grow(c, &sl.alt_feats, &sl.alt_feats_cap, sl.feats_cap)) return rc;
+    if (sl.alt_desc_cap < sl.desc_cap) {
+        if (sl.alt_desc) HIP_TRY(c, hipFree(sl.alt_desc));
+        sl.alt_desc = nullptr;
+        sl.alt_desc_cap = 0;
+        HIP_TRY(c, ctx_malloc(c, (void**)&sl.alt_desc, (size_t)sl.desc_cap * 128 * sizeof(float)));
+        sl.alt_desc_cap = sl.desc_cap;
+    }
+    if (u8 && nd) {
+        if (int rc = slot_u8_ready(c, sl)) return rc;
+        if (!c->ev_u8) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_u8, hipEventDisableTiming));
+    }
+    /* finish() has synchronised the compute stream: the slab is complete, and copy_stream needs no event to wait on.
+     * Bytes: the pass runs on the compute stream -- idle now, and ahead of the next submit's kernels -- and the byte copy
+     * waits for it.  On the copy stream it would queue behind other contexts' kernels on a shared hardware queue
+     * (keypoint-sparse host to host 6.7-7.4 instead of 9.4-9.5 Gpix/s).  It reads the slab that becomes
+     * alt_desc below, which the next batch does not write. */
+    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->copy_stream));
+    if (nd && u8) {
+        HIP_TRY(c, launch_desc_bytes(sl.d_desc, (int)nd, sl.d_desc_u8, c->stream));
+        HIP_TRY(c, hipEventRecord(c->ev_u8, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_u8, 0));
+        HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc_u8, nd * 128, hipMemcpyDeviceToHost, c->copy_stream));
+        sl.u8_read = true;
+    }
+    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
+    std::swap(sl.d_feats, sl.alt_feats);
+    std::swap(sl.feats_cap, sl.alt_feats_cap);
+    std::swap(sl.d_desc, sl.alt_desc); /* both hold desc_cap descriptors now; d_map / d_rot stay with the slot */
+    refresh_caps(c);
+    c->copy_pending = true;
+    c->copy_seq = c->submit_seq;
+    sl.moved = true;
+    return 0;
+}
+
 /* planes of image 0 of the batch (debug / parity hooks) */
 int plane_ptr(popsift_hip_ctx* c, int octave, int kind, int level, float** p, const OctDesc** odp)
 {
@@ -1469,6 +1563,7 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
         if (sl.d_ovf) (void)hipFree(sl.d_ovf);
         if (sl.alt_feats) (void)hipFree(sl.alt_feats);
         if (sl.alt_desc) (void)hipFree(sl.alt_desc);
+        if (sl.d_desc_u8) (void)hipFree(sl.d_desc_u8);
         if (sl.d_frames) (void)hipFree(sl.d_frames);
         if (sl.h_frames) (void)hipHostFree(sl.h_frames);
         if (sl.d_fcounts) (void)hipFree(sl.d_fcounts);
@@ -1484,6 +1579,7 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
     if (c->h_ct) (void)hipHostFree(c->h_ct);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
+    if (c->ev_u8) (void)hipEventDestroy(c->ev_u8);
     delete c;
     return POPSIFT_HIP_OK;
 }
@@ -1592,15 +1688,16 @@ int popsift_hip_fetch_item(popsift_hip_ctx* c, int k, popsift_hip_feature* feats
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c, k)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch");
-    const size_t nf = (size_t)c->n_feat[k], nd = (size_t)c->n_desc[k];
-    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
-    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const ImageSlot& sl = c->slot[k];
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
-    if (nd) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return POPSIFT_HIP_OK;
+    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, (size_t)c->n_desc[k], false);
+}
+
+int popsift_hip_fetch_item_u8(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
+                              size_t desc_cap)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = results_here(c, k)) return rc;
+    POPSIFT_RANGE("popsift_hip: fetch_u8");
+    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, (size_t)c->n_desc[k], true);
 }
 
 int popsift_hip_results_dev_item(popsift_hip_ctx* c, int k, const void** d_feats, const void** d_desc)
@@ -1609,6 +1706,23 @@ int popsift_hip_results_dev_item(popsift_hip_ctx* c, int k, const void** d_feats
     if (int rc = results_here(c, k)) return rc;
     if (d_feats) *d_feats = c->slot[k].d_feats;
     if (d_desc) *d_desc = c->slot[k].d_desc;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_results_dev_item_u8(popsift_hip_ctx* c, int k, const void** d_feats, const void** d_desc_u8)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = results_here(c, k)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    ImageSlot& sl = c->slot[k];
+    if (int rc = slot_u8_ready(c, sl)) return rc;
+    if (c->n_desc[k] > 0) {
+        HIP_TRY(c, launch_desc_bytes(sl.d_desc, c->n_desc[k], sl.d_desc_u8, c->stream));
+        SYNC_CHK(c, "k_desc_bytes");
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (d_feats) *d_feats = sl.d_feats;
+    if (d_desc_u8) *d_desc_u8 = sl.d_desc_u8;
     return POPSIFT_HIP_OK;
 }
 
@@ -1626,14 +1740,12 @@ int popsift_hip_fetch(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t fea
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch");
-    const size_t nf = (size_t)c->n_feat[0], nd = (size_t)c->rep.ori_total;
-    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
-    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, c->slot[0].d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
-    if (nd) HIP_TRY(c, hipMemcpyAsync(desc, c->slot[0].d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return POPSIFT_HIP_OK;
+    return fetch_sync(c, 0, feats, feats_cap, desc, desc_cap, (size_t)c->rep.ori_total, false);
+}
+
+int popsift_hip_fetch_u8(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc, size_t desc_cap)
+{
+    return popsift_hip_fetch_item_u8(c, 0, feats, feats_cap, desc, desc_cap);
 }
 
 int popsift_hip_fetch_begin_item(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, float* desc,
@@ -1642,43 +1754,26 @@ int popsift_hip_fetch_begin_item(popsift_hip_ctx* c, int k, popsift_hip_feature*
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c, k)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch_begin");
-    const size_t nf = (size_t)c->n_feat[k], nd = (size_t)c->n_desc[k];
-    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
-    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    /* the other slabs may still be the source of the downloads of the batch before this one */
-    if (c->copy_pending && c->copy_seq != c->submit_seq)
-        if (int rc = drain_copy(c)) return rc;
-    /* The copy stream is made on first use: the runtime deals its few hardware queues to streams in the order they
-     * are created, so a second stream in EVERY context -- used or not -- takes queues from the streams that do the work
-     * (four active contexts next to sixteen idle ones: 7.8 -> 6.5 Gpix/s on the sparse workload). */
-    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    /* nothing has been issued or swapped yet: a failed allocation leaves the results where they are (plain fetch works) */
-    ImageSlot& sl = c->slot[k];
-    if (int rc = grow(c, &sl.alt_feats, &sl.alt_feats_cap, sl.feats_cap)) return rc;
-    if (sl.alt_desc_cap < sl.desc_cap) {
-        if (sl.alt_desc) HIP_TRY(c, hipFree(sl.alt_desc));
-        sl.alt_desc = nullptr;
-        sl.alt_desc_cap = 0;
-        HIP_TRY(c, ctx_malloc(c, (void**)&sl.alt_desc, (size_t)sl.desc_cap * 128 * sizeof(float)));
-        sl.alt_desc_cap = sl.desc_cap;
-    }
-    /* finish() has synchronised the compute stream: the slab is complete, and copy_stream needs no event to wait on */
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->copy_stream));
-    if (nd) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
-    std::swap(sl.d_feats, sl.alt_feats);
-    std::swap(sl.feats_cap, sl.alt_feats_cap);
-    std::swap(sl.d_desc, sl.alt_desc); /* both hold desc_cap descriptors now; d_map / d_rot stay with the slot */
-    refresh_caps(c);
-    c->copy_pending = true;
-    c->copy_seq = c->submit_seq;
-    sl.moved = true;
-    return POPSIFT_HIP_OK;
+    return fetch_begin(c, k, feats, feats_cap, desc, desc_cap, false);
+}
+
+int popsift_hip_fetch_begin_item_u8(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
+                                    size_t desc_cap)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = results_here(c, k)) return rc;
+    POPSIFT_RANGE("popsift_hip: fetch_begin_u8");
+    return fetch_begin(c, k, feats, feats_cap, desc, desc_cap, true);
 }
 
 int popsift_hip_fetch_begin(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t feats_cap, float* desc, size_t desc_cap)
 {
     return popsift_hip_fetch_begin_item(c, 0, feats, feats_cap, desc, desc_cap);
+}
+
+int popsift_hip_fetch_begin_u8(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc, size_t desc_cap)
+{
+    return popsift_hip_fetch_begin_item_u8(c, 0, feats, feats_cap, desc, desc_cap);
 }
 
 int popsift_hip_fetch_end(popsift_hip_ctx* c)
@@ -1839,6 +1934,21 @@ int popsift_hip_devfeatures_download(const popsift_hip_devfeatures* f, float* de
             return POPSIFT_HIP_ERR_DEVICE;
     }
     return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_devfeatures_download_u8(const popsift_hip_devfeatures* f, uint8_t* desc)
+{
+    if (!f || (f->n_desc > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
+    if (f->n_desc <= 0) return POPSIFT_HIP_OK;
+    if (hipSetDevice(f->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    const size_t bytes = (size_t)f->n_desc * 128;
+    uint8_t*     d_u8 = nullptr;
+    if (hipMalloc((void**)&d_u8, bytes) != hipSuccess) return POPSIFT_HIP_ERR_OOM;
+    /* the null stream: the pass is ordered after whatever wrote the set, the blocking copy after the pass */
+    const bool ok = launch_desc_bytes(f->d_desc, f->n_desc, d_u8, nullptr) == hipSuccess &&
+                    hipMemcpy(desc, d_u8, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    (void)hipFree(d_u8);
+    return ok ? POPSIFT_HIP_OK : POPSIFT_HIP_ERR_DEVICE;
 }
 
 static std::atomic<int> g_match_path{POPSIFT_HIP_MATCH_AUTO};

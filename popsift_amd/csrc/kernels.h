@@ -161,4 +161,8 @@ hipError_t launch_match_screen(const float* ldesc, int l_len, const float* rdesc
 /* Feature records (72-byte popsift::Feature layout) with device descriptor pointers for a cloned set */
 hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, float* desc_base, void* out, hipStream_t s);
 
+/* desc_bytes.hip: n_desc descriptors (128 floats each, 16-byte aligned) -> 128 bytes each, the rule of
+ * include/popsift_hip.h (popsift_hip_fetch_item_u8) */
+hipError_t launch_desc_bytes(const float* desc, int n_desc, uint8_t* out, hipStream_t s);
+
 }  // namespace popsift_hip

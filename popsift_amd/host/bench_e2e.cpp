@@ -4,13 +4,15 @@
  * PCIe-inclusive: every image is uploaded and its features + descriptors (about 53 MB for the dense
  * synthetic 1080p image) are downloaded into a FeaturesHost.  Never the headline `value` of bench.py.
  *   popsift-bench [--images N] [--width W] [--height H] [--inflight K] [--callers C] [--seed S] [--pgm a.pgm,b.pgm,...]
- *                 [--threshold T]
+ *                 [--threshold T] [--desc-bytes]
  * --callers: threads that enqueue and drain (each its share of the images and of the in-flight budget; default 1, the
  * reference's demo loop -- bench.py passes one per GPU: a single caller copies about 10 GB/s of images, enough for one GPU
  * on dense images and not for eight).  The line reports what a caller thread spends per image: in enqueue() (the copy of
  * the image into a pinned block), blocked in get(), and in the two deletes.
  * --threshold: popsift::Config::setThreshold (0.04 by default; 0.17 leaves ~2 features per 1000 pixels of the synthetic
  * images -- the keypoint-sparse regime, where the results are a few MB and PCIe is no longer the limit).
+ * --desc-bytes: popsift::Config::ByteDescriptors -- the descriptors are quantized on the GPU and 128 bytes instead of 512
+ * cross PCIe per descriptor (d2h_mb_per_image reports the results' bytes of either format).
  * --pgm: the images to cycle through (bench.py passes the popsift_amd/synth.py images of the headline workload);
  * without it a cheap built-in generator is used.
  * Contexts per GPU come from POPSIFT_CONTEXTS_PER_DEVICE, GPUs from POPSIFT_DEVICES.
@@ -64,8 +66,15 @@ int main(int argc, char** argv)
     int images = 64, w = 1920, h = 1080, inflight = 16, callers = 1;
     unsigned seed = 1;
     float    threshold = -1.0f;
+    bool     desc_bytes = false;
     std::string pgm;
-    for (int i = 1; i + 1 < argc; i += 2) {
+    for (int i = 1; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--desc-bytes")) { /* the one option without a value */
+            desc_bytes = true;
+            i--;
+            continue;
+        }
+        if (i + 1 >= argc) break;
         if (!strcmp(argv[i], "--pgm")) pgm = argv[i + 1];
         else if (!strcmp(argv[i], "--images")) images = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--width")) w = atoi(argv[i + 1]);
@@ -99,6 +108,7 @@ int main(int argc, char** argv)
 
     popsift::Config config;
     if (threshold >= 0.0f) config.setThreshold(threshold);
+    if (desc_bytes) config.setDescriptorFormat(popsift::Config::ByteDescriptors);
     PopSift         sift(config, popsift::Config::ExtractingMode, PopSift::ByteImages);
 
     if (callers < 1) callers = 1;
@@ -175,10 +185,13 @@ int main(int argc, char** argv)
     printf("{\"e2e_host_api_mpix_s\": %.1f, \"images\": %d, \"width\": %d, \"height\": %d, \"contexts\": %d, "
            "\"in_flight\": %d, \"callers\": %d, \"ms_per_image\": %.3f, \"features_per_image\": %.0f, "
            "\"descriptors_per_image\": %.0f, \"caller_us_per_image\": {\"enqueue\": %.1f, \"get_blocked\": %.1f, "
-           "\"delete\": %.1f}, \"warmup_passes_mpix_s\": [%s], \"input\": \"%s\"}\n",
+           "\"delete\": %.1f}, \"warmup_passes_mpix_s\": [%s], \"input\": \"%s\", \"desc_format\": \"%s\", "
+           "\"d2h_mb_per_image\": %.2f}\n",
            (double)images * w * h / sec / 1e6, images, w, h, sift.getContextCount(), inflight, callers, sec * 1e3 / images,
            (double)ct.feats / images, (double)ct.descs / images, ct.enqueue * 1e6 / images, ct.get * 1e6 / images,
-           ct.del * 1e6 / images, warm_rates.c_str(), pgm.empty() ? "built-in generator" : "pgm files");
+           ct.del * 1e6 / images, warm_rates.c_str(), pgm.empty() ? "built-in generator" : "pgm files", desc_bytes ? "u8" : "f32",
+           /* what the downloads carry: the 52-byte POD feature records and 128 floats or 128 bytes per descriptor */
+           ((double)ct.feats * 52 + (double)ct.descs * (desc_bytes ? 128 : 512)) / images / 1e6);
     sift.uninit();
     return 0;
 }

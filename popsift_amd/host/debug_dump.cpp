@@ -100,7 +100,10 @@ void write_descriptors(const Config& conf, ostream& ostr, FeaturesHost* features
             else
                 ostr << setprecision(5) << xpos << " " << ypos << " " << 1.0f / (sigma * sigma) << " 0 "
                      << 1.0f / (sigma * sigma) << " ";
-            if (really)
+            if (really && features->hasDescriptorBytes()) {
+                const unsigned char* b = features->descriptorBytes(i, ori);
+                for (int k = 0; b && k < 128; k++) ostr << (int)b[k] << " ";
+            } else if (really)
                 for (int k = 0; k < 128; k++) ostr << ext.desc[ori]->features[k] << " ";
             ostr << endl;
         }

@@ -118,6 +118,10 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& in
          "--norm-multi=9 or similar",
          [&] { write_as_uchar = true; });
     flag("dont-write", 0, "Informational", "Suppress descriptor output", [&] { dont_write = true; });
+    flag("desc-bytes", 0, "Extensions",
+         "Descriptors as bytes, quantized on the GPU (a quarter of the download); the output file has the layout of "
+         "--write-as-uchar.\nScaling is not automatic: combine with --norm-multi=9 or similar",
+         [&] { config.setDescriptorFormat(popsift::Config::ByteDescriptors); });
     flag("pgmread-loading", 0, "Informational", "Use the old image loader instead of LibDevIL",
          [&] { pgmread_loading = true; });
     flag("float-mode", 0, "Informational", "Upload image to GPU as float instead of byte", [&] { float_mode = true; });

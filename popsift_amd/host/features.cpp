@@ -146,12 +146,16 @@ FeaturesHost::~FeaturesHost()
 {
     pool().put(_ext);
     pool().put(_ori);
+    pool().put(_bytes);
 }
 
 void FeaturesHost::reset(int num_ext, int num_ori)
 {
     pool().put(_ext);
     pool().put(_ori);
+    pool().put(_bytes);
+    _bytes = 0;
+    _desc_idx.clear();
     /* page-aligned like the reference (features.cu:63,72); zero-sized results stay valid objects */
     _ext = (Feature*)pool().get(std::max<size_t>((size_t)num_ext * sizeof(Feature), 1), t_pool_node);
     if (_ext == 0) {
@@ -169,9 +173,50 @@ void FeaturesHost::reset(int num_ext, int num_ori)
     setDescriptorCount(num_ori);
 }
 
+void FeaturesHost::resetBytes(int num_ext, int num_ori)
+{
+    pool().put(_ext);
+    pool().put(_ori);
+    pool().put(_bytes);
+    _ori = 0;
+    _ext = (Feature*)pool().get(std::max<size_t>((size_t)num_ext * sizeof(Feature), 1), t_pool_node);
+    _bytes = (unsigned char*)pool().get(std::max<size_t>((size_t)num_ori * 128, 1), t_pool_node);
+    if (_ext == 0 || _bytes == 0) {
+        std::cerr << __FILE__ << ":" << __LINE__ << " Runtime error:" << std::endl
+                  << "    Failed to (re)allocate memory for downloading " << num_ext << " features / " << num_ori
+                  << " byte descriptors" << std::endl;
+        exit(-1);
+    }
+    _desc_idx.assign((size_t)num_ext * ORIENTATION_MAX_COUNT, -1);
+    setFeatureCount(num_ext);
+    setDescriptorCount(num_ori);
+}
+
+const unsigned char* FeaturesHost::descriptorBytes(int feature, int ori) const
+{
+    if (!_bytes || feature < 0 || feature >= size() || ori < 0 || ori >= _ext[feature].num_ori) return 0;
+    const int idx = _desc_idx[(size_t)feature * ORIENTATION_MAX_COUNT + ori];
+    return idx >= 0 ? _bytes + (size_t)idx * 128 : 0;
+}
+
 void FeaturesHost::print(std::ostream& ostr, bool write_as_uchar) const
 {
-    for (int i = 0; i < size(); i++) _ext[i].print(ostr, write_as_uchar);
+    if (!_bytes) {
+        for (int i = 0; i < size(); i++) _ext[i].print(ostr, write_as_uchar);
+        return;
+    }
+    /* Feature::print's layout; the bytes are the rounded values write_as_uchar prints, saturated to 0 .. 255 */
+    for (int i = 0; i < size(); i++) {
+        const Feature& f = _ext[i];
+        const float    sigval = 1.0f / (f.sigma * f.sigma);
+        for (int ori = 0; ori < f.num_ori; ori++) {
+            const unsigned char* b = descriptorBytes(i, ori);
+            if (!b) continue;
+            ostr << f.xpos << " " << f.ypos << " " << sigval << " 0 " << sigval << " ";
+            for (int k = 0; k < 128; k++) ostr << (int)b[k] << " ";
+            ostr << std::endl;
+        }
+    }
 }
 
 std::ostream& operator<<(std::ostream& ostr, const FeaturesHost& feature)

@@ -318,11 +318,30 @@ void PopSift::start_workers(int w, int h)
     g_live_pipelines++;
 }
 
-/* POD features -> popsift::Feature with descriptor pointers into the job's own block (prep_features, sift_pyramid.cu:249-279) */
+/* POD features -> popsift::Feature with descriptor pointers into the job's own block (prep_features, sift_pyramid.cu:249-279);
+ * in the byte format the pointers are null and the indices are kept for FeaturesHost::descriptorBytes */
 static void convert_features(const popsift_hip_feature* pod, int nf, popsift::FeaturesHost* features)
 {
     popsift::Feature*    out = features->getFeatures();
     popsift::Descriptor* base = features->getDescriptors();
+    if (features->hasDescriptorBytes()) {
+        int* idx = features->getDescriptorIndices();
+        for (int i = 0; i < nf; i++) {
+            const popsift_hip_feature& s = pod[i];
+            popsift::Feature&          f = out[i];
+            f.debug_octave = s.debug_octave;
+            f.xpos = s.xpos;
+            f.ypos = s.ypos;
+            f.sigma = s.sigma;
+            f.num_ori = s.num_ori;
+            for (int k = 0; k < ORIENTATION_MAX_COUNT; k++) {
+                f.orientation[k] = s.orientation[k];
+                f.desc[k] = 0;
+                idx[(size_t)i * ORIENTATION_MAX_COUNT + k] = s.desc_idx[k];
+            }
+        }
+        return;
+    }
     for (int i = 0; i < nf; i++) {
         const popsift_hip_feature& s = pod[i];
         popsift::Feature&          f = out[i];
@@ -336,6 +355,21 @@ static void convert_features(const popsift_hip_feature* pod, int nf, popsift::Fe
             f.desc[k] = s.desc_idx[k] >= 0 ? base + s.desc_idx[k] : 0;
         }
     }
+}
+
+/* the caller-visible result block of a job: float or byte descriptors (Config::DescriptorFormat at enqueue) */
+static popsift::FeaturesHost* new_features(const SiftJob* job, int nf, int nd)
+{
+    if (!job->wantsDescriptorBytes()) return new popsift::FeaturesHost(nf, nd);
+    popsift::FeaturesHost* f = new popsift::FeaturesHost();
+    f->resetBytes(nf, nd);
+    return f;
+}
+
+/* where a job's descriptors land (the copy's target) */
+static void* desc_target(popsift::FeaturesHost* f)
+{
+    return f->hasDescriptorBytes() ? (void*)f->getDescriptorBytes() : (void*)f->getDescriptors();
 }
 
 static_assert(sizeof(popsift::Frame) == sizeof(popsift_hip_frame) && offsetof(popsift::Frame, level) == offsetof(popsift_hip_frame, level),
@@ -449,15 +483,19 @@ void PopSift::worker_loop(Worker* me)
             rc = popsift_hip_wait_batch(me->ctx, &n, nfs, nds);
             if (rc != POPSIFT_HIP_OK || n != (int)jobs.size()) DIE(string("extraction failed: ") + popsift_hip_last_error(me->ctx));
             for (int k = 0; k < n; k++) {
-                popsift::FeaturesHost* features = new popsift::FeaturesHost(nfs[k], nds[k]);
+                popsift::FeaturesHost* features = new_features(jobs[(size_t)k], nfs[k], nds[k]);
                 if (nds[k] == 0) cerr << "Warning: no descriptors extracted" << endl; /* sift_desc.cu:88-92 */
                 if (nfs[k] == 0) {
                     jobs[(size_t)k]->setFeatures(features);
                     continue;
                 }
                 popsift_hip_feature* pod = pod_buffer((size_t)k, nfs[k]);
-                rc = popsift_hip_fetch_begin_item(me->ctx, k, pod, me->pods[(size_t)k].cap, (float*)features->getDescriptors(),
-                                                  (size_t)nds[k] * 128);
+                if (features->hasDescriptorBytes())
+                    rc = popsift_hip_fetch_begin_item_u8(me->ctx, k, pod, me->pods[(size_t)k].cap, features->getDescriptorBytes(),
+                                                         (size_t)nds[k] * 128);
+                else
+                    rc = popsift_hip_fetch_begin_item(me->ctx, k, pod, me->pods[(size_t)k].cap, (float*)desc_target(features),
+                                                      (size_t)nds[k] * 128);
                 if (rc != POPSIFT_HIP_OK) DIE(string("download failed: ") + popsift_hip_last_error(me->ctx));
                 Pending p;
                 p.job = jobs[(size_t)k];
@@ -500,12 +538,14 @@ void PopSift::worker_loop(Worker* me)
             continue;
         }
 
-        popsift::FeaturesHost* features = new popsift::FeaturesHost(nf, nd);
+        popsift::FeaturesHost* features = new_features(job, nf, nd);
+        const bool             bytes = features->hasDescriptorBytes();
         if (nd == 0) cerr << "Warning: no descriptors extracted" << endl; /* sift_desc.cu:88-92 */
         if (nf > 0) {
             popsift_hip_feature* pod = pod_buffer(0, nf);
             if (overlap) {
-                rc = popsift_hip_fetch_begin(me->ctx, pod, me->pods[0].cap, (float*)features->getDescriptors(), (size_t)nd * 128);
+                rc = bytes ? popsift_hip_fetch_begin_u8(me->ctx, pod, me->pods[0].cap, features->getDescriptorBytes(), (size_t)nd * 128)
+                           : popsift_hip_fetch_begin(me->ctx, pod, me->pods[0].cap, (float*)desc_target(features), (size_t)nd * 128);
                 if (rc != POPSIFT_HIP_OK) DIE(string("download failed: ") + popsift_hip_last_error(me->ctx));
                 Pending p;
                 p.job = job;
@@ -515,7 +555,8 @@ void PopSift::worker_loop(Worker* me)
                 pending.push_back(p);
                 continue;
             }
-            rc = popsift_hip_fetch(me->ctx, pod, me->pods[0].cap, (float*)features->getDescriptors(), (size_t)nd * 128);
+            rc = bytes ? popsift_hip_fetch_u8(me->ctx, pod, me->pods[0].cap, features->getDescriptorBytes(), (size_t)nd * 128)
+                       : popsift_hip_fetch(me->ctx, pod, me->pods[0].cap, (float*)desc_target(features), (size_t)nd * 128);
             if (rc != POPSIFT_HIP_OK) DIE(string("download failed: ") + popsift_hip_last_error(me->ctx));
             convert_features(pod, nf, features);
         }
@@ -590,6 +631,9 @@ SiftJob* PopSift::push(SiftJob* job, int w, int h)
     {
         std::lock_guard<std::mutex> lk(_mtx);
         if (_stopped) DIE("enqueue() after uninit()");
+        /* MatchingMode keeps the results on the GPU as floats: the descriptor format does not apply there */
+        job->setDescriptorBytes(_config.getDescriptorFormat() == popsift::Config::ByteDescriptors &&
+                                _proc_mode != popsift::Config::MatchingMode);
         if (!_started) start_workers(w, h);
         _queue.push(job);
     }

@@ -38,6 +38,7 @@ Config::Config()
     , _normalization_mode(getNormModeDefault())
     , _normalization_multiplier(0)
     , _print_gauss_tables(false)
+    , _descriptor_format(Config::FloatDescriptors)
 {
 }
 
@@ -102,7 +103,8 @@ bool Config::equal(const Config& o) const
            _threshold == o._threshold && _upscale_factor == o._upscale_factor && _scaling_mode == o._scaling_mode &&
            _max_extrema == o._max_extrema && _gauss_mode == o._gauss_mode && _sift_mode == o._sift_mode &&
            _assume_initial_blur == o._assume_initial_blur && _initial_blur == o._initial_blur &&
-           _normalization_mode == o._normalization_mode && _normalization_multiplier == o._normalization_multiplier;
+           _normalization_mode == o._normalization_mode && _normalization_multiplier == o._normalization_multiplier &&
+           _descriptor_format == o._descriptor_format;
 }
 
 }  // namespace popsift
