@@ -396,9 +396,8 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * (small values exercise the grow-and-rerun path of popsift_hip_wait); FAIL_ALLOC = n: the n-th device allocation
  * of this context from now on fails with POPSIFT_HIP_ERR_OOM (0 = off); DESC_ROWS = patch rows the loop descriptor
  * walks per pass (4 .. 128, default 128: small values make ordinary patches take the several passes that otherwise only
- * patches of more than 128 rows take -- sigma0 near 2 at the coarsest level; results do not depend on it); PYR_ORDER = 0:
- * level 1 of octave 1 after ALL levels of octave 0 (the default), 1: right behind the level that writes its source
- * plane (results do not depend on it; tools/pyr_order.sh times both); KP_WAVES = waves per image in the launches of
+ * patches of more than 128 rows take -- sigma0 near 2 at the coarsest level; results do not depend on it);
+ * KP_WAVES = waves per image in the launches of
  * the orientation and descriptor kernels (a multiple of 32; default 8 per wave slot of the device; results do not
  * depend on it; tools/kp_waves_sweep.sh: 8192 .. 131072 within 1.5 %); BLUR_PATH = which kernels build the pyramid's
  * plane-to-plane levels: 0 by plane size (default), 1 the one-tile-per-workgroup kernels only, 2 the strip-march kernels
@@ -412,7 +411,7 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * per octave (results do not depend on it); DESC_CAP = initial capacity of the descriptor buffer, in descriptors (0 = the default,
  * 2 * max_extrema: small values exercise the grow-and-rerun path of popsift_hip_wait for descriptors). */
 enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_HIP_DEBUG_OHIST_CAP = 3,
-       POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, POPSIFT_HIP_DEBUG_PYR_ORDER = 6,
+       POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, /* 6: retired, never reused */
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
        POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
        POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13 };

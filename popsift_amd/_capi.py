@@ -144,7 +144,7 @@ SYMBOLS = [
 ]
 MATCH_AUTO, MATCH_EXACT, MATCH_SCREEN = 0, 1, 2
 STAGES = ("pyramid", "detect", "refine", "orientation", "scan", "descriptor")
-DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_PYR_ORDER, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 6, 7
+DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 7  # 6: retired
 DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL, DEBUG_DIRECT_PATH, DEBUG_DESC_CAP = 8, 9, 10, 11, 12
 DEBUG_SCALE_PATH = 13
 MAX_BATCH = 16

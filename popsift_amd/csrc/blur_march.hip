@@ -37,9 +37,6 @@ constexpr int MCH = 32;  /* rows per step           */
 constexpr int MNR = 64;  /* ring rows: two chunks   */
 constexpr int MNT = 256; /* lanes per workgroup     */
 
-/* wait for this wave's LDS operations, then the workgroup barrier; vector-memory loads stay in flight */
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <bool EDGE>
 __device__ __forceinline__ v4f load_chunk(const float* __restrict__ row, int gx0, int w)
 {

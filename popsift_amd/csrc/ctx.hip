@@ -37,17 +37,13 @@ namespace {
 constexpr int PITCH_ALIGN = 64; /* floats: rows start on 256 B */
 constexpr int PROFILE_REPS = 4; /* launches per event pair in profile mode */
 
-struct HostTables {
-    float filter[POPSIFT_HIP_MAX_LEVELS * PS_GA];
-    int   span[POPSIFT_HIP_MAX_LEVELS];
-    float sigma[POPSIFT_HIP_MAX_LEVELS];
-};
-
-/* the dd table of the ScaleDirect scaling mode: row o blurs octave o's level 0 straight from the input image */
-struct DdTables {
-    float filter[POPSIFT_HIP_MAX_OCTAVES * PS_GA];
-    int   span[POPSIFT_HIP_MAX_OCTAVES];
-    float sigma[POPSIFT_HIP_MAX_OCTAVES];
+/* N rows of a Gauss table: inc and abs_o0 have one row per level, dd (ScaleDirect) one per octave -- row o blurs octave
+ * o's level 0 straight from the input image */
+template <int N>
+struct GaussRows {
+    float filter[N * PS_GA];
+    int   span[N];
+    float sigma[N];
 };
 
 struct EventPair {
@@ -56,73 +52,87 @@ struct EventPair {
     bool       big; /* level launch (MODE 0) with 64-row tiles */
 };
 
+/* A grow-only device buffer of `cap` units of PER elements each, grown by grow().  A failed grow or free leaves p and
+ * cap consistent: null with capacity 0, or the old buffer. */
+template <class T, size_t PER = 1>
+struct DevBuf {
+    T*     p = nullptr;
+    size_t cap = 0;
+    hipError_t release()
+    {
+        const hipError_t e = p ? hipFree(p) : hipSuccess;
+        if (e == hipSuccess) {
+            p = nullptr;
+            cap = 0;
+        }
+        return e;
+    }
+};
+
 }  // namespace
 
 /* Device memory of ONE image of a batch (sift_types.h, Slot): what a single-image context owned.  Grow-only. */
 struct ImageSlot {
-    void*   d_input = nullptr;
-    size_t  input_cap = 0;
-    void*   h_input = nullptr; /* pinned staging: submit() copies the caller's image before returning */
-    size_t  h_input_cap = 0;
-    float*  d_arena = nullptr;
-    size_t  arena_cap = 0; /* floats */
-    InitExt* d_iext = nullptr;
-    InitExt* d_iext2 = nullptr;      /* grid filter output (filter enabled only) */
-    FilterState* d_fstate = nullptr;
-    int*     d_fhist = nullptr;
-    Ext*     d_ext = nullptr;
-    float*   d_ohist = nullptr; /* raw orientation histograms, 36 floats per extremum (k_orientation -> k_scan_local) */
-    size_t   ohist_cap = 0;     /* extrema */
-    popsift_hip_feature* d_feats = nullptr;
-    size_t   iext_cap = 0, iext2_cap = 0, extrec_cap = 0, feats_cap = 0;
-    int*     d_map = nullptr;
-    float2*  d_rot = nullptr; /* (cos, sin) of every descriptor's orientation, correctly rounded (k_scan_apply) */
-    DescRec* d_drec = nullptr; /* per-descriptor constants of the loop descriptor (k_scan_apply -> k_descriptor) */
-    float*   d_desc = nullptr;
-    int      desc_cap = 0;
-    int2*    d_cand = nullptr;
-    int      cand_cap = 0;
-    int*     d_partial = nullptr; /* one partial sum per scan chunk */
-    size_t   partial_cap = 0;
-    int*     d_ovf = nullptr;     /* detection strips handed to the slow pass */
-    size_t   ovf_cap = 0;
-    bool     sized = false;       /* the buffers fit the context's current geometry */
+    DevBuf<char> input;
+    void*        h_input = nullptr; /* pinned staging: submit() copies the caller's image before returning */
+    size_t       h_input_cap = 0;
+    DevBuf<float>       arena;
+    DevBuf<InitExt>     iext;
+    DevBuf<InitExt>     iext2; /* grid filter output (filter enabled only) */
+    DevBuf<FilterState> fstate;
+    DevBuf<int>         fhist;
+    DevBuf<Ext>         ext;
+    DevBuf<float, PS_ORI_NBINS> ohist; /* raw orientation histograms, one per extremum (k_orientation -> k_scan_local) */
+    DevBuf<popsift_hip_feature> feats;
+    /* the descriptor group, grown as one (slot_desc_cap): desc_cap() descriptors */
+    DevBuf<float, 128> desc;
+    DevBuf<int>        map;
+    DevBuf<float2>     rot;  /* (cos, sin) of every descriptor's orientation, correctly rounded (k_scan_apply) */
+    DevBuf<DescRec>    drec; /* per-descriptor constants of the loop descriptor (k_scan_apply -> k_descriptor) */
+    DevBuf<int2>       cand;
+    DevBuf<int>        partial; /* one partial sum per scan chunk */
+    DevBuf<int>        ovf;     /* detection strips handed to the slow pass */
+    bool               sized = false; /* the buffers fit the context's current geometry */
     /* second result slab (popsift_hip_fetch_begin_item): the download of this image reads one slab on copy_stream while the
-     * kernels of the next batch write the other.  Invariant: alt caps <= the current slab's; fetch_begin equalises and swaps */
-    popsift_hip_feature* alt_feats = nullptr;
-    size_t   alt_feats_cap = 0;
-    float*   alt_desc = nullptr;
-    int      alt_desc_cap = 0;
-    bool     moved = false; /* the finished image's results went to fetch_begin: the current slab is stale */
-    /* descriptors as bytes (popsift_hip_fetch*_u8), allocated on the first byte request and grown with the slab: desc_cap
-     * descriptors of 128 bytes.  One buffer, not swapped: every path that writes it waits for a pending download first */
-    uint8_t* d_desc_u8 = nullptr;
-    int      desc_u8_cap = 0;
-    bool     u8_read = false; /* a popsift_hip_fetch_begin*_u8 download reads d_desc_u8 (until copy_stream is waited for) */
+     * kernels of the next batch write the other.  fetch_begin grows the alt buffers to the current slab's and swaps */
+    DevBuf<popsift_hip_feature> alt_feats;
+    DevBuf<float, 128>          alt_desc;
+    bool moved = false; /* the finished image's results went to fetch_begin: the current slab is stale */
+    /* descriptors as bytes (popsift_hip_fetch*_u8), allocated on the first byte request and grown with the slab.  One
+     * buffer, not swapped: every path that writes it waits for a pending download first */
+    DevBuf<uint8_t, 128> desc_u8;
+    bool u8_read = false; /* a popsift_hip_fetch_begin*_u8 download reads desc_u8 (until copy_stream is waited for) */
     /* describe (popsift_hip_describe_batch) only, grown on the first describe: the frames (device copy and pinned staging),
      * the per-chunk counts of the partition, list position <-> frame, k_scan_apply's records in list order */
-    popsift_hip_frame*   d_frames = nullptr;
-    popsift_hip_frame*   h_frames = nullptr;
-    size_t               frames_cap = 0, h_frames_cap = 0;
-    int*                 d_fcounts = nullptr;
-    size_t               fcounts_cap = 0;
-    int*                 d_perm = nullptr;
-    int*                 d_inv = nullptr;
-    size_t               perm_cap = 0, inv_cap = 0;
-    popsift_hip_feature* d_lfeats = nullptr;
-    size_t               lfeats_cap = 0;
-    int                  n_frames = 0; /* frames of the described image */
+    DevBuf<popsift_hip_frame>   frames;
+    popsift_hip_frame*          h_frames = nullptr;
+    DevBuf<int>                 fcounts, perm, inv;
+    DevBuf<popsift_hip_feature> lfeats;
+    int n_frames = 0; /* frames of the described image */
+
+    /* the descriptor group's capacity: 0 after a failed grow of any of its buffers */
+    size_t desc_cap() const { return std::min({desc.cap, map.cap, rot.cap, drec.cap}); }
+
+    /* every buffer of the slot (popsift_hip_ctx_destroy) */
+    void release()
+    {
+        auto each = [](auto&... b) { ((void)b.release(), ...); };
+        each(input, arena, iext, iext2, fstate, fhist, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
+             alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats);
+        if (h_input) (void)hipHostFree(h_input);
+        if (h_frames) (void)hipHostFree(h_frames);
+    }
 };
 
 struct popsift_hip_ctx {
     int                device = 0;
     popsift_hip_params p{};
     int                levels = 3, L = 6;
-    HostTables         tab{};
-    HostTables         abs0{};           /* vlfeat-direct (gauss_mode 2): abs_o0, octave 0's levels from the input image */
+    GaussRows<POPSIFT_HIP_MAX_LEVELS> tab{};
+    GaussRows<POPSIFT_HIP_MAX_LEVELS> abs0{}; /* vlfeat-direct (gauss_mode 2): abs_o0, octave 0's levels from the input image */
     float*             d_abs0 = nullptr; /* abs0.filter on the device (the fused kernel's taps), gauss_mode 2 only */
     int                direct_path = 0;  /* DIRECT_PATH debug switch: 0 fused octave-0 kernel, 1 one level-0 launch per level */
-    DdTables           dd{};             /* ScaleDirect (params.scale_direct = 1): dd, every octave's level 0 from the input */
+    GaussRows<POPSIFT_HIP_MAX_OCTAVES> dd{}; /* ScaleDirect (params.scale_direct = 1): dd, every octave's level 0 from the input */
     float*             d_dd = nullptr;   /* dd.filter on the device (the level-0 launch's horizontal taps), ScaleDirect only */
     int                scale_path = 0;   /* SCALE_PATH debug switch: 0 all-octave launches, 1 per-octave launches */
     SiftConsts         sc{};
@@ -147,14 +157,13 @@ struct popsift_hip_ctx {
     int       kp_waves = 65536; /* launch size of the keypoint kernels in waves (8 per wave slot of the device) */
     int       det_qcap = 1 << 30;  /* popsift_hip_debug_set hooks, see popsift_hip.h */
     int       desc_rows = 1 << 30;
-    int       pyr_order = 0;
     BlurTune  blur_tune{0, 0}; /* BLUR_PATH / BLUR_SEG debug switches */
     int       pyr_tail = 0;    /* PYR_TAIL: 0 the smallest octaves in one launch where they fit, 1 level launches only */
     int       cand_cap_init = 1 << 20;
     bool      cand_cap_user = false;
     int       ohist_cap_init = 0;
     int       desc_cap_init = 0; /* DESC_CAP debug switch: initial descriptor capacity (0 = 2 * max_extrema) */
-    size_t    ext_cap = 0; /* entries every one of d_iext/d_ext/d_feats(/d_iext2) of the sized slots holds */
+    size_t    ext_cap = 0; /* entries every one of iext/ext/feats(/iext2) of the sized slots holds */
     /* capacities the kernels are told: the smallest over the slots of the batch (refresh_caps) */
     int       cand_cap = 0, desc_cap = 0;
     size_t    ohist_cap = 0;
@@ -229,14 +238,15 @@ int span_for(int gauss_mode, float sigma)
     return std::min<int>(ceilf(4.0f * sigma) + 1, PS_GA - 1);
 }
 
-/* GaussTable::computeBlurTable (gauss_filter.cu:340-372): spans and normalised half filters of the n rows of sigma */
-void compute_filter_rows(float* filter, int* span, const float* sigma, int n, int gauss_mode)
+/* GaussTable::computeBlurTable (gauss_filter.cu:340-372): spans and normalised half filters of the N rows of t.sigma */
+template <int N>
+void compute_filter_rows(GaussRows<N>& t, int gauss_mode)
 {
-    for (int level = 0; level < n; level++) {
-        span[level] = std::min(span_for(gauss_mode, sigma[level]), PS_GA - 1);
-        const float sig = sigma[level];
-        const int   spn = span[level];
-        float*      f = &filter[level * PS_GA];
+    for (int level = 0; level < N; level++) {
+        t.span[level] = std::min(span_for(gauss_mode, t.sigma[level]), PS_GA - 1);
+        const float sig = t.sigma[level];
+        const int   spn = t.span[level];
+        float*      f = &t.filter[level * PS_GA];
         double      sum = 1.0;
         f[0] = 1.0f;
         for (int x = 1; x < spn; x++) {
@@ -249,8 +259,6 @@ void compute_filter_rows(float* filter, int* span, const float* sigma, int n, in
     }
 }
 
-void compute_filters(HostTables& t, int gauss_mode) { compute_filter_rows(t.filter, t.span, t.sigma, POPSIFT_HIP_MAX_LEVELS, gauss_mode); }
-
 /* init_filter (inc table; dd[0] is identical to inc[0]) gauss_filter.cu:163-181,340-372
  * and init_constants sift_constants.cu:22-31 */
 void init_tables(popsift_hip_ctx* c)
@@ -259,7 +267,7 @@ void init_tables(popsift_hip_ctx* c)
     const float sigma0 = p.sigma;
     const int   levels = c->levels;
     const float initial_blur = p.assume_initial_blur ? p.initial_blur * powf(2.0f, p.upscale_factor) : 0.0f;
-    HostTables& t = c->tab;
+    auto&       t = c->tab;
     memset(&t, 0, sizeof(t));
     t.sigma[0] = p.assume_initial_blur ? sqrtf(fabsf(sigma0 * sigma0 - initial_blur * initial_blur)) : sigma0;
     for (int lvl = 1; lvl < c->L; lvl++) {
@@ -267,30 +275,30 @@ void init_tables(popsift_hip_ctx* c)
         const float sigmaS = sigma0 * powf(2.0f, (float)(lvl) / (float)levels);
         t.sigma[lvl] = sqrtf(sigmaS * sigmaS - sigmaP * sigmaP);
     }
-    compute_filters(t, p.gauss_mode);
+    compute_filter_rows(t, p.gauss_mode);
     /* abs_o0 (gauss_filter.cu:190-199): octave 0's level l straight from the input image, sigma relative to the assumed
      * blur of the input; spans by the VLFeat rule (GaussInfo::getSpan for VLFeat_Relative_All).  abs0.sigma[0] equals
      * tab.sigma[0] (sqrt(RN(s * s)) == s), so level 0 is the default mode's level 0. */
-    HostTables& a0 = c->abs0;
+    auto& a0 = c->abs0;
     memset(&a0, 0, sizeof(a0));
     if (p.gauss_mode == POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL) {
         for (int lvl = 0; lvl < c->L; lvl++) {
             const float sigmaS = sigma0 * powf(2.0f, (float)lvl / (float)levels);
             a0.sigma[lvl] = sqrtf(fabsf(sigmaS * sigmaS - initial_blur * initial_blur));
         }
-        compute_filters(a0, p.gauss_mode);
+        compute_filter_rows(a0, p.gauss_mode);
     }
     /* dd (gauss_filter.cu:217-236): octave o's level 0 blurred straight from the input image; the blur is sigma0 * 2^o
      * less the assumed blur of the input, in octave-o pixels.  dd.sigma[0] equals tab.sigma[0], so octave 0 is the
      * default mode's octave 0. */
-    DdTables& dd = c->dd;
+    auto& dd = c->dd;
     memset(&dd, 0, sizeof(dd));
     for (int oct = 0; oct < POPSIFT_HIP_MAX_OCTAVES; oct++) {
         const float oct_sigma = ldexpf(sigma0, oct);
         const float b = sqrtf(fabsf(oct_sigma * oct_sigma - initial_blur * initial_blur));
         dd.sigma[oct] = ldexpf(b, -oct);
     }
-    compute_filter_rows(dd.filter, dd.span, dd.sigma, POPSIFT_HIP_MAX_OCTAVES, p.gauss_mode);
+    compute_filter_rows(dd, p.gauss_mode);
     SiftConsts& sc = c->sc;
     sc.sigma0 = sigma0;
     sc.sigma_k = powf(2.0f, 1.0f / levels);
@@ -331,112 +339,69 @@ hipError_t ctx_malloc(popsift_hip_ctx* c, void** p, size_t bytes)
     return hipMalloc(p, bytes);
 }
 
-template <typename T>
-int grow(popsift_hip_ctx* c, T** ptr, size_t* cap, size_t need)
+template <class T, size_t PER>
+int grow(popsift_hip_ctx* c, DevBuf<T, PER>& b, size_t need)
 {
-    if (need <= *cap) return 0;
-    if (*ptr) HIP_TRY(c, hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    HIP_TRY(c, ctx_malloc(c, (void**)ptr, need * sizeof(T)));
-    *cap = need;
+    if (need <= b.cap) return 0;
+    HIP_TRY(c, b.release());
+    HIP_TRY(c, ctx_malloc(c, (void**)&b.p, need * PER * sizeof(T)));
+    b.cap = need;
     return 0;
 }
 
 /* the capacities the kernels are told = the smallest over the slots of the batch, and the kernels' slot table */
 void refresh_caps(popsift_hip_ctx* c)
 {
-    int    cand = 1 << 30, desc = 1 << 30;
-    size_t hist = (size_t)1 << 40;
+    size_t cand = 1 << 30, desc = 1 << 30, hist = (size_t)1 << 40;
     for (int k = 0; k < c->nb; k++) {
         const ImageSlot& s = c->slot[k];
-        cand = std::min(cand, s.cand_cap);
-        desc = std::min(desc, s.desc_cap);
-        hist = std::min(hist, s.ohist_cap);
+        cand = std::min(cand, s.cand.cap);
+        desc = std::min(desc, s.desc_cap());
+        hist = std::min(hist, s.ohist.cap);
         Slot& v = c->bd.s[k];
-        v.arena = s.d_arena;
+        v.arena = s.arena.p;
         v.ct = c->d_ct + k;
-        v.cand = s.d_cand;
-        v.ovf = s.d_ovf;
-        v.iext = s.d_iext;
-        v.iext2 = s.d_iext2;
-        v.fstate = s.d_fstate;
-        v.fhist = s.d_fhist;
-        v.ohist = s.d_ohist;
-        v.ext = s.d_ext;
-        v.partial = s.d_partial;
-        v.map = s.d_map;
-        v.rot = s.d_rot;
-        v.drec = s.d_drec;
-        v.feats = s.d_feats;
-        v.desc = s.d_desc;
+        v.cand = s.cand.p;
+        v.ovf = s.ovf.p;
+        v.iext = s.iext.p;
+        v.iext2 = s.iext2.p;
+        v.fstate = s.fstate.p;
+        v.fhist = s.fhist.p;
+        v.ohist = s.ohist.p;
+        v.ext = s.ext.p;
+        v.partial = s.partial.p;
+        v.map = s.map.p;
+        v.rot = s.rot.p;
+        v.drec = s.drec.p;
+        v.feats = s.feats.p;
+        v.desc = s.desc.p;
     }
-    c->cand_cap = cand;
-    c->desc_cap = desc;
+    c->cand_cap = (int)cand;
+    c->desc_cap = (int)desc;
     c->ohist_cap = hist;
 }
 
-int slot_desc_cap(popsift_hip_ctx* c, ImageSlot& s, int need)
+/* the descriptor group: all four buffers are freed, then allocated in order, so that a failure anywhere leaves
+ * desc_cap() = 0 and the next grow allocates all four again */
+int slot_desc_cap(popsift_hip_ctx* c, ImageSlot& s, size_t need)
 {
-    if (need <= s.desc_cap) return 0;
-    if (s.d_desc) HIP_TRY(c, hipFree(s.d_desc));
-    if (s.d_map) HIP_TRY(c, hipFree(s.d_map));
-    if (s.d_rot) HIP_TRY(c, hipFree(s.d_rot));
-    if (s.d_drec) HIP_TRY(c, hipFree(s.d_drec));
-    s.d_desc = nullptr;
-    s.d_map = nullptr;
-    s.d_rot = nullptr;
-    s.d_drec = nullptr;
-    s.desc_cap = 0;
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_desc, (size_t)need * 128 * sizeof(float)));
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_map, (size_t)need * sizeof(int)));
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_rot, (size_t)need * sizeof(float2)));
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_drec, (size_t)need * sizeof(DescRec)));
-    s.desc_cap = need;
-    return 0;
+    if (need <= s.desc_cap()) return 0;
+    HIP_TRY(c, s.desc.release());
+    HIP_TRY(c, s.map.release());
+    HIP_TRY(c, s.rot.release());
+    HIP_TRY(c, s.drec.release());
+    if (int rc = grow(c, s.desc, need)) return rc;
+    if (int rc = grow(c, s.map, need)) return rc;
+    if (int rc = grow(c, s.rot, need)) return rc;
+    return grow(c, s.drec, need);
 }
 
-int slot_ohist_cap(popsift_hip_ctx* c, ImageSlot& s, size_t need)
-{
-    if (need <= s.ohist_cap) return 0;
-    if (s.d_ohist) HIP_TRY(c, hipFree(s.d_ohist));
-    s.d_ohist = nullptr;
-    s.ohist_cap = 0;
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_ohist, need * PS_ORI_NBINS * sizeof(float)));
-    s.ohist_cap = need;
-    return 0;
-}
-
-int slot_cand_cap(popsift_hip_ctx* c, ImageSlot& s, int need)
-{
-    if (need <= s.cand_cap) return 0;
-    if (s.d_cand) HIP_TRY(c, hipFree(s.d_cand));
-    s.d_cand = nullptr;
-    s.cand_cap = 0;
-    HIP_TRY(c, ctx_malloc(c, (void**)&s.d_cand, (size_t)need * sizeof(int2)));
-    s.cand_cap = need;
-    return 0;
-}
-
-/* grow a list of every slot of the batch; the kernels' capacities follow whatever the outcome */
-int ensure_desc_cap(popsift_hip_ctx* c, int need)
+/* grow a buffer of every slot of the batch (grow_slot); the kernels' capacities follow whatever the outcome */
+template <typename F>
+int ensure_cap(popsift_hip_ctx* c, F grow_slot)
 {
     int rc = 0;
-    for (int k = 0; k < c->nb && !rc; k++) rc = slot_desc_cap(c, c->slot[k], need);
-    refresh_caps(c);
-    return rc;
-}
-int ensure_ohist_cap(popsift_hip_ctx* c, size_t need)
-{
-    int rc = 0;
-    for (int k = 0; k < c->nb && !rc; k++) rc = slot_ohist_cap(c, c->slot[k], need);
-    refresh_caps(c);
-    return rc;
-}
-int ensure_cand_cap(popsift_hip_ctx* c, int need)
-{
-    int rc = 0;
-    for (int k = 0; k < c->nb && !rc; k++) rc = slot_cand_cap(c, c->slot[k], need);
+    for (int k = 0; k < c->nb && !rc; k++) rc = grow_slot(c->slot[k]);
     refresh_caps(c);
     return rc;
 }
@@ -511,22 +476,21 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
     for (int k = 0; k < nb; k++) {
         ImageSlot& s = c->slot[k];
         if (s.sized) continue;
-        if (int rc = grow(c, &s.d_arena, &s.arena_cap, total)) return rc;
+        if (int rc = grow(c, s.arena, total)) return rc;
         /* each buffer keeps its own capacity: a failed grow leaves the others consistent */
-        if (int rc = grow(c, &s.d_iext, &s.iext_cap, need_ext)) return rc;
-        if (int rc = grow(c, &s.d_ext, &s.extrec_cap, need_ext)) return rc;
-        if (int rc = grow(c, &s.d_feats, &s.feats_cap, need_ext)) return rc;
+        if (int rc = grow(c, s.iext, need_ext)) return rc;
+        if (int rc = grow(c, s.ext, need_ext)) return rc;
+        if (int rc = grow(c, s.feats, need_ext)) return rc;
         if (c->sc.filter_max > 0) {
-            if (int rc = grow(c, &s.d_iext2, &s.iext2_cap, need_ext)) return rc;
-            if (!s.d_fstate) HIP_TRY(c, ctx_malloc(c, (void**)&s.d_fstate, sizeof(FilterState)));
-            if (!s.d_fhist) HIP_TRY(c, ctx_malloc(c, (void**)&s.d_fhist, filter_hist_bytes(c->sc.grid_size)));
+            if (int rc = grow(c, s.iext2, need_ext)) return rc;
+            if (int rc = grow(c, s.fstate, 1)) return rc;
+            if (int rc = grow(c, s.fhist, filter_hist_bytes(c->sc.grid_size) / sizeof(int))) return rc;
         }
-        if (int rc = grow(c, &s.d_partial, &s.partial_cap, (need_ext / scan_chunk() + 2) * scan_partials_per_chunk())) return rc;
+        if (int rc = grow(c, s.partial, (need_ext / scan_chunk() + 2) * scan_partials_per_chunk())) return rc;
         /* sift_pyramid.cu:149: max(2*max_extrema, max_orientations) descriptors to start with */
         const int desc0 = c->desc_cap_init > 0 ? c->desc_cap_init
                                                : std::max(2 * c->sc.max_extrema, c->sc.max_extrema + c->sc.max_extrema / 4);
-        if (int rc = slot_desc_cap(c, s, std::max(desc0, c->desc_cap)))
-            return rc;
+        if (int rc = slot_desc_cap(c, s, std::max(desc0, c->desc_cap))) return rc;
         /* candidates: 64 region slices of one buffer (extrema.hip); a default-sized buffer grows with the pyramid, so that
          * the first image of a 4K stream does not overflow a slice and re-run (a test's explicit CAND_CAP is taken as is) */
         int cand0 = std::max(c->cand_cap_init, DET_SUBQ);
@@ -535,14 +499,14 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
             for (int o = 0; o < pd.n_oct; o++) px += (double)pd.o[o].w * pd.o[o].h;
             cand0 = std::max(cand0, (int)std::min(px / 8.0, 64.0 * 1024 * 1024));
         }
-        if (int rc = slot_cand_cap(c, s, std::max(cand0, c->cand_cap))) return rc;
+        if (int rc = grow(c, s.cand, std::max(cand0, c->cand_cap))) return rc;
         /* orientation histograms: 2 * max_extrema extrema to start with (all octaves together seldom exceed one octave's
          * cap); finish() grows the buffer and re-runs the keypoint stages when an image has more */
-        if (int rc = slot_ohist_cap(c, s, std::max(c->ohist_cap_init > 0 ? (size_t)c->ohist_cap_init
-                                                                        : std::min(need_ext, (size_t)2 * c->sc.max_extrema),
-                                                   c->slot[0].sized ? c->ohist_cap : (size_t)0)))
+        if (int rc = grow(c, s.ohist, std::max(c->ohist_cap_init > 0 ? (size_t)c->ohist_cap_init
+                                                                      : std::min(need_ext, (size_t)2 * c->sc.max_extrema),
+                                               c->slot[0].sized ? c->ohist_cap : (size_t)0)))
             return rc;
-        if (int rc = grow(c, &s.d_ovf, &s.ovf_cap, (size_t)pd.total_tiles + 1)) return rc;
+        if (int rc = grow(c, s.ovf, (size_t)pd.total_tiles + 1)) return rc;
         s.sized = true;
     }
     c->ext_cap = need_ext;
@@ -563,7 +527,11 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
     return 0;
 }
 
-int blur_launch(popsift_hip_ctx* c, const BlurArgs& a, int mode, int span, int tile_h, double alg_bytes)
+/* Profile mode 1 brackets PROFILE_REPS back-to-back launches with one event pair: the event-to-kernel gap (~4 us, as large
+ * as a small launch itself) is amortised instead of being billed per launch.  Every launch timed here is idempotent (a
+ * level launch reads plane l-1, writes plane l and DoG l-1).  big: a level launch (MODE 0) with 64-row tiles. */
+template <typename F>
+int timed_launch(popsift_hip_ctx* c, double alg_bytes, const char* what, F launch, bool big = false)
 {
     if (c->profile == 1) {
         if (c->blur_events_used == c->blur_events.size()) {
@@ -574,18 +542,34 @@ int blur_launch(popsift_hip_ctx* c, const BlurArgs& a, int mode, int span, int t
         }
         EventPair& ep = c->blur_events[c->blur_events_used++];
         ep.bytes = alg_bytes * c->nb;
-        ep.big = (mode == 0 && tile_h == 64);
-        /* A level launch is idempotent (reads plane l-1, writes plane l and DoG l-1), so profile mode
-         * brackets PROFILE_REPS back-to-back launches with one event pair: the event-to-kernel gap
-         * (~4 us, as large as a small launch itself) is amortised instead of being billed per launch. */
+        ep.big = big;
         HIP_TRY(c, hipEventRecord(ep.a, c->stream));
-        for (int rep = 0; rep < PROFILE_REPS; rep++) HIP_TRY(c, launch_blur(a, c->bd, c->nb, mode, span, tile_h, c->stream, c->blur_tune));
+        for (int rep = 0; rep < PROFILE_REPS; rep++) HIP_TRY(c, launch());
         HIP_TRY(c, hipEventRecord(ep.b, c->stream));
     } else {
-        HIP_TRY(c, launch_blur(a, c->bd, c->nb, mode, span, tile_h, c->stream, c->blur_tune));
-        SYNC_CHK(c, "k_blur_tile");
+        HIP_TRY(c, launch());
+        SYNC_CHK(c, what);
     }
+    (void)what;
     return 0;
+}
+
+int blur_launch(popsift_hip_ctx* c, const BlurArgs& a, int mode, int span, int tile_h, double alg_bytes)
+{
+    return timed_launch(
+        c, alg_bytes, "k_blur_tile", [&] { return launch_blur(a, c->bd, c->nb, mode, span, tile_h, c->stream, c->blur_tune); },
+        mode == 0 && tile_h == 64);
+}
+
+/* the size of octave o's plane and its tile grid for tile_h-row tiles (BlurArgs, DirectArgs) */
+template <typename A>
+void set_plane(A& a, const OctDesc& od, int tile_h)
+{
+    a.w = od.w;
+    a.h = od.h;
+    a.pitch = od.pitch;
+    a.tiles_x = (od.w + blur_tile_w() - 1) / blur_tile_w();
+    a.tiles_y = (od.h + tile_h - 1) / tile_h;
 }
 
 /* arguments of the launch that produces plane `level` (>= 1) of octave o from plane level - 1 */
@@ -594,12 +578,7 @@ BlurArgs level_args(const popsift_hip_ctx* c, int o, int level)
     const PyrDesc& pd = c->pd;
     const OctDesc& od = pd.o[o];
     BlurArgs       a{};
-    a.w = od.w;
-    a.h = od.h;
-    a.pitch = od.pitch;
-    const int thd = blur_tile_h(od.w, od.h), twd = blur_tile_w();
-    a.tiles_x = (od.w + twd - 1) / twd;
-    a.tiles_y = (od.h + thd - 1) / thd;
+    set_plane(a, od, blur_tile_h(od.w, od.h));
     memcpy(a.taps.g, &c->tab.filter[level * PS_GA], sizeof(a.taps.g));
     a.dst_off = od.data_off + level * od.plane_stride;
     a.src_off = od.data_off + (level - 1) * od.plane_stride;
@@ -618,30 +597,28 @@ float input_shift(const popsift_hip_ctx* c)
     return 0.5f;
 }
 
-/* profile mode 1 brackets PROFILE_REPS back-to-back launches with one event pair (see blur_launch); every launch of
- * the octave-0 paths below is idempotent */
-template <typename F>
-int timed_launch(popsift_hip_ctx* c, double alg_bytes, const char* what, F launch)
+/* Arguments of a launch that samples the input image into level 0 of octave o, tile_h-row tiles (horiz_from_input_image,
+ * s_pyramid_build.cu:96-126); the taps are the caller's.  The launch also clears the images' counters
+ * (enqueue_keypoint_stages(c, true)). */
+BlurArgs input_args(const popsift_hip_ctx* c, int o, int tile_h, int is_f32, int pitch, bool aligned4)
 {
-    if (c->profile == 1) {
-        if (c->blur_events_used == c->blur_events.size()) {
-            EventPair ep;
-            HIP_TRY(c, hipEventCreate(&ep.a));
-            HIP_TRY(c, hipEventCreate(&ep.b));
-            c->blur_events.push_back(ep);
-        }
-        EventPair& ep = c->blur_events[c->blur_events_used++];
-        ep.bytes = alg_bytes * c->nb;
-        ep.big = false;
-        HIP_TRY(c, hipEventRecord(ep.a, c->stream));
-        for (int rep = 0; rep < PROFILE_REPS; rep++) HIP_TRY(c, launch());
-        HIP_TRY(c, hipEventRecord(ep.b, c->stream));
-    } else {
-        HIP_TRY(c, launch());
-        SYNC_CHK(c, what);
-    }
-    (void)what;
-    return 0;
+    const OctDesc& od = c->pd.o[o];
+    BlurArgs       a{};
+    set_plane(a, od, tile_h);
+    a.dst_off = od.data_off;
+    a.src_off = 0;
+    a.dog_off = -1;
+    a.next0_off = -1;
+    a.in_w = c->in_w;
+    a.in_h = c->in_h;
+    a.in_pitch = pitch;
+    a.shift = input_shift(c);
+    /* weights of the linear upscale are exactly {0, 1/2}: k_blur_tile's copy / average path */
+    a.fast2x = (c->p.upscale_factor == 1.0f && a.shift == 1.0f && od.w == 2 * c->in_w && od.h == 2 * c->in_h) ? 1 : 0;
+    /* ... and u8 images whose rows all start on 4-byte boundaries: the texels are fetched as aligned dwords */
+    if (a.fast2x && !is_f32 && aligned4) a.fast2x = 2;
+    a.zero_words = (int)(sizeof(Counters) / sizeof(int));
+    return a;
 }
 
 /*
@@ -657,54 +634,34 @@ int enqueue_direct_octave0(popsift_hip_ctx* c, int is_f32, int pitch, bool align
     const PyrDesc& pd = c->pd;
     const OctDesc& od = pd.o[0];
     const int      L = pd.L;
-    const int      zero_words = (int)(sizeof(Counters) / sizeof(int));
     const int64_t  next0_off = pd.n_oct > 1 ? pd.o[1].data_off : -1;
     const double   in_bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1);
     const double   px = (double)od.w * od.h;
     if (c->direct_path == 0) {
         DirectArgs a{};
+        set_plane(a, od, pyr_direct_tile_h());
         a.dst_off = od.data_off;
         a.dog_off = pd.dog_fly ? -1 : od.dog_off;
         a.plane_stride = od.plane_stride;
         a.next0_off = next0_off;
         a.taps = c->d_abs0;
-        a.w = od.w;
-        a.h = od.h;
-        a.pitch = od.pitch;
         a.next_pitch = pd.n_oct > 1 ? pd.o[1].pitch : 0;
-        a.tiles_x = (od.w + blur_tile_w() - 1) / blur_tile_w();
-        a.tiles_y = (od.h + pyr_direct_tile_h() - 1) / pyr_direct_tile_h();
         a.in_w = c->in_w;
         a.in_h = c->in_h;
         a.in_pitch = pitch;
         a.shift = input_shift(c);
         a.L = L;
         for (int l = 0; l < L; l++) a.halo[l] = c->abs0.span[l] - 1;
-        a.zero_words = zero_words;
+        a.zero_words = (int)(sizeof(Counters) / sizeof(int));
         const double bytes = in_bytes + 4.0 * px * (L + (pd.dog_fly ? 0 : L - 1)) + (next0_off >= 0 ? px : 0.0);
         return timed_launch(c, bytes, "k_pyr_direct", [&] { return launch_pyr_direct(a, c->bd, c->nb, is_f32, c->stream); });
     }
-    const int thd = blur_tile_h(od.w, od.h), twd = blur_tile_w();
+    const int thd = blur_tile_h(od.w, od.h);
     for (int l = 0; l < L; l++) {
-        BlurArgs a{};
-        a.w = od.w;
-        a.h = od.h;
-        a.pitch = od.pitch;
-        a.tiles_x = (od.w + twd - 1) / twd;
-        a.tiles_y = (od.h + thd - 1) / thd;
+        BlurArgs a = input_args(c, 0, thd, is_f32, pitch, aligned4);
         memcpy(a.taps.g, &c->abs0.filter[l * PS_GA], sizeof(a.taps.g));
-        a.dst_off = od.data_off + l * od.plane_stride;
-        a.src_off = 0;
-        a.dog_off = -1;
-        a.next0_off = -1;
-        a.in_w = c->in_w;
-        a.in_h = c->in_h;
-        a.in_pitch = pitch;
-        a.shift = input_shift(c);
-        /* the level-0 kernel's exact-2x paths, as in the default mode's level-0 launch */
-        a.fast2x = (c->p.upscale_factor == 1.0f && a.shift == 1.0f && od.w == 2 * c->in_w && od.h == 2 * c->in_h) ? 1 : 0;
-        if (a.fast2x && !is_f32 && aligned4) a.fast2x = 2;
-        a.zero_words = l == 0 ? zero_words : 0;
+        a.dst_off += l * od.plane_stride;
+        if (l > 0) a.zero_words = 0; /* the first launch clears the counters */
         const int span = c->abs0.span[l];
         if (int rc = timed_launch(c, in_bytes + 4.0 * px, "k_blur_tile (direct level)",
                                   [&] { return launch_blur(a, c->bd, c->nb, is_f32 ? 2 : 1, span, thd, c->stream, c->blur_tune); }))
@@ -741,29 +698,17 @@ int enqueue_scale_direct(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned
 {
     const PyrDesc& pd = c->pd;
     const int      L = pd.L;
-    const int      zero_words = (int)(sizeof(Counters) / sizeof(int));
     const double   in_bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1);
     Taps           vt;
     memcpy(vt.g, &c->tab.filter[0], sizeof(vt.g)); /* inc[0]: every octave's vertical pass of level 0 */
     int halo0 = c->tab.span[0] - 1;
     for (int o = 0; o < pd.n_oct; o++) halo0 = std::max(halo0, c->dd.span[o] - 1);
-    /* level 0: the input image and octave 0's sampling */
-    BlurArgs a0{};
-    a0.src_off = 0;
-    a0.dog_off = -1;
-    a0.next0_off = -1;
-    a0.in_w = c->in_w;
-    a0.in_h = c->in_h;
-    a0.in_pitch = pitch;
-    a0.shift = input_shift(c);
-    const OctDesc& od0 = pd.o[0];
-    a0.fast2x = (c->p.upscale_factor == 1.0f && a0.shift == 1.0f && od0.w == 2 * c->in_w && od0.h == 2 * c->in_h) ? 1 : 0;
-    if (a0.fast2x && !is_f32 && aligned4) a0.fast2x = 2;
-    a0.zero_words = zero_words;
     double px_all = 0.0;
     for (int o = 0; o < pd.n_oct; o++) px_all += (double)pd.o[o].w * pd.o[o].h;
     const double lvl_bpp = pd.dog_fly ? 8.0 : 12.0; /* read plane l-1, write plane l (and DoG l-1) */
     if (c->scale_path == 0) {
+        /* level 0: the input image and octave 0's sampling; the kernel takes each octave's plane and taps */
+        const BlurArgs a0 = input_args(c, 0, scale_tile_h(), is_f32, pitch, aligned4);
         if (int rc = timed_launch(c, in_bytes + 4.0 * px_all, "k_pyr_level0_octaves", [&] {
                 return launch_pyr_level0_octaves(a0, vt, c->d_dd, c->d_pd, pd, c->bd, c->nb, halo0, is_f32, c->stream);
             }))
@@ -781,13 +726,7 @@ int enqueue_scale_direct(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned
     }
     for (int o = 0; o < pd.n_oct; o++) {
         const OctDesc& od = pd.o[o];
-        BlurArgs       a = a0;
-        a.w = od.w;
-        a.h = od.h;
-        a.pitch = od.pitch;
-        a.tiles_x = (od.w + blur_tile_w() - 1) / blur_tile_w();
-        a.tiles_y = (od.h + scale_tile_h() - 1) / scale_tile_h();
-        a.dst_off = od.data_off;
+        BlurArgs       a = input_args(c, o, scale_tile_h(), is_f32, pitch, aligned4);
         memcpy(a.taps.g, &c->dd.filter[o * PS_GA], sizeof(a.taps.g));
         if (o > 0) {
             a.shift = 0.5f; /* s_pyramid_build.cu:109-114: octave 0's shift only */
@@ -834,38 +773,13 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
     if (direct) {
         if (int rc = enqueue_direct_octave0(c, is_f32, pitch, aligned4)) return rc;
     } else {
-        /* horiz_from_input_image, s_pyramid_build.cu:96-126 */
         const OctDesc& od = pd.o[0];
-        BlurArgs       a{};
-        a.w = od.w;
-        a.h = od.h;
-        a.pitch = od.pitch;
-        const int thd = blur_tile_h(od.w, od.h), twd = blur_tile_w();
-        a.tiles_x = (od.w + twd - 1) / twd;
-        a.tiles_y = (od.h + thd - 1) / thd;
+        const int      thd = blur_tile_h(od.w, od.h);
+        BlurArgs       a = input_args(c, 0, thd, is_f32, pitch, aligned4);
         memcpy(a.taps.g, &c->tab.filter[0], sizeof(a.taps.g));
-        a.dst_off = od.data_off;
-        a.src_off = 0;
-        a.dog_off = -1;
-        a.next0_off = -1;
-        float shift = 0.5f;
-        if (c->p.sift_mode == POPSIFT_HIP_SIFT_POPSIFT || c->p.sift_mode == POPSIFT_HIP_SIFT_VLFEAT)
-            shift = 0.5f * powf(2.0f, c->p.upscale_factor - 0);
-        a.in_w = c->in_w;
-        a.in_h = c->in_h;
-        a.in_pitch = pitch;
-        a.shift = shift;
-        /* weights of the linear upscale are exactly {0, 1/2}: k_blur_tile's copy / average path */
-        a.fast2x = (c->p.upscale_factor == 1.0f && shift == 1.0f && od.w == 2 * c->in_w && od.h == 2 * c->in_h) ? 1 : 0;
-        /* ... and u8 images whose rows all start on 4-byte boundaries: the texels are fetched as aligned dwords */
-        if (a.fast2x && !is_f32 && aligned4) a.fast2x = 2;
-        a.zero_words = (int)(sizeof(Counters) / sizeof(int)); /* this launch clears the images' counters (enqueue_keypoint_stages(c, true)) */
         const double bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1) + 4.0 * (double)od.w * od.h;
         if (int rc = blur_launch(c, a, is_f32 ? 2 : 1, c->tab.span[0], thd, bytes)) return rc;
     }
-    /* Level 1 of octave 1 reads what level L-3 of octave 0 has just written (every second pixel, 1/4 of a plane): launched
-     * right behind it, that plane still sits in the L2s; after levels L-2 and L-1 of octave 0 (2 x 66 MB through the
-     * caches) it came from HBM, and the launch took 14 us instead of 8 (round 2's "octave-1 anomaly"). */
     /* The smallest octaves -- from the first one whose plane fits the LDS of one workgroup -- are built by ONE launch
      * (pyr_tail.hip) instead of three dependent launches per octave; `n_front` octaves take the level launches. */
     int n_front = pd.n_oct;
@@ -893,21 +807,14 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
             }
         }
     }
-    /* vlfeat-direct: octave 0 is complete, octave 1's level 0 included, so "early" is any time from here on and the
-     * octave loop below takes level 1 of octave 1 in its place */
-    const bool early1 = !direct && c->pyr_order == 1 && n_front >= 2 && L - 3 >= 1;
-    for (int level = 1; level < L && !direct; level++) {
+    for (int level = 1; level < L && !direct; level++)
         if (int rc = single(0, level)) return rc;
-        if (early1 && level == L - 3)
-            if (int rc = single(1, 1)) return rc;
-    }
     for (int o = 1; o < n_front; o++) {
         /* per-launch profiling keeps one kernel per event pair; BLUR_PATH = 2 sends every plane-to-plane level through
          * the march kernels, so no level of it is paired into k_blur_duo */
         const bool pair = c->profile != 1 && c->blur_tune.path != 2 && o >= 2 && blur_tile_h(pd.o[o].w, pd.o[o].h) == 32 &&
                           blur_tile_h(pd.o[o - 1].w, pd.o[o - 1].h) == 32;
         for (int level = 1; level <= L - 3; level++) {
-            if (early1 && o == 1 && level == 1) continue; /* launched behind level L-3 of octave 0 */
             const int trail = L - 3 + level; /* L-2, L-1 of the octave before */
             if (pair && level <= 2) {
                 const BlurArgs a = level_args(c, o, level), b = level_args(c, o - 1, trail);
@@ -934,7 +841,7 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
 /* Pyramid::step2 + prep_features: extrema -> orientation -> scan -> descriptors -> features */
 InitExt* final_iext(popsift_hip_ctx* c, int k = 0)
 {
-    return c->sc.filter_max > 0 && !c->describe ? c->slot[k].d_iext2 : c->slot[k].d_iext; /* frames are not grid-filtered */
+    return c->sc.filter_max > 0 && !c->describe ? c->slot[k].iext2.p : c->slot[k].iext.p; /* frames are not grid-filtered */
 }
 
 /* counters_cleared: the level-0 launch of this batch has zeroed the counters (submit); re-runs clear them here */
@@ -981,13 +888,13 @@ int enqueue_describe_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     BatchDesc  lb = c->bd; /* k_scan_apply writes its feature records in list order, k_frame_out moves them */
     for (int k = 0; k < c->nb; k++) {
         const ImageSlot& sl = c->slot[k];
-        fb.s[k].frames = sl.d_frames;
-        fb.s[k].counts = sl.d_fcounts;
-        fb.s[k].perm = sl.d_perm;
-        fb.s[k].inv = sl.d_inv;
-        fb.s[k].lfeats = sl.d_lfeats;
+        fb.s[k].frames = sl.frames.p;
+        fb.s[k].counts = sl.fcounts.p;
+        fb.s[k].perm = sl.perm.p;
+        fb.s[k].inv = sl.inv.p;
+        fb.s[k].lfeats = sl.lfeats.p;
         fb.s[k].n = sl.n_frames;
-        lb.s[k].feats = sl.d_lfeats;
+        lb.s[k].feats = sl.lfeats.p;
     }
     if (!counters_cleared) HIP_TRY(c, hipMemsetAsync(c->d_ct, 0, sizeof(Counters) * (size_t)c->nb, c->stream));
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DETECT));
@@ -1030,15 +937,12 @@ struct DescribeArgs {
 int prepare_frames(popsift_hip_ctx* c, ImageSlot& s)
 {
     const size_t n = (size_t)c->sc.max_extrema;
-    if (int rc = grow(c, &s.d_frames, &s.frames_cap, n)) return rc;
-    if (int rc = grow(c, &s.d_fcounts, &s.fcounts_cap, (size_t)PS_MAX_OCT * frame_chunks(c->sc.max_extrema))) return rc;
-    if (int rc = grow(c, &s.d_perm, &s.perm_cap, n)) return rc;
-    if (int rc = grow(c, &s.d_inv, &s.inv_cap, n)) return rc;
-    if (int rc = grow(c, &s.d_lfeats, &s.lfeats_cap, n)) return rc;
-    if (!s.h_frames) {
-        HIP_TRY(c, hipHostMalloc((void**)&s.h_frames, n * sizeof(popsift_hip_frame), hipHostMallocDefault));
-        s.h_frames_cap = n;
-    }
+    if (int rc = grow(c, s.frames, n)) return rc;
+    if (int rc = grow(c, s.fcounts, (size_t)PS_MAX_OCT * frame_chunks(c->sc.max_extrema))) return rc;
+    if (int rc = grow(c, s.perm, n)) return rc;
+    if (int rc = grow(c, s.inv, n)) return rc;
+    if (int rc = grow(c, s.lfeats, n)) return rc;
+    if (!s.h_frames) HIP_TRY(c, hipHostMalloc((void**)&s.h_frames, n * sizeof(popsift_hip_frame), hipHostMallocDefault));
     return 0;
 }
 
@@ -1076,16 +980,11 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
             aligned4 = aligned4 && ((uintptr_t)imgs[k] & 3) == 0;
             continue;
         }
-        size_t cap = s.input_cap;
-        char*  buf = (char*)s.d_input;
-        const int rc_in = grow(c, &buf, &cap, (size_t)w * h * esz);
-        s.d_input = buf; /* also after a failed grow, which has freed the old buffer */
-        s.input_cap = cap;
-        if (rc_in) return rc_in;
         const size_t bytes = (size_t)w * h * esz;
+        if (int rc = grow(c, s.input, bytes)) return rc;
         if (where == 2) {
             /* page-locked memory of the caller, valid until wait(): uploaded from where it lies */
-            HIP_TRY(c, hipMemcpy2DAsync(s.d_input, (size_t)w * esz, imgs[k], (size_t)pitch * esz, (size_t)w * esz, (size_t)h,
+            HIP_TRY(c, hipMemcpy2DAsync(s.input.p, (size_t)w * esz, imgs[k], (size_t)pitch * esz, (size_t)w * esz, (size_t)h,
                                         hipMemcpyHostToDevice, c->stream));
         } else {
             /* Like Image::load (s_image.cu:71-79) the caller's buffer is copied into pinned memory before
@@ -1100,9 +999,9 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
             }
             for (int y = 0; y < h; y++)
                 memcpy((char*)s.h_input + (size_t)y * w * esz, (const char*)imgs[k] + (size_t)y * pitch * esz, (size_t)w * esz);
-            HIP_TRY(c, hipMemcpyAsync(s.d_input, s.h_input, bytes, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(s.input.p, s.h_input, bytes, hipMemcpyHostToDevice, c->stream));
         }
-        c->bd.s[k].input = s.d_input;
+        c->bd.s[k].input = s.input.p;
         dpitch = w;
     }
     if (where != 1) aligned4 = (dpitch & 3) == 0; /* hipMalloc'd buffers are aligned */
@@ -1118,7 +1017,7 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
         c->frames_max = std::max(c->frames_max, nf);
         if (nf > 0) {
             memcpy(s.h_frames, da->frames[k], (size_t)nf * sizeof(popsift_hip_frame));
-            HIP_TRY(c, hipMemcpyAsync(s.d_frames, s.h_frames, (size_t)nf * sizeof(popsift_hip_frame), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(s.frames.p, s.h_frames, (size_t)nf * sizeof(popsift_hip_frame), hipMemcpyHostToDevice, c->stream));
         }
     }
     c->blur_events_used = 0;
@@ -1165,11 +1064,15 @@ int finish(popsift_hip_ctx* c)
         /* more candidates / descriptors than the buffers hold (the reference reallocates between
          * stages, sift_pyramid.cu:179-209): grow and redo the keypoint stages of this batch */
         if (desc_short)
-            if (int rc = ensure_desc_cap(c, ori_max + ori_max / 8 + 1024)) return rc;
+            if (int rc = ensure_cap(c, [&](ImageSlot& s) { return slot_desc_cap(c, s, ori_max + ori_max / 8 + 1024); }))
+                return rc;
         if (cand_short)
-            if (int rc = ensure_cand_cap(c, DET_SUBQ * (qmax + qmax / 8 + 64))) return rc;
-        if (hist_short)
-            if (int rc = ensure_ohist_cap(c, (size_t)ext_max + (size_t)ext_max / 8 + 1024)) return rc;
+            if (int rc = ensure_cap(c, [&](ImageSlot& s) { return grow(c, s.cand, DET_SUBQ * (qmax + qmax / 8 + 64)); }))
+                return rc;
+        if (hist_short) {
+            const size_t need = (size_t)ext_max + (size_t)ext_max / 8 + 1024;
+            if (int rc = ensure_cap(c, [&](ImageSlot& s) { return grow(c, s.ohist, need); })) return rc;
+        }
         if (int rc = c->describe ? enqueue_describe_stages(c) : enqueue_keypoint_stages(c)) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_end, c->stream));
         rerun = true;
@@ -1260,13 +1163,7 @@ int slot_u8_ready(popsift_hip_ctx* c, ImageSlot& sl)
 {
     if (sl.u8_read && c->copy_pending) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     sl.u8_read = false;
-    if (sl.desc_u8_cap >= sl.desc_cap && sl.d_desc_u8) return 0;
-    if (sl.d_desc_u8) HIP_TRY(c, hipFree(sl.d_desc_u8));
-    sl.d_desc_u8 = nullptr;
-    sl.desc_u8_cap = 0;
-    HIP_TRY(c, ctx_malloc(c, (void**)&sl.d_desc_u8, (size_t)std::max(sl.desc_cap, 1) * 128));
-    sl.desc_u8_cap = sl.desc_cap;
-    return 0;
+    return grow(c, sl.desc_u8, std::max<size_t>(sl.desc_cap(), 1));
 }
 
 /* image k's results into caller memory, descriptors as floats (u8 = false) or as bytes, on the compute stream */
@@ -1280,12 +1177,12 @@ int fetch_sync(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t fea
     ImageSlot& sl = c->slot[k];
     if (u8 && nd) {
         if (int rc = slot_u8_ready(c, sl)) return rc;
-        HIP_TRY(c, launch_desc_bytes(sl.d_desc, (int)nd, sl.d_desc_u8, c->stream));
+        HIP_TRY(c, launch_desc_bytes(sl.desc.p, (int)nd, sl.desc_u8.p, c->stream));
         SYNC_CHK(c, "k_desc_bytes");
     }
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
-    if (nd && u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc_u8, nd * 128, hipMemcpyDeviceToHost, c->stream));
-    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.feats.p, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
+    if (nd && u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc_u8.p, nd * 128, hipMemcpyDeviceToHost, c->stream));
+    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc.p, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1306,14 +1203,8 @@ int fetch_begin(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t fe
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     /* nothing has been issued or swapped yet: a failed allocation leaves the results where they are (plain fetch works) */
     ImageSlot& sl = c->slot[k];
-    if (int rc = grow(c, &sl.alt_feats, &sl.alt_feats_cap, sl.feats_cap)) return rc;
-    if (sl.alt_desc_cap < sl.desc_cap) {
-        if (sl.alt_desc) HIP_TRY(c, hipFree(sl.alt_desc));
-        sl.alt_desc = nullptr;
-        sl.alt_desc_cap = 0;
-        HIP_TRY(c, ctx_malloc(c, (void**)&sl.alt_desc, (size_t)sl.desc_cap * 128 * sizeof(float)));
-        sl.alt_desc_cap = sl.desc_cap;
-    }
+    if (int rc = grow(c, sl.alt_feats, sl.feats.cap)) return rc;
+    if (int rc = grow(c, sl.alt_desc, sl.desc_cap())) return rc;
     if (u8 && nd) {
         if (int rc = slot_u8_ready(c, sl)) return rc;
         if (!c->ev_u8) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_u8, hipEventDisableTiming));
@@ -1323,18 +1214,17 @@ int fetch_begin(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t fe
      * waits for it.  On the copy stream it would queue behind other contexts' kernels on a shared hardware queue
      * (keypoint-sparse host to host 6.7-7.4 instead of 9.4-9.5 Gpix/s).  It reads the slab that becomes
      * alt_desc below, which the next batch does not write. */
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.d_feats, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->copy_stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.feats.p, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->copy_stream));
     if (nd && u8) {
-        HIP_TRY(c, launch_desc_bytes(sl.d_desc, (int)nd, sl.d_desc_u8, c->stream));
+        HIP_TRY(c, launch_desc_bytes(sl.desc.p, (int)nd, sl.desc_u8.p, c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_u8, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_u8, 0));
-        HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc_u8, nd * 128, hipMemcpyDeviceToHost, c->copy_stream));
+        HIP_TRY(c, hipMemcpyAsync(desc, sl.desc_u8.p, nd * 128, hipMemcpyDeviceToHost, c->copy_stream));
         sl.u8_read = true;
     }
-    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.d_desc, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
-    std::swap(sl.d_feats, sl.alt_feats);
-    std::swap(sl.feats_cap, sl.alt_feats_cap);
-    std::swap(sl.d_desc, sl.alt_desc); /* both hold desc_cap descriptors now; d_map / d_rot stay with the slot */
+    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc.p, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
+    std::swap(sl.feats, sl.alt_feats);
+    std::swap(sl.desc, sl.alt_desc); /* both hold desc_cap() descriptors now; map / rot / drec stay with the slot */
     refresh_caps(c);
     c->copy_pending = true;
     c->copy_seq = c->submit_seq;
@@ -1348,7 +1238,7 @@ int plane_ptr(popsift_hip_ctx* c, int octave, int kind, int level, float** p, co
     if (!c || !c->have_image) return POPSIFT_HIP_ERR_STATE;
     if (octave < 0 || octave >= c->pd.n_oct || level < 0) return fail(c, POPSIFT_HIP_ERR_INVALID, "bad octave/level");
     const OctDesc& od = c->pd.o[octave];
-    float*         arena = c->slot[0].d_arena;
+    float*         arena = c->slot[0].arena.p;
     if (kind == 0 && level < c->L)
         *p = arena + od.data_off + level * od.plane_stride;
     else if (kind == 1 && level < c->L - 1)
@@ -1357,6 +1247,14 @@ int plane_ptr(popsift_hip_ctx* c, int octave, int kind, int level, float** p, co
         return fail(c, POPSIFT_HIP_ERR_INVALID, "bad plane kind/level");
     *odp = &od;
     return 0;
+}
+
+/* ERR_NO_DEVICE without a usable GPU, ERR_INVALID for an index out of range */
+int check_device(int device)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
+    return device < 0 || device >= n ? POPSIFT_HIP_ERR_INVALID : POPSIFT_HIP_OK;
 }
 
 }  // namespace
@@ -1419,9 +1317,7 @@ int popsift_hip_device_count(int* count)
 int popsift_hip_get_device_info(int device, popsift_hip_device_info* out)
 {
     if (!out) return POPSIFT_HIP_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= n) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_device(device)) return rc;
     hipDeviceProp_t pr;
     if (hipGetDeviceProperties(&pr, device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     memset(out, 0, sizeof(*out));
@@ -1448,9 +1344,7 @@ int popsift_hip_device_numa_node(int device, int* node)
 {
     if (!node) return POPSIFT_HIP_ERR_INVALID;
     *node = -1;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= n) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_device(device)) return rc;
     char bus[64] = {0};
     if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     for (char* q = bus; *q; q++)
@@ -1482,9 +1376,7 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
         (p->filter_grid_size < 1 || p->filter_grid_size > 64 || p->filter_sorting < 0 || p->filter_sorting > 2))
         return POPSIFT_HIP_ERR_INVALID;
     if (p->scale_direct != 0 && p->scale_direct != 1) return POPSIFT_HIP_ERR_INVALID;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= n) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_device(device)) return rc;
 
     popsift_hip_ctx* c = new (std::nothrow) popsift_hip_ctx();
     if (!c) return POPSIFT_HIP_ERR_OOM;
@@ -1543,34 +1435,7 @@ int popsift_hip_ctx_destroy(popsift_hip_ctx* c)
         if (c->ev_stage[k]) (void)hipEventDestroy(c->ev_stage[k]);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-    for (ImageSlot& sl : c->slot) {
-        if (sl.d_input) (void)hipFree(sl.d_input);
-        if (sl.h_input) (void)hipHostFree(sl.h_input);
-        if (sl.d_arena) (void)hipFree(sl.d_arena);
-        if (sl.d_iext) (void)hipFree(sl.d_iext);
-        if (sl.d_iext2) (void)hipFree(sl.d_iext2);
-        if (sl.d_fstate) (void)hipFree(sl.d_fstate);
-        if (sl.d_fhist) (void)hipFree(sl.d_fhist);
-        if (sl.d_ext) (void)hipFree(sl.d_ext);
-        if (sl.d_ohist) (void)hipFree(sl.d_ohist);
-        if (sl.d_feats) (void)hipFree(sl.d_feats);
-        if (sl.d_map) (void)hipFree(sl.d_map);
-        if (sl.d_rot) (void)hipFree(sl.d_rot);
-        if (sl.d_drec) (void)hipFree(sl.d_drec);
-        if (sl.d_desc) (void)hipFree(sl.d_desc);
-        if (sl.d_cand) (void)hipFree(sl.d_cand);
-        if (sl.d_partial) (void)hipFree(sl.d_partial);
-        if (sl.d_ovf) (void)hipFree(sl.d_ovf);
-        if (sl.alt_feats) (void)hipFree(sl.alt_feats);
-        if (sl.alt_desc) (void)hipFree(sl.alt_desc);
-        if (sl.d_desc_u8) (void)hipFree(sl.d_desc_u8);
-        if (sl.d_frames) (void)hipFree(sl.d_frames);
-        if (sl.h_frames) (void)hipHostFree(sl.h_frames);
-        if (sl.d_fcounts) (void)hipFree(sl.d_fcounts);
-        if (sl.d_perm) (void)hipFree(sl.d_perm);
-        if (sl.d_inv) (void)hipFree(sl.d_inv);
-        if (sl.d_lfeats) (void)hipFree(sl.d_lfeats);
-    }
+    for (ImageSlot& sl : c->slot) sl.release();
     if (c->d_ct) (void)hipFree(c->d_ct);
     if (c->d_pd) (void)hipFree(c->d_pd);
     if (c->d_abs0) (void)hipFree(c->d_abs0);
@@ -1704,8 +1569,8 @@ int popsift_hip_results_dev_item(popsift_hip_ctx* c, int k, const void** d_feats
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c, k)) return rc;
-    if (d_feats) *d_feats = c->slot[k].d_feats;
-    if (d_desc) *d_desc = c->slot[k].d_desc;
+    if (d_feats) *d_feats = c->slot[k].feats.p;
+    if (d_desc) *d_desc = c->slot[k].desc.p;
     return POPSIFT_HIP_OK;
 }
 
@@ -1717,12 +1582,12 @@ int popsift_hip_results_dev_item_u8(popsift_hip_ctx* c, int k, const void** d_fe
     ImageSlot& sl = c->slot[k];
     if (int rc = slot_u8_ready(c, sl)) return rc;
     if (c->n_desc[k] > 0) {
-        HIP_TRY(c, launch_desc_bytes(sl.d_desc, c->n_desc[k], sl.d_desc_u8, c->stream));
+        HIP_TRY(c, launch_desc_bytes(sl.desc.p, c->n_desc[k], sl.desc_u8.p, c->stream));
         SYNC_CHK(c, "k_desc_bytes");
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-    if (d_feats) *d_feats = sl.d_feats;
-    if (d_desc_u8) *d_desc_u8 = sl.d_desc_u8;
+    if (d_feats) *d_feats = sl.feats.p;
+    if (d_desc_u8) *d_desc_u8 = sl.desc_u8.p;
     return POPSIFT_HIP_OK;
 }
 
@@ -1789,8 +1654,8 @@ int popsift_hip_results_dev(popsift_hip_ctx* c, const void** d_feats, const void
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c)) return rc;
-    if (d_feats) *d_feats = c->slot[0].d_feats;
-    if (d_desc) *d_desc = c->slot[0].d_desc;
+    if (d_feats) *d_feats = c->slot[0].feats.p;
+    if (d_desc) *d_desc = c->slot[0].desc.p;
     return POPSIFT_HIP_OK;
 }
 
@@ -1813,11 +1678,11 @@ int popsift_hip_clone_results(popsift_hip_ctx* c, popsift_hip_devfeatures** out)
         HIP_TRY(c, hipMalloc((void**)&f->d_desc, sizeof(float) * 128 * (size_t)std::max(f->n_desc, 1)));
         HIP_TRY(c, hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(f->n_desc, 1)));
         /* sift_pyramid.cu:323-345: prep_features into the clone, then the two device-to-device copies */
-        HIP_TRY(c, launch_clone_features(c->slot[0].d_feats, f->n_feat, f->d_desc, f->d_feat, c->stream));
+        HIP_TRY(c, launch_clone_features(c->slot[0].feats.p, f->n_feat, f->d_desc, f->d_feat, c->stream));
         if (f->n_desc > 0) {
-            HIP_TRY(c, hipMemcpyAsync(f->d_desc, c->slot[0].d_desc, sizeof(float) * 128 * (size_t)f->n_desc,
+            HIP_TRY(c, hipMemcpyAsync(f->d_desc, c->slot[0].desc.p, sizeof(float) * 128 * (size_t)f->n_desc,
                                       hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(f->d_rev, c->slot[0].d_map, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToDevice,
+            HIP_TRY(c, hipMemcpyAsync(f->d_rev, c->slot[0].map.p, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToDevice,
                                       c->stream));
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1872,9 +1737,7 @@ int popsift_hip_devfeatures_alloc(int device, int n_feat, int n_desc, popsift_hi
 {
     if (!out || n_feat < 0 || n_desc < 0) return POPSIFT_HIP_ERR_INVALID;
     *out = nullptr;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= nd) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_device(device)) return rc;
     if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
     if (!f) return POPSIFT_HIP_ERR_OOM;
@@ -1899,9 +1762,7 @@ int popsift_hip_devfeatures_from_host(int device, const float* desc, int n, pops
 {
     if (!out || n < 0 || (n > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
     *out = nullptr;
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    if (device < 0 || device >= nd) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_device(device)) return rc;
     if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
     if (!f) return POPSIFT_HIP_ERR_OOM;
@@ -2084,8 +1945,8 @@ int popsift_hip_download_plane(popsift_hip_ctx* c, int octave, int kind, int lev
     if (int rc = plane_ptr(c, octave, kind, level, &p, &od)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (kind == 1 && c->pd.dog_fly) /* not stored: DoG(l) = G(l+1) - G(l) into the (otherwise unused) DoG plane */
-        HIP_TRY(c, launch_dog_plane(p, c->slot[0].d_arena + od->data_off + (level + 1) * od->plane_stride,
-                                    c->slot[0].d_arena + od->data_off + level * od->plane_stride, (size_t)od->plane_stride, c->stream));
+        HIP_TRY(c, launch_dog_plane(p, c->slot[0].arena.p + od->data_off + (level + 1) * od->plane_stride,
+                                    c->slot[0].arena.p + od->data_off + level * od->plane_stride, (size_t)od->plane_stride, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy2D(out, (size_t)od->w * 4, p, (size_t)od->pitch * 4, (size_t)od->w * 4, od->h,
                            hipMemcpyDeviceToHost));
@@ -2157,9 +2018,6 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_KP_WAVES:
         c->kp_waves = std::min(std::max(value / 32 * 32, 32), 1 << 20);
-        return POPSIFT_HIP_OK;
-    case POPSIFT_HIP_DEBUG_PYR_ORDER:
-        c->pyr_order = value;
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_BLUR_PATH:
         if (value < 0 || value > 2) return fail(c, POPSIFT_HIP_ERR_INVALID, "BLUR_PATH: 0, 1 or 2");

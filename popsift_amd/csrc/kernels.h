@@ -60,7 +60,7 @@ hipError_t launch_blur_duo(const BlurArgs& a, int span_a, const BlurArgs& b, int
 #define PYR_TAIL_MAX_PX 4096        /* pixels of the first plane the tail takes */
 struct TailArgs {
     int     n_oct, first_oct, L;
-    int     halo[PYR_TAIL_MAX_L];                     /* span - 1 of level l, rounded up to an instantiated HALO */
+    int     halo[PYR_TAIL_MAX_L];                     /* span - 1 of level l (the tap loops are rolled: no HALO instances) */
     float   g[PYR_TAIL_MAX_L][PYR_TAIL_PAD + 1];      /* taps of level l, zero beyond its span */
     int     w[PS_MAX_OCT], h[PS_MAX_OCT], pitch[PS_MAX_OCT];
     int64_t data_off[PS_MAX_OCT], plane_stride[PS_MAX_OCT]; /* floats from the arena base / between planes */

@@ -39,17 +39,6 @@ constexpr int TW = BLUR_TW; /* tile width (outputs) */
 constexpr int TH = 64;      /* tile height: a taller tile amortises the halo rows of the H pass (1.3x at 20 taps, not 1.6x) */
 constexpr int NT = 512;     /* one 4x4 output block per lane */
 
-/* One axis of a CUDA linear-filter fetch at normalised coordinate r (s_image.cu:140-169), as in pyramid.hip */
-__device__ __forceinline__ void lin_coord(float r, int n, int& i0, float& alpha)
-{
-    const float xb = r * (float)n - 0.5f;
-    const float fl = floorf(xb);
-    float       a = xb - fl;
-    a = floorf(a * 256.0f + 0.5f) * (1.0f / 256.0f);
-    i0 = (int)fl;
-    alpha = a;
-}
-
 template <int HALO>
 struct Geo {
     static constexpr int HP = (HALO + 3) & ~3; /* left/right halo of U, padded to 16 B */

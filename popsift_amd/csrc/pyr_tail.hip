@@ -35,11 +35,6 @@ constexpr int TPAD = PYR_TAIL_PAD;  /* border of the LDS plane on every side (>=
 constexpr int TPLANE = PYR_TAIL_PLANE_FLOATS;
 constexpr int TNEXT = PYR_TAIL_PLANE_FLOATS / 4 + 256; /* level 0 of the next octave, compact */
 
-/* workgroup barrier that waits for this wave's LDS operations only: the stores of the finished level to HBM -- which nothing
- * in this launch reads -- stay in flight (__syncthreads() drains them: ~1.5 us of write latency at each of the four
- * barriers of a level, 65 instead of 25 us for the tail of a 1080p image) */
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 /* One level: A (level l-1, border replicated in x) -> B (horizontal pass, then rows 0 / h-1 repeated above / below:
  * intm(x, clamp(y +- k))) -> A (level l) + the plane in HBM.  want_next: also every second pixel into nx (compact, row pitch
  * w2) and into level 0 of the next octave in HBM.

@@ -32,18 +32,6 @@ namespace {
 
 constexpr int TW = BLUR_TW; /* tile width  (outputs) */
 
-/* One axis of a CUDA linear-filter fetch at normalised coordinate r
- * (s_image.cu:140-169: normalised coords, clamp, linear, 1.8 fixed-point weight). */
-__device__ __forceinline__ void lin_coord(float r, int n, int& i0, float& alpha)
-{
-    const float xb = r * (float)n - 0.5f;
-    const float fl = floorf(xb);
-    float       a = xb - fl;
-    a = floorf(a * 256.0f + 0.5f) * (1.0f / 256.0f);
-    i0 = (int)fl;
-    alpha = a;
-}
-
 template <typename T>
 __device__ __forceinline__ float texel(const T* img, int w, int h, int pitch, int x, int y);
 template <>
