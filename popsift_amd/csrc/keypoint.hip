@@ -601,13 +601,15 @@ __device__ __forceinline__ DescRec make_desc_rec(const PyrDesc* __restrict__ pdp
     r.crsbp = cos_t / SBP;
     r.srsbp = sin_t / SBP;
     r.ang_bins = angle * (4.0f / F_PI);
-    r.fscale = scalbnf(1.0f, fbits);
+    /* the hardware reciprocal, formed here once per descriptor instead of in all 64 lanes of its wave: the same
+     * instruction on the same float, so the row spans of k_descriptor are what they were */
+    r.inv_c = (fabsf(r.crsbp) > 1e-20f) ? __builtin_amdgcn_rcpf(r.crsbp) : 0.0f;
+    r.inv_s = (fabsf(r.srsbp) > 1e-20f) ? __builtin_amdgcn_rcpf(r.srsbp) : 0.0f;
     r.xymin = ((unsigned int)xmin & 0xffffu) | ((unsigned int)ymin << 16);
     r.xymax = ((unsigned int)xmax & 0xffffu) | ((unsigned int)ymax << 16);
     r.off_lo = (unsigned int)((unsigned long long)off & 0xffffffffull);
     r.off_hi = (unsigned int)((unsigned long long)off >> 32);
     r.misc = (unsigned int)od->pitch | ((unsigned int)fbits << 16) | ((SBP != 0.0f) ? (1u << 24) : 0u);
-    r.pad = 0u;
     return r;
 }
 
@@ -830,18 +832,11 @@ constexpr int DESC_COPIES = DESC_NCOPY;
 constexpr int DESC_RS = 36;                /* words per cell row */
 constexpr int DESC_CS = 3 * DESC_RS + 32;  /* words per copy (the last row needs no padding): 140 */
 constexpr int DESC_MAXROWS = 128; /* patch rows handled by the span path */
-#ifndef DESC_GROUPS
-/* Lane groups, each on its own 1 / DESC_GROUPS of the sample list.  Round 2 ran FOUR (16 lanes each, on four distant
- * parts of the patch: fewer lanes of a wave fall into one cell, 61 % fewer LDS bank conflicts) while the kernel was bound
- * by vector issue and LDS.  Round 3 took a fifth of the issue slots out of the loop, and what bound the kernel next was the
- * L1 -> L2 request stream of its taps (L1 hit rate 68 %, the L1 stalled on pending data 46 % of the time,
- * tools/desc_batch_counters.sh): four streams touch four times the cache lines per wave step.  ONE group -- 64 lanes on
- * 64 consecutive samples, i.e. on one and a half to two neighbouring patch rows, whose up / down taps are each other's
- * centre rows -- leaves the kernel's own time unchanged and makes the timed loop 4.8 % faster (1 / 2 / 4 / 8 groups:
- * 3.36 / 3.36 / 3.20 / 2.74 Gpix/s): the requests it no longer makes are L2 bandwidth for the kernels beside it. */
-#define DESC_GROUPS 1
-#endif
-constexpr int DESC_GL = 64 / DESC_GROUPS; /* lanes per group */
+/* The 64 lanes walk 64 CONSECUTIVE samples of the list, i.e. one and a half to two neighbouring patch rows, whose up /
+ * down taps are each other's centre rows.  Round 2 ran four lane groups (16 lanes each, on four distant parts of the
+ * patch: 61 % fewer LDS bank conflicts) while the kernel was bound by vector issue and LDS; once round 3 had slimmed the
+ * loop, the L1 -> L2 request stream of the taps bound it (four streams touch four times the cache lines per wave step),
+ * and one group made the timed loop 4.8 % faster (1 / 2 / 4 / 8 groups: 3.36 / 3.36 / 3.20 / 2.74 Gpix/s). */
 
 __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, SiftConsts sc, int desc_cap)
 {
@@ -858,7 +853,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
     static_assert(ROW_WORDS * 4 >= 352, "cell (-1, -1) of copy 0 stays inside the wave's LDS");
     __shared__ __attribute__((aligned(16))) unsigned int s_lds[KP_NW][ROW_WORDS + 2 * DESC_COPIES * DESC_CS];
     const int     lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int     grp = lane / DESC_GL, sub = lane % DESC_GL, cpy = lane & (DESC_COPIES - 1);
+    const int     cpy = lane & (DESC_COPIES - 1);
     unsigned int* rinfo = s_lds[wave];
     fix64*        hall = (fix64*)(s_lds[wave] + ROW_WORDS);
     /* 32-bit LDS addresses: the row records, this lane's histogram copy (as a float: the cell addresses are formed by FMAs) */
@@ -880,20 +875,26 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
         const float        x = uniformf(__uint_as_float(q0.x)), y = uniformf(__uint_as_float(q0.y));
         const float        crsbp = uniformf(__uint_as_float(q0.z)), srsbp = uniformf(__uint_as_float(q0.w));
         const float        ang_bins = uniformf(__uint_as_float(q1.x));
+        const float        inv_c = uniformf(__uint_as_float(q1.y)), inv_s = uniformf(__uint_as_float(q2.w));
         const int          pmin = uniform((int)q1.z), pmax = uniform((int)q1.w);
         const unsigned int misc = (unsigned int)uniform((int)q2.z);
         const int          pitch = (int)(misc & 0xffffu), fbits = (int)((misc >> 16) & 0xffu);
         const float*       layer = arena + uniform64((long long)(((unsigned long long)q2.y << 32) | q2.x));
 
         {
-            /* the zero pair is made here, every time: left to itself the compiler keeps one alive across the whole sample
-             * loop, which is the 65th and 66th vector register (a spill, and with it scratch set-up for every wave) */
-            unsigned int zlo, zhi;
-            asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(zlo), "=v"(zhi));
-            const fix64 zero = ((fix64)zhi << 32) | zlo;
+            /* the zeros are made here, every time: left to itself the compiler keeps them alive across the whole sample
+             * loop, which is the 65th vector register and up (a spill, and with it scratch set-up for every wave).
+             * 16-byte stores (the histograms start on a 16-byte boundary, ROW_WORDS): five per lane where 8-byte stores
+             * took nine */
+            u4 zero;
+            asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0"
+                         : "=v"(zero.x), "=v"(zero.y), "=v"(zero.z), "=v"(zero.w));
+            constexpr int CLEAR16 = DESC_COPIES * DESC_CS / 2; /* 16-byte pieces of the histogram copies */
+            static_assert(DESC_COPIES * DESC_CS % 2 == 0, "whole 16-byte pieces");
+            u4*           h16 = reinterpret_cast<u4*>(hall);
 #pragma unroll
-            for (int k = 0; k < (DESC_COPIES * DESC_CS + 63) / 64; k++)
-                if (lane + 64 * k < DESC_COPIES * DESC_CS) hall[lane + 64 * k] = zero;
+            for (int k = 0; k < (CLEAR16 + 63) / 64; k++)
+                if (lane + 64 * k < CLEAR16) h16[lane + 64 * k] = zero;
         }
 
         if (misc & (1u << 24)) { /* DESC_MAGNIFY * sigma != 0 */
@@ -901,8 +902,6 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
             const int   xmax = (int)(short)(pmax & 0xffff), ymax = pmax >> 16;
             const int   wx = xmax - xmin + 1;
             const int   hy_all = ymax - ymin0 + 1;
-            const float inv_c = (fabsf(crsbp) > 1e-20f) ? __builtin_amdgcn_rcpf(crsbp) : 0.0f;
-            const float inv_s = (fabsf(srsbp) > 1e-20f) ? __builtin_amdgcn_rcpf(srsbp) : 0.0f;
             /* the Gaussian window weight comes out of v_exp already multiplied by the fixed-point scale 2^fbits */
             const float ffbits = (float)fbits;
 
@@ -919,7 +918,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
              * (prefix sum) and the wave walks that flat list, so nearly every lane holds a sample
              * that passes the exact test below.  The intervals only have to be a superset of the
              * samples inside the square. */
-            int T = 0;
+            int T = 0, grow = 0; /* list length; the first row that holds a sample */
             {
                 int         carry = 0;
                 for (int r0 = 0; r0 < hy; r0 += 64) {
@@ -957,6 +956,8 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                     const int incl = wave_incl_scan(len);
                     const int start = carry + incl - len;
                     if (r < hy) rinfo[r] = (unsigned int)start | ((unsigned int)(start - (jlo - xmin)) << 16);
+                    const unsigned long long live = __ballot(len > 0);
+                    if (carry == 0 && live != 0ull) grow = r0 + __ffsll((long long)live) - 1;
                     carry += __builtin_amdgcn_readlane(incl, 63);
                 }
                 T = carry;
@@ -971,43 +972,22 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
             }
             wave_lds_sync();
 
-            const int   loops = T;
-            /* every lane group takes its own part of the list */
-            /* ... a whole number of double steps each, so that no lane of a group ever walks into the next group's part: what
-             * lies beyond the list's end drops out by itself (above) */
-            const int   quarter = ((loops + DESC_GROUPS - 1) / DESC_GROUPS + 2 * DESC_GL - 1) & ~(2 * DESC_GL - 1);
-            const int   ibeg = grp * quarter;
+            /* steps of 64 list positions, exactly: the last one may be partial (what lies beyond the list's end drops out by
+             * itself, above), none is empty */
 #ifdef DESC_PROBE_NOLOOP
-            const int   iters = 0;
+            const int   steps = 0;
 #else
-            const int   iters = quarter / DESC_GL;
+            const int   steps = (T + 63) >> 6;
 #endif
             /* the lane's place in the row records: LDS address of its current row's record, that row (counted from the top of
-             * the PATCH, as a float: it only feeds FMAs), the record and the one of the row below */
-            unsigned int rp = rbase32;
-            float        fr = (float)rb;
+             * the PATCH, as a float: it only feeds FMAs, see coord()), the record and the one of the row below.  Every lane
+             * starts in the row of the list's first sample, which the span pass has found (coord() walks on from there to
+             * the lane's own). */
+            unsigned int rp = rbase32 + 4u * (unsigned int)grow;
+            float        fr = (float)(rb + grow);
             unsigned int cur = 0;
             unsigned int nxt = 0x7fff0000u | 0xffffu;
-            if (loops > 0) {
-                /* The row that holds the first sample of this lane's GROUP (coord() walks on from there to the lane's
-                 * own): the one non-empty row r with start(r) <= key < start(r + 1).  Every row looks at its own
-                 * interval, a ballot per group finds it -- two LDS reads instead of the seven dependent ones of a
-                 * binary search per lane. */
-                int grow = 0;
-                for (int rbk = 0; rbk < hy; rbk += 64) {
-                    const int  r = rbk + lane;
-                    const bool in = r < hy;
-                    const int  st = in ? (int)(rinfo[r] & 0xffffu) : 0x7fffffff;
-                    const int  en = in ? (int)(rinfo[r + 1] & 0xffffu) : 0x7fffffff;
-#pragma unroll
-                    for (int g = 0; g < DESC_GROUPS; g++) {
-                        const int                key = min(g * quarter, loops - 1);
-                        const unsigned long long m = __ballot(st <= key && key < en);
-                        if (m != 0ull && grp == g) grow = rbk + __ffsll((long long)m) - 1;
-                    }
-                }
-                rp = rbase32 + 4u * (unsigned int)grow;
-                fr = (float)(rb + grow); /* rows are counted from the top of the PATCH, whatever the pass: see coord() */
+            if (T > 0) {
                 cur = rinfo[grow];
                 nxt = rinfo[grow + 1];
             }
@@ -1131,18 +1111,29 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
 #else
 #define PS_TAPS(OFF, A0, A1, A2, A3) taps.load_b(OFF, A0, A1, A2, A3);
 #endif
-            if (loops > 0) {
-                coord(ibeg + sub, off_a, u_a, v_a);
+            if (T > 0) {
+                coord(lane, off_a, u_a, v_a);
                 PS_TAPS(off_a, a0, a1, a2, a3)
             }
-            for (int t = 0, i = ibeg + sub; t < iters; t += 2, i += 2 * DESC_GL) {
-                coord(i + DESC_GL, off_b, u_b, v_b);
+            /* double steps while a further step follows them: only then is the set requested at the end ever binned */
+            int t = steps, i = lane;
+            for (; t > 2; t -= 2, i += 128) {
+                coord(i + 64, off_b, u_b, v_b);
                 PS_TAPS(off_b, b0, b1, b2, b3)
                 bin(u_a, v_a, a0 - a1, a2 - a3);
-                coord(i + 2 * DESC_GL, off_a, u_a, v_a);
+                coord(i + 128, off_a, u_a, v_a);
                 PS_TAPS(off_a, a0, a1, a2, a3)
                 bin(u_b, v_b, b0 - b1, b2 - b3);
             }
+            /* the last one or two steps (wave-uniform branches): nothing is requested beyond the list's last step, and a
+             * step that holds no sample is not walked -- rounding the list up to whole double steps walked 64 empty
+             * positions per descriptor on average, coordinates, row walk and four tap loads each */
+            if (t == 2) {
+                coord(i + 64, off_b, u_b, v_b);
+                PS_TAPS(off_b, b0, b1, b2, b3)
+            }
+            if (t > 0) bin(u_a, v_a, a0 - a1, a2 - a3);
+            if (t == 2) bin(u_b, v_b, b0 - b1, b2 - b3);
             if (probe_acc == 0x12345u) desc[(size_t)d * 128 + lane] = 1.0f; /* never true: keeps the probe's arithmetic alive */
             wave_lds_sync(); /* ISA: end */
             } /* passes */

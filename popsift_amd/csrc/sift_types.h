@@ -77,11 +77,11 @@ struct DescRec {
     float        x, y;         /* position in the octave */
     float        crsbp, srsbp; /* cos, sin of the orientation / (DESC_MAGNIFY * sigma): pixel -> cell units */
     float        ang_bins;     /* orientation in descriptor bins (pi / 4) */
-    float        fscale;       /* 2^fbits: fixed-point scale of the histogram */
+    float        inv_c;        /* v_rcp of crsbp for the row spans, 0: |crsbp| <= 1e-20 (the constraint has no slope) */
     unsigned int xymin, xymax; /* patch bounding box, two signed 16-bit halves each (x low, y high) */
     unsigned int off_lo, off_hi; /* offset of the Gaussian plane in the arena, in floats (64 bits) */
     unsigned int misc;         /* pitch (16 bits) | fbits << 16 | valid << 24 */
-    unsigned int pad;
+    float        inv_s;        /* the same of srsbp */
 };
 
 static_assert(sizeof(DescRec) == 48, "three 16-byte loads");
