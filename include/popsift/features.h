@@ -7,6 +7,7 @@
  */
 #pragma once
 
+#include <cmath>
 #include <iostream>
 #include <vector>
 
@@ -136,6 +137,22 @@ public:
         float dist_best, dist_second; /* squared L2 */
     };
     std::vector<Match> matchAndGet(FeaturesDev* other);
+
+    /* extension: correspondences instead of one row per descriptor (popsift_hip_match_pairs).  Descriptor i of this set
+     * yields the pair (i, its nearest in `other`) iff dist_best / dist_second < ratio (0: no ratio test), dist_best <=
+     * maxDist2, and -- with crossCheck -- i is the nearest descriptor of this set to that one (ties to the lower index).
+     * Filtered on the GPU; pairs in ascending l.  The defaults give the rows matchAndGet accepts. */
+    struct MatchOptions {
+        float ratio = 0.8f;
+        float maxDist2 = INFINITY; /* squared L2 */
+        bool  crossCheck = false;
+    };
+    struct Pair {
+        int   l, r;                 /* descriptor indices in this set and in `other` */
+        float distBest, distSecond; /* squared L2 */
+    };
+    std::vector<Pair> matchPairs(FeaturesDev* other, const MatchOptions& opts);
+    std::vector<Pair> matchPairs(FeaturesDev* other) { return matchPairs(other, MatchOptions()); }
 
     /* DEVICE pointers */
     Feature*    getFeatures();

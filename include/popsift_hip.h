@@ -374,6 +374,45 @@ int popsift_hip_match_sets(const popsift_hip_devfeatures* l, const popsift_hip_d
 enum { POPSIFT_HIP_MATCH_AUTO = 0, POPSIFT_HIP_MATCH_EXACT = 1, POPSIFT_HIP_MATCH_SCREEN = 2 };
 int popsift_hip_match_set_path(int path);
 
+/*
+ * Correspondences: the rows of the search above, filtered on the GPU into a list of pairs (the expectation SiftGPU's
+ * GetSiftMatch(.., distmax, ratiomax, mutual_best_match) and OpenCV's BFMatcher(crossCheck) set).  With F = the rows of
+ * match_sets(l, r) and B = the rows of match_sets(r, l), left descriptor i yields the pair
+ * (i, F[i].best, F[i].dist_best, F[i].dist_second) iff
+ *     1. r has at least one descriptor,
+ *     2. ratio == 0, or F[i].dist_best / F[i].dist_second < ratio  (float division; a NaN quotient fails, as in `accept`),
+ *     3. F[i].dist_best <= max_dist2,
+ *     4. cross_check == 0, or B[F[i].best].best == i  (ties go to the lower index in both directions).
+ * Pairs come out in ascending l; the bytes are the same on every run and with every popsift_hip_match_set_path.  With the
+ * default options they are the rows of match_sets whose accept is 1.
+ *
+ * *n_pairs receives the number of pairs found; min(that, cap) of them are written to `pairs` (host memory), and the call
+ * returns POPSIFT_HIP_ERR_TOO_SMALL when there are more than cap.  l's descriptor count is always a sufficient cap;
+ * cap = 0 with pairs = NULL asks for the count alone.  Empty sets: 0 pairs, POPSIFT_HIP_OK.
+ * ERR_INVALID, checked before any GPU call: a NULL set, opts or n_pairs; pairs NULL with cap > 0; ratio negative, NaN or
+ * infinite; max_dist2 NaN; reserved != 0; cross_check other than 0 or 1.
+ *
+ * The forward search is match_sets' own (same kernels, same path choice) and stays on the GPU.  With the cross-check the
+ * reverse search runs only for the right descriptors that a row passing 2 and 3 points to: they are compacted into an
+ * ascending list, their descriptors gathered, and the same kernels match those rows against l -- on an image pair that
+ * mostly does not match this skips nearly all of the second search.  One download brings the count and the pairs.
+ * All scratch belongs to l (one match at a time per left set); r may be the left set of another thread's call.  Sets on
+ * different GPUs: r's descriptors are copied to l's GPU once and both searches run there.
+ */
+typedef struct popsift_hip_match_opts {
+    float   ratio;       /* 0: no ratio test; else a pair needs dist_best / dist_second < ratio (0.8 = match_sets' accept) */
+    float   max_dist2;   /* a pair needs dist_best <= max_dist2 (squared L2); +INFINITY: no cap                        */
+    int32_t cross_check; /* 1: a pair needs l to be the nearest left descriptor of its best right one                  */
+    int32_t reserved;    /* must be 0 */
+} popsift_hip_match_opts;
+typedef struct popsift_hip_pair {   /* 16 bytes */
+    int32_t l, r;                   /* descriptor indices in the left and the right set */
+    float   dist_best, dist_second; /* squared L2: to r, and to l's second nearest right descriptor */
+} popsift_hip_pair;
+void popsift_hip_default_match_opts(popsift_hip_match_opts* opts); /* {0.8f, INFINITY, 0, 0} */
+int  popsift_hip_match_pairs(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
+                             const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
+
 int popsift_hip_get_report(const popsift_hip_ctx* ctx, popsift_hip_report* rep);
 /* profile != 0: bracket every blur-level launch with HIP events (serialises the
  * octave streams; used by bench.py for the roofline object only). */

@@ -64,6 +64,11 @@ class DeviceInfo(C.Structure):
     ]
 
 
+class MatchOpts(C.Structure):
+    """popsift_hip_match_opts"""
+    _fields_ = [("ratio", C.c_float), ("max_dist2", C.c_float), ("cross_check", C.c_int32), ("reserved", C.c_int32)]
+
+
 FEATURE_DTYPE = np.dtype([
     ("debug_octave", np.int32), ("xpos", np.float32), ("ypos", np.float32),
     ("sigma", np.float32), ("num_ori", np.int32),
@@ -71,6 +76,8 @@ FEATURE_DTYPE = np.dtype([
 ])
 MATCH_DTYPE = np.dtype([("best", np.int32), ("second", np.int32), ("accept", np.int32),
                         ("dist_best", np.float32), ("dist_second", np.float32)])
+# popsift_hip_pair: one correspondence of DevFeatures.match_pairs
+PAIR_DTYPE = np.dtype([("l", np.int32), ("r", np.int32), ("dist_best", np.float32), ("dist_second", np.float32)])
 EXTREMUM_DTYPE = np.dtype([
     ("xpos", np.float32), ("ypos", np.float32), ("lpos", np.int32),
     ("sigma", np.float32), ("octave", np.int32), ("cell", np.int32),
@@ -133,6 +140,8 @@ SYMBOLS = [
     ("popsift_hip_devfeatures_download_u8", C.c_int, [_vp, _vp]),
     ("popsift_hip_match_sets", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_set_path", C.c_int, [C.c_int]),
+    ("popsift_hip_default_match_opts", None, [C.POINTER(MatchOpts)]),
+    ("popsift_hip_match_pairs", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
     ("popsift_hip_set_profile", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_octave_dims", C.c_int, [_vp, C.c_int, _ip, _ip]),
@@ -271,6 +280,19 @@ class DevFeatures:
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_match_sets")
         return out
+
+    def match_pairs(self, other, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """Correspondences (popsift_hip_match_pairs): the rows of match(other) that pass the ratio test (0: none), the cap
+        on the squared distance and, with cross_check, the mutual-nearest-neighbour check, as a PAIR_DTYPE array in
+        ascending l.  Filtered on the GPU; only the pairs are downloaded."""
+        _, _, nd = self.info()
+        out = np.zeros(nd, PAIR_DTYPE)
+        opts = MatchOpts(ratio, max_dist2, 1 if cross_check else 0, 0)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs(self._h, other._h, C.byref(opts), out.ctypes.data if nd else None, nd, C.byref(n))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs")
+        return out[:n.value]
 
     def close(self):
         if self._h:

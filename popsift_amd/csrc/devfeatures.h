@@ -30,4 +30,11 @@ struct popsift_hip_devfeatures {
     float* d_norm = nullptr;    /* |x|^2 per descriptor, computed on first use by a match */
     float* m_rnorm = nullptr;   /* norms of the right set of the current call */
     size_t m_rnorm_cap = 0;
+    /* scratch of popsift_hip_match_pairs with this set on the left */
+    void*  p_pairs = nullptr;   /* a 16-byte header ([0] = pair count, [1] = |J|) and popsift_hip_pair[n_desc] */
+    void*  p_host = nullptr;    /* pinned staging of the same size */
+    int*   p_idx = nullptr;     /* over the right set: flags, ranks, the list J; and the compaction's block counts */
+    size_t p_idx_cap = 0;       /* ints */
+    void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows and its redo list */
+    size_t p_back_cap = 0;      /* rows */
 };

@@ -158,6 +158,16 @@ hipError_t launch_norms(const float* desc, int n, float* out, hipStream_t s);
 hipError_t launch_match_screen(const float* ldesc, int l_len, const float* rdesc, int r_len, const float* lnorm,
                                const float* rnorm, int n_split, void* partial, popsift_hip_match* out, int* redo_list,
                                int* redo_count, hipStream_t s);
+/* match_pairs.hip: 2-NN rows -> pair list.  fwd: the forward sweep's rows, back: the reverse sweep's rows of the flagged
+ * right descriptors in the order of `list` (null without the cross-check), counts: pair_count_blocks(n) ints of scratch
+ * for a compaction over n elements.  l_len and r_len >= 1. */
+int        pair_count_blocks(int n);
+hipError_t launch_pair_targets(const popsift_hip_match* fwd, int l_len, int r_len, float ratio, float max_dist2, int* flags,
+                               int* counts, int* list, int* rank, int* n_list, hipStream_t s);
+hipError_t launch_gather_rows(const float* desc, const int* list, int n, float* out, hipStream_t s);
+hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
+                            const popsift_hip_match* back, const int* rank, int* counts, popsift_hip_pair* pairs, int* n_pairs,
+                            hipStream_t s);
 /* Feature records (72-byte popsift::Feature layout) with device descriptor pointers for a cloned set */
 hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, float* desc_base, void* out, hipStream_t s);
 

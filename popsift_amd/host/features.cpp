@@ -326,6 +326,24 @@ std::vector<FeaturesDev::Match> FeaturesDev::matchAndGet(FeaturesDev* other)
     return res;
 }
 
+std::vector<FeaturesDev::Pair> FeaturesDev::matchPairs(FeaturesDev* other, const MatchOptions& opts)
+{
+    static_assert(sizeof(Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
+    std::vector<Pair> res;
+    if (!_set || !other || !other->_set) return res;
+    res.resize((size_t)getDescriptorCount()); /* always enough */
+    popsift_hip_match_opts o;
+    popsift_hip_default_match_opts(&o);
+    o.ratio = opts.ratio;
+    o.max_dist2 = opts.maxDist2;
+    o.cross_check = opts.crossCheck ? 1 : 0;
+    int       n = 0;
+    const int rc = popsift_hip_match_pairs(_set, other->_set, &o, (popsift_hip_pair*)res.data(), res.size(), &n);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("matching failed", rc);
+    res.resize((size_t)n);
+    return res;
+}
+
 /* FeaturesDev::match + show_distance (features.cu:222-300): the reference prints from the device */
 void FeaturesDev::match(FeaturesDev* other)
 {

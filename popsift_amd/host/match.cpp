@@ -2,17 +2,23 @@
  * popsift-match -- the reference's matching demo (src/application/match.cpp:47-276) against this
  * library: extract two images in Config::MatchingMode (features stay on the GPU), print the counts,
  * brute-force match left against right (one accept / reject line per left descriptor).
+ * Extension: --pairs [--ratio R] [--max-dist D] [--cross-check] prints the correspondences instead.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
 #include <popsift/popsift.h>
 #include <popsift/sift_conf.h>
 
+#include <popsift_hip.h>
+
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <filesystem>
 #include <functional>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "cli_options.h"
 #include "pgmread.h"
@@ -24,6 +30,8 @@ static bool print_time_info = false;
 static bool write_as_uchar = false;
 static bool dont_write = false;
 static bool pgmread_loading = false;
+static bool print_pairs = false;
+static popsift::FeaturesDev::MatchOptions pair_opts;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -73,7 +81,27 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.flag("write-as-uchar", 0, "Informational", "Output descriptors rounded to int", [&] { write_as_uchar = true; });
     o.flag("dont-write", 0, "Informational", "Suppress descriptor output", [&] { dont_write = true; });
     o.flag("pgmread-loading", 0, "Informational", "Use the old image loader instead of LibDevIL", [&] { pgmread_loading = true; });
+    /* extension: correspondences (FeaturesDev::matchPairs) instead of the reference's line per left descriptor */
+    o.flag("pairs", 0, "Matching", "Print the matching pairs only: one line per pair, then their count", [&] { print_pairs = true; });
+    o.fval("ratio", "Matching", "With --pairs: a pair needs best / second squared distance below this (default 0.8, 0 = off)",
+           [&](float f) { pair_opts.ratio = f; });
+    o.fval("max-dist", "Matching", "With --pairs: a pair needs an L2 distance of at most this",
+           [&](float f) { pair_opts.maxDist2 = f * f; });
+    o.flag("cross-check", 0, "Matching", "With --pairs: keep mutual nearest neighbours only", [&] { pair_opts.crossCheck = true; });
     o.parse(argc, argv);
+}
+
+/* one line per pair through the sets' reverse maps (descriptor -> feature), then the count */
+static void print_matching_pairs(popsift::FeaturesDev* l, popsift::FeaturesDev* r)
+{
+    const vector<popsift::FeaturesDev::Pair> pairs = l->matchPairs(r, pair_opts);
+    vector<int> l_fem((size_t)l->getDescriptorCount()), r_fem((size_t)r->getDescriptorCount());
+    popsift_hip_devfeatures_download(l->getHandle(), 0, l_fem.data());
+    popsift_hip_devfeatures_download(r->getHandle(), 0, r_fem.data());
+    for (const popsift::FeaturesDev::Pair& p : pairs)
+        printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[(size_t)p.r], p.r,
+               sqrtf(p.distBest));
+    printf("Number of pairs:       %zu\n", pairs.size());
 }
 
 static SiftJob* process_image(const string& inputFile, PopSift& sift)
@@ -119,7 +147,8 @@ int main(int argc, char** argv)
     cout << "Number of features:    " << rFeatures->getFeatureCount() << endl;
     cout << "Number of descriptors: " << rFeatures->getDescriptorCount() << endl;
 
-    lFeatures->match(rFeatures);
+    if (print_pairs) print_matching_pairs(lFeatures, rFeatures);
+    else lFeatures->match(rFeatures);
 
     delete lFeatures;
     delete rFeatures;
