@@ -15,8 +15,11 @@
 #include "sift_extremum.h"
 
 struct popsift_hip_devfeatures;
+struct popsift_hip_bytefeatures;
 
 namespace popsift {
+
+class FeaturesDevBytes;
 
 struct Feature {
     int         debug_octave;
@@ -161,6 +164,41 @@ public:
 
     int                      getDevice() const;
     popsift_hip_devfeatures* getHandle() { return _set; }
+
+    /* extension: this set's descriptors as bytes, quantized on its GPU (the rule of Config::ByteDescriptors /
+     * popsift_hip_fetch_item_u8), with a copy of the reverse map.  The caller owns the result; null for an unset object. */
+    FeaturesDevBytes* toBytes() const;
+};
+
+/*
+ * Extension: a device-resident set of byte descriptors (popsift_hip_bytefeatures) -- a quarter of FeaturesDev's memory --
+ * and its exact matcher: squared distances are integers, ties go to the lower index, no float summation order is involved.
+ * matchAndGet / matchPairs mirror FeaturesDev's; maxDist2 is in byte units squared.
+ */
+class FeaturesDevBytes {
+    popsift_hip_bytefeatures* _set;
+
+    FeaturesDevBytes(const FeaturesDevBytes&);
+    FeaturesDevBytes& operator=(const FeaturesDevBytes&);
+
+public:
+    typedef FeaturesDev::Match        Match;
+    typedef FeaturesDev::MatchOptions MatchOptions;
+    typedef FeaturesDev::Pair         Pair;
+
+    /* takes ownership of a set made by the C ABI */
+    explicit FeaturesDevBytes(popsift_hip_bytefeatures* adopt) : _set(adopt) {}
+    /* num_ori x 128 bytes of host memory onto GPU `device` */
+    FeaturesDevBytes(const unsigned char* desc, int num_ori, int device = 0);
+    ~FeaturesDevBytes();
+
+    int getDescriptorCount() const;
+    int getDevice() const;
+    popsift_hip_bytefeatures* getHandle() { return _set; }
+
+    std::vector<Match> matchAndGet(FeaturesDevBytes* other);
+    std::vector<Pair>  matchPairs(FeaturesDevBytes* other, const MatchOptions& opts);
+    std::vector<Pair>  matchPairs(FeaturesDevBytes* other) { return matchPairs(other, MatchOptions()); }
 };
 
 }  // namespace popsift

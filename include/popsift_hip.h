@@ -312,7 +312,8 @@ int popsift_hip_results_dev(popsift_hip_ctx* ctx, const void** d_feats, const vo
  * such elements become 0.
  *
  * Same rules and errors as the float calls above (desc_cap counted in BYTES, >= n_descriptors * 128).  Extraction and
- * describe results alike; clone_results and matching stay float.  The float results are untouched: a context that never
+ * describe results alike.  clone_results and the float matcher stay float; byte sets and their own exact matcher are
+ * popsift_hip_bytefeatures below.  The float results are untouched: a context that never
  * asks for bytes allocates and launches nothing more.  The pass (desc_bytes.hip) writes a byte buffer of the image's
  * slot, allocated on the first byte request.  It runs on the context's stream; fetch_begin*_u8 enqueues it there before
  * it returns (ahead of the next submit's kernels) and its byte copy on the copy stream waits for it (protocol as above:
@@ -412,6 +413,48 @@ typedef struct popsift_hip_pair {   /* 16 bytes */
 void popsift_hip_default_match_opts(popsift_hip_match_opts* opts); /* {0.8f, INFINITY, 0, 0} */
 int  popsift_hip_match_pairs(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
                              const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
+
+/*
+ * Byte descriptors on the device, and their matcher.  A popsift_hip_bytefeatures is a device-resident set of n x 128
+ * uint8_t descriptors (the format q(d) above produces, VLFeat's and OpenCV's) with its descriptor -> feature map (-1 where
+ * no feature stands behind a descriptor) and its own match scratch and stream: a quarter of a float set's memory.  A
+ * separate type on purpose: handing a byte set to a float call, or the reverse, does not compile.
+ *   from_host         n_descriptors x 128 caller bytes (host memory); the map is all -1
+ *   from_set          f's descriptors quantized on f's GPU by q(d) (the pass of the byte fetch calls), f's map copied
+ *   clone_results_u8  the same for image k of the finished batch: the bytes popsift_hip_fetch_item_u8 would deliver, copied
+ *                     device to device, never through the host; state rules and errors of popsift_hip_fetch_item_u8
+ *   download          host copies: desc n x 128 bytes, rev n ints; either may be NULL
+ * ERR_INVALID: a NULL set or out, n_descriptors < 0, desc NULL with n_descriptors > 0; a bad device: ERR_NO_DEVICE /
+ * ERR_INVALID as for popsift_hip_devfeatures_from_host; a failed allocation: ERR_OOM.
+ *
+ * popsift_hip_match_bytes: one row per descriptor of l, like popsift_hip_match_sets, from integer arithmetic.
+ *     d(i, j)     = sum over k of (l[i][k] - r[j][k])^2, an integer <= 128 * 255^2 = 8 323 200 < 2^24
+ *     best, second  the two smallest under lexicographic (d, j): ties go to the lower index
+ *     dist_best, dist_second  those integers as float, which is exact
+ *     one right descriptor: second = 0, dist_second = +INFINITY (as the float matcher)
+ *     accept      = dist_best / dist_second < 0.8f in IEEE float division; 0 / 0 is NaN and fails
+ *     l empty: OK, nothing is written.  r empty: every row is {0, 0, 0, +INFINITY, +INFINITY} (as popsift_hip_match_sets).
+ * The rows equal popsift_hip_match_sets' on the same values as floats, bit for bit: integer-valued floats below 2^24 make
+ * the float matcher's sums exact.  One GEMM on the i8 matrix instructions gives them (match_u8.hip): no screening margin,
+ * no re-rank; popsift_hip_match_set_path does not apply.
+ *
+ * popsift_hip_match_pairs_bytes: the rule of popsift_hip_match_pairs, word for word, on these rows -- conditions 1 to 4,
+ * pairs in ascending l, *n_pairs and cap, ERR_TOO_SMALL, and the ERR_INVALID checks before any GPU call.  max_dist2 is in
+ * byte units squared.
+ *
+ * As for float sets: all scratch belongs to l (one match at a time per left set), r may be the left set of another thread's
+ * call, and with sets on different GPUs r's bytes are copied to l's GPU once per call.
+ */
+typedef struct popsift_hip_bytefeatures popsift_hip_bytefeatures;
+int popsift_hip_bytefeatures_from_host(int device, const uint8_t* desc, int n_descriptors, popsift_hip_bytefeatures** out);
+int popsift_hip_bytefeatures_from_set(const popsift_hip_devfeatures* f, popsift_hip_bytefeatures** out);
+int popsift_hip_clone_results_u8(popsift_hip_ctx* ctx, int k, popsift_hip_bytefeatures** out);
+int popsift_hip_bytefeatures_free(popsift_hip_bytefeatures* f);
+int popsift_hip_bytefeatures_info(const popsift_hip_bytefeatures* f, int* device, int* n_descriptors);
+int popsift_hip_bytefeatures_download(const popsift_hip_bytefeatures* f, uint8_t* desc, int32_t* rev);
+int popsift_hip_match_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, popsift_hip_match* out);
+int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r,
+                                  const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
 
 int popsift_hip_get_report(const popsift_hip_ctx* ctx, popsift_hip_report* rep);
 /* profile != 0: bracket every blur-level launch with HIP events (serialises the

@@ -142,6 +142,14 @@ SYMBOLS = [
     ("popsift_hip_match_set_path", C.c_int, [C.c_int]),
     ("popsift_hip_default_match_opts", None, [C.POINTER(MatchOpts)]),
     ("popsift_hip_match_pairs", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
+    ("popsift_hip_bytefeatures_from_host", C.c_int, [C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
+    ("popsift_hip_bytefeatures_from_set", C.c_int, [_vp, C.POINTER(_vp)]),
+    ("popsift_hip_clone_results_u8", C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
+    ("popsift_hip_bytefeatures_free", C.c_int, [_vp]),
+    ("popsift_hip_bytefeatures_info", C.c_int, [_vp, _ip, _ip]),
+    ("popsift_hip_bytefeatures_download", C.c_int, [_vp, _vp, _vp]),
+    ("popsift_hip_match_bytes", C.c_int, [_vp, _vp, _vp]),
+    ("popsift_hip_match_pairs_bytes", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
     ("popsift_hip_set_profile", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_octave_dims", C.c_int, [_vp, C.c_int, _ip, _ip]),
@@ -297,6 +305,78 @@ class DevFeatures:
     def close(self):
         if self._h:
             lib().popsift_hip_devfeatures_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ByteFeatures:
+    """popsift_hip_bytefeatures: a device-resident set of byte descriptors and its exact integer matcher."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def from_host(cls, desc, device=0):
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 128)
+        h = _vp()
+        rc = lib().popsift_hip_bytefeatures_from_host(device, desc.ctypes.data, len(desc), C.byref(h))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_bytefeatures_from_host")
+        return cls(h)
+
+    @classmethod
+    def from_set(cls, features):
+        """a DevFeatures set quantized on its GPU (the byte rule of popsift_hip_fetch_item_u8)"""
+        h = _vp()
+        rc = lib().popsift_hip_bytefeatures_from_set(features._h, C.byref(h))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_bytefeatures_from_set")
+        return cls(h)
+
+    def info(self):
+        """(device, n_descriptors)"""
+        d, nd = C.c_int(), C.c_int()
+        lib().popsift_hip_bytefeatures_info(self._h, C.byref(d), C.byref(nd))
+        return d.value, nd.value
+
+    def download(self):
+        """(desc (n, 128) uint8, descriptor -> feature map (n,) int32)"""
+        nd = self.info()[1]
+        desc = np.zeros((nd, 128), np.uint8)
+        rev = np.zeros(nd, np.int32)
+        rc = lib().popsift_hip_bytefeatures_download(self._h, desc.ctypes.data, rev.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_bytefeatures_download")
+        return desc, rev
+
+    def match(self, other):
+        """popsift_hip_match_bytes: a MATCH_DTYPE row per descriptor; the distances are integers held in floats"""
+        out = np.zeros(self.info()[1], MATCH_DTYPE)
+        rc = lib().popsift_hip_match_bytes(self._h, other._h, out.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_bytes")
+        return out
+
+    def match_pairs(self, other, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """popsift_hip_match_pairs_bytes: DevFeatures.match_pairs' rule on match()'s rows; max_dist2 in byte units squared"""
+        nd = self.info()[1]
+        out = np.zeros(nd, PAIR_DTYPE)
+        opts = MatchOpts(ratio, max_dist2, 1 if cross_check else 0, 0)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs_bytes(self._h, other._h, C.byref(opts), out.ctypes.data if nd else None, nd,
+                                                 C.byref(n))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_bytes")
+        return out[:n.value]
+
+    def close(self):
+        if self._h:
+            lib().popsift_hip_bytefeatures_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -594,6 +674,12 @@ class Context:
         h = _vp()
         self._chk(lib().popsift_hip_clone_results(self._h, C.byref(h)), "popsift_hip_clone_results")
         return DevFeatures(h)
+
+    def clone_results_u8(self, k=0):
+        """image k's descriptors as a device-resident byte set (popsift_hip_clone_results_u8)"""
+        h = _vp()
+        self._chk(lib().popsift_hip_clone_results_u8(self._h, k, C.byref(h)), "popsift_hip_clone_results_u8")
+        return ByteFeatures(h)
 
     def rerun_keypoint_stages(self):
         self._chk(lib().popsift_hip_rerun_keypoint_stages(self._h), "rerun_keypoint_stages")

@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "devfeatures.h"
@@ -1816,6 +1817,133 @@ int popsift_hip_devfeatures_download_u8(const popsift_hip_devfeatures* f, uint8_
     return ok ? POPSIFT_HIP_OK : POPSIFT_HIP_ERR_DEVICE;
 }
 
+/* ---- byte sets */
+
+int popsift_hip_bytefeatures_free(popsift_hip_bytefeatures* f)
+{
+    if (!f) return POPSIFT_HIP_OK;
+    (void)hipSetDevice(f->device);
+    if (f->m_stream) (void)hipStreamDestroy((hipStream_t)f->m_stream);
+    for (void* p : {(void*)f->d_desc, (void*)f->d_rev, f->m_partial, f->m_out, (void*)f->d_norm, (void*)f->m_rnorm, f->p_pairs,
+                    (void*)f->p_idx, f->p_back})
+        if (p) (void)hipFree(p);
+    if (f->m_host) (void)hipHostFree(f->m_host);
+    if (f->p_host) (void)hipHostFree(f->p_host);
+    delete f;
+    return POPSIFT_HIP_OK;
+}
+
+} /* extern "C" */
+
+namespace {
+
+/* an uninitialised set of n descriptors on `device`, made current (allocations of at least one element keep the pointers
+ * valid for empty sets) */
+int bytefeatures_new(int device, int n, popsift_hip_bytefeatures** out)
+{
+    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    popsift_hip_bytefeatures* f = new (std::nothrow) popsift_hip_bytefeatures();
+    if (!f) return POPSIFT_HIP_ERR_OOM;
+    f->device = device;
+    f->n_desc = n;
+    if (hipMalloc((void**)&f->d_desc, (size_t)128 * (size_t)std::max(n, 1)) != hipSuccess ||
+        hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(n, 1)) != hipSuccess) {
+        popsift_hip_bytefeatures_free(f);
+        return POPSIFT_HIP_ERR_OOM;
+    }
+    *out = f;
+    return POPSIFT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int popsift_hip_bytefeatures_from_host(int device, const uint8_t* desc, int n, popsift_hip_bytefeatures** out)
+{
+    if (!out || n < 0 || (n > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc = check_device(device)) return rc;
+    popsift_hip_bytefeatures* f = nullptr;
+    if (int rc = bytefeatures_new(device, n, &f)) return rc;
+    if (n > 0 && (hipMemcpy(f->d_desc, desc, (size_t)128 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+                  hipMemset(f->d_rev, 0xff, sizeof(int) * (size_t)n) != hipSuccess || /* -1: no feature behind it */
+                  hipDeviceSynchronize() != hipSuccess)) {
+        popsift_hip_bytefeatures_free(f);
+        return POPSIFT_HIP_ERR_DEVICE;
+    }
+    *out = f;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_bytefeatures_from_set(const popsift_hip_devfeatures* src, popsift_hip_bytefeatures** out)
+{
+    if (!src || !out) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    popsift_hip_bytefeatures* f = nullptr;
+    if (int rc = bytefeatures_new(src->device, src->n_desc, &f)) return rc;
+    /* the null stream: ordered after whatever wrote the set; the set's own match stream does not wait for it, so the
+     * call returns with the bytes in place */
+    const int n = src->n_desc;
+    if (n > 0 && (launch_desc_bytes(src->d_desc, n, f->d_desc, nullptr) != hipSuccess ||
+                  hipMemcpyAsync(f->d_rev, src->d_rev, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
+                  hipStreamSynchronize(nullptr) != hipSuccess)) {
+        popsift_hip_bytefeatures_free(f);
+        return POPSIFT_HIP_ERR_DEVICE;
+    }
+    *out = f;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_clone_results_u8(popsift_hip_ctx* c, int k, popsift_hip_bytefeatures** out)
+{
+    if (!c || !out) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc = results_here(c, k)) return rc;
+    const int                 n = c->n_desc[k];
+    popsift_hip_bytefeatures* f = nullptr;
+    if (int rc = bytefeatures_new(c->device, n, &f))
+        return fail(c, rc, "cannot allocate the byte set: %s", popsift_hip_strerror(rc));
+    ImageSlot& sl = c->slot[k];
+    const int  rc = [&]() -> int {
+        if (n == 0) return 0;
+        /* the bytes the byte fetch calls deliver: the slot's byte buffer, then device to device */
+        if (int e = slot_u8_ready(c, sl)) return e;
+        HIP_TRY(c, launch_desc_bytes(sl.desc.p, n, sl.desc_u8.p, c->stream));
+        SYNC_CHK(c, "k_desc_bytes");
+        HIP_TRY(c, hipMemcpyAsync(f->d_desc, sl.desc_u8.p, (size_t)128 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(f->d_rev, sl.map.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return 0;
+    }();
+    if (rc) {
+        popsift_hip_bytefeatures_free(f);
+        return rc;
+    }
+    *out = f;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_bytefeatures_info(const popsift_hip_bytefeatures* f, int* device, int* n_descriptors)
+{
+    if (!f) return POPSIFT_HIP_ERR_INVALID;
+    if (device) *device = f->device;
+    if (n_descriptors) *n_descriptors = f->n_desc;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_bytefeatures_download(const popsift_hip_bytefeatures* f, uint8_t* desc, int32_t* rev)
+{
+    if (!f) return POPSIFT_HIP_ERR_INVALID;
+    if (f->n_desc <= 0) return POPSIFT_HIP_OK;
+    if (hipSetDevice(f->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    if (desc && hipMemcpy(desc, f->d_desc, (size_t)128 * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
+        return POPSIFT_HIP_ERR_DEVICE;
+    if (rev && hipMemcpy(rev, f->d_rev, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
+        return POPSIFT_HIP_ERR_DEVICE;
+    return POPSIFT_HIP_OK;
+}
+
 static std::atomic<int> g_match_path{POPSIFT_HIP_MATCH_AUTO};
 
 int popsift_hip_match_set_path(int path)
@@ -1925,21 +2053,99 @@ void match_forward(MatchStatus& ok, popsift_hip_devfeatures* l, const popsift_hi
                     l->m_redo, s);
 }
 
-}  // namespace
+/* The reverse sweep of the cross-check: the n_list right descriptors of `list` (ascending) against all of l, on l's
+ * stream; returns their rows, in list order, in l's p_back. */
+const popsift_hip_match* match_reverse(MatchStatus& ok, popsift_hip_devfeatures* l, const float* rdesc, const int* list,
+                                       int n_list, int path)
+{
+    const int    l_len = l->n_desc;
+    hipStream_t  s = (hipStream_t)l->m_stream;
+    /* per member of J: 128 floats, a result row, a norm and a redo slot (+ the redo count) */
+    const size_t per = sizeof(float) * 128 + sizeof(popsift_hip_match) + sizeof(float) + sizeof(int);
+    if (!match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list + 1, per)) return nullptr;
+    float* const gdesc = (float*)l->p_back;
+    auto* const  rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
+    float* const gnorm = (float*)(rows + n_list);
+    int* const   redo = (int*)(gnorm + n_list);
+    const bool   screen = match_screens(path, n_list, l_len);
+    ok(launch_gather_rows(rdesc, list, n_list, gdesc, s));
+    if (screen) {
+        match_own_norms(ok, l, s);
+        if (ok.good()) ok(launch_norms(gdesc, n_list, gnorm, s));
+    }
+    if (ok.good()) match_sweep(ok, l, screen, gdesc, n_list, gnorm, l->d_desc, l_len, l->d_norm, rows, redo, s);
+    return rows;
+}
 
-extern "C" {
+/* ---- the same three steps for byte sets (match_u8.hip): one exact kernel, no path choice */
 
-int popsift_hip_match_sets(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r, popsift_hip_match* out)
+void match_own_norms(MatchStatus& ok, popsift_hip_bytefeatures* f, hipStream_t s)
+{
+    if (ok.good() && !f->d_norm && ok(hipMalloc((void**)&f->d_norm, sizeof(int) * (size_t)f->n_desc)))
+        ok(launch_norms_u8(f->d_desc, f->n_desc, f->d_norm, s));
+}
+
+void match_sweep_u8(MatchStatus& ok, popsift_hip_bytefeatures* own, const uint8_t* ldesc, int l_len, const int* lnorm,
+                    const uint8_t* rdesc, int r_len, const int* rnorm, popsift_hip_match* d_out, hipStream_t s)
+{
+    const int n_split = match_u8_splits(l_len, r_len);
+    if (!match_grow(ok, own->m_partial, own->m_partial_cap, match_u8_partial_bytes(l_len, n_split), 1)) return;
+    ok(launch_match_u8(ldesc, l_len, lnorm, rdesc, r_len, rnorm, n_split, own->m_partial, d_out, s));
+}
+
+void match_forward(MatchStatus& ok, popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, int /*path*/,
+                   const uint8_t** rdesc, uint8_t** r_copy)
+{
+    *rdesc = r->d_desc;
+    *r_copy = nullptr;
+    if (!l->m_stream) {
+        hipStream_t s = nullptr;
+        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
+    }
+    if (ok.good() && !l->m_out) ok(hipMalloc(&l->m_out, sizeof(popsift_hip_match) * (size_t)l->n_desc));
+    if (ok.good() && r->device != l->device && r->n_desc > 0) {
+        const size_t bytes = (size_t)128 * (size_t)r->n_desc;
+        if (ok(hipMalloc((void**)r_copy, bytes)) && ok(hipMemcpyPeer(*r_copy, l->device, r->d_desc, r->device, bytes)))
+            *rdesc = *r_copy;
+    }
+    hipStream_t s = (hipStream_t)l->m_stream;
+    match_own_norms(ok, l, s);
+    /* the right set may be the left set of another thread's match: its norms go to a buffer of this call */
+    if (match_grow(ok, l->m_rnorm, l->m_rnorm_cap, (size_t)r->n_desc, sizeof(int)))
+        ok(launch_norms_u8(*rdesc, r->n_desc, l->m_rnorm, s));
+    if (ok.good())
+        match_sweep_u8(ok, l, l->d_desc, l->n_desc, l->d_norm, *rdesc, r->n_desc, l->m_rnorm, (popsift_hip_match*)l->m_out, s);
+}
+
+const popsift_hip_match* match_reverse(MatchStatus& ok, popsift_hip_bytefeatures* l, const uint8_t* rdesc, const int* list,
+                                       int n_list, int /*path*/)
+{
+    hipStream_t  s = (hipStream_t)l->m_stream;
+    /* per member of J: 128 bytes, a result row and a norm */
+    const size_t per = 128 + sizeof(popsift_hip_match) + sizeof(int);
+    if (!match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list, per)) return nullptr;
+    uint8_t* const gdesc = (uint8_t*)l->p_back;
+    auto* const    rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
+    int* const     gnorm = (int*)(rows + n_list);
+    ok(launch_gather_rows_u8(rdesc, list, n_list, gdesc, s)) && ok(launch_norms_u8(gdesc, n_list, gnorm, s));
+    if (ok.good()) match_sweep_u8(ok, l, gdesc, n_list, gnorm, l->d_desc, l->n_desc, l->d_norm, rows, s);
+    return rows;
+}
+
+/* popsift_hip_match_sets / popsift_hip_match_bytes */
+template <class Set>
+int match_rows(const Set* lc, const Set* r, popsift_hip_match* out, int path)
 {
     if (!lc || !r || (lc->n_desc > 0 && !out)) return POPSIFT_HIP_ERR_INVALID;
     if (lc->n_desc == 0) return POPSIFT_HIP_OK;
-    popsift_hip_devfeatures* l = const_cast<popsift_hip_devfeatures*>(lc);
+    Set* l = const_cast<Set*>(lc);
     if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    typedef typename std::remove_pointer<decltype(l->d_desc)>::type Elem;
     MatchStatus  ok;
-    const float* rdesc = nullptr;
-    float*       r_copy = nullptr;
+    const Elem*  rdesc = nullptr;
+    Elem*        r_copy = nullptr;
     const size_t out_bytes = sizeof(popsift_hip_match) * (size_t)l->n_desc;
-    match_forward(ok, l, r, g_match_path.load(), &rdesc, &r_copy);
+    match_forward(ok, l, r, path, &rdesc, &r_copy);
     if (ok.good() && !l->m_host) ok(hipHostMalloc(&l->m_host, out_bytes, hipHostMallocDefault));
     hipStream_t s = (hipStream_t)l->m_stream;
     if (ok.good() && ok(hipMemcpyAsync(l->m_host, l->m_out, out_bytes, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s)))
@@ -1948,17 +2154,10 @@ int popsift_hip_match_sets(const popsift_hip_devfeatures* lc, const popsift_hip_
     return ok.rc;
 }
 
-void popsift_hip_default_match_opts(popsift_hip_match_opts* o)
-{
-    if (!o) return;
-    o->ratio = 0.8f;
-    o->max_dist2 = INFINITY;
-    o->cross_check = 0;
-    o->reserved = 0;
-}
-
-int popsift_hip_match_pairs(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r,
-                            const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs)
+/* popsift_hip_match_pairs / popsift_hip_match_pairs_bytes */
+template <class Set>
+int match_pairs(const Set* lc, const Set* r, const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap,
+                int* n_pairs, int path)
 {
     if (!lc || !r || !opts || !n_pairs || (cap > 0 && !pairs)) return POPSIFT_HIP_ERR_INVALID;
     if (!(opts->ratio >= 0.0f) || std::isinf(opts->ratio) || std::isnan(opts->max_dist2) || opts->reserved != 0 ||
@@ -1966,12 +2165,13 @@ int popsift_hip_match_pairs(const popsift_hip_devfeatures* lc, const popsift_hip
         return POPSIFT_HIP_ERR_INVALID;
     *n_pairs = 0;
     if (lc->n_desc == 0 || r->n_desc == 0) return POPSIFT_HIP_OK;
-    popsift_hip_devfeatures* l = const_cast<popsift_hip_devfeatures*>(lc);
+    Set* l = const_cast<Set*>(lc);
     if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    const int    l_len = l->n_desc, r_len = r->n_desc, path = g_match_path.load();
+    typedef typename std::remove_pointer<decltype(l->d_desc)>::type Elem;
+    const int    l_len = l->n_desc, r_len = r->n_desc;
     MatchStatus  ok;
-    const float* rdesc = nullptr;
-    float*       r_copy = nullptr;
+    const Elem*  rdesc = nullptr;
+    Elem*        r_copy = nullptr;
     match_forward(ok, l, r, path, &rdesc, &r_copy);
     hipStream_t  s = (hipStream_t)l->m_stream;
     const auto*  fwd = (const popsift_hip_match*)l->m_out;
@@ -2001,22 +2201,7 @@ int popsift_hip_match_pairs(const popsift_hip_devfeatures* lc, const popsift_hip
             if (r_copy) (void)hipFree(r_copy);
             return POPSIFT_HIP_OK;
         }
-        /* per member of J: 128 floats, a result row, a norm and a redo slot (+ the redo count) */
-        const size_t per = sizeof(float) * 128 + sizeof(popsift_hip_match) + sizeof(float) + sizeof(int);
-        if (match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list + 1, per)) {
-            float* const gdesc = (float*)l->p_back;
-            auto* const  rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
-            float* const gnorm = (float*)(rows + n_list);
-            int* const   redo = (int*)(gnorm + n_list);
-            const bool   screen = match_screens(path, n_list, l_len);
-            ok(launch_gather_rows(rdesc, list, n_list, gdesc, s));
-            if (screen) {
-                match_own_norms(ok, l, s);
-                if (ok.good()) ok(launch_norms(gdesc, n_list, gnorm, s));
-            }
-            if (ok.good()) match_sweep(ok, l, screen, gdesc, n_list, gnorm, l->d_desc, l_len, l->d_norm, rows, redo, s);
-            back = rows;
-        }
+        back = match_reverse(ok, l, rdesc, list, n_list, path);
         most = std::min(most, (size_t)n_list); /* every member of J has one nearest left descriptor */
     }
     auto* const d_pairs = (popsift_hip_pair*)((char*)l->p_pairs + head);
@@ -2032,6 +2217,41 @@ int popsift_hip_match_pairs(const popsift_hip_devfeatures* lc, const popsift_hip
     }
     if (r_copy) (void)hipFree(r_copy);
     return ok.rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int popsift_hip_match_sets(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, popsift_hip_match* out)
+{
+    return match_rows(l, r, out, g_match_path.load());
+}
+
+int popsift_hip_match_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, popsift_hip_match* out)
+{
+    return match_rows(l, r, out, 0);
+}
+
+void popsift_hip_default_match_opts(popsift_hip_match_opts* o)
+{
+    if (!o) return;
+    o->ratio = 0.8f;
+    o->max_dist2 = INFINITY;
+    o->cross_check = 0;
+    o->reserved = 0;
+}
+
+int popsift_hip_match_pairs(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
+                            const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs)
+{
+    return match_pairs(l, r, opts, pairs, cap, n_pairs, g_match_path.load());
+}
+
+int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r,
+                                  const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs)
+{
+    return match_pairs(l, r, opts, pairs, cap, n_pairs, 0);
 }
 
 void* popsift_hip_host_alloc(size_t bytes)

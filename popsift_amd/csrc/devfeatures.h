@@ -38,3 +38,26 @@ struct popsift_hip_devfeatures {
     void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows and its redo list */
     size_t p_back_cap = 0;      /* rows */
 };
+
+/* A set of byte descriptors (popsift_hip_bytefeatures).  The scratch members mean what their namesakes above mean; a
+ * zero-filled block reads as an empty set. */
+struct popsift_hip_bytefeatures {
+    int      device = 0;
+    int      n_desc = 0;
+    uint8_t* d_desc = nullptr; /* n_desc * 128, the caller's bytes */
+    int*     d_rev = nullptr;  /* n_desc: descriptor -> feature, -1 = none */
+    void*    m_stream = nullptr;
+    void*    m_partial = nullptr;
+    size_t   m_partial_cap = 0;
+    void*    m_out = nullptr;
+    void*    m_host = nullptr;
+    int*     d_norm = nullptr;  /* |x - 128|^2 per descriptor, computed on first use by a match */
+    int*     m_rnorm = nullptr;
+    size_t   m_rnorm_cap = 0;
+    void*    p_pairs = nullptr;
+    void*    p_host = nullptr;
+    int*     p_idx = nullptr;
+    size_t   p_idx_cap = 0;
+    void*    p_back = nullptr; /* of J: gathered descriptors, the reverse sweep's rows, their norms */
+    size_t   p_back_cap = 0;
+};

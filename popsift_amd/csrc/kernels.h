@@ -168,6 +168,14 @@ hipError_t launch_gather_rows(const float* desc, const int* list, int n, float* 
 hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
                             const popsift_hip_match* back, const int* rank, int* counts, popsift_hip_pair* pairs, int* n_pairs,
                             hipStream_t s);
+/* match_u8.hip: exact integer 2-NN of byte descriptors (128 bytes each, 16-byte aligned) on the i8 matrix instructions.
+ * Norms are |x - 128|^2 as int; `out` receives l_len rows whose distances are integers held in floats. */
+int        match_u8_splits(int l_len, int r_len);
+size_t     match_u8_partial_bytes(int l_len, int n_split);
+hipError_t launch_norms_u8(const uint8_t* desc, int n, int* out, hipStream_t s);
+hipError_t launch_match_u8(const uint8_t* ldesc, int l_len, const int* lnorm, const uint8_t* rdesc, int r_len,
+                           const int* rnorm, int n_split, void* partial, popsift_hip_match* out, hipStream_t s);
+hipError_t launch_gather_rows_u8(const uint8_t* desc, const int* list, int n, uint8_t* out, hipStream_t s);
 /* Feature records (72-byte popsift::Feature layout) with device descriptor pointers for a cloned set */
 hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, float* desc_base, void* out, hipStream_t s);
 

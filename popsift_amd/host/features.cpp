@@ -310,38 +310,97 @@ int FeaturesDev::getDevice() const
     return dev;
 }
 
-std::vector<FeaturesDev::Match> FeaturesDev::matchAndGet(FeaturesDev* other)
+namespace {
+
+/* matchAndGet / matchPairs of both set kinds: `match` and `pairs` are the C calls of the kind */
+template <class Set, class Fn>
+std::vector<FeaturesDev::Match> match_and_get(const Set* l, const Set* r, int l_len, Fn match)
 {
-    std::vector<Match> res;
-    if (!_set || !other || !other->_set) return res;
-    const int                      l_len = getDescriptorCount();
+    std::vector<FeaturesDev::Match> res;
+    if (!l || !r) return res;
     std::vector<popsift_hip_match> raw((size_t)l_len);
-    const int                      rc = popsift_hip_match_sets(_set, other->_set, raw.data());
+    const int                      rc = match(l, r, raw.data());
     if (rc != POPSIFT_HIP_OK) dev_fatal("matching failed", rc);
     res.resize((size_t)l_len);
     for (int i = 0; i < l_len; i++) {
         const popsift_hip_match& m = raw[(size_t)i];
-        res[(size_t)i] = Match{m.best, m.second, m.accept != 0, m.dist_best, m.dist_second};
+        res[(size_t)i] = FeaturesDev::Match{m.best, m.second, m.accept != 0, m.dist_best, m.dist_second};
     }
     return res;
 }
 
-std::vector<FeaturesDev::Pair> FeaturesDev::matchPairs(FeaturesDev* other, const MatchOptions& opts)
+template <class Set, class Fn>
+std::vector<FeaturesDev::Pair> match_pairs(const Set* l, const Set* r, int l_len, const FeaturesDev::MatchOptions& opts, Fn pairs)
 {
-    static_assert(sizeof(Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
-    std::vector<Pair> res;
-    if (!_set || !other || !other->_set) return res;
-    res.resize((size_t)getDescriptorCount()); /* always enough */
+    static_assert(sizeof(FeaturesDev::Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
+    std::vector<FeaturesDev::Pair> res;
+    if (!l || !r) return res;
+    res.resize((size_t)l_len); /* always enough */
     popsift_hip_match_opts o;
     popsift_hip_default_match_opts(&o);
     o.ratio = opts.ratio;
     o.max_dist2 = opts.maxDist2;
     o.cross_check = opts.crossCheck ? 1 : 0;
     int       n = 0;
-    const int rc = popsift_hip_match_pairs(_set, other->_set, &o, (popsift_hip_pair*)res.data(), res.size(), &n);
+    const int rc = pairs(l, r, &o, (popsift_hip_pair*)res.data(), res.size(), &n);
     if (rc != POPSIFT_HIP_OK) dev_fatal("matching failed", rc);
     res.resize((size_t)n);
     return res;
+}
+
+}  // namespace
+
+std::vector<FeaturesDev::Match> FeaturesDev::matchAndGet(FeaturesDev* other)
+{
+    return match_and_get(_set, other ? other->_set : 0, getDescriptorCount(), popsift_hip_match_sets);
+}
+
+std::vector<FeaturesDev::Pair> FeaturesDev::matchPairs(FeaturesDev* other, const MatchOptions& opts)
+{
+    return match_pairs(_set, other ? other->_set : 0, getDescriptorCount(), opts, popsift_hip_match_pairs);
+}
+
+FeaturesDevBytes* FeaturesDev::toBytes() const
+{
+    if (!_set) return 0;
+    popsift_hip_bytefeatures* b = 0;
+    const int                 rc = popsift_hip_bytefeatures_from_set(_set, &b);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot make the byte set", rc);
+    return new FeaturesDevBytes(b);
+}
+
+/* ------------------------------------------------------------------------ FeaturesDevBytes */
+
+FeaturesDevBytes::FeaturesDevBytes(const unsigned char* desc, int num_ori, int device) : _set(0)
+{
+    const int rc = popsift_hip_bytefeatures_from_host(device, desc, num_ori, &_set);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot allocate the byte set", rc);
+}
+
+FeaturesDevBytes::~FeaturesDevBytes() { popsift_hip_bytefeatures_free(_set); }
+
+int FeaturesDevBytes::getDescriptorCount() const
+{
+    int n = 0;
+    if (_set) popsift_hip_bytefeatures_info(_set, 0, &n);
+    return n;
+}
+
+int FeaturesDevBytes::getDevice() const
+{
+    int dev = 0;
+    if (_set) popsift_hip_bytefeatures_info(_set, &dev, 0);
+    return dev;
+}
+
+std::vector<FeaturesDevBytes::Match> FeaturesDevBytes::matchAndGet(FeaturesDevBytes* other)
+{
+    return match_and_get(_set, other ? other->_set : 0, getDescriptorCount(), popsift_hip_match_bytes);
+}
+
+std::vector<FeaturesDevBytes::Pair> FeaturesDevBytes::matchPairs(FeaturesDevBytes* other, const MatchOptions& opts)
+{
+    return match_pairs(_set, other ? other->_set : 0, getDescriptorCount(), opts, popsift_hip_match_pairs_bytes);
 }
 
 /* FeaturesDev::match + show_distance (features.cu:222-300): the reference prints from the device */

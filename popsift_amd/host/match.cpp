@@ -3,6 +3,7 @@
  * library: extract two images in Config::MatchingMode (features stay on the GPU), print the counts,
  * brute-force match left against right (one accept / reject line per left descriptor).
  * Extension: --pairs [--ratio R] [--max-dist D] [--cross-check] prints the correspondences instead.
+ * Extension: --bytes quantizes both sets on the GPU and matches the byte descriptors (exact integer distances).
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -31,6 +32,7 @@ static bool write_as_uchar = false;
 static bool dont_write = false;
 static bool pgmread_loading = false;
 static bool print_pairs = false;
+static bool match_bytes = false;
 static popsift::FeaturesDev::MatchOptions pair_opts;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
@@ -88,20 +90,49 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.fval("max-dist", "Matching", "With --pairs: a pair needs an L2 distance of at most this",
            [&](float f) { pair_opts.maxDist2 = f * f; });
     o.flag("cross-check", 0, "Matching", "With --pairs: keep mutual nearest neighbours only", [&] { pair_opts.crossCheck = true; });
+    o.flag("bytes", 0, "Matching",
+           "Match byte descriptors: both sets are quantized on the GPU (0 .. 255, rounded) and matched with exact integer\n"
+           "distances; --max-dist is then in byte units.  Needs --norm-multi (9 gives VLFeat-style bytes)",
+           [&] { match_bytes = true; });
     o.parse(argc, argv);
 }
 
-/* one line per pair through the sets' reverse maps (descriptor -> feature), then the count */
-static void print_matching_pairs(popsift::FeaturesDev* l, popsift::FeaturesDev* r)
+/* the reverse map (descriptor -> feature) of a float or a byte set */
+static vector<int> reverse_map(popsift::FeaturesDev* f)
+{
+    vector<int> fem((size_t)f->getDescriptorCount());
+    popsift_hip_devfeatures_download(f->getHandle(), 0, fem.data());
+    return fem;
+}
+static vector<int> reverse_map(popsift::FeaturesDevBytes* f)
+{
+    vector<int> fem((size_t)f->getDescriptorCount());
+    popsift_hip_bytefeatures_download(f->getHandle(), 0, fem.data());
+    return fem;
+}
+
+/* one line per pair through the sets' reverse maps, then the count */
+template <class Set>
+static void print_matching_pairs(Set* l, Set* r)
 {
     const vector<popsift::FeaturesDev::Pair> pairs = l->matchPairs(r, pair_opts);
-    vector<int> l_fem((size_t)l->getDescriptorCount()), r_fem((size_t)r->getDescriptorCount());
-    popsift_hip_devfeatures_download(l->getHandle(), 0, l_fem.data());
-    popsift_hip_devfeatures_download(r->getHandle(), 0, r_fem.data());
+    const vector<int>                        l_fem = reverse_map(l), r_fem = reverse_map(r);
     for (const popsift::FeaturesDev::Pair& p : pairs)
         printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[(size_t)p.r], p.r,
                sqrtf(p.distBest));
     printf("Number of pairs:       %zu\n", pairs.size());
+}
+
+/* --bytes without --pairs: FeaturesDev::match's line per left descriptor, from the byte matcher's rows */
+static void print_byte_matches(popsift::FeaturesDevBytes* l, popsift::FeaturesDevBytes* r)
+{
+    if (l->getDescriptorCount() == 0 || r->getDescriptorCount() == 0) return;
+    const vector<popsift::FeaturesDevBytes::Match> m = l->matchAndGet(r);
+    const vector<int>                              l_fem = reverse_map(l), r_fem = reverse_map(r);
+    for (size_t i = 0; i < m.size(); i++)
+        printf("%s feat %4d [%4d] matches feat %4d [%4d] ( 2nd feat %4d [%4d] ) dist %.3f vs %.3f\n",
+               m[i].accept ? "accept" : "reject", l_fem[i], (int)i, r_fem[(size_t)m[i].best], m[i].best,
+               r_fem[(size_t)m[i].second], m[i].second, m[i].dist_best, m[i].dist_second);
 }
 
 static SiftJob* process_image(const string& inputFile, PopSift& sift)
@@ -147,8 +178,18 @@ int main(int argc, char** argv)
     cout << "Number of features:    " << rFeatures->getFeatureCount() << endl;
     cout << "Number of descriptors: " << rFeatures->getDescriptorCount() << endl;
 
-    if (print_pairs) print_matching_pairs(lFeatures, rFeatures);
-    else lFeatures->match(rFeatures);
+    if (match_bytes) {
+        popsift::FeaturesDevBytes* lBytes = lFeatures->toBytes();
+        popsift::FeaturesDevBytes* rBytes = rFeatures->toBytes();
+        if (print_pairs) print_matching_pairs(lBytes, rBytes);
+        else print_byte_matches(lBytes, rBytes);
+        delete lBytes;
+        delete rBytes;
+    } else if (print_pairs) {
+        print_matching_pairs(lFeatures, rFeatures);
+    } else {
+        lFeatures->match(rFeatures);
+    }
 
     delete lFeatures;
     delete rFeatures;
