@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mpix/s of SIFT extraction on synthetic 1920x1080 grayscale (BASELINE.json config 2 / 4).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU.  Started WITHOUT a torch.distributed environment and with --gpus N > 1, this script starts its
@@ -14,7 +14,11 @@ resident like the reference's FeaturesDev).  Images are independent, so
 ranks never talk on the data path (weak scaling, no RCCL); torch.distributed is used for the barriers around the
 timed region and the MAX over ranks only.
 
-Rank 0 prints ONE JSON line with the driver contract fields plus
+A plain run does what the headline figure needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the
+result line (`roofline` and `cpu_baseline` null).  Everything else the benchmark measures takes runs of its own after the
+timed region and sits behind --full (--only-roofline, the single-context passes alone, implies its share of it).
+
+Rank 0 prints ONE JSON line with the driver contract fields plus `legs_s` and, with --full,
   roofline      -- the WHOLE pipeline of one image against the HBM roofline (B_alg / T_dev, T_dev from
                    HIP events on the context's stream), with a `kernels` list: per stage its device time (HIP events
                    between the launches, C-ABI profile mode 2), share, bound, achieved / peak / frac and the HBM
@@ -23,6 +27,7 @@ Rank 0 prints ONE JSON line with the driver contract fields plus
   cpu_baseline  -- the CPU oracle (kind "port") on a bounded sample, N=1 only
   sparse_image  -- the same pipeline on a keypoint-sparse image (about 2 features per 1000 pixels), where the pyramid
                    -- the part `north_star` calls bandwidth-bound -- carries the time
+and always
   legs_s        -- wall time of every leg of this run (the timed region is `timed`)
 """
 import argparse
@@ -58,11 +63,15 @@ def parse():
     ap.add_argument("--contexts", type=int, default=3, help="extraction contexts (streams) per GPU")
     ap.add_argument("--launch-batch", type=int, default=16,
                     help="images a context extracts per submit (popsift_hip_submit_batch: every kernel launched once for all of them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="timed loop only: no roofline / host-to-host / CPU legs (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the reported extras: single-image roofline and stage times, blur "
+                         "launch profile, keypoint-sparse image, configs 1 and 3, host-to-host legs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline leg")
+    ap.add_argument("--quick", action="store_true", help="timed loop only, short result line (A/B runs); overrides --full")
     ap.add_argument("--only-roofline", action="store_true",
-                    help="run only the single-context passes (the command the profiles/ *_single_image* files were taken with)")
-    ap.add_argument("--cpu-images", type=int, default=6, help="images timed for the CPU baseline")
+                    help="run only the single-context passes of --full (the command the profiles/ *_single_image* files were "
+                         "taken with)")
+    ap.add_argument("--cpu-images", type=int, default=6, help="images timed for the CPU baseline of --full")
     ap.add_argument("--debug", default="", help="tuning runs: popsift_hip_debug_set switches, what:value,...")
     ap.add_argument("--size", default=None, help="tuning runs (--quick): WxH of the synthetic images instead of 1920x1080 "
                                                  "(3840x2160: BASELINE.json config 3)")
@@ -74,6 +83,15 @@ def parse():
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
+
+
+def extra_legs(args):
+    """Which groups of reported extras a run does after its timed region: (device, host).  device: the single-context
+    passes on rank 0's GPU (single image, blur profile; with --full also the sparse image, configs 1 and 3, host to host
+    through one context); host: the C++ API child processes and the CPU baseline.  A plain run does neither."""
+    if args.quick:
+        return False, False
+    return args.full or args.only_roofline, args.full and not args.only_roofline
 
 
 def spawn_ranks(args):
@@ -458,7 +476,8 @@ def main():
 
     extra = {}
     roofline = cpu = None
-    if rank == 0 and not args.quick:
+    device_legs, host_legs = extra_legs(args)
+    if rank == 0 and device_legs:
         c0 = ctxs[0]
         # ---- one image on an otherwise idle GPU: T_dev, stage times, pipeline roofline ------------------------------
         ms_dev, stage_ms, rep = single_image(c0, ptrs[0], hip)
@@ -626,7 +645,7 @@ def main():
     if world > 1:
         dist.barrier()          # every rank has released its contexts: the C++ leg below gets the GPUs to itself
 
-    if rank == 0 and not args.quick and not args.only_roofline:
+    if rank == 0 and host_legs:
         # the drop-in C++ API (PopSift::enqueue ... SiftJob::get, pinned result pool) over EVERY GPU of the job:
         # a child process with one worker pool over POPSIFT_DEVICES; reported, never `value`
         exe = os.path.join(HERE, "popsift_amd", "popsift-bench")
@@ -696,7 +715,7 @@ def main():
                 "value": round(value, 2), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
                 "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-                "data": "synthetic",
+                "data": "synthetic", "full": bool(args.full),
                 "config": {"workload": "1920x1080 u8 grayscale, default popsift::Config (2x upscale, 9 octaves, "
                                        "3 levels, PopSift mode, loop descriptor, RootSift)",
                            "images_per_step_per_gpu": B, "distinct_images_per_gpu": U, "contexts_per_gpu": C,

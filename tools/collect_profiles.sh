@@ -17,7 +17,7 @@ cd /tmp && export TMPDIR=/tmp
 NIMG=3
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/quick -- python3 $R/bench.py --quick --steps 6 --warmup 2 > $RAW/quick.log 2> $RAW/quick.err || exit 1
 python3 $R/tools/mix_timeline.py $RAW/quick > $OUT/${TAG}_bench_quick_timeline.txt 2>&1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/bench -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $RAW/bench.log 2> $RAW/bench.err || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/bench -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $RAW/bench.log 2> $RAW/bench.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/single -- python3 $R/tools/prof_run.py 5 > $RAW/single.log 2>&1 || exit 1
 pass() {
     name=$1

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 N=${1:-4}
-BENCH_FORCE_DEVICE=0 BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus $N --contexts 2 --launch-batch 4 --steps 3 --warmup 1 --no-cpu-baseline \
+BENCH_FORCE_DEVICE=0 BENCH_BACKEND=gloo timeout -k 10 600 python3 bench.py --gpus $N --contexts 2 --launch-batch 4 --steps 3 --warmup 1 --full --no-cpu-baseline \
   > gpurun_out/bench_${N}rank_one_card.json 2> gpurun_out/bench_${N}rank_one_card.err
 echo "rc=$?"
 python3 - <<PY

@@ -64,7 +64,7 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     bench_line = [l for l in open(os.path.join(RAW, "bench.log")).read().splitlines() if l.startswith('{"metric"')][-1]
     open(os.path.join(OUT, "%s_bench_kernel_stats.txt" % TAG), "w").write(
-        "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline\n"
+        "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline\n"
         "# (1 MI355X; includes warm-up and the single-image / profile-mode / sparse / host-to-host legs: for the timed loop alone see\n"
         "#  %s_bench_quick_kernel_stats.txt)\n" % TAG
         + stats("bench") + "\n\n# bench.py output of this profiled run:\n" + bench_line + "\n")
