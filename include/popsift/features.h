@@ -157,6 +157,12 @@ public:
     std::vector<Pair> matchPairs(FeaturesDev* other, const MatchOptions& opts);
     std::vector<Pair> matchPairs(FeaturesDev* other) { return matchPairs(other, MatchOptions()); }
 
+    /* extension: (x, y, x', y') of each pair -- the positions of the features behind descriptor l of this set and
+     * descriptor r of `other` -- gathered on the GPU (popsift_hip_pair_points): the input of popsift::Verifier
+     * (popsift/verify.h).  The pairs of a byte match (FeaturesDevBytes::matchPairs) index the float sets the bytes came
+     * from, so they go through the same call on those. */
+    std::vector<float> pairPoints(FeaturesDev* other, const std::vector<Pair>& pairs);
+
     /* DEVICE pointers */
     Feature*    getFeatures();
     Descriptor* getDescriptors();

@@ -456,6 +456,90 @@ int popsift_hip_match_bytes(const popsift_hip_bytefeatures* l, const popsift_hip
 int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r,
                                   const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
 
+/*
+ * Geometric verification: RANSAC over point pairs (OpenCV's findHomography(.., RANSAC), CudaSift's FindHomography).  Given
+ * n pairs (x, y) -> (x', y') the verifier returns the model with the most inliers among T sampled hypotheses, its inlier
+ * count and a per-pair inlier mask.  The result is a function of (points, options) alone: the same bytes on every run.
+ * With m = 4 pairs per sample for a homography and 3 for an affine map, double = IEEE binary64, float = binary32, every
+ * line one IEEE operation, fma / fmaf fused:
+ *
+ * 1. Sample.  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32_t)
+ *    base = mix(mix(seed + 0x9e3779b9) ^ t); draw number c = 1, 2, .. of hypothesis t is the index
+ *    (uint64_t)mix(base + 0x9e3779b9 * c) * n >> 32.  Slot k = 0 .. m-1 takes the next draw; a draw equal to an earlier
+ *    slot of the sample is redrawn, at most 8 times; a slot whose 9 draws all repeat leaves itself and the later slots -1
+ *    and the hypothesis invalid.  The sample depends on (seed, t, n, model) alone.
+ * 2. Normalise, per side (left: x, y; right: x', y').  Of every column the smallest and the largest FINITE value, with -0
+ *    ordered below +0 (so that no reduction order matters); centre c = ((double)lo + (double)hi) * 0.5, half extent
+ *    e = ((double)hi - (double)lo) * 0.5; a column without finite values has c = e = 0.  s = max(e_x, e_y), or 1 when that
+ *    is 0; k = 1.0 / s.  A normalised coordinate is ((double)x - c_x) * k.
+ * 3. Solve, in double, on the normalised sample (x, y) -> (u, v).  Homography: unknowns g0 .. g7, g8 = 1, pair i gives the
+ *    rows [x y 1 0 0 0 -u*x -u*y | u] and [0 0 0 x y 1 -v*x -v*y | v] (rows 2i, 2i+1; -u*x is (-u) * x).  Affine map:
+ *    the 3 x 3 system [x y 1] with the two right-hand sides u and v; g6 = g7 = 0, g8 = 1.  Gaussian elimination, column
+ *    c = 0, 1, ..: the pivot row is the row r >= c with the largest |a[r][c]|, the lowest such row on a tie ('>' decides, so
+ *    a NaN never wins), swapped with row c; for r > c: f = a[r][c] / a[c][c], a[r][j] = fma(-f, a[c][j], a[r][j]) for
+ *    j > c.  Back substitution from the last row: s = b[i]; s = fma(-a[i][j], g[j], s) for j = i+1, i+2, ..; g[i] =
+ *    s / a[i][i].  Denormalise with the left side's (cx, cy, k) and the right side's (cx', cy', s'): for row i of g,
+ *    m[i][0] = g[i][0] * k, m[i][1] = g[i][1] * k, m[i][2] = fma(-m[i][0], cx, fma(-m[i][1], cy, g[i][2])); then
+ *    h[0][j] = fma(s', m[0][j], cx' * m[2][j]), h[1][j] = fma(s', m[1][j], cy' * m[2][j]), h[2][j] = m[2][j].  The nine h
+ *    are rounded to float: the model H.  The hypothesis is invalid iff a pivot is exactly 0 or one of the nine floats is
+ *    not finite.  No conditioning threshold: a near-degenerate sample yields a poor model, which scores low.  The
+ *    denominator of H is 1 at the centre of the left bounding box.
+ * 4. Score, in float: u = fmaf(h0, x, fmaf(h1, y, h2)), v = fmaf(h3, x, fmaf(h4, y, h5)), w = fmaf(h6, x, fmaf(h7, y, h8)),
+ *    dx = fmaf(-w, x', u), dy = fmaf(-w, y', v), e = fmaf(dx, dx, dy * dy), lim = (max_err * max_err) * (w * w).  A pair is
+ *    an inlier iff w > 0 && e <= lim (a NaN fails both): its transfer error in the right image is at most max_err pixels,
+ *    tested without a division.  The count of a hypothesis is its number of inliers, -1 for an invalid one.
+ * 5. Select.  The winner has the largest count, the lowest t on a tie.  No winner when no hypothesis is valid or the best
+ *    count is below m.  The mask is step 4 with the winner's H.
+ *
+ * ERR_INVALID, before any GPU call: a NULL verifier, opts or result; pts NULL with n > 0; n < 0 or n > 2^24; an unknown
+ * model; hypotheses outside 1 .. 65536; max_err not finite or <= 0; reserved != 0.  n < m: OK, no winner.  Without a
+ * winner hypothesis = -1, n_inliers = 0, H and the mask are zeros.
+ *
+ * A verifier owns a stream, device scratch and pinned staging, all grow-only, and serves one call at a time.  A call is
+ * one upload of the points, a fixed handful of launches (ransac.hip) and one download of the result with the mask.  The
+ * scoring kernel gives a workgroup POPSIFT_HIP_RANSAC_CHUNK pairs and POPSIFT_HIP_RANSAC_HYP_BLOCK hypotheses (stated here
+ * for the tests of their edges; results do not depend on them).
+ *
+ * popsift_hip_ransac_trace is the parity hook: the same computation, returning per hypothesis the sample (4 ints, -1 =
+ * unused or not found), the model (9 floats, zeros when invalid) and the count; any of the three may be NULL.
+ *
+ * popsift_hip_pair_points turns the pairs of popsift_hip_match_pairs into the points above: (x, y) of the feature behind
+ * descriptor pairs[i].l of l, (x', y') of the one behind pairs[i].r of r, gathered on l's GPU through the sets' maps
+ * (scratch belongs to l).  ERR_INVALID also for a pair index outside its set (checked before any GPU call) and for a
+ * descriptor whose map entry is -1 (sets made by popsift_hip_devfeatures_from_host).  Byte sets hold no positions: the pair
+ * indices of popsift_hip_match_pairs_bytes are the descriptor indices of the float sets the bytes came from
+ * (popsift_hip_bytefeatures_from_set, popsift_hip_clone_results_u8), so gather the points from those.
+ */
+enum { POPSIFT_HIP_MODEL_HOMOGRAPHY = 0 /* 4 pairs */, POPSIFT_HIP_MODEL_AFFINE = 1 /* 3 pairs */ };
+#define POPSIFT_HIP_RANSAC_CHUNK 1024
+#define POPSIFT_HIP_RANSAC_HYP_BLOCK 64
+typedef struct popsift_hip_ransac_opts {
+    int32_t  model;        /* POPSIFT_HIP_MODEL_*                                        */
+    int32_t  hypotheses;   /* T, 1 .. 65536                                              */
+    float    max_err;      /* inlier: transfer error in the right image <= max_err (px)  */
+    uint32_t seed;
+    int32_t  reserved[2];  /* must be 0 */
+} popsift_hip_ransac_opts;
+typedef struct popsift_hip_ransac_result {   /* 52 bytes */
+    float   H[9];          /* row major, right ~ H * left; zeros when hypothesis == -1   */
+    int32_t n_inliers;
+    int32_t hypothesis;    /* index of the winner, -1: none                              */
+    int32_t n_valid;       /* hypotheses that produced a model                           */
+    int32_t reserved;
+} popsift_hip_ransac_result;
+typedef struct popsift_hip_verifier popsift_hip_verifier;
+int  popsift_hip_verifier_create(int device, popsift_hip_verifier** out);
+int  popsift_hip_verifier_free(popsift_hip_verifier* v);
+void popsift_hip_default_ransac_opts(popsift_hip_ransac_opts* o); /* {HOMOGRAPHY, 2048, 2.0f, 0, {0, 0}} */
+/* pts: n x 4 floats (x, y, x', y') in host memory; inlier: n bytes (0 / 1) or NULL */
+int  popsift_hip_ransac(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o,
+                        popsift_hip_ransac_result* res, uint8_t* inlier);
+/* samples: T x 4, models: T x 9, counts: T */
+int  popsift_hip_ransac_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o,
+                              int32_t* samples, float* models, int32_t* counts);
+int  popsift_hip_pair_points(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
+                             const popsift_hip_pair* pairs, int n, float* pts);
+
 int popsift_hip_get_report(const popsift_hip_ctx* ctx, popsift_hip_report* rep);
 /* profile != 0: bracket every blur-level launch with HIP events (serialises the
  * octave streams; used by bench.py for the roofline object only). */

@@ -69,6 +69,12 @@ class MatchOpts(C.Structure):
     _fields_ = [("ratio", C.c_float), ("max_dist2", C.c_float), ("cross_check", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RansacOpts(C.Structure):
+    """popsift_hip_ransac_opts"""
+    _fields_ = [("model", C.c_int32), ("hypotheses", C.c_int32), ("max_err", C.c_float), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 2)]
+
+
 FEATURE_DTYPE = np.dtype([
     ("debug_octave", np.int32), ("xpos", np.float32), ("ypos", np.float32),
     ("sigma", np.float32), ("num_ori", np.int32),
@@ -78,6 +84,12 @@ MATCH_DTYPE = np.dtype([("best", np.int32), ("second", np.int32), ("accept", np.
                         ("dist_best", np.float32), ("dist_second", np.float32)])
 # popsift_hip_pair: one correspondence of DevFeatures.match_pairs
 PAIR_DTYPE = np.dtype([("l", np.int32), ("r", np.int32), ("dist_best", np.float32), ("dist_second", np.float32)])
+# popsift_hip_ransac_result: what Verifier.ransac returns beside the mask
+RANSAC_RESULT_DTYPE = np.dtype([("H", np.float32, (9,)), ("n_inliers", np.int32), ("hypothesis", np.int32),
+                                ("n_valid", np.int32), ("reserved", np.int32)])
+MODEL_HOMOGRAPHY, MODEL_AFFINE = 0, 1
+MODELS = {"homography": MODEL_HOMOGRAPHY, "affine": MODEL_AFFINE}
+RANSAC_CHUNK, RANSAC_HYP_BLOCK = 1024, 64  # POPSIFT_HIP_RANSAC_*: pairs / hypotheses per workgroup of the scoring kernel
 EXTREMUM_DTYPE = np.dtype([
     ("xpos", np.float32), ("ypos", np.float32), ("lpos", np.int32),
     ("sigma", np.float32), ("octave", np.int32), ("cell", np.int32),
@@ -150,6 +162,12 @@ SYMBOLS = [
     ("popsift_hip_bytefeatures_download", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_bytes", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_pairs_bytes", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
+    ("popsift_hip_verifier_create", C.c_int, [C.c_int, C.POINTER(_vp)]),
+    ("popsift_hip_verifier_free", C.c_int, [_vp]),
+    ("popsift_hip_default_ransac_opts", None, [C.POINTER(RansacOpts)]),
+    ("popsift_hip_ransac", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RansacOpts), _vp, _vp]),
+    ("popsift_hip_ransac_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RansacOpts), _vp, _vp, _vp]),
+    ("popsift_hip_pair_points", C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
     ("popsift_hip_set_profile", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_octave_dims", C.c_int, [_vp, C.c_int, _ip, _ip]),
@@ -302,6 +320,17 @@ class DevFeatures:
             raise PopsiftHipError(rc, "popsift_hip_match_pairs")
         return out[:n.value]
 
+    def pair_points(self, other, pairs):
+        """popsift_hip_pair_points: (x, y, x', y') of each pair of match_pairs(other) as an (n, 4) float32 array, gathered on
+        the GPU through the sets' descriptor -> feature maps; the input of Verifier.ransac"""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        pts = np.zeros((len(pairs), 4), np.float32)
+        rc = lib().popsift_hip_pair_points(self._h, other._h, pairs.ctypes.data if len(pairs) else None, len(pairs),
+                                           pts.ctypes.data if len(pairs) else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_pair_points")
+        return pts
+
     def close(self):
         if self._h:
             lib().popsift_hip_devfeatures_free(self._h)
@@ -377,6 +406,77 @@ class ByteFeatures:
     def close(self):
         if self._h:
             lib().popsift_hip_bytefeatures_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ransac_opts(model="homography", hypotheses=None, max_err=None, seed=None):
+    """popsift_hip_ransac_opts: the library's defaults with the given fields replaced; model by name or number"""
+    o = RansacOpts()
+    lib().popsift_hip_default_ransac_opts(C.byref(o))
+    o.model = MODELS.get(model, model)
+    if hypotheses is not None:
+        o.hypotheses = hypotheses
+    if max_err is not None:
+        o.max_err = max_err
+    if seed is not None:
+        o.seed = seed
+    return o
+
+
+class Verifier:
+    """popsift_hip_verifier: RANSAC over point pairs on one GPU (a stream and grow-only scratch; one call at a time)."""
+
+    def __init__(self, device=0):
+        self._h = None
+        h = _vp()
+        rc = lib().popsift_hip_verifier_create(device, C.byref(h))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_verifier_create")
+        self._h = h
+
+    @staticmethod
+    def _points(pts):
+        pts = np.ascontiguousarray(pts, np.float32)
+        if pts.size and (pts.ndim != 2 or pts.shape[1] != 4):
+            raise ValueError("points: (n, 4) float32 rows (x, y, x', y')")
+        return pts.reshape(-1, 4)
+
+    def ransac(self, pts, model="homography", hypotheses=None, max_err=None, seed=None, want_mask=True):
+        """popsift_hip_ransac -> (result, mask): result a RANSAC_RESULT_DTYPE record (H row major, n_inliers, hypothesis,
+        n_valid), mask n bytes (None with want_mask=False)"""
+        pts = self._points(pts)
+        n = len(pts)
+        res = np.zeros(1, RANSAC_RESULT_DTYPE)
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        o = ransac_opts(model, hypotheses, max_err, seed)
+        rc = lib().popsift_hip_ransac(self._h, pts.ctypes.data if n else None, n, C.byref(o), res.ctypes.data,
+                                      mask.ctypes.data if want_mask and n else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_ransac")
+        return res[0], mask
+
+    def trace(self, pts, model="homography", hypotheses=None, max_err=None, seed=None):
+        """popsift_hip_ransac_trace -> (samples (T, 4) int32, models (T, 9) float32, counts (T,) int32)"""
+        pts = self._points(pts)
+        n = len(pts)
+        o = ransac_opts(model, hypotheses, max_err, seed)
+        T = max(int(o.hypotheses), 0)
+        samples, models, counts = np.zeros((T, 4), np.int32), np.zeros((T, 9), np.float32), np.zeros(T, np.int32)
+        rc = lib().popsift_hip_ransac_trace(self._h, pts.ctypes.data if n else None, n, C.byref(o), samples.ctypes.data,
+                                            models.ctypes.data, counts.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_ransac_trace")
+        return samples, models, counts
+
+    def close(self):
+        if self._h:
+            lib().popsift_hip_verifier_free(self._h)
             self._h = None
 
     def __del__(self):

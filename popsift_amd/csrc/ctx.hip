@@ -1715,6 +1715,8 @@ int popsift_hip_devfeatures_free(popsift_hip_devfeatures* f)
     if (f->p_host) (void)hipHostFree(f->p_host);
     if (f->p_idx) (void)hipFree(f->p_idx);
     if (f->p_back) (void)hipFree(f->p_back);
+    if (f->v_buf) (void)hipFree(f->v_buf);
+    if (f->v_host) (void)hipHostFree(f->v_host);
     delete f;
     return POPSIFT_HIP_OK;
 }

@@ -37,6 +37,10 @@ struct popsift_hip_devfeatures {
     size_t p_idx_cap = 0;       /* ints */
     void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows and its redo list */
     size_t p_back_cap = 0;      /* rows */
+    /* scratch of popsift_hip_pair_points with this set on the left: a flag, the pairs, the points */
+    void*  v_buf = nullptr;
+    void*  v_host = nullptr;    /* pinned twin */
+    size_t v_cap = 0;           /* bytes */
 };
 
 /* A set of byte descriptors (popsift_hip_bytefeatures).  The scratch members mean what their namesakes above mean; a

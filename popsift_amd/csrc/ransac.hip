@@ -1,0 +1,651 @@
+/*
+ * ransac.hip -- geometric verification of correspondences on the GPU (popsift_hip_ransac, include/popsift_hip.h): T
+ * sampled hypotheses of a homography or an affine map, each scored against all n pairs, the best one's inlier mask.
+ * The rule in the header defines every operation; tests/ransac_ref.c restates it on the CPU and the results are equal
+ * as bytes.
+ *
+ *   k_ransac_bounds   bounding box of the finite coordinates, per column: integer max of order-preserving keys, so the
+ *                     result does not depend on the reduction order
+ *   k_ransac_models   one lane per hypothesis: sample, float64 solve in registers, denormalise, round to float32;
+ *                     counts[t] = 0 for a model, -1 for none
+ *   k_ransac_score    the T x n part.  A workgroup takes S_CHUNK pairs (four per lane, in registers for the whole
+ *                     sweep) and S_HYP hypotheses; a hypothesis' nine coefficients are wave-uniform loads; its count
+ *                     comes from ballots, crosses the waves through LDS and is added to counts[t] by one integer atomic
+ *                     per (chunk, hypothesis): integer sums do not depend on the order
+ *   k_ransac_select   arg-max under (count, -t) in one workgroup, writes the result record
+ *   k_ransac_mask     the winner's inlier bytes, four pairs per lane
+ *   k_pair_points     (x, y, x', y') of descriptor pairs through the sets' descriptor -> feature maps
+ */
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "devfeatures.h"
+#include "kernels.h"
+
+namespace popsift_hip {
+namespace {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int S_BLOCK = 256;                       /* lanes of a k_ransac_score workgroup */
+constexpr int S_PER_LANE = 4;                      /* pairs a lane keeps in registers */
+constexpr int S_CHUNK = POPSIFT_HIP_RANSAC_CHUNK;  /* pairs per workgroup */
+constexpr int S_HYP = POPSIFT_HIP_RANSAC_HYP_BLOCK; /* hypotheses per workgroup */
+static_assert(S_CHUNK == S_BLOCK * S_PER_LANE, "chunk = lanes x pairs per lane");
+static_assert(S_HYP <= S_BLOCK, "one lane per hypothesis merges the waves' counts");
+
+/* ---- rule 1: sample */
+
+__device__ __forceinline__ uint32_t mix(uint32_t x)
+{
+    x ^= x >> 16;
+    x *= 0x7feb352dU;
+    x ^= x >> 15;
+    x *= 0x846ca68bU;
+    x ^= x >> 16;
+    return x;
+}
+
+/* M distinct indices below n; false when a slot found no new index in its 9 draws (that slot and the later ones stay -1) */
+template <int M>
+__device__ __forceinline__ bool sample(uint32_t seed, int t, int n, int (&idx)[4])
+{
+    const uint32_t base = mix(mix(seed + 0x9e3779b9U) ^ (uint32_t)t);
+    uint32_t       c = 0;
+    bool           alive = true;
+    idx[0] = idx[1] = idx[2] = idx[3] = -1;
+#pragma unroll
+    for (int k = 0; k < M; k++) {
+        bool got = false;
+        for (int draw = 0; draw < 9 && alive && !got; draw++) {
+            c++;
+            const int i = (int)__umulhi(mix(base + 0x9e3779b9U * c), (uint32_t)n);
+            bool      seen = false;
+#pragma unroll
+            for (int j = 0; j < k; j++) seen |= idx[j] == i;
+            if (!seen) {
+                idx[k] = i;
+                got = true;
+            }
+        }
+        alive = alive && got;
+    }
+    return alive;
+}
+
+/* ---- rule 2: normalise */
+
+struct Norm {
+    double cx, cy, s, k;
+};
+
+/* float bits as an unsigned key that orders like the value, -0 below +0; no finite value has key 0 or ~0 */
+__device__ __forceinline__ uint32_t order_key(float f)
+{
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000U) ? ~b : (b | 0x80000000U);
+}
+__device__ __forceinline__ float key_value(uint32_t k)
+{
+    return __uint_as_float((k & 0x80000000U) ? (k & 0x7fffffffU) : ~k);
+}
+
+/* bounds: [col] = max key, [4 + col] = max of ~key (the minimum); 0 = no finite value in the column */
+__device__ __forceinline__ void centre_half(const uint32_t* __restrict__ bounds, int col, double* centre, double* half)
+{
+    const uint32_t hi = bounds[col], nlo = bounds[4 + col];
+    if (hi == 0) {
+        *centre = 0.0;
+        *half = 0.0;
+        return;
+    }
+    const double a = (double)key_value(~nlo), b = (double)key_value(hi);
+    *centre = (a + b) * 0.5;
+    *half = (b - a) * 0.5;
+}
+
+__device__ __forceinline__ Norm normaliser(const uint32_t* __restrict__ bounds, int col)
+{
+    Norm   q;
+    double hx, hy;
+    centre_half(bounds, col, &q.cx, &hx);
+    centre_half(bounds, col + 1, &q.cy, &hy);
+    const double e = hx > hy ? hx : hy;
+    q.s = e > 0.0 ? e : 1.0;
+    q.k = 1.0 / q.s;
+    return q;
+}
+
+__global__ __launch_bounds__(256) void k_ransac_bounds(const v4f* __restrict__ pts, int n, uint32_t* __restrict__ bounds)
+{
+    uint32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const v4f p = pts[i];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const float f = p[c];
+            if (isfinite(f)) {
+                const uint32_t k = order_key(f);
+                m[c] = max(m[c], k);
+                m[4 + c] = max(m[4 + c], ~k);
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[c] = max(m[c], (uint32_t)__shfl_xor((int)m[c], d));
+        if ((threadIdx.x & 63) == 0 && m[c] != 0) atomicMax(&bounds[c], m[c]);
+    }
+}
+
+/* ---- rule 3: solve.  Every index below is a compile-time constant after unrolling: the system stays in registers. */
+
+template <int R, int NB>
+__device__ __forceinline__ bool eliminate(double (&a)[R][R + NB])
+{
+    constexpr int C = R + NB;
+    bool          ok = true;
+#pragma unroll
+    for (int c = 0; c < R; c++) {
+        int    p = c;
+        double best = fabs(a[c][c]);
+#pragma unroll
+        for (int r = c + 1; r < R; r++) {
+            const double v = fabs(a[r][c]);
+            const bool   g = v > best;
+            best = g ? v : best;
+            p = g ? r : p;
+        }
+#pragma unroll
+        for (int r = c + 1; r < R; r++) {
+            const bool sw = p == r;
+#pragma unroll
+            for (int j = c; j < C; j++) { /* the columns before c are not read again */
+                const double lo = a[c][j], hi = a[r][j];
+                a[c][j] = sw ? hi : lo;
+                a[r][j] = sw ? lo : hi;
+            }
+        }
+        ok = ok && !(a[c][c] == 0.0);
+#pragma unroll
+        for (int r = c + 1; r < R; r++) {
+            const double f = a[r][c] / a[c][c];
+#pragma unroll
+            for (int j = c + 1; j < C; j++) a[r][j] = fma(-f, a[c][j], a[r][j]);
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+#pragma unroll
+        for (int i = R - 1; i >= 0; i--) {
+            double s = a[i][R + b];
+#pragma unroll
+            for (int j = i + 1; j < R; j++) s = fma(-a[i][j], a[j][R + b], s);
+            a[i][R + b] = s / a[i][i];
+        }
+    }
+    return ok;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
+                                                      const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                      int* __restrict__ samples, int* __restrict__ counts)
+{
+    constexpr int M = MODEL == POPSIFT_HIP_MODEL_AFFINE ? 3 : 4;
+    const int     t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= T) return;
+    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    int        idx[4];
+    bool       ok = sample<M>(seed, t, n, idx);
+    double     x[M], y[M], u[M], v[M];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const v4f p = pts[ok ? idx[i] : 0];
+        x[i] = ((double)p[0] - L.cx) * L.k;
+        y[i] = ((double)p[1] - L.cy) * L.k;
+        u[i] = ((double)p[2] - Rn.cx) * Rn.k;
+        v[i] = ((double)p[3] - Rn.cy) * Rn.k;
+    }
+    double g[9];
+    if (MODEL == POPSIFT_HIP_MODEL_AFFINE) {
+        double a[3][5];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            a[i][0] = x[i];
+            a[i][1] = y[i];
+            a[i][2] = 1.0;
+            a[i][3] = u[i];
+            a[i][4] = v[i];
+        }
+        ok = eliminate<3, 2>(a) && ok;
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            g[i] = a[i][3];
+            g[3 + i] = a[i][4];
+        }
+        g[6] = 0.0;
+        g[7] = 0.0;
+    } else {
+        double a[8][9];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            double(&r0)[9] = a[2 * i];
+            double(&r1)[9] = a[2 * i + 1];
+            r0[0] = x[i]; r0[1] = y[i]; r0[2] = 1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0;
+            r0[6] = -u[i] * x[i]; r0[7] = -u[i] * y[i]; r0[8] = u[i];
+            r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = x[i]; r1[4] = y[i]; r1[5] = 1.0;
+            r1[6] = -v[i] * x[i]; r1[7] = -v[i] * y[i]; r1[8] = v[i];
+        }
+        ok = eliminate<8, 1>(a) && ok;
+#pragma unroll
+        for (int i = 0; i < 8; i++) g[i] = a[i][8];
+    }
+    g[8] = 1.0;
+    /* denormalise: M = G * Tl, then H = Tr^-1 * M */
+    double mm[9], h[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        mm[3 * i] = g[3 * i] * L.k;
+        mm[3 * i + 1] = g[3 * i + 1] * L.k;
+        mm[3 * i + 2] = fma(-mm[3 * i], L.cx, fma(-mm[3 * i + 1], L.cy, g[3 * i + 2]));
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        h[j] = fma(Rn.s, mm[j], Rn.cx * mm[6 + j]);
+        h[3 + j] = fma(Rn.s, mm[3 + j], Rn.cy * mm[6 + j]);
+        h[6 + j] = mm[6 + j];
+    }
+    float H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        H[i] = (float)h[i];
+        ok = ok && isfinite(H[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? H[i] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) samples[4 * (size_t)t + i] = idx[i];
+    counts[t] = ok ? 0 : -1;
+}
+
+/* ---- rule 4: score */
+
+__device__ __forceinline__ bool inlier(const float (&H)[9], v4f p, float max_err2)
+{
+    const float u = fmaf(H[0], p[0], fmaf(H[1], p[1], H[2]));
+    const float v = fmaf(H[3], p[0], fmaf(H[4], p[1], H[5]));
+    const float w = fmaf(H[6], p[0], fmaf(H[7], p[1], H[8]));
+    const float dx = fmaf(-w, p[2], u);
+    const float dy = fmaf(-w, p[3], v);
+    const float e = fmaf(dx, dx, dy * dy);
+    const float lim = max_err2 * (w * w);
+    return w > 0.0f && e <= lim;
+}
+
+/* grid (hypothesis blocks, pair chunks).  A hypothesis without a model is all zeros: w = 0, no inlier, nothing is added to
+ * its -1. */
+__global__ __launch_bounds__(S_BLOCK) void k_ransac_score(const v4f* __restrict__ pts, int n, const float* __restrict__ models,
+                                                          int T, float max_err2, int* __restrict__ counts)
+{
+    __shared__ int s_cnt[S_HYP][S_BLOCK / 64];
+    const int      lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int      t0 = blockIdx.x * S_HYP;
+    const int      nh = min(S_HYP, T - t0);
+    v4f            p[S_PER_LANE];
+#pragma unroll
+    for (int r = 0; r < S_PER_LANE; r++) {
+        const int i = blockIdx.y * S_CHUNK + r * S_BLOCK + threadIdx.x;
+        /* past the end: NaN fails both tests */
+        p[r] = i < n ? pts[i] : v4f{NAN, NAN, NAN, NAN};
+    }
+    for (int k = 0; k < nh; k++) {
+        const float* __restrict__ m = models + 9 * (size_t)(t0 + k); /* the same address in every lane */
+        float H[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) H[i] = m[i];
+        int c = 0;
+#pragma unroll
+        for (int r = 0; r < S_PER_LANE; r++) c += __popcll(__ballot(inlier(H, p[r], max_err2)));
+        if (lane == 0) s_cnt[k][wave] = c;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nh) {
+        int s = 0;
+#pragma unroll
+        for (int w = 0; w < S_BLOCK / 64; w++) s += s_cnt[threadIdx.x][w];
+        if (s != 0) atomicAdd(&counts[t0 + threadIdx.x], s);
+    }
+}
+
+/* ---- rule 5: select.  One workgroup; key = (count, ~t): the largest count, then the lowest t */
+
+__global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ counts, const float* __restrict__ models, int T,
+                                                       int min_count, popsift_hip_ransac_result* __restrict__ res)
+{
+    __shared__ long long s_key[4];
+    __shared__ int       s_valid[4];
+    long long            key = -1; /* below every (count >= 0, t) */
+    int                  valid = 0;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const int c = counts[t];
+        if (c >= 0) {
+            valid++;
+            key = max(key, ((long long)c << 32) | (long long)(0xffffffffU - (uint32_t)t));
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        key = max(key, __shfl_xor(key, d));
+        valid += __shfl_xor(valid, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_key[threadIdx.x >> 6] = key;
+        s_valid[threadIdx.x >> 6] = valid;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 4; w++) {
+        key = max(key, s_key[w]);
+        valid += s_valid[w];
+    }
+    const int  count = (int)(key >> 32);
+    const int  t = (int)(0xffffffffU - (uint32_t)(key & 0xffffffffLL));
+    const bool won = key >= 0 && count >= min_count;
+    for (int i = 0; i < 9; i++) res->H[i] = won ? models[9 * (size_t)t + i] : 0.0f;
+    res->n_inliers = won ? count : 0;
+    res->hypothesis = won ? t : -1;
+    res->n_valid = valid;
+    res->reserved = 0;
+}
+
+/* four pairs and four mask bytes per lane; mask has room for n rounded up to a multiple of 4 */
+__global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts, int n,
+                                                     const popsift_hip_ransac_result* __restrict__ res, float max_err2,
+                                                     uint32_t* __restrict__ mask)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (4 * q >= n) return;
+    float H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) H[i] = res->H[i];
+    const bool won = res->hypothesis >= 0;
+    uint32_t   word = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int i = 4 * q + r;
+        if (won && i < n && inlier(H, pts[i], max_err2)) word |= 1u << (8 * r);
+    }
+    mask[q] = word;
+}
+
+/* ---- pair_points */
+
+/* *bad = 1 when a descriptor has no feature behind it (map entry outside 0 .. n_feat - 1) */
+__global__ __launch_bounds__(256) void k_pair_points(const popsift_hip_pair* __restrict__ pairs, int n,
+                                                     const DevFeature* __restrict__ lf, const int* __restrict__ lrev, int l_nfeat,
+                                                     const DevFeature* __restrict__ rf, const int* __restrict__ rrev, int r_nfeat,
+                                                     v4f* __restrict__ out, int* __restrict__ bad)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const popsift_hip_pair p = pairs[i];
+    const int              fl = lrev[p.l], fr = rrev[p.r];
+    if (fl < 0 || fl >= l_nfeat || fr < 0 || fr >= r_nfeat) {
+        *bad = 1;
+        out[i] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        return;
+    }
+    out[i] = v4f{lf[fl].xpos, lf[fl].ypos, rf[fr].xpos, rf[fr].ypos};
+}
+
+/* the first failing HIP call decides the status; the calls after it are skipped */
+struct Status {
+    int  rc = POPSIFT_HIP_OK;
+    bool good() const { return rc == POPSIFT_HIP_OK; }
+    bool operator()(hipError_t e)
+    {
+        if (e != hipSuccess && rc == POPSIFT_HIP_OK) rc = (e == hipErrorOutOfMemory) ? POPSIFT_HIP_ERR_OOM : POPSIFT_HIP_ERR_DEVICE;
+        return e == hipSuccess;
+    }
+};
+
+size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+}  // namespace
+}  // namespace popsift_hip
+
+using namespace popsift_hip;
+
+/* stream + grow-only scratch on one GPU */
+struct popsift_hip_verifier {
+    int         device = 0;
+    hipStream_t stream = nullptr;
+    char*       d_buf = nullptr; /* bounds, result record, mask, points, models, samples, counts */
+    size_t      d_cap = 0;
+    char*       h_buf = nullptr; /* pinned: the points going up; the result record, the mask and the trace coming down */
+    size_t      h_cap = 0;
+};
+
+namespace {
+
+constexpr int    MAX_PAIRS = 1 << 24;
+constexpr int    MAX_HYP = 65536;
+constexpr size_t HEAD = 64; /* bytes kept for the result record in front of the mask */
+static_assert(sizeof(popsift_hip_ransac_result) <= HEAD, "the record fits its slot");
+
+bool opts_valid(const popsift_hip_ransac_opts* o)
+{
+    return o && (o->model == POPSIFT_HIP_MODEL_HOMOGRAPHY || o->model == POPSIFT_HIP_MODEL_AFFINE) && o->hypotheses >= 1 &&
+           o->hypotheses <= MAX_HYP && std::isfinite(o->max_err) && o->max_err > 0.0f && o->reserved[0] == 0 &&
+           o->reserved[1] == 0;
+}
+
+bool grow(Status& ok, popsift_hip_verifier* v, size_t d_need, size_t h_need)
+{
+    if (ok.good() && d_need > v->d_cap) {
+        if (v->d_buf) (void)hipFree(v->d_buf);
+        v->d_buf = nullptr;
+        v->d_cap = 0;
+        if (ok(hipMalloc((void**)&v->d_buf, d_need))) v->d_cap = d_need;
+    }
+    if (ok.good() && h_need > v->h_cap) {
+        if (v->h_buf) (void)hipHostFree(v->h_buf);
+        v->h_buf = nullptr;
+        v->h_cap = 0;
+        if (ok(hipHostMalloc((void**)&v->h_buf, h_need, hipHostMallocDefault))) v->h_cap = h_need;
+    }
+    return ok.good();
+}
+
+/* popsift_hip_ransac and popsift_hip_ransac_trace: the same launches, the trace downloads three more arrays */
+int run(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, popsift_hip_ransac_result* res,
+        uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+{
+    if (!v || !opts_valid(o) || (!trace && !res) || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
+    const int T = o->hypotheses;
+    const int m = o->model == POPSIFT_HIP_MODEL_AFFINE ? 3 : 4;
+    if (n < m) { /* no sample exists */
+        if (res) {
+            memset(res, 0, sizeof *res);
+            res->hypothesis = -1;
+        }
+        if (inlier && n > 0) memset(inlier, 0, (size_t)n);
+        if (samples) memset(samples, 0xff, sizeof(int32_t) * 4 * (size_t)T);
+        if (models) memset(models, 0, sizeof(float) * 9 * (size_t)T);
+        if (counts) memset(counts, 0xff, sizeof(int32_t) * (size_t)T);
+        return POPSIFT_HIP_OK;
+    }
+    if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status       ok;
+    const size_t b_pts = sizeof(float) * 4 * (size_t)n, b_mask = round16((size_t)n);
+    const size_t b_models = round16(sizeof(float) * 9 * (size_t)T), b_samples = sizeof(int) * 4 * (size_t)T,
+                 b_counts = round16(sizeof(int) * (size_t)T);
+    /* device: [bounds 32][record 64][mask][points][models][samples][counts]; the record and the mask come down together,
+     * the last three are contiguous for the trace */
+    const size_t o_head = 32, o_mask = o_head + HEAD, o_pts = o_mask + b_mask, o_models = o_pts + b_pts,
+                 o_samples = o_models + b_models, o_counts = o_samples + b_samples, d_need = o_counts + b_counts;
+    const size_t b_trace = b_models + b_samples + b_counts;
+    /* pinned: [points][record + mask][trace] */
+    const size_t g_down = b_pts, g_trace = g_down + HEAD + b_mask, h_need = g_trace + b_trace;
+    if (!grow(ok, v, d_need, h_need)) return ok.rc;
+    hipStream_t const s = v->stream;
+    char* const       d = v->d_buf;
+    auto* const       d_bounds = (uint32_t*)d;
+    auto* const       d_res = (popsift_hip_ransac_result*)(d + o_head);
+    auto* const       d_pts = (const v4f*)(d + o_pts);
+    auto* const       d_models = (float*)(d + o_models);
+    auto* const       d_samples = (int*)(d + o_samples);
+    auto* const       d_counts = (int*)(d + o_counts);
+    const float       max_err2 = o->max_err * o->max_err;
+
+    memcpy(v->h_buf, pts, b_pts);
+    ok(hipMemcpyAsync(d + o_pts, v->h_buf, b_pts, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, 32, s));
+    if (ok.good()) {
+        const int blocks = std::min((n + 255) / 256, 512);
+        hipLaunchKernelGGL(k_ransac_bounds, dim3(blocks), dim3(256), 0, s, d_pts, n, d_bounds);
+        if (o->model == POPSIFT_HIP_MODEL_AFFINE)
+            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_AFFINE>, dim3((T + 63) / 64), dim3(64), 0, s, d_pts, n, T, o->seed,
+                               d_bounds, d_models, d_samples, d_counts);
+        else
+            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_HOMOGRAPHY>, dim3((T + 63) / 64), dim3(64), 0, s, d_pts, n, T,
+                               o->seed, d_bounds, d_models, d_samples, d_counts);
+        hipLaunchKernelGGL(k_ransac_score, dim3((T + S_HYP - 1) / S_HYP, (n + S_CHUNK - 1) / S_CHUNK), dim3(S_BLOCK), 0, s, d_pts,
+                           n, d_models, T, max_err2, d_counts);
+        hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, s, d_counts, d_models, T, m, d_res);
+        hipLaunchKernelGGL(k_ransac_mask, dim3((n + 1023) / 1024), dim3(256), 0, s, d_pts, n, d_res, max_err2,
+                           (uint32_t*)(d + o_mask));
+        ok(hipGetLastError());
+    }
+    const size_t down = HEAD + (inlier ? (size_t)n : 0);
+    ok.good() && ok(hipMemcpyAsync(v->h_buf + g_down, d + o_head, down, hipMemcpyDeviceToHost, s));
+    if (ok.good() && trace) ok(hipMemcpyAsync(v->h_buf + g_trace, d + o_models, b_trace, hipMemcpyDeviceToHost, s));
+    if (ok.good() && ok(hipStreamSynchronize(s))) {
+        if (res) memcpy(res, v->h_buf + g_down, sizeof *res);
+        if (inlier) memcpy(inlier, v->h_buf + g_down + HEAD, (size_t)n);
+        const char* tr = v->h_buf + g_trace;
+        if (models) memcpy(models, tr, sizeof(float) * 9 * (size_t)T);
+        if (samples) memcpy(samples, tr + b_models, b_samples);
+        if (counts) memcpy(counts, tr + b_models + b_samples, sizeof(int) * (size_t)T);
+    }
+    return ok.rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int popsift_hip_verifier_create(int device, popsift_hip_verifier** out)
+{
+    if (!out) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
+    if (device < 0 || device >= count) return POPSIFT_HIP_ERR_INVALID;
+    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    popsift_hip_verifier* v = new (std::nothrow) popsift_hip_verifier();
+    if (!v) return POPSIFT_HIP_ERR_OOM;
+    v->device = device;
+    if (hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete v;
+        return POPSIFT_HIP_ERR_DEVICE;
+    }
+    *out = v;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_verifier_free(popsift_hip_verifier* v)
+{
+    if (!v) return POPSIFT_HIP_OK;
+    (void)hipSetDevice(v->device);
+    if (v->stream) (void)hipStreamDestroy(v->stream);
+    if (v->d_buf) (void)hipFree(v->d_buf);
+    if (v->h_buf) (void)hipHostFree(v->h_buf);
+    delete v;
+    return POPSIFT_HIP_OK;
+}
+
+void popsift_hip_default_ransac_opts(popsift_hip_ransac_opts* o)
+{
+    if (!o) return;
+    o->model = POPSIFT_HIP_MODEL_HOMOGRAPHY;
+    o->hypotheses = 2048;
+    o->max_err = 2.0f;
+    o->seed = 0;
+    o->reserved[0] = o->reserved[1] = 0;
+}
+
+int popsift_hip_ransac(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o,
+                       popsift_hip_ransac_result* res, uint8_t* inlier)
+{
+    return run(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr);
+}
+
+int popsift_hip_ransac_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, int32_t* samples,
+                             float* models, int32_t* counts)
+{
+    return run(v, pts, n, o, nullptr, nullptr, true, samples, models, counts);
+}
+
+int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r, const popsift_hip_pair* pairs,
+                            int n, float* pts)
+{
+    if (!lc || !r || n < 0 || (n > 0 && (!pairs || !pts))) return POPSIFT_HIP_ERR_INVALID;
+    for (int i = 0; i < n; i++)
+        if (pairs[i].l < 0 || pairs[i].l >= lc->n_desc || pairs[i].r < 0 || pairs[i].r >= r->n_desc) return POPSIFT_HIP_ERR_INVALID;
+    if (n == 0) return POPSIFT_HIP_OK;
+    popsift_hip_devfeatures* l = const_cast<popsift_hip_devfeatures*>(lc);
+    if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status ok;
+    if (!l->m_stream) {
+        hipStream_t s = nullptr;
+        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
+    }
+    /* device block and its pinned twin: a flag, the pairs, the points */
+    const size_t b_pairs = sizeof(popsift_hip_pair) * (size_t)n, b_pts = sizeof(float) * 4 * (size_t)n, need = 16 + b_pairs + b_pts;
+    if (ok.good() && need > l->v_cap) {
+        if (l->v_buf) (void)hipFree(l->v_buf);
+        if (l->v_host) (void)hipHostFree(l->v_host);
+        l->v_buf = l->v_host = nullptr;
+        l->v_cap = 0;
+        if (ok(hipMalloc(&l->v_buf, need)) && ok(hipHostMalloc(&l->v_host, need, hipHostMallocDefault))) l->v_cap = need;
+    }
+    /* a right set on another GPU: its feature records and its map come over for the call */
+    const DevFeature* rf = r->d_feat;
+    const int*        rrev = r->d_rev;
+    char*             r_copy = nullptr;
+    if (ok.good() && r->device != l->device) {
+        const size_t bf = sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1), br = sizeof(int) * (size_t)r->n_desc;
+        if (ok(hipMalloc((void**)&r_copy, bf + br)) && ok(hipMemcpyPeer(r_copy, l->device, r->d_feat, r->device, bf)) &&
+            ok(hipMemcpyPeer(r_copy + bf, l->device, r->d_rev, r->device, br))) {
+            rf = (const DevFeature*)r_copy;
+            rrev = (const int*)(r_copy + bf);
+        }
+    }
+    if (ok.good()) {
+        hipStream_t const s = (hipStream_t)l->m_stream;
+        char* const       d = (char*)l->v_buf;
+        char* const       h = (char*)l->v_host;
+        memset(h, 0, 16);
+        memcpy(h + 16, pairs, b_pairs);
+        if (ok(hipMemcpyAsync(d, h, 16 + b_pairs, hipMemcpyHostToDevice, s))) {
+            hipLaunchKernelGGL(k_pair_points, dim3((n + 255) / 256), dim3(256), 0, s, (const popsift_hip_pair*)(d + 16), n,
+                               l->d_feat, l->d_rev, l->n_feat, rf, rrev, r->n_feat, (v4f*)(d + 16 + b_pairs), (int*)d);
+            ok(hipGetLastError());
+        }
+        /* the flag and the points come down; the pairs in between stay */
+        if (ok.good() && ok(hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, s)) &&
+            ok(hipMemcpyAsync(h + 16 + b_pairs, d + 16 + b_pairs, b_pts, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s))) {
+            if (*(const int*)h != 0) ok.rc = POPSIFT_HIP_ERR_INVALID;
+            else memcpy(pts, h + 16 + b_pairs, b_pts);
+        }
+    }
+    if (r_copy) (void)hipFree(r_copy);
+    return ok.rc;
+}
+
+} /* extern "C" */

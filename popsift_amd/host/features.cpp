@@ -360,6 +360,17 @@ std::vector<FeaturesDev::Pair> FeaturesDev::matchPairs(FeaturesDev* other, const
     return match_pairs(_set, other ? other->_set : 0, getDescriptorCount(), opts, popsift_hip_match_pairs);
 }
 
+std::vector<float> FeaturesDev::pairPoints(FeaturesDev* other, const std::vector<Pair>& pairs)
+{
+    static_assert(sizeof(Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
+    std::vector<float> pts(4 * pairs.size());
+    if (pairs.empty()) return pts;
+    const int rc = popsift_hip_pair_points(_set, other ? other->_set : 0, (const popsift_hip_pair*)pairs.data(), (int)pairs.size(),
+                                           pts.data());
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot gather the pairs' points", rc);
+    return pts;
+}
+
 FeaturesDevBytes* FeaturesDev::toBytes() const
 {
     if (!_set) return 0;

@@ -4,11 +4,14 @@
  * brute-force match left against right (one accept / reject line per left descriptor).
  * Extension: --pairs [--ratio R] [--max-dist D] [--cross-check] prints the correspondences instead.
  * Extension: --bytes quantizes both sets on the GPU and matches the byte descriptors (exact integer distances).
+ * Extension: --verify homography|affine [--hypotheses T] [--max-err E] [--seed S] with --pairs fits the model to the pairs
+ * by RANSAC on the GPU (popsift::Verifier) and prints it with its inlier count after the pair lines.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
 #include <popsift/popsift.h>
 #include <popsift/sift_conf.h>
+#include <popsift/verify.h>
 
 #include <popsift_hip.h>
 
@@ -34,6 +37,8 @@ static bool pgmread_loading = false;
 static bool print_pairs = false;
 static bool match_bytes = false;
 static popsift::FeaturesDev::MatchOptions pair_opts;
+static bool verify_pairs = false;
+static popsift::RansacOptions verify_opts;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -94,7 +99,27 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
            "Match byte descriptors: both sets are quantized on the GPU (0 .. 255, rounded) and matched with exact integer\n"
            "distances; --max-dist is then in byte units.  Needs --norm-multi (9 gives VLFeat-style bytes)",
            [&] { match_bytes = true; });
+    o.val("verify", 0, "Matching",
+          "With --pairs: fit a model to the pairs by RANSAC on the GPU, homography or affine; prints the 3 x 3 model and\n"
+          "the number of inliers after the pair lines",
+          [&](const string& v) {
+              if (v != "homography" && v != "affine") {
+                  cerr << "--verify: homography or affine, not " << v << endl;
+                  exit(-1);
+              }
+              verify_pairs = true;
+              verify_opts.model = v == "affine" ? popsift::RansacOptions::Affine : popsift::RansacOptions::Homography;
+          });
+    o.ival("hypotheses", "Matching", "With --verify: sampled hypotheses, 1 .. 65536 (default 2048)",
+           [&](int v) { verify_opts.hypotheses = v; });
+    o.fval("max-err", "Matching", "With --verify: an inlier lies within this many pixels of its image (default 2)",
+           [&](float f) { verify_opts.maxErr = f; });
+    o.ival("seed", "Matching", "With --verify: seed of the sampler (default 0)", [&](int v) { verify_opts.seed = (unsigned)v; });
     o.parse(argc, argv);
+    if (verify_pairs && !print_pairs) {
+        cerr << "--verify works on the pairs: add --pairs" << endl;
+        exit(-1);
+    }
 }
 
 /* the reverse map (descriptor -> feature) of a float or a byte set */
@@ -111,9 +136,19 @@ static vector<int> reverse_map(popsift::FeaturesDevBytes* f)
     return fem;
 }
 
-/* one line per pair through the sets' reverse maps, then the count */
+/* --verify: the model fitted to the pairs' points and its inliers.  lf / rf: the float sets the positions come from */
+static void print_verification(popsift::FeaturesDev* lf, popsift::FeaturesDev* rf, const vector<popsift::FeaturesDev::Pair>& pairs)
+{
+    popsift::Verifier           verifier(lf->getDevice());
+    const popsift::RansacResult fit = verifier.ransac(lf->pairPoints(rf, pairs), verify_opts);
+    printf("Model (%s):\n", verify_opts.model == popsift::RansacOptions::Affine ? "affine" : "homography");
+    for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", fit.H[3 * i], fit.H[3 * i + 1], fit.H[3 * i + 2]);
+    printf("Number of inliers:     %d of %zu\n", fit.inliers, pairs.size());
+}
+
+/* one line per pair through the sets' reverse maps, then the count; lf / rf: the float sets behind l and r */
 template <class Set>
-static void print_matching_pairs(Set* l, Set* r)
+static void print_matching_pairs(Set* l, Set* r, popsift::FeaturesDev* lf, popsift::FeaturesDev* rf)
 {
     const vector<popsift::FeaturesDev::Pair> pairs = l->matchPairs(r, pair_opts);
     const vector<int>                        l_fem = reverse_map(l), r_fem = reverse_map(r);
@@ -121,6 +156,7 @@ static void print_matching_pairs(Set* l, Set* r)
         printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[(size_t)p.r], p.r,
                sqrtf(p.distBest));
     printf("Number of pairs:       %zu\n", pairs.size());
+    if (verify_pairs) print_verification(lf, rf, pairs);
 }
 
 /* --bytes without --pairs: FeaturesDev::match's line per left descriptor, from the byte matcher's rows */
@@ -181,12 +217,12 @@ int main(int argc, char** argv)
     if (match_bytes) {
         popsift::FeaturesDevBytes* lBytes = lFeatures->toBytes();
         popsift::FeaturesDevBytes* rBytes = rFeatures->toBytes();
-        if (print_pairs) print_matching_pairs(lBytes, rBytes);
+        if (print_pairs) print_matching_pairs(lBytes, rBytes, lFeatures, rFeatures);
         else print_byte_matches(lBytes, rBytes);
         delete lBytes;
         delete rBytes;
     } else if (print_pairs) {
-        print_matching_pairs(lFeatures, rFeatures);
+        print_matching_pairs(lFeatures, rFeatures, lFeatures, rFeatures);
     } else {
         lFeatures->match(rFeatures);
     }

@@ -1,0 +1,49 @@
+/* popsift::Verifier on top of popsift_hip_ransac (include/popsift/verify.h) */
+#include "popsift/verify.h"
+
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+
+#include "popsift_hip.h"
+
+namespace popsift {
+
+namespace {
+[[noreturn]] void verify_fatal(const char* what, int rc)
+{
+    std::cerr << __FILE__ << std::endl << "E    " << what << ": " << popsift_hip_strerror(rc) << std::endl;
+    exit(-1);
+}
+}  // namespace
+
+Verifier::Verifier(int device) : _v(0)
+{
+    const int rc = popsift_hip_verifier_create(device, &_v);
+    if (rc != POPSIFT_HIP_OK) verify_fatal("cannot create the verifier", rc);
+}
+
+Verifier::~Verifier() { popsift_hip_verifier_free(_v); }
+
+RansacResult Verifier::ransac(const std::vector<float>& pts, const RansacOptions& opts)
+{
+    RansacResult              out;
+    const int                 n = (int)(pts.size() / 4);
+    popsift_hip_ransac_opts   o;
+    popsift_hip_ransac_result res;
+    popsift_hip_default_ransac_opts(&o);
+    o.model = (int)opts.model;
+    o.hypotheses = opts.hypotheses;
+    o.max_err = opts.maxErr;
+    o.seed = opts.seed;
+    out.mask.resize((size_t)n);
+    const int rc = popsift_hip_ransac(_v, n ? pts.data() : 0, n, &o, &res, n ? out.mask.data() : 0);
+    if (rc != POPSIFT_HIP_OK) verify_fatal("verification failed", rc);
+    memcpy(out.H, res.H, sizeof out.H);
+    out.inliers = res.n_inliers;
+    out.hypothesis = res.hypothesis;
+    out.valid = res.n_valid;
+    return out;
+}
+
+}  // namespace popsift
