@@ -54,6 +54,12 @@ struct Config {
      * A job takes the format the configuration has when it is enqueued.  MatchingMode ignores it (FeaturesDev is float). */
     enum DescriptorFormat { FloatDescriptors, ByteDescriptors };
 
+    /* Extension: the order of the features of an image.  ArrivalOrder (default): as the refinement workgroups appended
+     * them, different from run to run.  RasterOrder: by octave, then pixel row, pixel column, level and exact position
+     * (include/popsift_hip.h, POPSIFT_HIP_ORDER_RASTER): the same bytes on every run, which also makes matchPairs and
+     * Verifier::ransac on two extractions of an image pair repeat exactly. */
+    enum FeatureOrder { ArrivalOrder, RasterOrder };
+
     /* ---- setters (sift_conf.cu:51-258) -------------------------------------- */
     void setGaussMode(const std::string& m);
     void setGaussMode(GaussMode m) { _gauss_mode = m; }
@@ -88,6 +94,7 @@ struct Config {
     DEPRECATED(void setUseRootSift(bool on));
     void setNormalizationMultiplier(int mul) { _normalization_multiplier = mul; }
     void setDescriptorFormat(DescriptorFormat f) { _descriptor_format = f; }
+    void setFeatureOrder(FeatureOrder o) { _feature_order = o; }
 
     /* ---- getters ------------------------------------------------------------- */
     bool  hasInitialBlur() const { return _assume_initial_blur; }
@@ -115,9 +122,10 @@ struct Config {
     ScalingMode    getScalingMode() const { return _scaling_mode; }
     DescMode       getDescMode() const { return _desc_mode; }
     DescriptorFormat getDescriptorFormat() const { return _descriptor_format; }
+    FeatureOrder     getFeatureOrder() const { return _feature_order; }
 
     /* compares the 14 fields that decide whether tables must be rebuilt (sift_conf.cu:285-303), and the descriptor
-     * format */
+     * format and the feature order */
     bool equal(const Config& other) const;
 
     /* ---- public data members, as in the reference ------------------------------ */
@@ -145,6 +153,7 @@ private:
     int            _normalization_multiplier;
     bool           _print_gauss_tables;
     DescriptorFormat _descriptor_format;
+    FeatureOrder     _feature_order;
 };
 
 inline bool operator==(const Config& l, const Config& r) { return l.equal(r); }

@@ -75,8 +75,50 @@ typedef struct popsift_hip_params {
                                   * pixel of level L-3 of octave o-1; 1 ScaleDirect, every octave's level 0 is blurred
                                   * straight from the input image (popsift_hip_get_gauss_table_dd).  Not Config's enum
                                   * values: a zeroed struct keeps the default.  ScaleDirect takes Gauss modes 0, 2, 3. */
-    int32_t reserved[1];
+    int32_t feature_order;       /* POPSIFT_HIP_ORDER_*: 0 (default, a zeroed struct) arrival order, 1 raster order; see below */
 } popsift_hip_params;
+
+/*
+ * Feature order.  An extraction always returns the same keypoints, orientations and descriptors; feature_order says in
+ * which ORDER.  Features are octave-major in both modes, and within an octave they follow the octave's list of refined
+ * extrema (popsift_hip_download_extrema): feature records, descriptor slabs, byte descriptors, cloned sets and their
+ * reverse maps all inherit the list order, and the grid filter breaks its ties by list position.
+ *
+ * POPSIFT_HIP_ORDER_ARRIVAL: the order in which the refinement workgroups appended their survivors: grouped by image
+ * region, different from run to run.
+ *
+ * POPSIFT_HIP_ORDER_RASTER: the result is a function of (image, params) alone: the same bytes on every run, in every
+ * batch slot and with every debug switch.  Within octave o the records (xpos, ypos in octave units, lpos, sigma) are in
+ * ascending lexicographic order of the tuple
+ *     ( iy, ix, lpos, bits(ypos), bits(xpos), bits(sigma) )
+ *   iy = pix(ypos), ix = pix(xpos);  pix(v) = 0 if v is NaN or v <= 0, 32767 if v >= 32767, else (int)v (truncation)
+ *   lpos compares as the int32 it is
+ *   bits(v) is the float's bit pattern compared as uint32
+ * i.e. raster order over the pixels of the octave's grid, then level, then the exact sub-pixel position and scale.
+ * Refinement lets through only 0 <= xpos <= w - 1, 0 <= ypos <= h - 1 and 0 <= lpos (NaN fails no comparison, so a
+ * degenerate 3 x 3 solve can in principle pass one on: pix() and bits() give it a place all the same, and -0.0 sorts by its
+ * bits, after every positive value of the pixel).  For the non-negative finite values bits() orders numerically.  Two
+ * records equal under the whole tuple are byte-identical (cell is a function of the position), so their mutual order
+ * changes no output byte.  A caller can recompute the tuple from popsift_hip_download_extrema; a feature's xpos is its
+ * octave's times a power of two.
+ *
+ * The grid filter (filter_max_extrema > 0) runs on the ordered list, which makes its (scale, list position) selection --
+ * the survivor SET in POPSIFT_HIP_FILTER_RANDOM mode included -- a function of the image; its output is ordered again.
+ * popsift_hip_rerun_keypoint_stages and the grow-and-rerun paths of popsift_hip_wait order their lists too.
+ * popsift_hip_describe_batch accepts the field and is unchanged: its results are in caller order.
+ *
+ * The max_extrema cap: when more than max_extrema candidates of an octave survive refinement, which of them are kept is
+ * decided by arrival, so the surviving set is run-dependent (their order is still the rule's).  The guarantee holds for
+ * octaves whose count stays below the cap; a reported ext_ct[o] == max_extrema (popsift_hip_get_report; counts are
+ * clamped to the cap) is the sign that it may not have held.
+ *
+ * The pass (order.hip) runs between refinement and orientation, and again after the grid filter; a workgroup takes
+ * POPSIFT_HIP_ORDER_CHUNK records of a list (stated here for the tests of its edges; results do not depend on it).  A
+ * context created with POPSIFT_HIP_ORDER_ARRIVAL allocates and launches nothing for it.  Any other value of feature_order:
+ * popsift_hip_ctx_create returns POPSIFT_HIP_ERR_INVALID.
+ */
+enum { POPSIFT_HIP_ORDER_ARRIVAL = 0, POPSIFT_HIP_ORDER_RASTER = 1 };
+#define POPSIFT_HIP_ORDER_CHUNK 1024
 
 /* POD mirror of popsift::Feature (features.h:22-34): the four Descriptor*
  * become indices into the descriptor array (-1 = unused slot). */
@@ -552,7 +594,7 @@ int popsift_hip_download_plane(popsift_hip_ctx* ctx, int octave, int kind, int l
 /* Overwrite a plane (stage isolation in tests), then re-run later stages.  kind = 1 needs params.store_dog = 1
  * (POPSIFT_HIP_ERR_STATE otherwise: the consumers form DoG values from the Gaussian planes). */
 int popsift_hip_upload_plane(popsift_hip_ctx* ctx, int octave, int kind, int level, const float* in);
-/* Initial extrema of the last image, all octaves, in device compaction order. */
+/* Initial extrema of the last image, all octaves, in list order (params.feature_order). */
 int popsift_hip_download_extrema(popsift_hip_ctx* ctx, popsift_hip_extremum* out, size_t cap, int* n);
 /* Re-run extrema + orientation + descriptors on the planes currently in memory. */
 int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
@@ -575,12 +617,16 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * (results do not depend on it); SCALE_PATH (ScaleDirect only) = 0: level 0 of every octave by one launch and each
  * level of every octave by one launch (default), 1: one level-0 launch per octave and the default mode's level launches
  * per octave (results do not depend on it); DESC_CAP = initial capacity of the descriptor buffer, in descriptors (0 = the default,
- * 2 * max_extrema: small values exercise the grow-and-rerun path of popsift_hip_wait for descriptors). */
+ * 2 * max_extrema: small values exercise the grow-and-rerun path of popsift_hip_wait for descriptors); ORDER_COARSE
+ * (POPSIFT_HIP_ORDER_RASTER only) = b in 0 .. 15, default 0: the ordering pass buckets the records by iy >> b instead of
+ * by iy before it ranks each bucket by the whole tuple, so a bucket is a band of 2^b pixel rows, all levels, and with 15
+ * the whole octave (results do not depend on it: the rank is taken under the whole tuple; the tests run the ranking
+ * loop over long buckets with it). */
 enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_HIP_DEBUG_OHIST_CAP = 3,
        POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, /* 6: retired, never reused */
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
        POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
-       POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13 };
+       POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13, POPSIFT_HIP_DEBUG_ORDER_COARSE = 14 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

@@ -25,6 +25,8 @@ GAUSS_OPENCV_COMPUTE, GAUSS_FIXED9, GAUSS_FIXED15 = 3, 4, 5
 DESC_LOOP, DESC_ILOOP, DESC_GRID, DESC_IGRID, DESC_NOTILE = 0, 1, 2, 3, 4
 NORM_ROOTSIFT, NORM_CLASSIC = 0, 1
 SCALE_DEFAULT, SCALE_DIRECT = 0, 1  # params.scale_direct (not Config::ScalingMode's enum values)
+ORDER_ARRIVAL, ORDER_RASTER = 0, 1  # params.feature_order: POPSIFT_HIP_ORDER_* (tests/order_rule.py states the raster rule)
+ORDER_CHUNK = 1024  # POPSIFT_HIP_ORDER_CHUNK: records per workgroup of the ordering pass
 
 
 class Params(C.Structure):
@@ -36,7 +38,7 @@ class Params(C.Structure):
         ("norm_mode", C.c_int32), ("norm_multi", C.c_int32), ("max_extrema", C.c_int32),
         ("assume_initial_blur", C.c_int32), ("initial_blur", C.c_float),
         ("filter_grid_size", C.c_int32), ("filter_max_extrema", C.c_int32), ("filter_sorting", C.c_int32),
-        ("store_dog", C.c_int32), ("scale_direct", C.c_int32), ("reserved", C.c_int32 * 1),
+        ("store_dog", C.c_int32), ("scale_direct", C.c_int32), ("feature_order", C.c_int32),
     ]
 
 
@@ -181,7 +183,7 @@ MATCH_AUTO, MATCH_EXACT, MATCH_SCREEN = 0, 1, 2
 STAGES = ("pyramid", "detect", "refine", "orientation", "scan", "descriptor")
 DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 7  # 6: retired
 DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL, DEBUG_DIRECT_PATH, DEBUG_DESC_CAP = 8, 9, 10, 11, 12
-DEBUG_SCALE_PATH = 13
+DEBUG_SCALE_PATH, DEBUG_ORDER_COARSE = 13, 14
 MAX_BATCH = 16
 IMG_HOST_U8, IMG_HOST_F32, IMG_DEV_U8, IMG_DEV_F32, IMG_PINNED_U8, IMG_PINNED_F32 = range(6)
 

@@ -82,6 +82,8 @@ struct ImageSlot {
     DevBuf<InitExt>     iext2; /* grid filter output (filter enabled only) */
     DevBuf<FilterState> fstate;
     DevBuf<int>         fhist;
+    DevBuf<InitExt>     otmp;  /* raster feature order only (order.hip): scratch list, never the filter's iext2 */
+    DevBuf<int>         orows; /* ... and the row counters */
     DevBuf<Ext>         ext;
     DevBuf<float, PS_ORI_NBINS> ohist; /* raw orientation histograms, one per extremum (k_orientation -> k_scan_local) */
     DevBuf<popsift_hip_feature> feats;
@@ -118,7 +120,7 @@ struct ImageSlot {
     void release()
     {
         auto each = [](auto&... b) { ((void)b.release(), ...); };
-        each(input, arena, iext, iext2, fstate, fhist, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
+        each(input, arena, iext, iext2, fstate, fhist, otmp, orows, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
              alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats);
         if (h_input) (void)hipHostFree(h_input);
         if (h_frames) (void)hipHostFree(h_frames);
@@ -159,6 +161,7 @@ struct popsift_hip_ctx {
     int       det_qcap = 1 << 30;  /* popsift_hip_debug_set hooks, see popsift_hip.h */
     int       desc_rows = 1 << 30;
     BlurTune  blur_tune{0, 0}; /* BLUR_PATH / BLUR_SEG debug switches */
+    int       order_coarse = 0; /* ORDER_COARSE: row bits the ordering pass drops from its bucket key */
     int       pyr_tail = 0;    /* PYR_TAIL: 0 the smallest octaves in one launch where they fit, 1 level launches only */
     int       cand_cap_init = 1 << 20;
     bool      cand_cap_user = false;
@@ -486,6 +489,10 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
             if (int rc = grow(c, s.iext2, need_ext)) return rc;
             if (int rc = grow(c, s.fstate, 1)) return rc;
             if (int rc = grow(c, s.fhist, filter_hist_bytes(c->sc.grid_size) / sizeof(int))) return rc;
+        }
+        if (c->p.feature_order == POPSIFT_HIP_ORDER_RASTER) {
+            if (int rc = grow(c, s.otmp, need_ext)) return rc;
+            if (int rc = grow(c, s.orows, order_rows(pd))) return rc;
         }
         if (int rc = grow(c, s.partial, (need_ext / scan_chunk() + 2) * scan_partials_per_chunk())) return rc;
         /* sift_pyramid.cu:149: max(2*max_extrema, max_orientations) descriptors to start with */
@@ -845,6 +852,20 @@ InitExt* final_iext(popsift_hip_ctx* c, int k = 0)
     return c->sc.filter_max > 0 && !c->describe ? c->slot[k].iext2.p : c->slot[k].iext.p; /* frames are not grid-filtered */
 }
 
+/* POPSIFT_HIP_ORDER_RASTER: the lists `filtered ? iext2 : iext` of the batch into the header's order */
+hipError_t enqueue_order(popsift_hip_ctx* c, bool filtered)
+{
+    OrderBatch ob{};
+    for (int k = 0; k < c->nb; k++) {
+        const ImageSlot& sl = c->slot[k];
+        ob.s[k].list = filtered ? sl.iext2.p : sl.iext.p;
+        ob.s[k].tmp = sl.otmp.p;
+        ob.s[k].rows = sl.orows.p;
+        ob.s[k].ct = c->d_ct + k;
+    }
+    return launch_order(c->pd, c->sc, c->order_coarse, ob, c->nb, c->stream);
+}
+
 /* counters_cleared: the level-0 launch of this batch has zeroed the counters (submit); re-runs clear them here */
 int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
 {
@@ -857,10 +878,21 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     HIP_TRY(c, launch_extrema(c->pd, c->d_pd, c->bd, c->nb, c->sc, c->cand_cap, filtered, c->stream,
                               stages ? c->ev_stage[POPSIFT_HIP_STAGE_REFINE] : nullptr));
     SYNC_CHK(c, "k_detect / k_refine");
+    const bool raster = c->p.feature_order == POPSIFT_HIP_ORDER_RASTER;
+    if (raster) {
+        /* before the filter: its tie-break is the list position */
+        HIP_TRY(c, enqueue_order(c, false));
+        SYNC_CHK(c, "k_order (refined list)");
+    }
     if (filtered) {
         /* Pyramid::orientation's filter hook (s_orientation.cu:353-367); the 10 % test is taken on the device */
         HIP_TRY(c, launch_filter(c->pd.n_oct, c->sc, c->bd, c->nb, c->stream));
         SYNC_CHK(c, "grid filter");
+        if (raster) {
+            /* k_filter_compact appends its chunks by arrival */
+            HIP_TRY(c, enqueue_order(c, true));
+            SYNC_CHK(c, "k_order (filtered list)");
+        }
     }
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_ORIENTATION));
     HIP_TRY(c, launch_orientation(c->d_pd, c->bd, c->nb, c->sc, filtered, (int)c->ohist_cap, c->kp_waves, c->stream));
@@ -1377,6 +1409,8 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
         (p->filter_grid_size < 1 || p->filter_grid_size > 64 || p->filter_sorting < 0 || p->filter_sorting > 2))
         return POPSIFT_HIP_ERR_INVALID;
     if (p->scale_direct != 0 && p->scale_direct != 1) return POPSIFT_HIP_ERR_INVALID;
+    if (p->feature_order != POPSIFT_HIP_ORDER_ARRIVAL && p->feature_order != POPSIFT_HIP_ORDER_RASTER)
+        return POPSIFT_HIP_ERR_INVALID;
     if (int rc = check_device(device)) return rc;
 
     popsift_hip_ctx* c = new (std::nothrow) popsift_hip_ctx();
@@ -2393,6 +2427,10 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
     case POPSIFT_HIP_DEBUG_SCALE_PATH:
         if (value < 0 || value > 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "SCALE_PATH: 0 or 1");
         c->scale_path = value;
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_ORDER_COARSE:
+        if (value < 0 || value > 15) return fail(c, POPSIFT_HIP_ERR_INVALID, "ORDER_COARSE: 0 .. 15");
+        c->order_coarse = value;
         return POPSIFT_HIP_OK;
     }
     return fail(c, POPSIFT_HIP_ERR_INVALID, "unknown debug switch %d", what);

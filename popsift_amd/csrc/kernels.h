@@ -145,6 +145,11 @@ bool       filter_supported(int n_oct, int max_extrema, int grid_size);
 size_t     filter_hist_bytes(int grid_size);
 hipError_t launch_filter(int n_oct, const SiftConsts& sc, const BatchDesc& bd, int nb, hipStream_t s);
 
+/* order.hip: the per-octave extrema lists of `ob` (counts ext_ct, capped by max_extrema) into raster order, the rule of
+ * include/popsift_hip.h.  order_rows: row counters a slot needs for this pyramid; coarse: ORDER_COARSE, 0 .. 15 */
+size_t     order_rows(const PyrDesc& pd);
+hipError_t launch_order(const PyrDesc& pd, const SiftConsts& sc, int coarse, const OrderBatch& ob, int nb, hipStream_t s);
+
 /* match.hip: brute-force 2-NN (features.cu:157-300) */
 int        match_splits(int l_len, int r_len);
 size_t     match_partial_bytes(int l_len, int n_split);

@@ -174,3 +174,23 @@ struct FrameSlot {
 struct FrameBatch {
     FrameSlot s[PS_MAX_BATCH];
 };
+
+/* Raster feature order (order.hip), contexts created with feature_order = POPSIFT_HIP_ORDER_RASTER only.  A table of its
+ * own next to BatchDesc, like FrameBatch, so that the extraction kernels' argument block keeps its size: the list to
+ * order (the slot's iext, or iext2 after the grid filter), the scratch list of the same capacity and the row counters. */
+struct OrderSlot {
+    InitExt*        list;
+    InitExt*        tmp;
+    int*            rows;
+    const Counters* ct;
+};
+struct OrderBatch {
+    OrderSlot s[PS_MAX_BATCH];
+};
+struct OrderArgs {
+    int n_oct, coarse, max_extrema;
+    int chunks;     /* workgroups per octave = ceil(max_extrema / POPSIFT_HIP_ORDER_CHUNK) */
+    int rows_total; /* row counters in use */
+    int row_base[PS_MAX_OCT]; /* first row counter of octave o */
+    int rows[PS_MAX_OCT];     /* row counters of octave o = ((h - 1) >> coarse) + 1 */
+};

@@ -4,7 +4,7 @@
  * PCIe-inclusive: every image is uploaded and its features + descriptors (about 53 MB for the dense
  * synthetic 1080p image) are downloaded into a FeaturesHost.  Never the headline `value` of bench.py.
  *   popsift-bench [--images N] [--width W] [--height H] [--inflight K] [--callers C] [--seed S] [--pgm a.pgm,b.pgm,...]
- *                 [--threshold T] [--desc-bytes]
+ *                 [--threshold T] [--desc-bytes] [--feature-order arrival|raster]
  * --callers: threads that enqueue and drain (each its share of the images and of the in-flight budget; default 1, the
  * reference's demo loop -- bench.py passes one per GPU: a single caller copies about 10 GB/s of images, enough for one GPU
  * on dense images and not for eight).  The line reports what a caller thread spends per image: in enqueue() (the copy of
@@ -13,6 +13,7 @@
  * images -- the keypoint-sparse regime, where the results are a few MB and PCIe is no longer the limit).
  * --desc-bytes: popsift::Config::ByteDescriptors -- the descriptors are quantized on the GPU and 128 bytes instead of 512
  * cross PCIe per descriptor (d2h_mb_per_image reports the results' bytes of either format).
+ * --feature-order: popsift::Config::setFeatureOrder -- raster adds the ordering pass (order.hip) to every extraction.
  * --pgm: the images to cycle through (bench.py passes the popsift_amd/synth.py images of the headline workload);
  * without it a cheap built-in generator is used.
  * Contexts per GPU come from POPSIFT_CONTEXTS_PER_DEVICE, GPUs from POPSIFT_DEVICES.
@@ -66,7 +67,7 @@ int main(int argc, char** argv)
     int images = 64, w = 1920, h = 1080, inflight = 16, callers = 1;
     unsigned seed = 1;
     float    threshold = -1.0f;
-    bool     desc_bytes = false;
+    bool     desc_bytes = false, raster = false;
     std::string pgm;
     for (int i = 1; i < argc; i += 2) {
         if (!strcmp(argv[i], "--desc-bytes")) { /* the one option without a value */
@@ -83,6 +84,13 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--callers")) callers = atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--seed")) seed = (unsigned)atoi(argv[i + 1]);
         else if (!strcmp(argv[i], "--threshold")) threshold = (float)atof(argv[i + 1]);
+        else if (!strcmp(argv[i], "--feature-order")) {
+            if (strcmp(argv[i + 1], "arrival") && strcmp(argv[i + 1], "raster")) {
+                fprintf(stderr, "popsift-bench: --feature-order arrival|raster, not %s\n", argv[i + 1]);
+                return 2;
+            }
+            raster = !strcmp(argv[i + 1], "raster");
+        }
     }
     std::vector<std::vector<unsigned char>> pool;
     if (!pgm.empty()) {
@@ -109,6 +117,7 @@ int main(int argc, char** argv)
     popsift::Config config;
     if (threshold >= 0.0f) config.setThreshold(threshold);
     if (desc_bytes) config.setDescriptorFormat(popsift::Config::ByteDescriptors);
+    if (raster) config.setFeatureOrder(popsift::Config::RasterOrder);
     PopSift         sift(config, popsift::Config::ExtractingMode, PopSift::ByteImages);
 
     if (callers < 1) callers = 1;

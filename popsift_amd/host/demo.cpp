@@ -129,6 +129,14 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& in
     val("output-file", 0, "Extensions", "Feature file to write (default output-features.txt)",
         [&](const string& s) { output_file = s; });
     ival("max-extrema", "Extensions", "Extrema kept per octave (default 100000)", [&](int v) { config.setMaxExtrema(v); });
+    val("feature-order", 0, "Extensions",
+        "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
+        "pixel column, level: the same bytes on every run)",
+        [&](const string& s) {
+            if (s == "arrival") config.setFeatureOrder(popsift::Config::ArrivalOrder);
+            else if (s == "raster") config.setFeatureOrder(popsift::Config::RasterOrder);
+            else opts.error("the argument ('" + s + "') for option '--feature-order' is invalid");
+        });
 
     opts.parse(argc, argv);
 }

@@ -115,6 +115,14 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.fval("max-err", "Matching", "With --verify: an inlier lies within this many pixels of its image (default 2)",
            [&](float f) { verify_opts.maxErr = f; });
     o.ival("seed", "Matching", "With --verify: seed of the sampler (default 0)", [&](int v) { verify_opts.seed = (unsigned)v; });
+    o.val("feature-order", 0, "Extensions",
+          "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
+          "pixel column, level: the same bytes on every run)",
+          [&](const string& s) {
+              if (s == "arrival") config.setFeatureOrder(popsift::Config::ArrivalOrder);
+              else if (s == "raster") config.setFeatureOrder(popsift::Config::RasterOrder);
+              else o.error("the argument ('" + s + "') for option '--feature-order' is invalid");
+          });
     o.parse(argc, argv);
     if (verify_pairs && !print_pairs) {
         cerr << "--verify works on the pairs: add --pairs" << endl;

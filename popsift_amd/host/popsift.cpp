@@ -65,6 +65,7 @@ popsift_hip_params to_params(const popsift::Config& c)
     p.filter_max_extrema = c.getFilterMaxExtrema();
     p.filter_sorting = (int)c.getFilterSorting(); /* RandomScale, LargestScaleFirst, SmallestScaleFirst */
     p.scale_direct = c.getScalingMode() == popsift::Config::ScaleDirect ? 1 : 0;
+    p.feature_order = c.getFeatureOrder() == popsift::Config::RasterOrder ? POPSIFT_HIP_ORDER_RASTER : POPSIFT_HIP_ORDER_ARRIVAL;
     return p;
 }
 
