@@ -603,8 +603,11 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * slow pass); CAND_CAP / OHIST_CAP = initial capacity of the candidate buffer / of the orientation-histogram buffer
  * (small values exercise the grow-and-rerun path of popsift_hip_wait); FAIL_ALLOC = n: the n-th device allocation
  * of this context from now on fails with POPSIFT_HIP_ERR_OOM (0 = off); DESC_ROWS = patch rows the loop descriptor
- * walks per pass (4 .. 128, default 128: small values make ordinary patches take the several passes that otherwise only
- * patches of more than 128 rows take -- sigma0 near 2 at the coarsest level; results do not depend on it);
+ * walks per pass (4 .. 96, default 96: small values make ordinary patches take the several passes that otherwise only
+ * the largest patches take; results do not depend on it); DESC_LIST = list positions (samples of the patch's rows laid
+ * end to end) the loop descriptor walks per pass, clamped to 64 .. the capacity of its row-end bit table (3456, the
+ * default: patches of the coarsest levels have up to 5200 and take two passes; a pass that fills up ends inside a row
+ * and the next one takes the rest of that row; results do not depend on it);
  * KP_WAVES = waves per image in the launches of
  * the orientation and descriptor kernels (a multiple of 32; default 8 per wave slot of the device; results do not
  * depend on it; tools/kp_waves_sweep.sh: 8192 .. 131072 within 1.5 %); BLUR_PATH = which kernels build the pyramid's
@@ -626,7 +629,8 @@ enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_H
        POPSIFT_HIP_DEBUG_FAIL_ALLOC = 4, POPSIFT_HIP_DEBUG_DESC_ROWS = 5, /* 6: retired, never reused */
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
        POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
-       POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13, POPSIFT_HIP_DEBUG_ORDER_COARSE = 14 };
+       POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13, POPSIFT_HIP_DEBUG_ORDER_COARSE = 14,
+       POPSIFT_HIP_DEBUG_DESC_LIST = 15 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

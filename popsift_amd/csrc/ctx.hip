@@ -160,6 +160,7 @@ struct popsift_hip_ctx {
     int       kp_waves = 65536; /* launch size of the keypoint kernels in waves (8 per wave slot of the device) */
     int       det_qcap = 1 << 30;  /* popsift_hip_debug_set hooks, see popsift_hip.h */
     int       desc_rows = 1 << 30;
+    int       desc_list = 1 << 30;
     BlurTune  blur_tune{0, 0}; /* BLUR_PATH / BLUR_SEG debug switches */
     int       order_coarse = 0; /* ORDER_COARSE: row bits the ordering pass drops from its bucket key */
     int       pyr_tail = 0;    /* PYR_TAIL: 0 the smallest octaves in one launch where they fit, 1 level launches only */
@@ -319,6 +320,7 @@ void init_tables(popsift_hip_ctx* c)
     sc.filter_mode = p.filter_sorting;
     sc.det_qcap = c->det_qcap;
     sc.desc_rows = c->desc_rows;
+    sc.desc_list = c->desc_list;
 }
 
 /* PopSift::private_init, popsift.cpp:89-120 */
@@ -2419,6 +2421,9 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_DESC_ROWS:
         c->desc_rows = c->sc.desc_rows = std::max(value, 4);
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_DESC_LIST:
+        c->desc_list = c->sc.desc_list = std::max(value, 64);
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_DIRECT_PATH:
         if (value < 0 || value > 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "DIRECT_PATH: 0 or 1");

@@ -316,6 +316,8 @@ __device__ __forceinline__ float atan2_bins9(float y, float x)
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) fix64 lds_fix64;
 typedef __attribute__((address_space(3))) unsigned int lds_u32;
+typedef __attribute__((address_space(3))) short lds_i16;
+typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 
 /* ISA: end */
 #ifndef KP_NW
@@ -831,7 +833,15 @@ constexpr int DESC_COPIES = DESC_NCOPY;
  * what the (ix + iy) rotation of the 32-word layout did for the four lane groups working on different rows. */
 constexpr int DESC_RS = 36;                /* words per cell row */
 constexpr int DESC_CS = 3 * DESC_RS + 32;  /* words per copy (the last row needs no padding): 140 */
-constexpr int DESC_MAXROWS = 128; /* patch rows handled by the span path */
+/* A pass of the span path: at most DESC_MAXROWS patch rows (the default configuration's largest patches have 93) and at
+ * most DESC_LISTCAP list positions.  In front of a wave's histograms lie, per pass, one 16-bit record per row and one bit
+ * per list position (k_descriptor); the table has one 64-bit word more than the positions need, because the sample loop
+ * reads the word of the step AFTER the one it works on.  Records and table are sized together: with the histograms they
+ * fill the 5120 bytes that 32 waves per CU leave each wave. */
+constexpr int DESC_MAXROWS = 96;
+constexpr int DESC_REC_WORDS = (((DESC_MAXROWS + 1) * 2 + 7) / 8) * 2; /* 50 words: the rows' records and the sentinel */
+constexpr int DESC_TAB64 = 55;                                          /* 64-bit words of the row-end bits */
+constexpr int DESC_LISTCAP = (DESC_TAB64 - 1) * 64;                     /* 3456 list positions per pass */
 /* The 64 lanes walk 64 CONSECUTIVE samples of the list, i.e. one and a half to two neighbouring patch rows, whose up /
  * down taps are each other's centre rows.  Round 2 ran four lane groups (16 lanes each, on four distant parts of the
  * patch: 61 % fewer LDS bank conflicts) while the kernel was bound by vector issue and LDS; once round 3 had slimmed the
@@ -844,25 +854,37 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
     const Counters* __restrict__ ct = bd.s[blockIdx.y].ct;
     const DescRec* __restrict__ drec = bd.s[blockIdx.y].drec;
     float* __restrict__         desc = bd.s[blockIdx.y].desc;
-    /* LDS of a wave: the row records first, then the histogram copies.  The records -- per patch row of the current pass:
-     * flat index of its first sample (low 16 bits) | that index minus the first column of its span relative to xmin
-     * (high 16 bits, signed), so that column = flat index - (word >> 16) -- lie IN FRONT of the histograms so that the
-     * address of cell (-1, -1) of copy 0, which the cell arithmetic forms although no weight ever goes there (352 bytes
-     * before the copy), is still a non-negative LDS address. */
-    constexpr int ROW_WORDS = (DESC_MAXROWS + 1 + 3) & ~3; /* 132: the histograms start on a 16-byte boundary */
+    /* LDS of a wave: the row records, the row-end bits, then the histogram copies.  The rows' column intervals of the
+     * current pass are laid end to end as one flat list.  Record k (16 bits, signed) belongs to the k-th row from the first
+     * one that holds a sample: the first column of the row's interval relative to xmin minus the flat index of its first
+     * sample, so that column = flat index + record.  Bit p of the table is set where list position p is the LAST of its
+     * row.  The row of position p is then the number of bits below p: the bits of the earlier 64-bit words are a
+     * running count, those of p's own word below p are one v_mbcnt pair -- no search.  Every row between the first and
+     * the last of a pass holds at least one position, so that count IS the index of the row's record.  All this lies IN
+     * FRONT of the histograms so that the address of cell (-1, -1) of copy 0, which the cell arithmetic forms although
+     * no weight ever goes there (352 bytes before the copy), is still a non-negative LDS address. */
+    constexpr int ROW_WORDS = DESC_REC_WORDS + 2 * DESC_TAB64; /* 160 */
+    static_assert(ROW_WORDS % 4 == 0 && DESC_REC_WORDS % 2 == 0, "the histograms start on a 16-byte boundary, the table on an 8-byte one");
     static_assert(ROW_WORDS * 4 >= 352, "cell (-1, -1) of copy 0 stays inside the wave's LDS");
+    static_assert((ROW_WORDS + 2 * DESC_COPIES * DESC_CS) * 4 <= 5120, "32 waves per CU share 160 KiB");
+    static_assert(DESC_TAB64 <= 64, "one lane clears one word of the table");
     __shared__ __attribute__((aligned(16))) unsigned int s_lds[KP_NW][ROW_WORDS + 2 * DESC_COPIES * DESC_CS];
     const int     lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int     cpy = lane & (DESC_COPIES - 1);
-    unsigned int* rinfo = s_lds[wave];
+    short*        rec = (short*)s_lds[wave];
+    unsigned int* tab = s_lds[wave] + DESC_REC_WORDS;
     fix64*        hall = (fix64*)(s_lds[wave] + ROW_WORDS);
-    /* 32-bit LDS addresses: the row records, this lane's histogram copy (as a float: the cell addresses are formed by FMAs) */
-    const unsigned int rbase32 = (unsigned int)(size_t)(lds_u32*)rinfo;
+    /* 32-bit LDS addresses: the row records, the bit table, this lane's histogram copy (as a float: the cell addresses are
+     * formed by FMAs) */
+    const unsigned int rbase32 = (unsigned int)(size_t)(lds_i16*)rec;
+    const unsigned int tbase32 = (unsigned int)(size_t)(lds_u32*)tab;
     const float        hbasef = (float)(unsigned int)(size_t)(lds_fix64*)(hall + cpy * DESC_CS);
     const float        cpy8f = (float)(cpy << 3);
     const int     total = min(ct->ori_total, desc_cap);
-    /* rows per pass: DESC_MAXROWS, or fewer when a test asks for it (popsift_hip_debug_set DESC_ROWS) */
+    /* rows and list positions per pass: DESC_MAXROWS and DESC_LISTCAP, or fewer when a test asks for it
+     * (popsift_hip_debug_set DESC_ROWS / DESC_LIST) */
     const int     maxrows = min(max(sc.desc_rows, 4), DESC_MAXROWS);
+    const int     maxlist = min(max(sc.desc_list, 64), DESC_LISTCAP);
 
     for (XcdSlice sl = xcd_slice<KP_NW>(); sl.more(total); sl.s += sl.step) {
         const int d = sl.index();
@@ -905,12 +927,17 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
             /* the Gaussian window weight comes out of v_exp already multiplied by the fixed-point scale 2^fbits */
             const float ffbits = (float)fbits;
 
-            /* A patch is walked in passes of at most `maxrows` rows (ONE pass for every patch of sigma0 <= 1.78 at three
-             * levels; the largest the library accepts -- sigma0 = 2, two levels -- spans 173 rows).  The histogram sums are
-             * integers, so the split changes nothing. */
-            for (int rb = 0; rb < hy_all && wx > 0; rb += maxrows) {
+            /* A patch is walked in passes of at most `maxrows` rows and `maxlist` list positions (the default
+             * configuration's patches: up to 93 rows and 5200 positions, so the largest take two passes; the largest the
+             * library accepts -- sigma0 = 2, two levels -- span 173 rows).  A pass starts at row rb, `skip` columns into
+             * that row's interval: the row in which the list fills up is cut there and the next pass takes the rest of it.
+             * The histogram sums are integers, so the split changes nothing. */
+            for (int rb = 0, skip = 0; rb < hy_all && wx > 0;) {
             const int   ymin = ymin0 + rb;
             const int   hy = min(hy_all - rb, maxrows);
+            /* the row-end bits of the previous pass go (the first pass clears what the previous descriptor left) */
+            if (lane < DESC_TAB64) ((unsigned long long*)tab)[lane] = 0ull;
+            wave_lds_sync();
 
             /* Row spans.  The samples that count lie in the square |u|,|v| < 2.5 (cell units, rotated
              * by ang), which fills only 1/(|cos|+|sin|)^2 = 50..100 % of its bounding box.  Per patch
@@ -918,7 +945,8 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
              * (prefix sum) and the wave walks that flat list, so nearly every lane holds a sample
              * that passes the exact test below.  The intervals only have to be a superset of the
              * samples inside the square. */
-            int T = 0, grow = 0; /* list length; the first row that holds a sample */
+            int T = 0, grow = 0, nrec = 0; /* list length; the first row that holds a sample; rows from there to the last */
+            int rb_next = rb + hy, skip_next = 0; /* where the next pass starts */
             {
                 int         carry = 0;
                 for (int r0 = 0; r0 < hy; r0 += 64) {
@@ -951,24 +979,58 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                         jlo = max(xmin, (int)floorf(x + lo - 1e-3f) + 1);
                         const int jhi = min(xmax, (int)ceilf(x + hi + 1e-3f) - 1);
                         len = ok ? max(jhi - jlo + 1, 0) : 0;
+                        /* the pass's first row: what the previous pass took of it */
+                        if (r == 0) {
+                            const int s = min(skip, len);
+                            jlo += s;
+                            len -= s;
+                        }
                         if (len == 0) jlo = xmin;
                     }
+                    /* In exact geometry the rows that hold a sample are contiguous.  The bit count below is a row INDEX only
+                     * if they are, so a row without a sample below the first one that has some gets one position (column
+                     * xmin: inside the image, outside the square -- the exact test drops it). */
+                    const unsigned long long live = __ballot(len > 0);
+                    bool                     below = carry > 0;
+                    if (carry == 0 && live != 0ull) {
+                        const int first = __ffsll((long long)live) - 1;
+                        grow = r0 + first;
+                        below = lane > first;
+                    }
+                    if (below && r < hy && len == 0) len = 1;
                     const int incl = wave_incl_scan(len);
                     const int start = carry + incl - len;
-                    if (r < hy) rinfo[r] = (unsigned int)start | ((unsigned int)(start - (jlo - xmin)) << 16);
-                    const unsigned long long live = __ballot(len > 0);
-                    if (carry == 0 && live != 0ull) grow = r0 + __ffsll((long long)live) - 1;
+                    /* the list is full: the first row that ends beyond `maxlist` is cut there, the rows below it wait for the
+                     * next pass (the prefix sum never falls, so they are the lanes above) */
+                    const unsigned long long over = __ballot(carry + incl > maxlist);
+                    if (over != 0ull) {
+                        const int cut = __ffsll((long long)over) - 1;
+                        if (lane == cut) len = maxlist - start;
+                        if (lane > cut) len = 0;
+                        rb_next = rb + r0 + cut;
+                        skip_next = __builtin_amdgcn_readlane(len, cut) + ((r0 + cut == 0) ? skip : 0);
+                    }
+                    if (len > 0) {
+                        const int last = start + len - 1;
+                        rec[r - grow] = (short)((jlo - xmin) - start);
+                        __hip_atomic_fetch_or((lds_u32*)(size_t)(tbase32 + 4u * (unsigned int)(last >> 5)), 1u << (last & 31),
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                    const unsigned long long kept = __ballot(len > 0);
+                    if (kept != 0ull) nrec = r0 + 64 - __builtin_clzll(kept) - grow;
+                    if (over != 0ull) {
+                        carry = maxlist;
+                        break;
+                    }
                     carry += __builtin_amdgcn_readlane(incl, 63);
                 }
                 T = carry;
-                /* Two sentinels close the list: a flat index at or beyond T ends up in "row" hy at column -32767 -- a sample far
-                 * outside the patch, which the in-square test drops (its taps are read at byte offset 0 of the patch: the
-                 * negative offset saturates in the conversion) -- and stops there: the record after it starts at 65535.  So
-                 * no index needs clamping and no lane needs a "past the end" flag. */
-                if (lane == 0) {
-                    rinfo[hy] = (unsigned int)T | 0x7fff0000u;
-                    rinfo[hy + 1] = 0xffffu;
-                }
+                /* A sentinel closes the records: a flat index at or beyond T has all the pass's bits below it, so it ends up
+                 * in the "row" after the last at column -32767 -- a sample far outside the patch, which the in-square test
+                 * drops (its taps are read inside the plane: at the byte offset of that column where it is positive, at
+                 * offset 0 of the patch where not -- the negative offset saturates in the conversion).  So no index needs
+                 * clamping and no lane needs a "past the end" flag. */
+                if (lane == 0) rec[nrec] = -32767;
             }
             wave_lds_sync();
 
@@ -979,18 +1041,14 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
 #else
             const int   steps = (T + 63) >> 6;
 #endif
-            /* the lane's place in the row records: LDS address of its current row's record, that row (counted from the top of
-             * the PATCH, as a float: it only feeds FMAs, see coord()), the record and the one of the row below.  Every lane
-             * starts in the row of the list's first sample, which the span pass has found (coord() walks on from there to
-             * the lane's own). */
-            unsigned int rp = rbase32 + 4u * (unsigned int)grow;
-            float        fr = (float)(rb + grow);
-            unsigned int cur = 0;
-            unsigned int nxt = 0x7fff0000u | 0xffffu;
-            if (T > 0) {
-                cur = rinfo[grow];
-                nxt = rinfo[grow + 1];
-            }
+            /* The wave's place in the row-end bits, all wave-uniform: the word of the step whose coordinates come next
+             * (read one step ahead, with the taps, so no coord() waits for it), the LDS address of the word after it, and the
+             * rows that end before that step -- counted from the top of the PATCH, so that the count plus the bits below
+             * the lane is the lane's patch row; the records are addressed from row 0 of the patch to match. */
+            unsigned long long rmask = *(const unsigned long long*)tab;
+            unsigned int       rnext = tbase32 + 8u;
+            unsigned int       rows_done = (unsigned int)(rb + grow);
+            const unsigned int rec0 = rbase32 - 2u * (unsigned int)(rb + grow);
 
             /* Sample (row r, column c), both counted from the corner (ymin0, xmin) of the PATCH (so that the arithmetic does not
              * depend on how the patch is cut into passes): cell-unit position
@@ -1010,22 +1068,25 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
              * What an instruction costs decides the form of everything below (tools/ubench/valu_rate.hip, MI355X): f32
              * add / mul / FMA, 32-bit add / and / xor / arithmetic shift issue at twice the rate of compares, selects,
              * conversions, floor, min / max, shifts-with-add and 24-bit multiplies.  So row and column enter as floats
-             * (one conversion, the row advances by a float add), and the byte offset of the taps is one FMA -- exact:
+             * (one conversion each), and the byte offset of the taps is one FMA -- exact:
              * 4 * (row * pitch + column) < 2^24 -- and one conversion, instead of a 24-bit multiply and a shift-add. */
-            auto coord = [&](int i, unsigned int& off, float& u, float& v) { /* ISA: coordinates */
-                /* the record of the row below the lane's current one stays in a register: no LDS read -- which would queue
-                 * behind the four atomics the lane has just issued -- unless the lane moves on to another row
-                 * (k_descriptor 421 -> 411 us) */
-                while (i >= (int)(nxt & 0xffffu)) {
-                    fr += 1.0f;
-                    rp += 4u;
-                    cur = nxt;
-                    nxt = *(lds_u32*)(size_t)(rp + 4u);
-                }
-                const float fc = (float)(i - ((int)cur >> 16));
+            /* Patch row and column of the lane's position in the step that comes next (the steps are taken in order, so the
+             * word and the count move on): the rows that end before the step's 64 positions plus those that end below the
+             * lane inside them give the row, its record the column.  `ahead` is where the word after this step's lies from
+             * rnext (which the callers move on: the double step once for both its halves). */
+            auto coord = [&](int i, unsigned int ahead, unsigned int& off, float& u, float& v) { /* ISA: coordinates */
+                const unsigned int lo = (unsigned int)rmask, hi = (unsigned int)(rmask >> 32);
+                const unsigned int row = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, rows_done));
+                /* rows_done += popcount(word): the instruction adds as it counts (the compiler forms count, count, add) */
+                asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(rows_done) : "v"(lo));
+                asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(rows_done) : "v"(hi));
+                rmask = *(lds_u64*)(size_t)(rnext + ahead);
+                const int   rcd = *(lds_i16*)(size_t)(rec0 + 2u * row);
+                const float fr = (float)row;
+                const float fc = (float)(i + rcd);
                 u = fmaf(crsbp, fc, fmaf(srsbp, fr, u0));
                 v = fmaf(crsbp, fr, fmaf(-srsbp, fc, v0));
-                /* the end-of-list sentinel (column -32767 of a row that does not exist) makes this product negative, and the
+                /* the end-of-list sentinel (column -32767 of a row that does not exist) can make this sum negative, and the
                  * lane must then read offset 0: v_cvt_u32_f32 saturates a negative input to 0 by definition, whereas the
                  * C++ cast of an out-of-range float is undefined (fptoui poison) -- so the instruction is named, as for
                  * v_cvt_rpi_i32_f32 in k_orientation */
@@ -1112,30 +1173,34 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
 #define PS_TAPS(OFF, A0, A1, A2, A3) taps.load_b(OFF, A0, A1, A2, A3);
 #endif
             if (T > 0) {
-                coord(lane, off_a, u_a, v_a);
+                coord(lane, 0u, off_a, u_a, v_a);
+                rnext += 8u;
                 PS_TAPS(off_a, a0, a1, a2, a3)
             }
             /* double steps while a further step follows them: only then is the set requested at the end ever binned */
             int t = steps, i = lane;
             for (; t > 2; t -= 2, i += 128) {
-                coord(i + 64, off_b, u_b, v_b);
+                coord(i + 64, 0u, off_b, u_b, v_b);
                 PS_TAPS(off_b, b0, b1, b2, b3)
                 bin(u_a, v_a, a0 - a1, a2 - a3);
-                coord(i + 128, off_a, u_a, v_a);
+                coord(i + 128, 8u, off_a, u_a, v_a);
                 PS_TAPS(off_a, a0, a1, a2, a3)
                 bin(u_b, v_b, b0 - b1, b2 - b3);
+                rnext += 16u;
             }
             /* the last one or two steps (wave-uniform branches): nothing is requested beyond the list's last step, and a
              * step that holds no sample is not walked -- rounding the list up to whole double steps walked 64 empty
-             * positions per descriptor on average, coordinates, row walk and four tap loads each */
+             * positions per descriptor on average, coordinates, row lookup and four tap loads each */
             if (t == 2) {
-                coord(i + 64, off_b, u_b, v_b);
+                coord(i + 64, 0u, off_b, u_b, v_b);
                 PS_TAPS(off_b, b0, b1, b2, b3)
             }
             if (t > 0) bin(u_a, v_a, a0 - a1, a2 - a3);
             if (t == 2) bin(u_b, v_b, b0 - b1, b2 - b3);
             if (probe_acc == 0x12345u) desc[(size_t)d * 128 + lane] = 1.0f; /* never true: keeps the probe's arithmetic alive */
             wave_lds_sync(); /* ISA: end */
+            rb = rb_next;
+            skip = skip_next;
             } /* passes */
         }
         wave_lds_sync();

@@ -49,6 +49,7 @@ struct SiftConsts {
     int   filter_max;  /* Config::getFilterMaxExtrema(), <= 0: grid filter off */
     int   filter_mode; /* POPSIFT_HIP_FILTER_* */
     int   desc_rows;   /* patch rows k_descriptor walks per pass (tests shrink it) */
+    int   desc_list;   /* list positions k_descriptor walks per pass (tests shrink it) */
 };
 
 /* sift_extremum.h:24-33 InitialExtremum (without the grid-filter bookkeeping) */
