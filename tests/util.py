@@ -129,6 +129,12 @@ def feature_parity(orc, fh, dh, grid_mode=False):
     <= max(1, n_feat // 2000); orientations outside 1e-3 rad
     <= max(2, n_desc // 2000); descriptors: descriptor_parity.
 
+    These allowances are statistical and give no reason per keypoint.  The place where they are ACCOUNTED for is the
+    per-keypoint check of tests/ori_rule.py (tests/test_ori_rule.py, tests/test_gpu_ori_rule.py): a float64 restatement
+    of the orientation rule with an explicit uncertainty says for each keypoint either "decided" -- number of
+    orientations and every angle fixed, no allowance -- or "open", with the samples on bin edges or the tie that leave
+    it open.  A change that moves one of the counts here should be explained there first.
+
     grid_mode (DescMode::Grid, s_desc_grid.cu:19-147): the descriptor snaps its 4096 sample points to pixels, so it is a
     STEP function of the orientation -- one ulp of the angle moves 4.6 .. 5.1 % of the oracle's own grid descriptors beyond
     1e-3 on ordinary planes, 8 .. 10 % at 180 x 140, 23 .. 25 % on thin planes (tests/test_oracle_grid_sensitivity.py), and the
