@@ -582,6 +582,69 @@ int  popsift_hip_ransac_trace(popsift_hip_verifier* v, const float* pts, int n, 
 int  popsift_hip_pair_points(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
                              const popsift_hip_pair* pairs, int n, float* pts);
 
+/*
+ * Epipolar verification: RANSAC for the fundamental matrix of two views of a 3-D scene (OpenCV's findFundamentalMat(..,
+ * FM_RANSAC)), on the same verifier under entry points of its own: popsift_hip_ransac and its options do not change.  The
+ * pairs of such a scene follow no homography; they satisfy [x' y' 1] F [x y 1]^T = 0.  popsift_hip_epipolar returns the F
+ * with the most inliers among T hypotheses of m = 8 pairs each (the 8-point algorithm), its count and the mask; res->H
+ * holds F, row major.  Points, mask, result record, "n < m is answered on the host", "one call at a time" and the trace are
+ * popsift_hip_ransac's with m = 8 (a sample is 8 ints).  Calls of both kinds may alternate on one verifier: each returns
+ * the bytes a fresh verifier returns.  The result is a function of (points, options) alone.  Steps 3 to 5 run in double,
+ * step 6 in float; every line one IEEE operation, fma / fmaf fused, sqrt and '/' correctly rounded:
+ *
+ * 1. Sample.  Step 1 of popsift_hip_ransac with m = 8: the same hash, the same nine draws per slot.
+ * 2. Normalise.  Step 2 of popsift_hip_ransac, unchanged: (cx, cy, s, k) of the left side, (cx', cy', s', k') of the right.
+ * 3. Solve.  Pair i of the normalised sample (x, y) -> (u, v) gives row i of the 8 x 9 system A f = 0:
+ *    [u*x, u*y, u, v*x, v*y, v, x, y, 1].  Gaussian elimination with complete pivoting, k = 0 .. 7; perm[j] = j at first.
+ *    The pivot is the entry of largest |a[r][c]| over k <= r <= 7, k <= c <= 8: best = |a[k][k]|, then c = k .. 8 and
+ *    within a column r = k .. 7, an entry replaces the pivot when its magnitude > best (the lowest column, then the lowest
+ *    row, wins a tie; a NaN never wins).  Row r is swapped with row k; column c with column k in all eight rows, and
+ *    perm[c] with perm[k].  For r > k: q = a[r][k] / a[k][k], a[r][j] = fma(-q, a[k][j], a[r][j]) for j > k.  After the
+ *    eight steps column 8 is free: z[8] = 1, and for i = 7 .. 0: s = -a[i][8]; s = fma(-a[i][j], z[j], s) for
+ *    j = i+1 .. 7; z[i] = s / a[i][i].  f[perm[j]] = z[j].  (Fixing f8 = 1 instead would be wrong: a camera that moves
+ *    sideways has F[2][2] = 0.)  Fn is f as a row-major 3 x 3 matrix.
+ * 4. Rank 2.  m[i][j] = fma(Fn[0][i], Fn[0][j], fma(Fn[1][i], Fn[1][j], Fn[2][i] * Fn[2][j])) for i <= j (Fn^T Fn,
+ *    symmetric), V = identity.  Six sweeps of the Jacobi rotations (p, q) = (0, 1), (0, 2), (1, 2), o the third index.  A
+ *    rotation with m[p][q] == 0 is skipped.  Otherwise d = m[q][q] - m[p][p], e = 2 * m[p][q], theta = d / e,
+ *    root = sqrt(fma(theta, theta, 1)), den = |theta| + root, t = copysign(1, theta) / den, c = 1 / sqrt(fma(t, t, 1)),
+ *    s = t * c; then m[p][p] = fma(-t, m[p][q], m[p][p]), m[q][q] = fma(t, m[p][q], m[q][q]) (both with the old m[p][q]),
+ *    m[p][q] = 0, and with the old a = m[o][p], b = m[o][q]: m[o][p] = fma(-s, b, c * a), m[o][q] = fma(s, a, c * b);
+ *    for each row r of V with the old a = V[r][p], b = V[r][q]: V[r][p] = fma(-s, b, c * a), V[r][q] = fma(s, a, c * b).
+ *    w is the column of V under the smallest m[i][i] ('<' decides from i = 0, so the lowest index wins a tie).  For each
+ *    row i: fw = fma(Fn[i][0], w[0], fma(Fn[i][1], w[1], Fn[i][2] * w[2])), Fn[i][j] = fma(-fw, w[j], Fn[i][j]): the
+ *    closest matrix of rank 2 in the Frobenius norm, without an SVD.
+ * 5. Denormalise and scale: F = Tr^T Fn Tl.  For row i: g[i][0] = Fn[i][0] * k, g[i][1] = Fn[i][1] * k,
+ *    g[i][2] = fma(-g[i][0], cx, fma(-g[i][1], cy, Fn[i][2])); for column j: h[0][j] = g[0][j] * k',
+ *    h[1][j] = g[1][j] * k', h[2][j] = fma(-h[0][j], cx', fma(-h[1][j], cy', g[2][j])).  d is the h of largest magnitude
+ *    in row-major order ('>' decides, the lowest index wins a tie); the model is (float)(h / d), nine values, the largest
+ *    exactly 1.  The hypothesis is invalid iff a pivot is exactly 0, d is 0, or one of the nine floats is not finite.  No
+ *    conditioning threshold.
+ * 6. Score, in float: a = fmaf(F0, x, fmaf(F1, y, F2)), b = fmaf(F3, x, fmaf(F4, y, F5)), c = fmaf(F6, x, fmaf(F7, y, F8)),
+ *    d = fmaf(F0, x', fmaf(F3, y', F6)), e = fmaf(F1, x', fmaf(F4, y', F7)), r = fmaf(a, x', fmaf(b, y', c)),
+ *    g = fmaf(a, a, fmaf(b, b, fmaf(d, d, e * e))), lim = (max_err * max_err) * g.  A pair is an inlier iff
+ *    g > 0 && g < +inf && r * r <= lim: its Sampson distance is at most max_err pixels, tested without a division.  A NaN
+ *    fails every test.  An invalid hypothesis is an all-zero model, r = g = 0: `g > 0` keeps it from counting every pair.
+ *    A pair with an infinite coordinate has g = +inf (or NaN) and r * r = lim = +inf: `g < +inf` keeps it out.
+ * 7. Select.  Step 5 of popsift_hip_ransac with m = 8.
+ *
+ * ERR_INVALID, before any GPU call: as popsift_hip_ransac, with reserved[0 .. 2] != 0.  A minimal sample of 8 needs more
+ * hypotheses than a homography's 4: with an inlier share w a sample is clean with probability w^8.
+ */
+#define POPSIFT_HIP_EPIPOLAR_SAMPLE 8
+typedef struct popsift_hip_epipolar_opts {   /* 24 bytes */
+    int32_t  hypotheses;   /* T, 1 .. 65536 */
+    float    max_err;      /* inlier: Sampson distance <= max_err (px) */
+    uint32_t seed;
+    int32_t  reserved[3];  /* must be 0 */
+} popsift_hip_epipolar_opts;
+void popsift_hip_default_epipolar_opts(popsift_hip_epipolar_opts* o);   /* {2048, 2.0f, 0, {0, 0, 0}} */
+/* res->H holds F, row major: [x' y' 1] F [x y 1]^T = 0; zeros when hypothesis == -1 */
+int  popsift_hip_epipolar(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
+                          popsift_hip_ransac_result* res, uint8_t* inlier);
+/* samples: T x 8, models: T x 9, counts: T; any may be NULL */
+int  popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
+                                int32_t* samples, float* models, int32_t* counts);
+
 int popsift_hip_get_report(const popsift_hip_ctx* ctx, popsift_hip_report* rep);
 /* profile != 0: bracket every blur-level launch with HIP events (serialises the
  * octave streams; used by bench.py for the roofline object only). */

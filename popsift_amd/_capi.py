@@ -77,6 +77,11 @@ class RansacOpts(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class EpipolarOpts(C.Structure):
+    """popsift_hip_epipolar_opts"""
+    _fields_ = [("hypotheses", C.c_int32), ("max_err", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
 FEATURE_DTYPE = np.dtype([
     ("debug_octave", np.int32), ("xpos", np.float32), ("ypos", np.float32),
     ("sigma", np.float32), ("num_ori", np.int32),
@@ -92,6 +97,7 @@ RANSAC_RESULT_DTYPE = np.dtype([("H", np.float32, (9,)), ("n_inliers", np.int32)
 MODEL_HOMOGRAPHY, MODEL_AFFINE = 0, 1
 MODELS = {"homography": MODEL_HOMOGRAPHY, "affine": MODEL_AFFINE}
 RANSAC_CHUNK, RANSAC_HYP_BLOCK = 1024, 64  # POPSIFT_HIP_RANSAC_*: pairs / hypotheses per workgroup of the scoring kernel
+EPIPOLAR_SAMPLE = 8                        # POPSIFT_HIP_EPIPOLAR_SAMPLE: pairs per hypothesis of Verifier.epipolar
 EXTREMUM_DTYPE = np.dtype([
     ("xpos", np.float32), ("ypos", np.float32), ("lpos", np.int32),
     ("sigma", np.float32), ("octave", np.int32), ("cell", np.int32),
@@ -170,6 +176,9 @@ SYMBOLS = [
     ("popsift_hip_ransac", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RansacOpts), _vp, _vp]),
     ("popsift_hip_ransac_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RansacOpts), _vp, _vp, _vp]),
     ("popsift_hip_pair_points", C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    ("popsift_hip_default_epipolar_opts", None, [C.POINTER(EpipolarOpts)]),
+    ("popsift_hip_epipolar", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp]),
+    ("popsift_hip_epipolar_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp, _vp]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
     ("popsift_hip_set_profile", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_octave_dims", C.c_int, [_vp, C.c_int, _ip, _ip]),
@@ -431,6 +440,19 @@ def ransac_opts(model="homography", hypotheses=None, max_err=None, seed=None):
     return o
 
 
+def epipolar_opts(hypotheses=None, max_err=None, seed=None):
+    """popsift_hip_epipolar_opts: the library's defaults with the given fields replaced"""
+    o = EpipolarOpts()
+    lib().popsift_hip_default_epipolar_opts(C.byref(o))
+    if hypotheses is not None:
+        o.hypotheses = hypotheses
+    if max_err is not None:
+        o.max_err = max_err
+    if seed is not None:
+        o.seed = seed
+    return o
+
+
 class Verifier:
     """popsift_hip_verifier: RANSAC over point pairs on one GPU (a stream and grow-only scratch; one call at a time)."""
 
@@ -474,6 +496,34 @@ class Verifier:
                                             models.ctypes.data, counts.ctypes.data)
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_ransac_trace")
+        return samples, models, counts
+
+    def epipolar(self, pts, hypotheses=None, max_err=None, seed=None, want_mask=True):
+        """popsift_hip_epipolar -> (result, mask): as ransac(), with the fundamental matrix F in result["H"] (row major,
+        [x' y' 1] F [x y 1]^T = 0) and max_err a Sampson distance"""
+        pts = self._points(pts)
+        n = len(pts)
+        res = np.zeros(1, RANSAC_RESULT_DTYPE)
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        o = epipolar_opts(hypotheses, max_err, seed)
+        rc = lib().popsift_hip_epipolar(self._h, pts.ctypes.data if n else None, n, C.byref(o), res.ctypes.data,
+                                        mask.ctypes.data if want_mask and n else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_epipolar")
+        return res[0], mask
+
+    def epipolar_trace(self, pts, hypotheses=None, max_err=None, seed=None):
+        """popsift_hip_epipolar_trace -> (samples (T, 8) int32, models (T, 9) float32, counts (T,) int32)"""
+        pts = self._points(pts)
+        n = len(pts)
+        o = epipolar_opts(hypotheses, max_err, seed)
+        T = max(int(o.hypotheses), 0)
+        samples, models, counts = (np.zeros((T, EPIPOLAR_SAMPLE), np.int32), np.zeros((T, 9), np.float32),
+                                   np.zeros(T, np.int32))
+        rc = lib().popsift_hip_epipolar_trace(self._h, pts.ctypes.data if n else None, n, C.byref(o), samples.ctypes.data,
+                                              models.ctypes.data, counts.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_epipolar_trace")
         return samples, models, counts
 
     def close(self):

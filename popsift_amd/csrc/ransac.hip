@@ -1,17 +1,20 @@
 /*
- * ransac.hip -- geometric verification of correspondences on the GPU (popsift_hip_ransac, include/popsift_hip.h): T
- * sampled hypotheses of a homography or an affine map, each scored against all n pairs, the best one's inlier mask.
- * The rule in the header defines every operation; tests/ransac_ref.c restates it on the CPU and the results are equal
- * as bytes.
+ * ransac.hip -- geometric verification of correspondences on the GPU (popsift_hip_ransac and popsift_hip_epipolar,
+ * include/popsift_hip.h): T sampled hypotheses of a homography, an affine map or a fundamental matrix, each scored against
+ * all n pairs, the best one's inlier mask.  The rules in the header define every operation; tests/ransac_ref.c and
+ * tests/epipolar_ref.c restate them on the CPU and the results are equal as bytes.
  *
  *   k_ransac_bounds   bounding box of the finite coordinates, per column: integer max of order-preserving keys, so the
  *                     result does not depend on the reduction order
  *   k_ransac_models   one lane per hypothesis: sample, float64 solve in registers, denormalise, round to float32;
  *                     counts[t] = 0 for a model, -1 for none
+ *   k_epipolar_models the same for a fundamental matrix: 8 pairs, the null vector of the 8 x 9 system by elimination with
+ *                     complete pivoting, the closest rank-2 matrix by a Jacobi eigenvector, denormalise, scale
  *   k_ransac_score    the T x n part.  A workgroup takes S_CHUNK pairs (four per lane, in registers for the whole
  *                     sweep) and S_HYP hypotheses; a hypothesis' nine coefficients are wave-uniform loads; its count
  *                     comes from ballots, crosses the waves through LDS and is added to counts[t] by one integer atomic
- *                     per (chunk, hypothesis): integer sums do not depend on the order
+ *                     per (chunk, hypothesis): integer sums do not depend on the order.  The inlier rule (transfer
+ *                     error or Sampson distance) is a template parameter, here and in k_ransac_mask
  *   k_ransac_select   arg-max under (count, -t) in one workgroup, writes the result record
  *   k_ransac_mask     the winner's inlier bytes, four pairs per lane
  *   k_pair_points     (x, y, x', y') of descriptor pairs through the sets' descriptor -> feature maps
@@ -50,13 +53,14 @@ __device__ __forceinline__ uint32_t mix(uint32_t x)
 }
 
 /* M distinct indices below n; false when a slot found no new index in its 9 draws (that slot and the later ones stay -1) */
-template <int M>
-__device__ __forceinline__ bool sample(uint32_t seed, int t, int n, int (&idx)[4])
+template <int M, int SLOTS>
+__device__ __forceinline__ bool sample(uint32_t seed, int t, int n, int (&idx)[SLOTS])
 {
     const uint32_t base = mix(mix(seed + 0x9e3779b9U) ^ (uint32_t)t);
     uint32_t       c = 0;
     bool           alive = true;
-    idx[0] = idx[1] = idx[2] = idx[3] = -1;
+#pragma unroll
+    for (int k = 0; k < SLOTS; k++) idx[k] = -1;
 #pragma unroll
     for (int k = 0; k < M; k++) {
         bool got = false;
@@ -273,22 +277,242 @@ __global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pt
     counts[t] = ok ? 0 : -1;
 }
 
-/* ---- rule 4: score */
+/* ---- popsift_hip_epipolar, rules 3 to 5: one fundamental matrix per lane.  As above every index is a compile-time
+ * constant after unrolling; row and column swaps are selects. */
 
-__device__ __forceinline__ bool inlier(const float (&H)[9], v4f p, float max_err2)
+/* rule 3: the null vector of the 8 x 9 system, complete pivoting; false when a pivot is exactly 0 */
+__device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
 {
-    const float u = fmaf(H[0], p[0], fmaf(H[1], p[1], H[2]));
-    const float v = fmaf(H[3], p[0], fmaf(H[4], p[1], H[5]));
-    const float w = fmaf(H[6], p[0], fmaf(H[7], p[1], H[8]));
-    const float dx = fmaf(-w, p[2], u);
-    const float dy = fmaf(-w, p[3], v);
-    const float e = fmaf(dx, dx, dy * dy);
-    const float lim = max_err2 * (w * w);
-    return w > 0.0f && e <= lim;
+    bool ok = true;
+    int  perm[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) perm[j] = j;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        int    pr = k, pc = k;
+        double best = fabs(a[k][k]);
+#pragma unroll
+        for (int c = k; c < 9; c++) { /* column-major: the lowest column, then the lowest row, wins a tie */
+#pragma unroll
+            for (int r = (c == k ? k + 1 : k); r < 8; r++) {
+                const double v = fabs(a[r][c]);
+                const bool   g = v > best;
+                best = g ? v : best;
+                pr = g ? r : pr;
+                pc = g ? c : pc;
+            }
+        }
+#pragma unroll
+        for (int r = k + 1; r < 8; r++) {
+            const bool sw = pr == r;
+#pragma unroll
+            for (int j = k; j < 9; j++) { /* the columns before k of these rows are not read again */
+                const double lo = a[k][j], hi = a[r][j];
+                a[k][j] = sw ? hi : lo;
+                a[r][j] = sw ? lo : hi;
+            }
+        }
+#pragma unroll
+        for (int c = k + 1; c < 9; c++) {
+            const bool sw = pc == c;
+#pragma unroll
+            for (int r = 0; r < 8; r++) { /* the rows above k too: back substitution reads them */
+                const double lo = a[r][k], hi = a[r][c];
+                a[r][k] = sw ? hi : lo;
+                a[r][c] = sw ? lo : hi;
+            }
+            const int lo = perm[k], hi = perm[c];
+            perm[k] = sw ? hi : lo;
+            perm[c] = sw ? lo : hi;
+        }
+        ok = ok && !(a[k][k] == 0.0);
+#pragma unroll
+        for (int r = k + 1; r < 8; r++) {
+            const double q = a[r][k] / a[k][k];
+#pragma unroll
+            for (int j = k + 1; j < 9; j++) a[r][j] = fma(-q, a[k][j], a[r][j]);
+        }
+    }
+    double z[9];
+    z[8] = 1.0; /* the free column's unknown */
+#pragma unroll
+    for (int i = 7; i >= 0; i--) {
+        double s = -a[i][8];
+#pragma unroll
+        for (int j = i + 1; j < 8; j++) s = fma(-a[i][j], z[j], s);
+        z[i] = s / a[i][i];
+    }
+#pragma unroll
+    for (int c = 0; c < 9; c++) {
+        double v = 0.0;
+#pragma unroll
+        for (int j = 0; j < 9; j++) v = perm[j] == c ? z[j] : v;
+        f[c] = v;
+    }
+    return ok;
 }
 
-/* grid (hypothesis blocks, pair chunks).  A hypothesis without a model is all zeros: w = 0, no inlier, nothing is added to
- * its -1. */
+/* rule 4: one Jacobi rotation of the symmetric m that zeroes m[P][Q]; O is the third index; v collects the rotations */
+template <int P, int Q, int O>
+__device__ __forceinline__ void rotate(double (&m)[3][3], double (&v)[3][3])
+{
+    if (m[P][Q] == 0.0) return;
+    const double d = m[Q][Q] - m[P][P];
+    const double e = 2.0 * m[P][Q];
+    const double theta = d / e;
+    const double root = sqrt(fma(theta, theta, 1.0));
+    const double den = fabs(theta) + root;
+    const double t = copysign(1.0, theta) / den;
+    const double c = 1.0 / sqrt(fma(t, t, 1.0));
+    const double s = t * c;
+    m[P][P] = fma(-t, m[P][Q], m[P][P]);
+    m[Q][Q] = fma(t, m[P][Q], m[Q][Q]);
+    m[P][Q] = m[Q][P] = 0.0;
+    const double mp = m[O][P], mq = m[O][Q];
+    m[O][P] = m[P][O] = fma(-s, mq, c * mp);
+    m[O][Q] = m[Q][O] = fma(s, mp, c * mq);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const double vp = v[r][P], vq = v[r][Q];
+        v[r][P] = fma(-s, vq, c * vp);
+        v[r][Q] = fma(s, vp, c * vq);
+    }
+}
+
+/* f <- f - (f w) w^T, w the eigenvector of f^T f under its smallest eigenvalue: the closest matrix of rank 2 */
+__device__ __forceinline__ void rank2(double (&f)[9])
+{
+    double m[3][3], v[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = i; j < 3; j++) m[i][j] = m[j][i] = fma(f[i], f[j], fma(f[3 + i], f[3 + j], f[6 + i] * f[6 + j]));
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) v[i][j] = i == j ? 1.0 : 0.0;
+    }
+    for (int sweep = 0; sweep < 6; sweep++) {
+        rotate<0, 1, 2>(m, v);
+        rotate<0, 2, 1>(m, v);
+        rotate<1, 2, 0>(m, v);
+    }
+    int    b = 0;
+    double mb = m[0][0];
+    if (m[1][1] < mb) {
+        b = 1;
+        mb = m[1][1];
+    }
+    if (m[2][2] < mb) b = 2;
+    double w[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) w[j] = b == 0 ? v[j][0] : b == 1 ? v[j][1] : v[j][2];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const double fw = fma(f[3 * i], w[0], fma(f[3 * i + 1], w[1], f[3 * i + 2] * w[2]));
+#pragma unroll
+        for (int j = 0; j < 3; j++) f[3 * i + j] = fma(-fw, w[j], f[3 * i + j]);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
+                                                        const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                        int* __restrict__ samples, int* __restrict__ counts)
+{
+    constexpr int M = POPSIFT_HIP_EPIPOLAR_SAMPLE;
+    const int     t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= T) return;
+    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    int        idx[M];
+    bool       ok = sample<M>(seed, t, n, idx);
+    double     a[M][9], f[9];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const v4f    p = pts[ok ? idx[i] : 0];
+        const double x = ((double)p[0] - L.cx) * L.k;
+        const double y = ((double)p[1] - L.cy) * L.k;
+        const double u = ((double)p[2] - Rn.cx) * Rn.k;
+        const double v = ((double)p[3] - Rn.cy) * Rn.k;
+        a[i][0] = u * x; a[i][1] = u * y; a[i][2] = u;
+        a[i][3] = v * x; a[i][4] = v * y; a[i][5] = v;
+        a[i][6] = x; a[i][7] = y; a[i][8] = 1.0;
+    }
+    ok = null_vector(a, f) && ok;
+    rank2(f);
+    /* rule 5, denormalise: G = Fn * Tl, then H = Tr^T * G */
+    double g[9], h[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        g[3 * i] = f[3 * i] * L.k;
+        g[3 * i + 1] = f[3 * i + 1] * L.k;
+        g[3 * i + 2] = fma(-g[3 * i], L.cx, fma(-g[3 * i + 1], L.cy, f[3 * i + 2]));
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        h[j] = g[j] * Rn.k;
+        h[3 + j] = g[3 + j] * Rn.k;
+        h[6 + j] = fma(-h[j], Rn.cx, fma(-h[3 + j], Rn.cy, g[6 + j]));
+    }
+    /* scale: the entry of largest magnitude becomes 1 */
+    double d = h[0], best = fabs(h[0]);
+#pragma unroll
+    for (int i = 1; i < 9; i++) {
+        const double v = fabs(h[i]);
+        const bool   gt = v > best;
+        best = gt ? v : best;
+        d = gt ? h[i] : d;
+    }
+    ok = ok && !(d == 0.0);
+    float F[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        F[i] = (float)(h[i] / d);
+        ok = ok && isfinite(F[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? F[i] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < M; i++) samples[M * (size_t)t + i] = idx[i];
+    counts[t] = ok ? 0 : -1;
+}
+
+/* ---- rule 4: score */
+
+/* transfer error in the right image, popsift_hip_ransac */
+struct Transfer {
+    static __device__ __forceinline__ bool inlier(const float (&H)[9], v4f p, float max_err2)
+    {
+        const float u = fmaf(H[0], p[0], fmaf(H[1], p[1], H[2]));
+        const float v = fmaf(H[3], p[0], fmaf(H[4], p[1], H[5]));
+        const float w = fmaf(H[6], p[0], fmaf(H[7], p[1], H[8]));
+        const float dx = fmaf(-w, p[2], u);
+        const float dy = fmaf(-w, p[3], v);
+        const float e = fmaf(dx, dx, dy * dy);
+        const float lim = max_err2 * (w * w);
+        return w > 0.0f && e <= lim;
+    }
+};
+
+/* Sampson distance to the epipolar constraint, popsift_hip_epipolar (rule 6 there) */
+struct Sampson {
+    static __device__ __forceinline__ bool inlier(const float (&F)[9], v4f p, float max_err2)
+    {
+        const float a = fmaf(F[0], p[0], fmaf(F[1], p[1], F[2]));
+        const float b = fmaf(F[3], p[0], fmaf(F[4], p[1], F[5]));
+        const float c = fmaf(F[6], p[0], fmaf(F[7], p[1], F[8]));
+        const float d = fmaf(F[0], p[2], fmaf(F[3], p[3], F[6]));
+        const float e = fmaf(F[1], p[2], fmaf(F[4], p[3], F[7]));
+        const float r = fmaf(a, p[2], fmaf(b, p[3], c));
+        const float g = fmaf(a, a, fmaf(b, b, fmaf(d, d, e * e)));
+        const float lim = max_err2 * g;
+        return g > 0.0f && g < INFINITY && r * r <= lim;
+    }
+};
+
+/* grid (hypothesis blocks, pair chunks).  A hypothesis without a model is all zeros: w = 0 (g = 0), no inlier, nothing is
+ * added to its -1. */
+template <class Rule>
 __global__ __launch_bounds__(S_BLOCK) void k_ransac_score(const v4f* __restrict__ pts, int n, const float* __restrict__ models,
                                                           int T, float max_err2, int* __restrict__ counts)
 {
@@ -310,7 +534,7 @@ __global__ __launch_bounds__(S_BLOCK) void k_ransac_score(const v4f* __restrict_
         for (int i = 0; i < 9; i++) H[i] = m[i];
         int c = 0;
 #pragma unroll
-        for (int r = 0; r < S_PER_LANE; r++) c += __popcll(__ballot(inlier(H, p[r], max_err2)));
+        for (int r = 0; r < S_PER_LANE; r++) c += __popcll(__ballot(Rule::inlier(H, p[r], max_err2)));
         if (lane == 0) s_cnt[k][wave] = c;
     }
     __syncthreads();
@@ -364,6 +588,7 @@ __global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ c
 }
 
 /* four pairs and four mask bytes per lane; mask has room for n rounded up to a multiple of 4 */
+template <class Rule>
 __global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts, int n,
                                                      const popsift_hip_ransac_result* __restrict__ res, float max_err2,
                                                      uint32_t* __restrict__ mask)
@@ -378,7 +603,7 @@ __global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int i = 4 * q + r;
-        if (won && i < n && inlier(H, pts[i], max_err2)) word |= 1u << (8 * r);
+        if (won && i < n && Rule::inlier(H, pts[i], max_err2)) word |= 1u << (8 * r);
     }
     mask[q] = word;
 }
@@ -445,6 +670,22 @@ bool opts_valid(const popsift_hip_ransac_opts* o)
            o->reserved[1] == 0;
 }
 
+bool epipolar_opts_valid(const popsift_hip_epipolar_opts* o)
+{
+    return o && o->hypotheses >= 1 && o->hypotheses <= MAX_HYP && std::isfinite(o->max_err) && o->max_err > 0.0f &&
+           o->reserved[0] == 0 && o->reserved[1] == 0 && o->reserved[2] == 0;
+}
+
+/* what a call fits: the two models of popsift_hip_ransac_opts, or a fundamental matrix */
+enum { FIT_HOMOGRAPHY = POPSIFT_HIP_MODEL_HOMOGRAPHY, FIT_AFFINE = POPSIFT_HIP_MODEL_AFFINE, FIT_EPIPOLAR };
+struct Fit {
+    int      what, hypotheses;
+    float    max_err;
+    uint32_t seed;
+    int      m() const { return what == FIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : what == FIT_AFFINE ? 3 : 4; } /* pairs per sample */
+    int      slots() const { return what == FIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : 4; } /* ints per row of the samples */
+};
+
 bool grow(Status& ok, popsift_hip_verifier* v, size_t d_need, size_t h_need)
 {
     if (ok.good() && d_need > v->d_cap) {
@@ -462,20 +703,22 @@ bool grow(Status& ok, popsift_hip_verifier* v, size_t d_need, size_t h_need)
     return ok.good();
 }
 
-/* popsift_hip_ransac and popsift_hip_ransac_trace: the same launches, the trace downloads three more arrays */
-int run(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, popsift_hip_ransac_result* res,
-        uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+/* the four entry points: the same launches but for the model kernel and the inlier rule; a trace downloads three more
+ * arrays.  The layout of the scratch is a function of (n, T, fit) and every byte a call reads it has written before, so
+ * nothing of an earlier call, whatever its kind, reaches a later one. */
+int run(popsift_hip_verifier* v, const float* pts, int n, const Fit& fit, popsift_hip_ransac_result* res, uint8_t* inlier,
+        bool trace, int32_t* samples, float* models, int32_t* counts)
 {
-    if (!v || !opts_valid(o) || (!trace && !res) || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
-    const int T = o->hypotheses;
-    const int m = o->model == POPSIFT_HIP_MODEL_AFFINE ? 3 : 4;
+    if (!v || (!trace && !res) || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
+    const int T = fit.hypotheses;
+    const int m = fit.m();
     if (n < m) { /* no sample exists */
         if (res) {
             memset(res, 0, sizeof *res);
             res->hypothesis = -1;
         }
         if (inlier && n > 0) memset(inlier, 0, (size_t)n);
-        if (samples) memset(samples, 0xff, sizeof(int32_t) * 4 * (size_t)T);
+        if (samples) memset(samples, 0xff, sizeof(int32_t) * fit.slots() * (size_t)T);
         if (models) memset(models, 0, sizeof(float) * 9 * (size_t)T);
         if (counts) memset(counts, 0xff, sizeof(int32_t) * (size_t)T);
         return POPSIFT_HIP_OK;
@@ -483,7 +726,7 @@ int run(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_rans
     if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     Status       ok;
     const size_t b_pts = sizeof(float) * 4 * (size_t)n, b_mask = round16((size_t)n);
-    const size_t b_models = round16(sizeof(float) * 9 * (size_t)T), b_samples = sizeof(int) * 4 * (size_t)T,
+    const size_t b_models = round16(sizeof(float) * 9 * (size_t)T), b_samples = sizeof(int) * fit.slots() * (size_t)T,
                  b_counts = round16(sizeof(int) * (size_t)T);
     /* device: [bounds 32][record 64][mask][points][models][samples][counts]; the record and the mask come down together,
      * the last three are contiguous for the trace */
@@ -501,24 +744,33 @@ int run(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_rans
     auto* const       d_models = (float*)(d + o_models);
     auto* const       d_samples = (int*)(d + o_samples);
     auto* const       d_counts = (int*)(d + o_counts);
-    const float       max_err2 = o->max_err * o->max_err;
+    const float       max_err2 = fit.max_err * fit.max_err;
 
     memcpy(v->h_buf, pts, b_pts);
     ok(hipMemcpyAsync(d + o_pts, v->h_buf, b_pts, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, 32, s));
     if (ok.good()) {
         const int blocks = std::min((n + 255) / 256, 512);
         hipLaunchKernelGGL(k_ransac_bounds, dim3(blocks), dim3(256), 0, s, d_pts, n, d_bounds);
-        if (o->model == POPSIFT_HIP_MODEL_AFFINE)
-            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_AFFINE>, dim3((T + 63) / 64), dim3(64), 0, s, d_pts, n, T, o->seed,
+        const dim3 g_models((T + 63) / 64), g_score((T + S_HYP - 1) / S_HYP, (n + S_CHUNK - 1) / S_CHUNK), g_mask((n + 1023) / 1024);
+        auto* const d_mask = (uint32_t*)(d + o_mask);
+        if (fit.what == FIT_AFFINE)
+            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_AFFINE>, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed, d_bounds,
+                               d_models, d_samples, d_counts);
+        else if (fit.what == FIT_HOMOGRAPHY)
+            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_HOMOGRAPHY>, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed,
                                d_bounds, d_models, d_samples, d_counts);
         else
-            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_HOMOGRAPHY>, dim3((T + 63) / 64), dim3(64), 0, s, d_pts, n, T,
-                               o->seed, d_bounds, d_models, d_samples, d_counts);
-        hipLaunchKernelGGL(k_ransac_score, dim3((T + S_HYP - 1) / S_HYP, (n + S_CHUNK - 1) / S_CHUNK), dim3(S_BLOCK), 0, s, d_pts,
-                           n, d_models, T, max_err2, d_counts);
+            hipLaunchKernelGGL(k_epipolar_models, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed, d_bounds, d_models, d_samples,
+                               d_counts);
+        if (fit.what == FIT_EPIPOLAR)
+            hipLaunchKernelGGL(k_ransac_score<Sampson>, g_score, dim3(S_BLOCK), 0, s, d_pts, n, d_models, T, max_err2, d_counts);
+        else
+            hipLaunchKernelGGL(k_ransac_score<Transfer>, g_score, dim3(S_BLOCK), 0, s, d_pts, n, d_models, T, max_err2, d_counts);
         hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, s, d_counts, d_models, T, m, d_res);
-        hipLaunchKernelGGL(k_ransac_mask, dim3((n + 1023) / 1024), dim3(256), 0, s, d_pts, n, d_res, max_err2,
-                           (uint32_t*)(d + o_mask));
+        if (fit.what == FIT_EPIPOLAR)
+            hipLaunchKernelGGL(k_ransac_mask<Sampson>, g_mask, dim3(256), 0, s, d_pts, n, d_res, max_err2, d_mask);
+        else
+            hipLaunchKernelGGL(k_ransac_mask<Transfer>, g_mask, dim3(256), 0, s, d_pts, n, d_res, max_err2, d_mask);
         ok(hipGetLastError());
     }
     const size_t down = HEAD + (inlier ? (size_t)n : 0);
@@ -582,13 +834,38 @@ void popsift_hip_default_ransac_opts(popsift_hip_ransac_opts* o)
 int popsift_hip_ransac(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o,
                        popsift_hip_ransac_result* res, uint8_t* inlier)
 {
-    return run(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr);
+    if (!opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return run(v, pts, n, Fit{o->model, o->hypotheses, o->max_err, o->seed}, res, inlier, false, nullptr, nullptr, nullptr);
 }
 
 int popsift_hip_ransac_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, int32_t* samples,
                              float* models, int32_t* counts)
 {
-    return run(v, pts, n, o, nullptr, nullptr, true, samples, models, counts);
+    if (!opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return run(v, pts, n, Fit{o->model, o->hypotheses, o->max_err, o->seed}, nullptr, nullptr, true, samples, models, counts);
+}
+
+void popsift_hip_default_epipolar_opts(popsift_hip_epipolar_opts* o)
+{
+    if (!o) return;
+    o->hypotheses = 2048;
+    o->max_err = 2.0f;
+    o->seed = 0;
+    o->reserved[0] = o->reserved[1] = o->reserved[2] = 0;
+}
+
+int popsift_hip_epipolar(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
+                         popsift_hip_ransac_result* res, uint8_t* inlier)
+{
+    if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return run(v, pts, n, Fit{FIT_EPIPOLAR, o->hypotheses, o->max_err, o->seed}, res, inlier, false, nullptr, nullptr, nullptr);
+}
+
+int popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
+                               int32_t* samples, float* models, int32_t* counts)
+{
+    if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return run(v, pts, n, Fit{FIT_EPIPOLAR, o->hypotheses, o->max_err, o->seed}, nullptr, nullptr, true, samples, models, counts);
 }
 
 int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r, const popsift_hip_pair* pairs,

@@ -4,8 +4,9 @@
  * brute-force match left against right (one accept / reject line per left descriptor).
  * Extension: --pairs [--ratio R] [--max-dist D] [--cross-check] prints the correspondences instead.
  * Extension: --bytes quantizes both sets on the GPU and matches the byte descriptors (exact integer distances).
- * Extension: --verify homography|affine [--hypotheses T] [--max-err E] [--seed S] with --pairs fits the model to the pairs
- * by RANSAC on the GPU (popsift::Verifier) and prints it with its inlier count after the pair lines.
+ * Extension: --verify homography|affine|epipolar [--hypotheses T] [--max-err E] [--seed S] with --pairs fits the model to
+ * the pairs by RANSAC on the GPU (popsift::Verifier) and prints it with its inlier count after the pair lines; epipolar is
+ * the fundamental matrix of two views of a 3-D scene.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -39,6 +40,7 @@ static bool match_bytes = false;
 static popsift::FeaturesDev::MatchOptions pair_opts;
 static bool verify_pairs = false;
 static popsift::RansacOptions verify_opts;
+static bool verify_epipolar = false;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -100,19 +102,20 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
            "distances; --max-dist is then in byte units.  Needs --norm-multi (9 gives VLFeat-style bytes)",
            [&] { match_bytes = true; });
     o.val("verify", 0, "Matching",
-          "With --pairs: fit a model to the pairs by RANSAC on the GPU, homography or affine; prints the 3 x 3 model and\n"
-          "the number of inliers after the pair lines",
+          "With --pairs: fit a model to the pairs by RANSAC on the GPU, homography, affine or epipolar (the fundamental\n"
+          "matrix F of two views, x'^T F x = 0); prints the 3 x 3 model and the number of inliers after the pair lines",
           [&](const string& v) {
-              if (v != "homography" && v != "affine") {
-                  cerr << "--verify: homography or affine, not " << v << endl;
+              if (v != "homography" && v != "affine" && v != "epipolar") {
+                  cerr << "--verify: homography, affine or epipolar, not " << v << endl;
                   exit(-1);
               }
               verify_pairs = true;
+              verify_epipolar = v == "epipolar";
               verify_opts.model = v == "affine" ? popsift::RansacOptions::Affine : popsift::RansacOptions::Homography;
           });
     o.ival("hypotheses", "Matching", "With --verify: sampled hypotheses, 1 .. 65536 (default 2048)",
            [&](int v) { verify_opts.hypotheses = v; });
-    o.fval("max-err", "Matching", "With --verify: an inlier lies within this many pixels of its image (default 2)",
+    o.fval("max-err", "Matching", "With --verify: an inlier lies within this many pixels of its image, or of its epipolar line (default 2)",
            [&](float f) { verify_opts.maxErr = f; });
     o.ival("seed", "Matching", "With --verify: seed of the sampler (default 0)", [&](int v) { verify_opts.seed = (unsigned)v; });
     o.val("feature-order", 0, "Extensions",
@@ -147,9 +150,14 @@ static vector<int> reverse_map(popsift::FeaturesDevBytes* f)
 /* --verify: the model fitted to the pairs' points and its inliers.  lf / rf: the float sets the positions come from */
 static void print_verification(popsift::FeaturesDev* lf, popsift::FeaturesDev* rf, const vector<popsift::FeaturesDev::Pair>& pairs)
 {
-    popsift::Verifier           verifier(lf->getDevice());
-    const popsift::RansacResult fit = verifier.ransac(lf->pairPoints(rf, pairs), verify_opts);
-    printf("Model (%s):\n", verify_opts.model == popsift::RansacOptions::Affine ? "affine" : "homography");
+    popsift::Verifier        verifier(lf->getDevice());
+    const vector<float>      pts = lf->pairPoints(rf, pairs);
+    popsift::EpipolarOptions two_view;
+    two_view.hypotheses = verify_opts.hypotheses;
+    two_view.maxErr = verify_opts.maxErr;
+    two_view.seed = verify_opts.seed;
+    const popsift::RansacResult fit = verify_epipolar ? verifier.epipolar(pts, two_view) : verifier.ransac(pts, verify_opts);
+    printf("Model (%s):\n", verify_epipolar ? "epipolar" : verify_opts.model == popsift::RansacOptions::Affine ? "affine" : "homography");
     for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", fit.H[3 * i], fit.H[3 * i + 1], fit.H[3 * i + 2]);
     printf("Number of inliers:     %d of %zu\n", fit.inliers, pairs.size());
 }

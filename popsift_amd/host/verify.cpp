@@ -1,4 +1,4 @@
-/* popsift::Verifier on top of popsift_hip_ransac (include/popsift/verify.h) */
+/* popsift::Verifier on top of popsift_hip_ransac and popsift_hip_epipolar (include/popsift/verify.h) */
 #include "popsift/verify.h"
 
 #include <cstdlib>
@@ -14,6 +14,14 @@ namespace {
 {
     std::cerr << __FILE__ << std::endl << "E    " << what << ": " << popsift_hip_strerror(rc) << std::endl;
     exit(-1);
+}
+
+void take(RansacResult& out, const popsift_hip_ransac_result& res)
+{
+    memcpy(out.H, res.H, sizeof out.H);
+    out.inliers = res.n_inliers;
+    out.hypothesis = res.hypothesis;
+    out.valid = res.n_valid;
 }
 }  // namespace
 
@@ -39,10 +47,24 @@ RansacResult Verifier::ransac(const std::vector<float>& pts, const RansacOptions
     out.mask.resize((size_t)n);
     const int rc = popsift_hip_ransac(_v, n ? pts.data() : 0, n, &o, &res, n ? out.mask.data() : 0);
     if (rc != POPSIFT_HIP_OK) verify_fatal("verification failed", rc);
-    memcpy(out.H, res.H, sizeof out.H);
-    out.inliers = res.n_inliers;
-    out.hypothesis = res.hypothesis;
-    out.valid = res.n_valid;
+    take(out, res);
+    return out;
+}
+
+RansacResult Verifier::epipolar(const std::vector<float>& pts, const EpipolarOptions& opts)
+{
+    RansacResult              out;
+    const int                 n = (int)(pts.size() / 4);
+    popsift_hip_epipolar_opts o;
+    popsift_hip_ransac_result res;
+    popsift_hip_default_epipolar_opts(&o);
+    o.hypotheses = opts.hypotheses;
+    o.max_err = opts.maxErr;
+    o.seed = opts.seed;
+    out.mask.resize((size_t)n);
+    const int rc = popsift_hip_epipolar(_v, n ? pts.data() : 0, n, &o, &res, n ? out.mask.data() : 0);
+    if (rc != POPSIFT_HIP_OK) verify_fatal("epipolar verification failed", rc);
+    take(out, res);
     return out;
 }
 
