@@ -135,6 +135,13 @@ def feature_parity(orc, fh, dh, grid_mode=False):
     orientations and every angle fixed, no allowance -- or "open", with the samples on bin edges or the tie that leave
     it open.  A change that moves one of the counts here should be explained there first.
 
+    The descriptor bar (descriptor_parity: 1e-3 relative L2, max(1, n // 5000) beyond it) is close to blind for the loop
+    descriptor, where one patch pixel dropped, doubled or read from the wrong row moves a descriptor by 1e-4 .. 1e-3.  Its
+    per-descriptor counterpart is tests/desc_rule.py (tests/test_desc_rule.py, tests/test_gpu_desc_rule.py): a float64
+    restatement of descriptor_one with a bound per element derived from k_descriptor's arithmetic, no
+    allowance, in the device's own frames -- also on frames that extraction never produces (orientation +-0, the largest
+    accepted scale).
+
     grid_mode (DescMode::Grid, s_desc_grid.cu:19-147): the descriptor snaps its 4096 sample points to pixels, so it is a
     STEP function of the orientation -- one ulp of the angle moves 4.6 .. 5.1 % of the oracle's own grid descriptors beyond
     1e-3 on ordinary planes, 8 .. 10 % at 180 x 140, 23 .. 25 % on thin planes (tests/test_oracle_grid_sensitivity.py), and the
