@@ -331,12 +331,15 @@ def error_ratio(rule, descriptor, floor=0.0):
     return float(np.nanmax(q))
 
 
+def offender_rows(bad, limit=8):
+    return ["cell (%d, %d) bin %d: %.9g, expected %.9g in [%.9g, %.9g]: off by %.3g, bound %.3g; raw %.6g +- %.3g (%s), %s dominates" % (
+        o["cell"][0], o["cell"][1], o["bin"], o["value"], o["expected"], o["lo"], o["hi"], abs(o["value"] - o["expected"]), o["bound"],
+        o["raw"], o["delta"], ", ".join("%s %.2g" % kv for kv in o["terms"].items()), o["dominant"]) for o in bad[:limit]]
+
+
 def format_offenders(rule, bad, name="", limit=8):
     p = rule.patch
     head = "%s(%.4f, %.4f) sigma %.4f angle %.7f, %s x 2^%d, %d samples in %d rows, fbits %d, eps %.2g: %d element(s) outside" % (
         name + " " if name else "", p.x, p.y, p.sigma, p.angle, "RootSift" if rule.norm_mode == ROOTSIFT else "classic",
         rule.norm_multi, p.n, p.rows if p.n else 0, p.fbits, rule.eps, len(bad))
-    rows = ["cell (%d, %d) bin %d: %.9g, expected %.9g in [%.9g, %.9g]: off by %.3g, bound %.3g; raw %.6g +- %.3g (%s), %s dominates" % (
-        o["cell"][0], o["cell"][1], o["bin"], o["value"], o["expected"], o["lo"], o["hi"], abs(o["value"] - o["expected"]), o["bound"],
-        o["raw"], o["delta"], ", ".join("%s %.2g" % kv for kv in o["terms"].items()), o["dominant"]) for o in bad[:limit]]
-    return head + "\n        " + "\n        ".join(rows)
+    return head + "\n        " + "\n        ".join(offender_rows(bad, limit))
