@@ -157,6 +157,30 @@ public:
     std::vector<Pair> matchPairs(FeaturesDev* other, const MatchOptions& opts);
     std::vector<Pair> matchPairs(FeaturesDev* other) { return matchPairs(other, MatchOptions()); }
 
+    /* extension: guided matching (popsift_hip_match_pairs_guided; the rule is stated in popsift_hip.h).  With the model of
+     * the image pair known -- popsift::Verifier's H or F, or any other -- descriptor i of this set is searched for only
+     * among the descriptors of `other` whose feature lies within maxErr pixels of where the model puts i's: of its image
+     * under the homography M (an affine map is one whose last row is 0 0 1), or of its epipolar line under the fundamental
+     * matrix M (Sampson distance).  ratio, maxDist2 and crossCheck then act on those rows as in matchPairs; the
+     * cross-check's search the other way round is guided too.  Both sets need features behind their descriptors. */
+    struct GuidedOptions {
+        enum Model { Homography = 0, Epipolar = 1 };
+        Model model = Homography;
+        float M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; /* row major: right ~ M * left, or [x' y' 1] M [x y 1]^T = 0 */
+        float maxErr = 2.0f;                      /* pixels */
+        float ratio = 0.8f;
+        float maxDist2 = INFINITY;
+        bool  crossCheck = false;
+    };
+    std::vector<Pair> matchGuided(FeaturesDev* other, const GuidedOptions& opts);
+    /* the rows behind it, one per descriptor (popsift_hip_match_guided): best / second are -1 where there is none */
+    std::vector<Match> matchGuidedRows(FeaturesDev* other, const GuidedOptions& opts);
+
+    /* extension: a set of num descriptors (num x 128 floats) with their positions (num x 2 floats: x, y), one feature
+     * each, from host memory onto GPU `device` (popsift_hip_devfeatures_from_host_points): for keypoints and descriptors
+     * that come from elsewhere.  The caller owns the result. */
+    static FeaturesDev* fromHostPoints(const float* desc, const float* xy, int num, int device = 0);
+
     /* extension: (x, y, x', y') of each pair -- the positions of the features behind descriptor l of this set and
      * descriptor r of `other` -- gathered on the GPU (popsift_hip_pair_points): the input of popsift::Verifier
      * (popsift/verify.h).  The pairs of a byte match (FeaturesDevBytes::matchPairs) index the float sets the bytes came

@@ -441,6 +441,8 @@ int popsift_hip_match_set_path(int path);
  * mostly does not match this skips nearly all of the second search.  One download brings the count and the pairs.
  * All scratch belongs to l (one match at a time per left set); r may be the left set of another thread's call.  Sets on
  * different GPUs: r's descriptors are copied to l's GPU once and both searches run there.
+ * When a model of the image pair is known, popsift_hip_match_pairs_guided (below) searches among the right descriptors that
+ * agree with it.
  */
 typedef struct popsift_hip_match_opts {
     float   ratio;       /* 0: no ratio test; else a pair needs dist_best / dist_second < ratio (0.8 = match_sets' accept) */
@@ -486,6 +488,9 @@ int  popsift_hip_match_pairs(const popsift_hip_devfeatures* l, const popsift_hip
  *
  * As for float sets: all scratch belongs to l (one match at a time per left set), r may be the left set of another thread's
  * call, and with sets on different GPUs r's bytes are copied to l's GPU once per call.
+ *
+ * Byte sets hold no positions, so there is no guided byte matcher (popsift_hip_match_pairs_guided): guide the float sets
+ * the bytes came from.
  */
 typedef struct popsift_hip_bytefeatures popsift_hip_bytefeatures;
 int popsift_hip_bytefeatures_from_host(int device, const uint8_t* desc, int n_descriptors, popsift_hip_bytefeatures** out);
@@ -644,6 +649,89 @@ int  popsift_hip_epipolar(popsift_hip_verifier* v, const float* pts, int n, cons
 /* samples: T x 8, models: T x 9, counts: T; any may be NULL */
 int  popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
                                 int32_t* samples, float* models, int32_t* counts);
+
+/*
+ * Guided matching: nearest neighbours under a known model (the expectation SiftGPU's GetGuidedSiftMatch(.., H, F, distmax,
+ * ratiomax, hsearch_thresh, fsearch_thresh, mutual) sets).  With the homography or the fundamental matrix of an image pair
+ * known -- from popsift_hip_ransac / popsift_hip_epipolar, or from anywhere else -- each left descriptor is searched for only
+ * among the right descriptors whose POSITION agrees with the model.  This is not "match, then filter": a row whose global
+ * nearest neighbour fails the geometry is answered by its nearest candidate, and a row whose second nearest neighbour in
+ * the whole right set spoiled the ratio test is measured against the few candidates only.
+ *
+ * The position of descriptor i of a set is (xpos, ypos) of the feature its descriptor -> feature map names: the floats
+ * popsift_hip_pair_points gathers.  M is the caller's 3 x 3 row-major float model; float = IEEE binary32, every line one
+ * operation, fmaf fused.
+ *
+ * Candidate test ok(i, j), left descriptor i at (x, y), right descriptor j at (x', y'):
+ *   POPSIFT_HIP_GUIDE_HOMOGRAPHY  step 4 of popsift_hip_ransac with H = M, operation for operation: u, v, w, dx, dy, e, lim
+ *                                 as written there; ok = w > 0 && e <= lim.  An affine model is a homography whose last row
+ *                                 is 0 0 1.
+ *   POPSIFT_HIP_GUIDE_EPIPOLAR    step 6 of popsift_hip_epipolar with F = M, operation for operation;
+ *                                 ok = g > 0 && g < +inf && r * r <= lim.
+ * A NaN fails every comparison, so a feature with a NaN coordinate is nobody's candidate; so is one with an infinite
+ * coordinate as long as lim stays finite (always under the epipolar test, which asks for g < +inf).  Consequence: a pair in
+ * the verifier's inlier mask is a candidate under the verifier's own model and max_err.  The test is always evaluated
+ * left -> right, also for the cross-check below.
+ *
+ * Distance d(i, j): the squared L2 distance exactly as popsift_hip_match_sets (POPSIFT_HIP_MATCH_EXACT) forms it.  For chunk
+ * c = 0 .. 31 with x, y, z, w = l[4c .. 4c+3] - r[4c .. 4c+3]: p(c) = fmaf(w, w, fmaf(z, z, fmaf(y, y, x * x))); then
+ * n1(i) = p(i) + p(i+16), n2(i) = n1(i) + n1(i+8), n3(i) = n2(i) + n2(i+4), n4(i) = n3(i) + n3(i+2), d = n4(0) + n4(1).
+ * d is the same bits in both directions.
+ *
+ * Row of left descriptor i, over C(i) = { j : ok(i, j) and d(i, j) < +inf } (a NaN distance drops out): best and second are
+ * the two smallest under lexicographic (d, j).  |C(i)| = 0: best = second = -1, both distances +inf.  |C(i)| = 1:
+ * second = -1, dist_second = +inf.  accept = dist_best / dist_second < 0.8f in IEEE float division: 0 for an empty row
+ * (inf / inf is NaN), 1 for a single candidate, no special case.  The record is popsift_hip_match.
+ *
+ * Pairs: the rule of popsift_hip_match_pairs, word for word, on these rows.  Condition 1 becomes "best >= 0"; in condition
+ * 4, B is the guided search the other way round: for right descriptor j the nearest under (d, i') among { i' : ok(i', j) }.
+ * Pairs in ascending l; *n_pairs, cap, ERR_TOO_SMALL and "cap = 0 with pairs = NULL asks for the count" as there; the same
+ * bytes on every run.  popsift_hip_match_set_path does not apply: nothing is screened, every distance is exact.
+ *
+ * popsift_hip_match_guided returns the rows (parity hook and API): it reads model, M and max_err only, and still rejects
+ * invalid other fields.  out has l's descriptor count entries.
+ *
+ * popsift_hip_devfeatures_from_host_points builds a set of n features and n descriptors from host memory, for callers who
+ * bring keypoints and descriptors from elsewhere: feature i sits at (xy[2i], xy[2i+1]) with sigma = 0, num_ori = 1,
+ * orientation[0] = 0, its desc[0] points to descriptor i, and the map is i -> i.  Errors as
+ * popsift_hip_devfeatures_from_host, plus xy NULL with n > 0.  pair_points, match_sets and match_pairs work on such a set
+ * like on any other.
+ *
+ * ERR_INVALID, before any GPU call: a NULL set, opts, or out / n_pairs; pairs NULL with cap > 0; an unknown model; max_err
+ * not finite or <= 0; a non-finite entry of M; ratio negative, NaN or infinite; max_dist2 NaN; cross_check other than 0 / 1;
+ * reserved != 0.  ERR_INVALID also when a map entry of either set names no feature (sets of
+ * popsift_hip_devfeatures_from_host have -1 everywhere): as in popsift_hip_pair_points this is found on the device, when both
+ * sets hold descriptors, and nothing is written then.  Empty l or r: OK; the rows of an empty r are the empty row above;
+ * 0 pairs.
+ *
+ * All scratch belongs to l and is grow-only; one guided call at a time per left set; r is only read and may be the left set
+ * of another thread's call.  Sets on different GPUs: what is needed of r is copied to l's GPU once per call.  One download
+ * brings the count and the pairs (or the rows).
+ *
+ * The kernel (match_guided.hip): a wave owns POPSIFT_HIP_GUIDED_ROWS left rows and walks the right positions
+ * POPSIFT_HIP_GUIDED_STEP at a time; the pairs that pass ok() wait in a queue of POPSIFT_HIP_GUIDED_QUEUE entries for their
+ * distances (stated here for the tests of their edges; results do not depend on them).
+ */
+enum { POPSIFT_HIP_GUIDE_HOMOGRAPHY = 0, POPSIFT_HIP_GUIDE_EPIPOLAR = 1 };
+#define POPSIFT_HIP_GUIDED_ROWS 64
+#define POPSIFT_HIP_GUIDED_STEP 256
+#define POPSIFT_HIP_GUIDED_QUEUE 512
+typedef struct popsift_hip_guided_opts {   /* 64 bytes */
+    int32_t model;        /* POPSIFT_HIP_GUIDE_*                                                  */
+    float   M[9];         /* row major: right ~ M * left, or [x' y' 1] M [x y 1]^T = 0            */
+    float   max_err;      /* px: transfer error in the right image / Sampson distance             */
+    float   ratio;        /* as popsift_hip_match_opts                                            */
+    float   max_dist2;
+    int32_t cross_check;
+    int32_t reserved[2];  /* must be 0 */
+} popsift_hip_guided_opts;
+void popsift_hip_default_guided_opts(popsift_hip_guided_opts* opts); /* {HOMOGRAPHY, identity, 2.0f, 0.8f, INFINITY, 0, {0, 0}} */
+int  popsift_hip_match_guided(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
+                              const popsift_hip_guided_opts* opts, popsift_hip_match* out);
+int  popsift_hip_match_pairs_guided(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
+                                    const popsift_hip_guided_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
+int  popsift_hip_devfeatures_from_host_points(int device, const float* desc, const float* xy, int n,
+                                              popsift_hip_devfeatures** out);
 
 int popsift_hip_get_report(const popsift_hip_ctx* ctx, popsift_hip_report* rep);
 /* profile != 0: bracket every blur-level launch with HIP events (serialises the

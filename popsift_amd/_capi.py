@@ -71,6 +71,12 @@ class MatchOpts(C.Structure):
     _fields_ = [("ratio", C.c_float), ("max_dist2", C.c_float), ("cross_check", C.c_int32), ("reserved", C.c_int32)]
 
 
+class GuidedOpts(C.Structure):
+    """popsift_hip_guided_opts"""
+    _fields_ = [("model", C.c_int32), ("M", C.c_float * 9), ("max_err", C.c_float), ("ratio", C.c_float),
+                ("max_dist2", C.c_float), ("cross_check", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class RansacOpts(C.Structure):
     """popsift_hip_ransac_opts"""
     _fields_ = [("model", C.c_int32), ("hypotheses", C.c_int32), ("max_err", C.c_float), ("seed", C.c_uint32),
@@ -98,6 +104,10 @@ MODEL_HOMOGRAPHY, MODEL_AFFINE = 0, 1
 MODELS = {"homography": MODEL_HOMOGRAPHY, "affine": MODEL_AFFINE}
 RANSAC_CHUNK, RANSAC_HYP_BLOCK = 1024, 64  # POPSIFT_HIP_RANSAC_*: pairs / hypotheses per workgroup of the scoring kernel
 EPIPOLAR_SAMPLE = 8                        # POPSIFT_HIP_EPIPOLAR_SAMPLE: pairs per hypothesis of Verifier.epipolar
+GUIDE_HOMOGRAPHY, GUIDE_EPIPOLAR = 0, 1    # POPSIFT_HIP_GUIDE_*: the model of DevFeatures.match_guided
+GUIDES = {"homography": GUIDE_HOMOGRAPHY, "affine": GUIDE_HOMOGRAPHY, "epipolar": GUIDE_EPIPOLAR}
+# POPSIFT_HIP_GUIDED_*: left rows per workgroup, right positions per step, queue entries of the guided matcher's kernel
+GUIDED_ROWS, GUIDED_STEP, GUIDED_QUEUE = 64, 256, 512
 EXTREMUM_DTYPE = np.dtype([
     ("xpos", np.float32), ("ypos", np.float32), ("lpos", np.int32),
     ("sigma", np.float32), ("octave", np.int32), ("cell", np.int32),
@@ -179,6 +189,10 @@ SYMBOLS = [
     ("popsift_hip_default_epipolar_opts", None, [C.POINTER(EpipolarOpts)]),
     ("popsift_hip_epipolar", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp]),
     ("popsift_hip_epipolar_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp, _vp]),
+    ("popsift_hip_default_guided_opts", None, [C.POINTER(GuidedOpts)]),
+    ("popsift_hip_match_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp]),
+    ("popsift_hip_match_pairs_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp, C.c_size_t, _ip]),
+    ("popsift_hip_devfeatures_from_host_points", C.c_int, [C.c_int, _vp, _vp, C.c_int, C.POINTER(_vp)]),
     ("popsift_hip_get_report", C.c_int, [_vp, C.POINTER(Report)]),
     ("popsift_hip_set_profile", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_octave_dims", C.c_int, [_vp, C.c_int, _ip, _ip]),
@@ -287,6 +301,19 @@ class DevFeatures:
             raise PopsiftHipError(rc, "popsift_hip_devfeatures_from_host")
         return cls(h)
 
+    @classmethod
+    def from_host_points(cls, desc, xy, device=0):
+        """popsift_hip_devfeatures_from_host_points: descriptors (n, 128) with their positions (n, 2), one feature each"""
+        desc = np.ascontiguousarray(desc, np.float32).reshape(-1, 128)
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        if len(xy) != len(desc):
+            raise ValueError("from_host_points: %d descriptors, %d positions" % (len(desc), len(xy)))
+        h = _vp()
+        rc = lib().popsift_hip_devfeatures_from_host_points(device, desc.ctypes.data, xy.ctypes.data, len(desc), C.byref(h))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_devfeatures_from_host_points")
+        return cls(h)
+
     def info(self):
         d, nf, nd = C.c_int(), C.c_int(), C.c_int()
         lib().popsift_hip_devfeatures_info(self._h, C.byref(d), C.byref(nf), C.byref(nd))
@@ -329,6 +356,30 @@ class DevFeatures:
         rc = lib().popsift_hip_match_pairs(self._h, other._h, C.byref(opts), out.ctypes.data if nd else None, nd, C.byref(n))
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_match_pairs")
+        return out[:n.value]
+
+    def match_guided(self, other, model, M, max_err=2.0):
+        """popsift_hip_match_guided: a MATCH_DTYPE row per descriptor, its two nearest among the descriptors of `other`
+        whose positions agree with the 3 x 3 model M (by name or number: homography / affine / epipolar) within max_err
+        pixels; best / second are -1 where there is none"""
+        _, _, nd = self.info()
+        out = np.zeros(nd, MATCH_DTYPE)
+        opts = guided_opts(model, M, max_err)
+        rc = lib().popsift_hip_match_guided(self._h, other._h, C.byref(opts), out.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_guided")
+        return out
+
+    def match_pairs_guided(self, other, model, M, max_err=2.0, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """popsift_hip_match_pairs_guided: match_pairs' rule on match_guided's rows, as a PAIR_DTYPE array in ascending l"""
+        _, _, nd = self.info()
+        out = np.zeros(nd, PAIR_DTYPE)
+        opts = guided_opts(model, M, max_err, ratio, max_dist2, cross_check)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs_guided(self._h, other._h, C.byref(opts), out.ctypes.data if nd else None, nd,
+                                                  C.byref(n))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_guided")
         return out[:n.value]
 
     def pair_points(self, other, pairs):
@@ -424,6 +475,25 @@ class ByteFeatures:
             self.close()
         except Exception:
             pass
+
+
+def guided_opts(model="homography", M=None, max_err=None, ratio=None, max_dist2=None, cross_check=None):
+    """popsift_hip_guided_opts: the library's defaults with the given fields replaced; model by name or number, M any
+    array of nine numbers in row-major order"""
+    o = GuidedOpts()
+    lib().popsift_hip_default_guided_opts(C.byref(o))
+    o.model = GUIDES.get(model, model)
+    if M is not None:
+        o.M[:] = [float(v) for v in np.asarray(M, np.float32).reshape(9)]
+    if max_err is not None:
+        o.max_err = max_err
+    if ratio is not None:
+        o.ratio = ratio
+    if max_dist2 is not None:
+        o.max_dist2 = max_dist2
+    if cross_check is not None:
+        o.cross_check = 1 if cross_check else 0
+    return o
 
 
 def ransac_opts(model="homography", hypotheses=None, max_err=None, seed=None):

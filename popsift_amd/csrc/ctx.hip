@@ -1753,6 +1753,8 @@ int popsift_hip_devfeatures_free(popsift_hip_devfeatures* f)
     if (f->p_back) (void)hipFree(f->p_back);
     if (f->v_buf) (void)hipFree(f->v_buf);
     if (f->v_host) (void)hipHostFree(f->v_host);
+    if (f->g_buf) (void)hipFree(f->g_buf);
+    if (f->g_host) (void)hipHostFree(f->g_host);
     delete f;
     return POPSIFT_HIP_OK;
 }
@@ -1818,6 +1820,45 @@ int popsift_hip_devfeatures_from_host(int device, const float* desc, int n, pops
     if (ok && n > 0) {
         ok = hipMemcpy(f->d_desc, desc, sizeof(float) * 128 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
              hipMemset(f->d_rev, 0xff, sizeof(int) * (size_t)n) == hipSuccess; /* -1: no feature behind it */
+    }
+    if (!ok) {
+        popsift_hip_devfeatures_free(f);
+        return POPSIFT_HIP_ERR_OOM;
+    }
+    *out = f;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_devfeatures_from_host_points(int device, const float* desc, const float* xy, int n, popsift_hip_devfeatures** out)
+{
+    if (!out || n < 0 || (n > 0 && (!desc || !xy))) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc = check_device(device)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
+    if (!f) return POPSIFT_HIP_ERR_OOM;
+    f->device = device;
+    f->n_feat = n;
+    f->n_desc = n;
+    bool ok = hipMalloc((void**)&f->d_feat, sizeof(DevFeature) * (size_t)std::max(n, 1)) == hipSuccess &&
+              hipMalloc((void**)&f->d_desc, sizeof(float) * 128 * (size_t)std::max(n, 1)) == hipSuccess &&
+              hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(n, 1)) == hipSuccess;
+    if (ok && n > 0) {
+        /* the records are built here: one feature per descriptor, its desc[0] pointing into the device array */
+        std::vector<DevFeature> feat((size_t)n);
+        std::vector<int>        rev((size_t)n);
+        for (int i = 0; i < n; i++) {
+            DevFeature& o = feat[(size_t)i];
+            memset(&o, 0, sizeof o);
+            o.xpos = xy[2 * (size_t)i];
+            o.ypos = xy[2 * (size_t)i + 1];
+            o.num_ori = 1;
+            o.desc[0] = f->d_desc + (size_t)i * 128;
+            rev[(size_t)i] = i;
+        }
+        ok = hipMemcpy(f->d_desc, desc, sizeof(float) * 128 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(f->d_feat, feat.data(), sizeof(DevFeature) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+             hipMemcpy(f->d_rev, rev.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
     }
     if (!ok) {
         popsift_hip_devfeatures_free(f);

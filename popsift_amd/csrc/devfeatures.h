@@ -41,6 +41,11 @@ struct popsift_hip_devfeatures {
     void*  v_buf = nullptr;
     void*  v_host = nullptr;    /* pinned twin */
     size_t v_cap = 0;           /* bytes */
+    /* scratch of the guided matcher with this set on the left (match_guided.hip): a 16-byte header ([0] = a map entry
+     * names no feature) and the forward rows, then both sets' positions, the reverse rows and the compaction's counts */
+    void*  g_buf = nullptr;
+    size_t g_cap = 0;           /* bytes */
+    void*  g_host = nullptr;    /* pinned twin of the header and the forward rows */
 };
 
 /* A set of byte descriptors (popsift_hip_bytefeatures).  The scratch members mean what their namesakes above mean; a

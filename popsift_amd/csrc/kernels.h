@@ -173,6 +173,10 @@ hipError_t launch_gather_rows(const float* desc, const int* list, int n, float* 
 hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
                             const popsift_hip_match* back, const int* rank, int* counts, popsift_hip_pair* pairs, int* n_pairs,
                             hipStream_t s);
+/* the same over the guided matcher's rows (match_guided.hip): a row without a candidate has best = -1; back: a row per
+ * right descriptor, or null without the cross-check */
+hipError_t launch_pair_emit_guided(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
+                                   const popsift_hip_match* back, int* counts, popsift_hip_pair* pairs, int* n_pairs, hipStream_t s);
 /* match_u8.hip: exact integer 2-NN of byte descriptors (128 bytes each, 16-byte aligned) on the i8 matrix instructions.
  * Norms are |x - 128|^2 as int; `out` receives l_len rows whose distances are integers held in floats. */
 int        match_u8_splits(int l_len, int r_len);

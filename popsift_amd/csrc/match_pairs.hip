@@ -51,6 +51,20 @@ struct PairKept {
     }
 };
 
+/* the same for the guided matcher's rows (match_guided.hip): a row without a candidate has best = -1, and `back` holds a
+ * row for every right descriptor */
+struct GuidedPairKept {
+    const popsift_hip_match* fwd;
+    const popsift_hip_match* back; /* null: no cross-check */
+    float                    ratio, max_dist2;
+    __device__ bool operator()(int i) const
+    {
+        const popsift_hip_match m = fwd[i];
+        if (m.best < 0 || !row_passes(m, ratio, max_dist2)) return false;
+        return !back || back[m.best].best == i;
+    }
+};
+
 struct WriteIndex {
     int* list;
     int* rank;
@@ -174,6 +188,16 @@ hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio
     const PairKept keep{fwd, back, rank, ratio, max_dist2};
     hipLaunchKernelGGL(k_count<PairKept>, dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep, l_len, counts);
     hipLaunchKernelGGL((k_compact<PairKept, WritePair>), dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep,
+                       WritePair{fwd, pairs}, l_len, counts, n_pairs);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_emit_guided(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
+                                   const popsift_hip_match* back, int* counts, popsift_hip_pair* pairs, int* n_pairs, hipStream_t s)
+{
+    const GuidedPairKept keep{fwd, back, ratio, max_dist2};
+    hipLaunchKernelGGL(k_count<GuidedPairKept>, dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep, l_len, counts);
+    hipLaunchKernelGGL((k_compact<GuidedPairKept, WritePair>), dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep,
                        WritePair{fwd, pairs}, l_len, counts, n_pairs);
     return hipGetLastError();
 }

@@ -360,6 +360,53 @@ std::vector<FeaturesDev::Pair> FeaturesDev::matchPairs(FeaturesDev* other, const
     return match_pairs(_set, other ? other->_set : 0, getDescriptorCount(), opts, popsift_hip_match_pairs);
 }
 
+namespace {
+popsift_hip_guided_opts guided_opts(const FeaturesDev::GuidedOptions& opts)
+{
+    popsift_hip_guided_opts o;
+    popsift_hip_default_guided_opts(&o);
+    o.model = opts.model == FeaturesDev::GuidedOptions::Epipolar ? POPSIFT_HIP_GUIDE_EPIPOLAR : POPSIFT_HIP_GUIDE_HOMOGRAPHY;
+    for (int i = 0; i < 9; i++) o.M[i] = opts.M[i];
+    o.max_err = opts.maxErr;
+    o.ratio = opts.ratio;
+    o.max_dist2 = opts.maxDist2;
+    o.cross_check = opts.crossCheck ? 1 : 0;
+    return o;
+}
+}  // namespace
+
+std::vector<FeaturesDev::Pair> FeaturesDev::matchGuided(FeaturesDev* other, const GuidedOptions& opts)
+{
+    static_assert(sizeof(Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
+    std::vector<Pair> res;
+    if (!_set || !other || !other->_set) return res;
+    res.resize((size_t)getDescriptorCount()); /* always enough */
+    const popsift_hip_guided_opts o = guided_opts(opts);
+    int                           n = 0;
+    const int rc = popsift_hip_match_pairs_guided(_set, other->_set, &o, (popsift_hip_pair*)res.data(), res.size(), &n);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("guided matching failed", rc);
+    res.resize((size_t)n);
+    return res;
+}
+
+std::vector<FeaturesDev::Match> FeaturesDev::matchGuidedRows(FeaturesDev* other, const GuidedOptions& opts)
+{
+    if (getDescriptorCount() == 0) return std::vector<Match>(); /* the C call wants a buffer even then */
+    const popsift_hip_guided_opts o = guided_opts(opts);
+    return match_and_get(_set, other ? other->_set : 0, getDescriptorCount(),
+                         [&o](const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, popsift_hip_match* out) {
+                             return popsift_hip_match_guided(l, r, &o, out);
+                         });
+}
+
+FeaturesDev* FeaturesDev::fromHostPoints(const float* desc, const float* xy, int num, int device)
+{
+    popsift_hip_devfeatures* set = 0;
+    const int                rc = popsift_hip_devfeatures_from_host_points(device, desc, xy, num, &set);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot make the set from host points", rc);
+    return new FeaturesDev(set);
+}
+
 std::vector<float> FeaturesDev::pairPoints(FeaturesDev* other, const std::vector<Pair>& pairs)
 {
     static_assert(sizeof(Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");

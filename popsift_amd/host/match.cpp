@@ -7,6 +7,8 @@
  * Extension: --verify homography|affine|epipolar [--hypotheses T] [--max-err E] [--seed S] with --pairs fits the model to
  * the pairs by RANSAC on the GPU (popsift::Verifier) and prints it with its inlier count after the pair lines; epipolar is
  * the fundamental matrix of two views of a 3-D scene.
+ * Extension: --guided [--guided-err E] with --verify matches again under the model just found (FeaturesDev::matchGuided)
+ * and prints those pairs after the model block.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -41,6 +43,8 @@ static popsift::FeaturesDev::MatchOptions pair_opts;
 static bool verify_pairs = false;
 static popsift::RansacOptions verify_opts;
 static bool verify_epipolar = false;
+static bool guided_pairs = false;
+static float guided_err = 0.0f; /* 0: --max-err */
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -118,6 +122,12 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.fval("max-err", "Matching", "With --verify: an inlier lies within this many pixels of its image, or of its epipolar line (default 2)",
            [&](float f) { verify_opts.maxErr = f; });
     o.ival("seed", "Matching", "With --verify: seed of the sampler (default 0)", [&](int v) { verify_opts.seed = (unsigned)v; });
+    o.flag("guided", 0, "Matching",
+           "With --verify: match again under the model just found -- each left descriptor among the right ones within\n"
+           "--guided-err pixels of its image (homography, affine) or of its epipolar line -- with --ratio, --max-dist and\n"
+           "--cross-check as given; prints those pairs after the model, then their count",
+           [&] { guided_pairs = true; });
+    o.fval("guided-err", "Matching", "With --guided: the distance in pixels (default: --max-err)", [&](float f) { guided_err = f; });
     o.val("feature-order", 0, "Extensions",
           "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
           "pixel column, level: the same bytes on every run)",
@@ -129,6 +139,14 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.parse(argc, argv);
     if (verify_pairs && !print_pairs) {
         cerr << "--verify works on the pairs: add --pairs" << endl;
+        exit(-1);
+    }
+    if (guided_pairs && !verify_pairs) {
+        cerr << "--guided matches under the model --verify finds: add --verify" << endl;
+        exit(-1);
+    }
+    if (guided_pairs && match_bytes) {
+        cerr << "--guided needs positions, which byte sets do not hold: drop --bytes" << endl;
         exit(-1);
     }
 }
@@ -160,6 +178,21 @@ static void print_verification(popsift::FeaturesDev* lf, popsift::FeaturesDev* r
     printf("Model (%s):\n", verify_epipolar ? "epipolar" : verify_opts.model == popsift::RansacOptions::Affine ? "affine" : "homography");
     for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", fit.H[3 * i], fit.H[3 * i + 1], fit.H[3 * i + 2]);
     printf("Number of inliers:     %d of %zu\n", fit.inliers, pairs.size());
+    if (!guided_pairs) return;
+    /* --guided: the search again, among the right descriptors that agree with the model */
+    popsift::FeaturesDev::GuidedOptions g;
+    g.model = verify_epipolar ? popsift::FeaturesDev::GuidedOptions::Epipolar : popsift::FeaturesDev::GuidedOptions::Homography;
+    for (int i = 0; i < 9; i++) g.M[i] = fit.H[i];
+    g.maxErr = guided_err > 0.0f ? guided_err : verify_opts.maxErr;
+    g.ratio = pair_opts.ratio;
+    g.maxDist2 = pair_opts.maxDist2;
+    g.crossCheck = pair_opts.crossCheck;
+    const vector<popsift::FeaturesDev::Pair> guided = lf->matchGuided(rf, g);
+    const vector<int>                        l_fem = reverse_map(lf), r_fem = reverse_map(rf);
+    for (const popsift::FeaturesDev::Pair& p : guided)
+        printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[(size_t)p.r], p.r,
+               sqrtf(p.distBest));
+    printf("Number of guided pairs: %zu\n", guided.size());
 }
 
 /* one line per pair through the sets' reverse maps, then the count; lf / rf: the float sets behind l and r */
