@@ -411,11 +411,20 @@ typedef struct popsift_hip_match {
  * descriptor of `l` among the descriptors of `r`; out has l's descriptor count entries (host memory).
  * Sets on different GPUs are allowed (the right set is copied to the left set's GPU). */
 int popsift_hip_match_sets(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, popsift_hip_match* out);
-/* Which kernels popsift_hip_match_sets uses, process-wide (tests compare the paths; results are identical):
+/* Which kernels popsift_hip_match_sets uses, process-wide (tests compare the paths):
  * AUTO (default): matrix-core screening + exact re-rank from 4e6 pairs on, the exact brute-force kernel below;
- * EXACT: the exact kernel only; SCREEN: screening for every size. */
+ * EXACT: the exact kernel only; SCREEN: screening for every size.
+ * Every path writes the same bytes for any float input: values of any magnitude and sign, zero rows, NaN and +-Inf
+ * elements, and rows whose squared norm overflows while their distances do not.  A pair whose float32 distance is NaN
+ * or +Inf is nobody's best or second; a row without two such candidates keeps index 0 and distance +INFINITY in the
+ * empty places.  The screening pass decides a row only where its rounding margin holds and the norms it works from are
+ * finite; every other row is matched by the exact kernel. */
 enum { POPSIFT_HIP_MATCH_AUTO = 0, POPSIFT_HIP_MATCH_EXACT = 1, POPSIFT_HIP_MATCH_SCREEN = 2 };
 int popsift_hip_match_set_path(int path);
+/* Test hook, not part of the matching interface: *count receives the number of rows that l's last forward sweep on the
+ * screening path left to the exact kernel, or -1 when l has never been the left set of a screened sweep.  Waits for l's
+ * stream and copies one int; changes nothing.  ERR_INVALID: l or count NULL. */
+int popsift_hip_devfeatures_debug_redo_count(const popsift_hip_devfeatures* l, int* count);
 
 /*
  * Correspondences: the rows of the search above, filtered on the GPU into a list of pairs (the expectation SiftGPU's

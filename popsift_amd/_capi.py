@@ -170,6 +170,7 @@ SYMBOLS = [
     ("popsift_hip_devfeatures_download_u8", C.c_int, [_vp, _vp]),
     ("popsift_hip_match_sets", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_set_path", C.c_int, [C.c_int]),
+    ("popsift_hip_devfeatures_debug_redo_count", C.c_int, [_vp, _ip]),
     ("popsift_hip_default_match_opts", None, [C.POINTER(MatchOpts)]),
     ("popsift_hip_match_pairs", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
     ("popsift_hip_bytefeatures_from_host", C.c_int, [C.c_int, _vp, C.c_int, C.POINTER(_vp)]),
@@ -344,6 +345,15 @@ class DevFeatures:
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_match_sets")
         return out
+
+    def debug_redo_count(self):
+        """Test hook (popsift_hip_devfeatures_debug_redo_count): rows the last forward screened sweep with this set on
+        the left gave to the exact kernel; -1 before the first such sweep"""
+        n = C.c_int(0)
+        rc = lib().popsift_hip_devfeatures_debug_redo_count(self._h, C.byref(n))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_devfeatures_debug_redo_count")
+        return n.value
 
     def match_pairs(self, other, ratio=0.8, max_dist2=np.inf, cross_check=False):
         """Correspondences (popsift_hip_match_pairs): the rows of match(other) that pass the ratio test (0: none), the cap

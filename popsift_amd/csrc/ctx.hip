@@ -2067,10 +2067,10 @@ bool match_screens(int path, int l_len, int r_len)
     return path == POPSIFT_HIP_MATCH_SCREEN || (path == POPSIFT_HIP_MATCH_AUTO && (double)l_len * (double)r_len >= 4.0e6);
 }
 
-/* |x|^2 of the set's own descriptors, computed on first use */
+/* |x|^2 of the set's own descriptors (and launch_norms' flag behind them), computed on first use */
 void match_own_norms(MatchStatus& ok, popsift_hip_devfeatures* f, hipStream_t s)
 {
-    if (ok.good() && !f->d_norm && ok(hipMalloc((void**)&f->d_norm, sizeof(float) * (size_t)f->n_desc)))
+    if (ok.good() && !f->d_norm && ok(hipMalloc((void**)&f->d_norm, sizeof(float) * ((size_t)f->n_desc + 1))))
         ok(launch_norms(f->d_desc, f->n_desc, f->d_norm, s));
 }
 
@@ -2124,7 +2124,7 @@ void match_forward(MatchStatus& ok, popsift_hip_devfeatures* l, const popsift_hi
         if (!l->m_redo) ok(hipMalloc((void**)&l->m_redo, sizeof(int) * ((size_t)l->n_desc + 1)));
         match_own_norms(ok, l, s);
         /* the right set may be the left set of another thread's match: its norms go to a buffer of this call */
-        if (match_grow(ok, l->m_rnorm, l->m_rnorm_cap, (size_t)r->n_desc, sizeof(float)))
+        if (match_grow(ok, l->m_rnorm, l->m_rnorm_cap, (size_t)r->n_desc + 1, sizeof(float)))
             ok(launch_norms(*rdesc, r->n_desc, l->m_rnorm, s));
     }
     if (ok.good())
@@ -2139,13 +2139,13 @@ const popsift_hip_match* match_reverse(MatchStatus& ok, popsift_hip_devfeatures*
 {
     const int    l_len = l->n_desc;
     hipStream_t  s = (hipStream_t)l->m_stream;
-    /* per member of J: 128 floats, a result row, a norm and a redo slot (+ the redo count) */
+    /* per member of J: 128 floats, a result row, a norm and a redo slot (+ the norms' flag and the redo count) */
     const size_t per = sizeof(float) * 128 + sizeof(popsift_hip_match) + sizeof(float) + sizeof(int);
     if (!match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list + 1, per)) return nullptr;
     float* const gdesc = (float*)l->p_back;
     auto* const  rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
     float* const gnorm = (float*)(rows + n_list);
-    int* const   redo = (int*)(gnorm + n_list);
+    int* const   redo = (int*)(gnorm + n_list + 1);
     const bool   screen = match_screens(path, n_list, l_len);
     ok(launch_gather_rows(rdesc, list, n_list, gdesc, s));
     if (screen) {
@@ -2305,6 +2305,18 @@ extern "C" {
 int popsift_hip_match_sets(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, popsift_hip_match* out)
 {
     return match_rows(l, r, out, g_match_path.load());
+}
+
+int popsift_hip_devfeatures_debug_redo_count(const popsift_hip_devfeatures* l, int* count)
+{
+    if (!l || !count) return POPSIFT_HIP_ERR_INVALID;
+    *count = -1;
+    if (!l->m_redo) return POPSIFT_HIP_OK;
+    if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    if (hipStreamSynchronize((hipStream_t)l->m_stream) != hipSuccess ||
+        hipMemcpy(count, l->m_redo, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return POPSIFT_HIP_ERR_DEVICE;
+    return POPSIFT_HIP_OK;
 }
 
 int popsift_hip_match_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, popsift_hip_match* out)

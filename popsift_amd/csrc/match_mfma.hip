@@ -61,6 +61,8 @@ __device__ __forceinline__ void cand_insert(Cand& c, float d, int i)
     }
 }
 
+/* out[n] (zeroed by the launcher) becomes 1 when a norm is not finite: k_match_select then decides nothing against
+ * this set (see there) */
 __global__ __launch_bounds__(256) void k_norms(const float* __restrict__ desc, int n, float* __restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -75,6 +77,7 @@ __global__ __launch_bounds__(256) void k_norms(const float* __restrict__ desc, i
         s = fmaf(v.w, v.w, s);
     }
     out[i] = s;
+    if (!(s < INFINITY)) out[n] = 1.0f; /* every writer stores the same value */
 }
 
 /*
@@ -214,11 +217,25 @@ __global__ __launch_bounds__(256) void k_match_select(const float* __restrict__ 
         for (int k = 0; k < S_K; k++) cand_insert(c, o.d[k], o.i[k]);
     }
     const float ln = lnorm[l];
-    /* screened distance = ln + d; margin 2 eps with eps = 3e-5 (|l|^2 + |r|^2) >= the GEMM-form rounding plus the
-     * reference's own (both ~ 1e-5 relative for 128 terms) */
+    /* Screened distance = ln + d.  With u = 2^-24, L = |l|^2, R = |r|^2 and D the true squared distance:
+     *   k_norms' FMA chain of 128 terms is off by at most 128 u R, the MFMA chain by 128 u sum |l_k r_k| <= 128 u sqrt(L R),
+     *   and d = R - 2 l.r adds one rounding, u |d|: the screened distance of a pair is within
+     *       e(r) = 128 u (L + R + 2 sqrt(L R)) + u |d| <= 2 * 128 u (L + R) + u |d| < 1.6e-5 (L + R)   of D;
+     *   the reference's own float32 distance carries at most 11 roundings (subtraction, square, 4 FMAs, 5 tree adds):
+     *   within 11 u D <= 22 u (L + R) < 1.4e-6 (L + R) of D.
+     * eps = 3e-5 (L + max(R2, L)), R2 the norm of the second candidate, covers both for the kept candidates whose norm
+     * is at most max(R2, L).  A right row j outside the four with a larger norm R_j has a larger e(r_j), but also
+     * D_j >= (sqrt(R_j) - sqrt(L))^2: tests/match_rule.py (mixed_norms) builds such rows against this margin.
+     * Below the normal range the bounds are absolute, not relative: each of the few hundred products and sums behind a
+     * screened distance may lose up to 2^-126 ~ 1.2e-38 where the matrix cores flush denormals, together under 1e-35,
+     * which eps carries as a floor (nothing next to 3e-5 (L + R) from norms of 1e-30 on).
+     * The margin means nothing where a norm is not finite although distances may be (|x|^2 overflows from |x| ~ 1.8e19
+     * on): such a left row, and every row of a sweep whose right set has such a norm (rnorm[r_len] != 0), goes to the
+     * exact kernel. */
     const float rn2 = (c.d[1] < INFINITY) ? rnorm[c.i[1]] : 0.0f;
-    const float eps = 3e-5f * (ln + fmaxf(rn2, ln));
-    const bool  separable = !(c.d[S_K - 1] < INFINITY) || (c.d[S_K - 1] > c.d[1] + 2.0f * eps);
+    const float eps = 3e-5f * (ln + fmaxf(rn2, ln)) + 1e-35f;
+    const bool  representable = ln < INFINITY && rnorm[r_len] == 0.0f;
+    const bool  separable = representable && (!(c.d[S_K - 1] < INFINITY) || (c.d[S_K - 1] > c.d[1] + 2.0f * eps));
     if (!separable) {
         if (lane == 0) redo_list[atomicAdd(redo_count, 1)] = l;
         return;
@@ -277,9 +294,11 @@ int screen_splits(int l_len, int r_len)
 
 size_t screen_partial_bytes(int l_len, int n_split) { return (size_t)std::max(l_len, 1) * n_split * sizeof(Cand); }
 
+/* out: n norms and, in out[n], the flag "one of them is not finite" */
 hipError_t launch_norms(const float* desc, int n, float* out, hipStream_t s)
 {
-    if (n <= 0) return hipSuccess;
+    const hipError_t err = hipMemsetAsync(out + std::max(n, 0), 0, sizeof(float), s);
+    if (err != hipSuccess || n <= 0) return err;
     hipLaunchKernelGGL(k_norms, dim3((n + 255) / 256), dim3(256), 0, s, desc, n, out);
     return hipGetLastError();
 }

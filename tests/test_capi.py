@@ -82,6 +82,8 @@ def test_invalid_arguments_are_rejected_without_a_gpu(hip):
     assert lib.popsift_hip_ctx_destroy(None) == hip.OK
     assert lib.popsift_hip_wait(None, None, None) == hip.ERR_INVALID
     assert lib.popsift_hip_device_count(None) == hip.ERR_INVALID
+    n = C.c_int(7)
+    assert lib.popsift_hip_devfeatures_debug_redo_count(None, C.byref(n)) == hip.ERR_INVALID and n.value == 7
 
 
 def test_no_gpu_means_no_context_not_a_fallback(hip):
