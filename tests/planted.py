@@ -118,6 +118,31 @@ class Planted:
             self.dog.append(dog_planes(w, h, bt, levels + 2))
             self.gauss.append(gauss_planes(w, h, rng, planes=levels + 3))
 
+    @classmethod
+    def from_tables(cls, dims, tables, seed=0, levels=LEVELS):
+        """a Planted from caller-chosen bump tables: tables = {octave: bump_table(...)} (octaves left out are empty).
+        Bumps that share a level and a sub-pixel offset triple refine to bit-identical sigmas (the DoG values around
+        them are the same numbers), so scale ties of any size can be planted; the Gaussian planes are drawn from `seed`."""
+        rng = np.random.default_rng(seed)
+        self = cls.__new__(cls)
+        self.levels = levels
+        self.dims = list(dims)
+        self.counts = [0] * len(self.dims)
+        self.bumps, self.dog, self.gauss = [], [], []
+        for o, (w, h) in enumerate(self.dims):
+            bt = np.ascontiguousarray(tables.get(o, np.zeros(0, BUMP_DTYPE)), BUMP_DTYPE)
+            if len(bt):
+                if len(set(zip(bt["x"].tolist(), bt["y"].tolist()))) != len(bt):
+                    raise ValueError("octave %d: two bumps at one site" % o)
+                if bt["x"].min() < 1 or bt["x"].max() > w - 2 or bt["y"].min() < 1 or bt["y"].max() > h - 2 or \
+                        bt["z"].min() < 1 or bt["z"].max() > levels:
+                    raise ValueError("octave %d (%d x %d): a bump outside the detectable volume" % (o, w, h))
+            self.bumps.append(bt)
+            self.counts[o] = len(bt)
+            self.dog.append(dog_planes(w, h, bt, levels + 2))
+            self.gauss.append(gauss_planes(w, h, rng, planes=levels + 3))
+        return self
+
     @property
     def total(self):
         return sum(self.counts)
@@ -146,6 +171,35 @@ class Planted:
         got = [tuple(octave_dims(o)) for o in range(n_oct)]
         if got != [tuple(d) for d in self.dims]:
             raise ValueError("planted for octaves %s, the target has %s" % (self.dims, got))
+
+
+BUMP_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("z", np.int32), ("xc", np.float64), ("yc", np.float64),
+                       ("zc", np.float64), ("sign", np.int32)])
+
+
+def bump_table(x, y, z, off, sign=1):
+    """bumps[o] of a Planted from sites (x, y), levels z, sub-pixel offsets off = (n, 3) (dx, dy, dz) and signs"""
+    bt = np.zeros(len(x), BUMP_DTYPE)
+    off = np.asarray(off, np.float64).reshape(len(x), 3)
+    bt["x"], bt["y"], bt["z"], bt["sign"] = x, y, z, sign
+    bt["xc"], bt["yc"], bt["zc"] = bt["x"] + off[:, 0], bt["y"] + off[:, 1], bt["z"] + off[:, 2]
+    return bt
+
+
+def cell_sites(w, h, grid, sift_mode=0, reach=0.31):
+    """the lattice sites of a w x h octave with the grid filter's cell of each (tests/filter_rule.py cell_of) and
+    `inside`: the whole box of +-reach pixels around the site lies in that one cell, so a bump planted there with
+    offsets up to 0.3 is counted in it wherever its centre falls.  Structured: x, y, cell, inside."""
+    from filter_rule import cell_of
+    pts = lattice(w, h, sift_mode)
+    out = np.zeros(len(pts), [("x", np.int32), ("y", np.int32), ("cell", np.int32), ("inside", bool)])
+    out["x"], out["y"] = pts[:, 0], pts[:, 1]
+    out["cell"] = cell_of(out["x"], out["y"], w, h, grid)
+    out["inside"] = True
+    for dx in (-reach, reach):
+        for dy in (-reach, reach):
+            out["inside"] &= cell_of(out["x"] + dx, out["y"] + dy, w, h, grid) == out["cell"]
+    return out
 
 
 def dog_planes(w, h, bumps, n_planes=DOG_PLANES):

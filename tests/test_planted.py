@@ -128,3 +128,37 @@ def test_oracle_finds_exactly_the_planted_extrema_at_levels_9(oracle_mod, sift_m
         assert len(pl.dog[o]) == 11 and len(pl.gauss[o]) == 12
         assert set(bt["z"]) == set(range(1, 10)), o
         assert np.isclose(bt["zc"].min(), 0.7) and np.isclose(bt["zc"].max(), 9.3), o
+
+
+def test_tables_give_the_requested_cells_and_tie_groups(oracle_mod):
+    """Planted.from_tables: bumps on `inside` sites of chosen grid cells with 4 shared offset triples per octave -- the
+    oracle finds exactly the requested number in every cell and exactly triples x levels distinct sigma bit patterns"""
+    O = oracle_mod
+    grid, triples = 3, 4
+    dims = P.octave_dims(O, W, H, OCT)
+    rng = np.random.default_rng(77)
+    want = {0: [40, 0, 25, 31, 60, 1, 17, 0, 33], 1: [12, 9, 0, 20, 15, 12, 0, 3, 14], 2: [3, 4, 5, 0, 6, 3, 4, 5, 3]}
+    tables = {}
+    for o, counts in want.items():
+        cs = P.cell_sites(*dims[o], grid)
+        assert len(cs) == P.capacity(*dims[o]) and cs["inside"].sum() > 0.8 * len(cs)
+        off = rng.uniform(0.05, 0.3, (triples, 3)) * rng.choice([-1.0, 1.0], (triples, 3))
+        at = np.concatenate([rng.permutation(np.flatnonzero((cs["cell"] == c) & cs["inside"]))[:n] for c, n in enumerate(counts)])
+        k = np.arange(len(at)) % triples
+        tables[o] = P.bump_table(cs["x"][at], cs["y"][at], 1 + (np.arange(len(at)) // triples) % P.LEVELS, off[k],
+                                 rng.choice([-1, 1], len(at)))
+    pl = P.Planted.from_tables(dims, tables, seed=3)
+    assert pl.counts == [sum(want[0]), sum(want[1]), sum(want[2]), 0]
+    orc = O.Oracle(O.default_params(filter_grid_size=grid, **P.params_kw(OCT)), threads=4)
+    orc.run(np.zeros((H, W), np.uint8), keypoints=False)
+    pl.load_oracle(orc)
+    _check(pl, orc)
+    e = orc.extrema()
+    for o, counts in want.items():
+        eo = e[e["octave"] == o]
+        assert np.bincount(eo["cell"], minlength=grid * grid).tolist() == counts, o
+        assert len(set(eo["sigma"].view(np.uint32).tolist())) == triples * P.LEVELS, o
+    with pytest.raises(ValueError):
+        P.Planted.from_tables(dims, {0: P.bump_table([5, 5], [9, 9], [1, 2], np.zeros((2, 3)))})
+    with pytest.raises(ValueError):
+        P.Planted.from_tables(dims, {3: P.bump_table([dims[3][0] - 1], [9], [1], np.zeros((1, 3)))})
