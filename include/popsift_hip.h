@@ -208,6 +208,13 @@ int popsift_hip_get_device_info(int device, popsift_hip_device_info* out);
  * reference. */
 int popsift_hip_device_numa_node(int device, int* node);
 
+/* What the pyramid of a w x h image takes under params p, answered without a device: the octaves it gets and the bytes
+ * of one image's plane arena (a batch has one arena per image).  POPSIFT_HIP_ERR_INVALID for parameters a context would
+ * refuse and for an image a submit would refuse: empty after scaling, a side above 32767 pixels after scaling, or an
+ * arena of 4 GiB or more (the detection kernels address the arena with unsigned 32-bit byte offsets); the two outputs
+ * are still filled in where the sizes could be formed.  Either output may be NULL. */
+int popsift_hip_plan_arena(const popsift_hip_params* p, int w, int h, int* n_octaves, int64_t* arena_bytes);
+
 /* Replaces PopSift::configure (popsift.cpp:63-87: init_filter + init_constants)
  * and Pyramid::Pyramid (sift_pyramid.cu:108-165); buffers are sized lazily on
  * the first image and only grow (contrast sift_octave.cu:55-89). */

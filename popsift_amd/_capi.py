@@ -130,6 +130,7 @@ SYMBOLS = [
     ("popsift_hip_device_count", C.c_int, [_ip]),
     ("popsift_hip_get_device_info", C.c_int, [C.c_int, C.POINTER(DeviceInfo)]),
     ("popsift_hip_device_numa_node", C.c_int, [C.c_int, _ip]),
+    ("popsift_hip_plan_arena", C.c_int, [C.POINTER(Params), C.c_int, C.c_int, _ip, C.POINTER(C.c_int64)]),
     ("popsift_hip_ctx_create", C.c_int, [C.c_int, C.POINTER(Params), C.POINTER(_vp)]),
     ("popsift_hip_ctx_destroy", C.c_int, [_vp]),
     ("popsift_hip_get_gauss_table", C.c_int, [_vp, _vp, _vp, _vp, _ip]),
@@ -271,6 +272,15 @@ def default_params(**kw):
             raise AttributeError(k)
         setattr(p, k, v)
     return p
+
+
+def plan_arena(w, h, params=None):
+    """(status, octaves, bytes of one image's plane arena) of a w x h image; needs no GPU.  The status is ERR_INVALID
+    for an image a submit would refuse (empty, a side above 32767 after scaling, an arena of 4 GiB or more)."""
+    p = params if params is not None else default_params()
+    n, b = C.c_int(0), C.c_int64(0)
+    rc = lib().popsift_hip_plan_arena(C.byref(p), w, h, C.byref(n), C.byref(b))
+    return rc, n.value, b.value
 
 
 def device_count():

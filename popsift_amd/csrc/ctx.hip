@@ -324,15 +324,74 @@ void init_tables(popsift_hip_ctx* c)
 }
 
 /* PopSift::private_init, popsift.cpp:89-120 */
-void plan_dims(const popsift_hip_ctx* c, int w, int h, int octaves_cfg, int* n_oct, int* bw, int* bh)
+void plan_dims(const popsift_hip_params& p, int w, int h, int octaves_cfg, int* n_oct, int* bw, int* bh)
 {
-    const float scaleFactor = 1.0f / powf(2.0f, -c->p.upscale_factor);
+    const float scaleFactor = 1.0f / powf(2.0f, -p.upscale_factor);
     int         oct = octaves_cfg;
     if (oct < 0) oct = std::max(int(floorf(logf((float)std::min(w, h)) / logf(2.0f)) - 3.0f + scaleFactor), 1);
     oct = std::min(oct, PS_MAX_OCT);
     *n_oct = oct;
     *bw = (int)ceilf(w * scaleFactor);
     *bh = (int)ceilf(h * scaleFactor);
+}
+
+/* Pyramid::Pyramid, sizes only: the octaves of a w x h image under params p (levels = DoG search levels, L = levels + 3
+ * Gaussian planes, octaves_cfg < 0: as many as the image allows), their planes as float offsets into one arena, the
+ * detection work units and the arena's size in floats.  No device, no context: popsift_hip_plan_arena answers from here
+ * as well.  Returns nullptr, or what is wrong with the geometry. */
+const char* plan_pyramid(const popsift_hip_params& p, int levels, int L, int octaves_cfg, int w, int h, PyrDesc* out,
+                         size_t* arena_floats, int* base_w, int* base_h)
+{
+    int n_oct, bw, bh;
+    memset(out, 0, sizeof(*out));
+    *arena_floats = 0;
+    plan_dims(p, w, h, octaves_cfg, &n_oct, &bw, &bh);
+    *base_w = bw;
+    *base_h = bh;
+    if (bw < 1 || bh < 1) return "scaled image is empty";
+    /* candidates pack (x, y) into 16 bits each; the reference's Plane2D uses short dims too (plane_2d.h:257) */
+    if (bw > 32767 || bh > 32767) return "scaled image exceeds 32767 pixels per side";
+    PyrDesc& pd = *out;
+    size_t   total = 0;
+    pd.n_oct = n_oct;
+    pd.levels = levels;
+    pd.L = L;
+    /* DoG planes are not stored (params.store_dog = 0): detection and refinement subtract the Gaussian planes they
+     * load -- the same f32 subtraction make_dog does (s_pyramid_build.cu:74-92), so results are bit-identical, with a
+     * third fewer bytes per level launch and an octave-0 working set that fits the last-level cache.  An arena then
+     * holds L planes per octave plus ONE scratch plane (the size of octave 0's) into which the debug download forms a
+     * DoG plane on demand; with store_dog = 1 it holds the reference's 2L-1 planes per octave.  Planes are described
+     * by their float offsets from the arena base, the same for every image of a batch (OctDesc::data_off / dog_off;
+     * the absolute pointers of OctDesc are not used). */
+    pd.dog_fly = p.store_dog ? 0 : 1;
+    int ow = bw, oh = bh, tiles = 0;
+    for (int o = 0; o < n_oct; o++) {
+        OctDesc& od = pd.o[o];
+        od.w = ow;
+        od.h = oh;
+        od.pitch = (ow + PITCH_ALIGN - 1) / PITCH_ALIGN * PITCH_ALIGN;
+        od.plane_stride = (int64_t)od.pitch * oh;
+        od.tile_begin = tiles;
+        tiles += extrema_units(ow, oh);
+        od.data_off = (int64_t)total;
+        total += (size_t)od.plane_stride * (size_t)L;
+        if (!pd.dog_fly) {
+            od.dog_off = (int64_t)total;
+            total += (size_t)od.plane_stride * (size_t)(L - 1);
+        }
+        ow = (int)ceilf(ow / 2.0f); /* sift_pyramid.cu:132-133 */
+        oh = (int)ceilf(oh / 2.0f);
+    }
+    if (pd.dog_fly) {
+        for (int o = 0; o < n_oct; o++) pd.o[o].dog_off = (int64_t)total; /* download_plane(kind = 1) only */
+        total += (size_t)pd.o[0].plane_stride;
+    }
+    pd.total_tiles = tiles;
+    *arena_floats = total;
+    /* detection and refinement address a plane element as the arena's base plus an unsigned 32-bit byte offset
+     * (extrema.hip), as the keypoint kernels do within a plane */
+    if (total * sizeof(float) >= ((size_t)1 << 32)) return "pyramid arena of 4 GiB or more: the image is too large";
+    return nullptr;
 }
 
 /* every device allocation of a context goes through here, so that tests can make the n-th one fail */
@@ -423,14 +482,12 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
     int        bw = c->rep.base_w, bh = c->rep.base_h;
     size_t     total = 0;
     if (!same) {
-        int n_oct;
-        plan_dims(c, w, h, c->frozen_octaves, &n_oct, &bw, &bh);
-        if (bw < 1 || bh < 1) return fail(c, POPSIFT_HIP_ERR_INVALID, "scaled image is empty");
-        /* candidates pack (x, y) into 16 bits each; the reference's Plane2D uses short dims too (plane_2d.h:257) */
-        if (bw > 32767 || bh > 32767) return fail(c, POPSIFT_HIP_ERR_INVALID, "scaled image exceeds 32767 pixels per side");
-        if (c->sc.filter_max > 0 && !filter_supported(n_oct, c->sc.max_extrema, c->sc.grid_size))
+        PyrDesc plan;
+        if (const char* why = plan_pyramid(c->p, c->levels, c->L, c->frozen_octaves, w, h, &plan, &total, &bw, &bh))
+            return fail(c, POPSIFT_HIP_ERR_INVALID, why);
+        if (c->sc.filter_max > 0 && !filter_supported(plan.n_oct, c->sc.max_extrema, c->sc.grid_size))
             return fail(c, POPSIFT_HIP_ERR_INVALID, "grid filter: grid size > 64 or octaves * max_extrema >= 2^25");
-        c->frozen_octaves = n_oct; /* popsift.cpp:111: decided by the first image */
+        c->frozen_octaves = plan.n_oct; /* popsift.cpp:111: decided by the first image */
 
         c->in_w = c->in_h = 0;
         c->have_image = false;
@@ -438,41 +495,7 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
         c->ext_cap = 0;
         for (int k = 0; k < PS_MAX_BATCH; k++) c->slot[k].sized = false;
 
-        memset(&pd, 0, sizeof(pd));
-        pd.n_oct = n_oct;
-        pd.levels = c->levels;
-        pd.L = c->L;
-        /* DoG planes are not stored (params.store_dog = 0): detection and refinement subtract the Gaussian planes they
-         * load -- the same f32 subtraction make_dog does (s_pyramid_build.cu:74-92), so results are bit-identical, with a
-         * third fewer bytes per level launch and an octave-0 working set that fits the last-level cache.  An arena then
-         * holds L planes per octave plus ONE scratch plane (the size of octave 0's) into which the debug download forms a
-         * DoG plane on demand; with store_dog = 1 it holds the reference's 2L-1 planes per octave.  Planes are described
-         * by their float offsets from the arena base, the same for every image of a batch (OctDesc::data_off / dog_off;
-         * the absolute pointers of OctDesc are not used). */
-        pd.dog_fly = c->p.store_dog ? 0 : 1;
-        int ow = bw, oh = bh, tiles = 0;
-        for (int o = 0; o < n_oct; o++) {
-            OctDesc& od = pd.o[o];
-            od.w = ow;
-            od.h = oh;
-            od.pitch = (ow + PITCH_ALIGN - 1) / PITCH_ALIGN * PITCH_ALIGN;
-            od.plane_stride = (int64_t)od.pitch * oh;
-            od.tile_begin = tiles;
-            tiles += extrema_units(ow, oh);
-            od.data_off = (int64_t)total;
-            total += (size_t)od.plane_stride * (size_t)c->L;
-            if (!pd.dog_fly) {
-                od.dog_off = (int64_t)total;
-                total += (size_t)od.plane_stride * (size_t)(c->L - 1);
-            }
-            ow = (int)ceilf(ow / 2.0f); /* sift_pyramid.cu:132-133 */
-            oh = (int)ceilf(oh / 2.0f);
-        }
-        if (pd.dog_fly) {
-            for (int o = 0; o < n_oct; o++) pd.o[o].dog_off = (int64_t)total; /* download_plane(kind = 1) only */
-            total += (size_t)pd.o[0].plane_stride;
-        }
-        pd.total_tiles = tiles;
+        pd = plan;
     } else {
         const OctDesc& last = pd.o[pd.n_oct - 1];
         total = pd.dog_fly ? (size_t)pd.o[0].dog_off + (size_t)pd.o[0].plane_stride
@@ -1394,10 +1417,9 @@ int popsift_hip_device_numa_node(int device, int* node)
     return POPSIFT_HIP_OK;
 }
 
-int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_ctx** out)
+/* the parameter ranges a context accepts */
+static int check_params(const popsift_hip_params* p)
 {
-    if (!p || !out) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
     /* gauss_filter.cu:131-144: sigma > 2 or too many levels is fatal in the reference */
     if (!(p->sigma > 0.0f) || p->sigma > 2.0f) return POPSIFT_HIP_ERR_INVALID;
     if (p->levels > POPSIFT_HIP_MAX_LEVELS - 3) return POPSIFT_HIP_ERR_INVALID;
@@ -1413,6 +1435,28 @@ int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_
     if (p->scale_direct != 0 && p->scale_direct != 1) return POPSIFT_HIP_ERR_INVALID;
     if (p->feature_order != POPSIFT_HIP_ORDER_ARRIVAL && p->feature_order != POPSIFT_HIP_ORDER_RASTER)
         return POPSIFT_HIP_ERR_INVALID;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_plan_arena(const popsift_hip_params* p, int w, int h, int* n_octaves, int64_t* arena_bytes)
+{
+    if (!p || w < 1 || h < 1) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = check_params(p)) return rc;
+    const int   levels = std::max(2, p->levels);
+    PyrDesc     pd;
+    size_t      total = 0;
+    int         bw, bh;
+    const char* why = plan_pyramid(*p, levels, levels + 3, p->octaves, w, h, &pd, &total, &bw, &bh);
+    if (n_octaves) *n_octaves = pd.n_oct;
+    if (arena_bytes) *arena_bytes = (int64_t)(total * sizeof(float));
+    return why ? POPSIFT_HIP_ERR_INVALID : POPSIFT_HIP_OK;
+}
+
+int popsift_hip_ctx_create(int device, const popsift_hip_params* p, popsift_hip_ctx** out)
+{
+    if (!p || !out) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc = check_params(p)) return rc;
     if (int rc = check_device(device)) return rc;
 
     popsift_hip_ctx* c = new (std::nothrow) popsift_hip_ctx();

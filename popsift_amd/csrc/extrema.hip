@@ -27,16 +27,36 @@ namespace {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+/* a value every lane of the wave holds identically, moved to scalar registers */
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+/* The float at byte offset `b` behind a wave-uniform `base`.  With an UNSIGNED 32-bit offset the load takes the
+ * scalar-base + vector-offset form and costs no vector instruction; with a 64-bit offset every load pays a 64-bit
+ * vector add of its own.  An arena is below 4 GiB (ctx.hip refuses a larger one). */
+__device__ __forceinline__ float ld_b(const char* base, unsigned int b) { return *(const float*)(base + (size_t)b); }
+
 template <bool FLY>
 struct DogView {
-    const float* base;  /* stored DoG planes, or (fly) the Gaussian planes: DoG(z) = G(z+1) - G(z), the subtraction
-                         * make_dog does (s_pyramid_build.cu:74-92) on the very same f32 values */
-    int64_t      ps;
+    const char*  arena; /* wave-uniform; the lanes' candidates may be of different octaves, so everything else is per lane */
+    unsigned int off;   /* first float of the octave's stored DoG planes, or (fly) of its Gaussian planes: DoG(z) =
+                         * G(z+1) - G(z), the subtraction make_dog does (s_pyramid_build.cu:74-92) on the very same f32
+                         * values.  Float indices into an arena below 4 GiB: 30 bits, and their byte offsets 32. */
+    unsigned int ps;
     int          w, h, pitch, nl; /* nl = number of DoG planes */
+    /* byte offset of float i.  The empty asm keeps it a 32-bit value defined in the block of its load: where the
+     * compiler merges the loads of two branches or moves an address out of refine()'s loop, it widens the offset to
+     * 64 bits away from the load and the scalar-base form is lost. */
+    __device__ __forceinline__ unsigned int byte_off(unsigned int i) const
+    {
+        unsigned int b = 4u * i;
+        asm volatile("" : "+v"(b));
+        return b;
+    }
+    __device__ __forceinline__ float el(unsigned int i) const { return ld_b(arena, byte_off(i)); }
     __device__ __forceinline__ float raw(int x, int y, int z) const /* caller guarantees 0<=x<w, 0<=y<h, 0<=z<nl */
     {
-        const float* q = base + z * ps + (int64_t)y * pitch + x;
-        return FLY ? q[ps] - q[0] : q[0];
+        const unsigned int i = off + (unsigned int)z * ps + (unsigned int)y * (unsigned int)pitch + (unsigned int)x;
+        return FLY ? el(i + ps) - el(i) : el(i);
     }
     __device__ __forceinline__ float at(int x, int y, int z) const
     {
@@ -140,8 +160,8 @@ __device__ bool refine(const DogView<FLY>& dog, const SiftConsts& sc, int x, int
              * plane nl-1 as in DogView::at) */
             const int     zc = clampi(nz, 1, dog.nl - 1);
             const bool    top = (zc + 1 > dog.nl - 1);
-            const float*  g = dog.base + (int64_t)(zc - 1) * dog.ps;
-            const int64_t ps3 = (top ? 2 : 3) * dog.ps; /* Gaussian level zc+2 does not exist when top */
+            const unsigned int g = dog.off + (unsigned int)(zc - 1) * dog.ps;
+            const unsigned int ps3 = (top ? 2u : 3u) * dog.ps; /* Gaussian level zc+2 does not exist when top */
             constexpr int DX[9] = {0, 1, -1, 0, 0, -1, -1, 1, 1}, DY[9] = {0, 0, 0, 1, -1, -1, 1, -1, 1};
             float         g0[5], g1[9], g2[9], g3[5];
             if (nx >= 1 && nx <= width - 2 && ny >= 1 && ny <= height - 2) {
@@ -151,27 +171,27 @@ __device__ bool refine(const DogView<FLY>& dog, const SiftConsts& sc, int x, int
                  * the number of scattered requests its lanes put to the L1 (28 dwords per candidate and iteration before:
                  * 36 us for 150 000 candidates), not by their bytes: 12 requests instead of 28. */
                 struct f3 { float a, b, c; };
-                auto row3 = [](const float* p) -> f3 { f3 v; __builtin_memcpy(&v, p, 12); return v; };
-                const float* c0 = g + (int64_t)ny * dog.pitch + (nx - 1);
-                const float* c1 = c0 + dog.ps;
-                const float* c2 = c1 + dog.ps;
-                const float* c3 = g + ps3 + (int64_t)ny * dog.pitch + (nx - 1);
-                const int    pt = dog.pitch;
+                auto row3 = [&](unsigned int i) -> f3 { f3 v; __builtin_memcpy(&v, dog.arena + (size_t)dog.byte_off(i), 12); return v; };
+                const unsigned int pt = (unsigned int)dog.pitch;
+                const unsigned int c0 = g + (unsigned int)ny * pt + (unsigned int)(nx - 1);
+                const unsigned int c1 = c0 + dog.ps;
+                const unsigned int c2 = c1 + dog.ps;
+                const unsigned int c3 = c0 + ps3;
                 const f3 a0 = row3(c0), a3 = row3(c3);
                 const f3 m1 = row3(c1 - pt), z1 = row3(c1), p1 = row3(c1 + pt);
                 const f3 m2 = row3(c2 - pt), z2 = row3(c2), p2 = row3(c2 + pt);
-                g0[2] = a0.a, g0[0] = a0.b, g0[1] = a0.c, g0[3] = c0[pt + 1], g0[4] = c0[1 - pt];
-                g3[2] = a3.a, g3[0] = a3.b, g3[1] = a3.c, g3[3] = c3[pt + 1], g3[4] = c3[1 - pt];
+                g0[2] = a0.a, g0[0] = a0.b, g0[1] = a0.c, g0[3] = dog.el(c0 + pt + 1), g0[4] = dog.el(c0 + 1 - pt);
+                g3[2] = a3.a, g3[0] = a3.b, g3[1] = a3.c, g3[3] = dog.el(c3 + pt + 1), g3[4] = dog.el(c3 + 1 - pt);
                 g1[2] = z1.a, g1[0] = z1.b, g1[1] = z1.c, g1[6] = p1.a, g1[3] = p1.b, g1[8] = p1.c, g1[5] = m1.a, g1[4] = m1.b, g1[7] = m1.c;
                 g2[2] = z2.a, g2[0] = z2.b, g2[1] = z2.c, g2[6] = p2.a, g2[3] = p2.b, g2[8] = p2.c, g2[5] = m2.a, g2[4] = m2.b, g2[7] = m2.c;
             } else {
 #pragma unroll
                 for (int i = 0; i < 9; i++) {
-                    const int64_t off = (int64_t)ys[DY[i] + 1] * dog.pitch + xs[DX[i] + 1];
-                    if (i < 5) g0[i] = g[off];
-                    g1[i] = g[dog.ps + off];
-                    g2[i] = g[2 * dog.ps + off];
-                    if (i < 5) g3[i] = g[ps3 + off];
+                    const unsigned int e = g + (unsigned int)ys[DY[i] + 1] * (unsigned int)dog.pitch + (unsigned int)xs[DX[i] + 1];
+                    if (i < 5) g0[i] = dog.el(e);
+                    g1[i] = dog.el(e + dog.ps);
+                    g2[i] = dog.el(e + 2u * dog.ps);
+                    if (i < 5) g3[i] = dog.el(e + ps3);
                 }
             }
 #pragma unroll
@@ -346,7 +366,12 @@ struct RowRed {
  * seen outside synthetic stress images; typical is ~50) is handed to the SLOW instantiation of this
  * kernel, which re-does it with a flush per row.
  */
-constexpr int DET_G = 4;   /* rows per load group (2 and 8, and a double-buffered variant, measured no better) */
+#ifndef DET_GROUP
+#define DET_GROUP 4
+#endif
+/* rows per load group.  2 and 8, and a double-buffered variant, measured no better at 161 registers; at 121 (scalar
+ * bases, occupancy 4): 2 rows (85 registers) 853 us per launch of 16 images, 4 rows 842, 6 rows (160 registers) 894 */
+constexpr int DET_G = DET_GROUP;
 constexpr int DET_Q = 512; /* per-wave candidate queue (entries) */
 
 template <int MODE, int LEVELS, bool SLOW, bool FLY>
@@ -373,8 +398,11 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
      * workgroup's 256 columns, the row above and below its 32 rows -- are fetched from HBM once instead of
      * once per XCD. */
     const int wg = SLOW ? (int)blockIdx.x : xcd_run(blockIdx.x, gridDim.x);
-    for (int ui = wg * 4 + (threadIdx.x >> 6); ui < n_units; ui += gridDim.x * 4) {
-        const int unit = SLOW ? ovf[ui] : ui;
+    /* A strip belongs to a wave: its unit, its octave's record, its rows and every plane and row base are the same in
+     * all 64 lanes.  Said so (uniform()), they live in scalar registers, the octave record comes through the scalar
+     * cache, and a lane owns nothing of an address but three byte offsets that hold for the whole strip. */
+    for (int ui = wg * 4 + uniform(threadIdx.x >> 6); ui < n_units; ui += gridDim.x * 4) {
+        const int unit = SLOW ? uniform(ovf[ui]) : ui;
         int       o = 0;
         while (o + 1 < n_oct && unit >= pdp->o[o + 1].tile_begin) o++;
         const OctDesc od = pdp->o[o];
@@ -414,19 +442,32 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
         /* left / centre / right neighbours are three overlapping row loads (same cache lines, the
          * texture path sorts it out) rather than lane shifts: wave-wide DPP shifts turned out to
          * stall the wave for tens of cycles each on gfx950 */
-        const float* base = arena + (FLY ? od.data_off : od.dog_off);
+        const char*   base = (const char*)(arena + (FLY ? od.data_off : od.dog_off));
         constexpr int NRAW = FLY ? 3 * (NP + 1) : 3 * NP; /* FLY: NP + 1 Gaussian planes, subtracted when a row is consumed */
-        const int    xl = max(x - 1, 0), xr = min(x + 1, w - 1);
+        /* a row's byte offset in its plane fits 32 bits (both sides of a plane are below 32768, ctx.hip) */
+        const unsigned int pitch_b = 4u * (unsigned int)od.pitch;
+        const size_t       plane_b = (size_t)od.plane_stride * 4u;
+        /* the lane's part of every address: the byte offsets of its column and of the two beside it.  They pass
+         * through an empty asm at the head of each block that loads with them (pin_cols), so the compiler cannot
+         * widen them to 64 bits once outside the loop: it would then no longer see the scalar-base + 32-bit-offset
+         * pattern where it picks the load. */
+        unsigned int bc = 4u * (unsigned int)xc, bl = 4u * (unsigned int)max(x - 1, 0), br = 4u * (unsigned int)min(x + 1, w - 1);
+#define pin_cols() asm volatile("" : "+v"(bc), "+v"(bl), "+v"(br))
         RowRed<NP>   A, B, C;
         float        vB[NP], smx[NP], smn[NP];
 
         auto fetch_row = [&](int y, float* raw) {
-            const float* p = base + (int64_t)y * od.pitch;
+            const char* p = base + (size_t)((unsigned int)y * pitch_b); /* scalar */
 #pragma unroll
             for (int z = 0; z < NRAW / 3; z++) {
-                raw[3 * z + 0] = p[z * od.plane_stride + xc];
-                raw[3 * z + 1] = p[z * od.plane_stride + xl];
-                raw[3 * z + 2] = p[z * od.plane_stride + xr];
+                const char* pz = p + z * plane_b; /* scalar */
+                raw[3 * z + 0] = ld_b(pz, bc);
+                raw[3 * z + 1] = ld_b(pz, bl);
+                raw[3 * z + 2] = ld_b(pz, br);
+                /* the loads go out in this order: row by row as the rows are consumed, and the three loads of one plane
+                 * row -- the same cache lines -- next to each other.  Left to itself the scheduler groups them by their
+                 * offset register, eight bases at a time: 903 us for a launch of 16 images against 842 (parent 870). */
+                __builtin_amdgcn_sched_barrier(0);
             }
         };
         auto reduce_row = [&](const float* raw, RowRed<NP>& R, float* v, float* sx_, float* sn_) {
@@ -435,6 +476,12 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
                 const float c = FLY ? raw[3 * z + 3] - raw[3 * z + 0] : raw[3 * z + 0];
                 const float l = FLY ? raw[3 * z + 4] - raw[3 * z + 1] : raw[3 * z + 1];
                 const float r = FLY ? raw[3 * z + 5] - raw[3 * z + 2] : raw[3 * z + 2];
+                if (z == 0 || z == NP - 1) {
+                    /* the two outer planes are never searched: only the extremes of (l, c, r) are read, one max3 / min3 */
+                    R.mx[z] = fmaxf(fmaxf(l, r), c);
+                    R.mn[z] = fminf(fminf(l, r), c);
+                    continue;
+                }
                 v[z] = c;
                 sx_[z] = fmaxf(l, r);
                 sn_[z] = fminf(l, r);
@@ -444,17 +491,20 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
         };
         {
             float tv[NP], ts[NP], tn[NP], ra[NRAW], rb[NRAW];
+            pin_cols();
             fetch_row(yb - 1, ra);
             fetch_row(yb, rb);
             reduce_row(ra, A, tv, ts, tn);
             reduce_row(rb, B, vB, smx, smn);
         }
-        /* one row: q holds row y+1 */
+        /* one row: q holds row y+1.  Whether row y takes candidates at all (the strip's last group runs past ye, the
+         * OpenCV mode leaves out 5 border rows) is a scalar condition. */
         auto step = [&](int y, const float* q) {
             float vC[NP], cmx[NP], cmn[NP];
             reduce_row(q, C, vC, cmx, cmn);
-            bool row_ok = lane_ok && (y <= ye);
-            if (MODE == POPSIFT_HIP_SIFT_OPENCV) row_ok = row_ok && (y >= 5 && y < h - 5);
+            bool y_ok = (y <= ye);
+            if (MODE == POPSIFT_HIP_SIFT_OPENCV) y_ok = y_ok && (y >= 5 && y < h - 5);
+            const bool row_ok = lane_ok && y_ok;
             /* full 3x3 extremes of every plane (centre column included) */
             float fmx[NP], fmn[NP];
 #pragma unroll
@@ -496,6 +546,7 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
         if (SLOW) {
             for (int y = yb; y <= ye; y++) {
                 float q[NRAW];
+                pin_cols();
                 fetch_row(y + 1, q);
                 step(y, q);
                 if (n_buf > QCAP - 64 * LEVELS) n_buf = flush(n_buf);
@@ -504,6 +555,7 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
         } else {
             for (int y0 = yb; y0 <= ye; y0 += DET_G) {
                 float q[DET_G][NRAW];
+                pin_cols();
 #pragma unroll
                 for (int k = 0; k < DET_G; k++) fetch_row(min(y0 + k + 1, ye + 1), q[k]);
 #pragma unroll
@@ -516,6 +568,7 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
                 flush(n_buf);
             }
         }
+#undef pin_cols
     }
 }
 
@@ -539,7 +592,7 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
      * planes is in LDS before its record arrives -- the sub-queue sizes and the octaves' geometry -- and its own DoG
      * value is taken from the first iteration's loads (refine()) instead of a round trip of its own: cand -> planes ->
      * solve where it was qcnt -> cand -> octave record -> value -> planes -> solve. */
-    __shared__ int64_t s_off[PS_MAX_OCT], s_ps[PS_MAX_OCT];
+    __shared__ unsigned int s_off[PS_MAX_OCT], s_ps[PS_MAX_OCT]; /* floats: an arena is below 4 GiB (ctx.hip) */
     __shared__ int     s_w[PS_MAX_OCT], s_h[PS_MAX_OCT], s_pitch[PS_MAX_OCT];
     const int      lane = threadIdx.x & 63;
     const int      L = pdp->L, n_oct = pdp->n_oct;
@@ -559,8 +612,8 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
     } else if ((int)threadIdx.x - 64 < n_oct) {
         const int      o = (int)threadIdx.x - 64;
         const OctDesc* od = &pdp->o[o];
-        s_off[o] = FLY ? od->data_off : od->dog_off;
-        s_ps[o] = od->plane_stride;
+        s_off[o] = (unsigned int)(FLY ? od->data_off : od->dog_off);
+        s_ps[o] = (unsigned int)od->plane_stride;
         s_w[o] = od->w;
         s_h[o] = od->h;
         s_pitch[o] = od->pitch;
@@ -587,7 +640,8 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
                 const int  x = cd.x & 0xffff, y = cd.x >> 16, level = cd.y & 0xff;
                 o = cd.y >> 8;
                 DogView<FLY>   dog;
-                dog.base = arena + s_off[o];
+                dog.arena = (const char*)arena;
+                dog.off = s_off[o];
                 dog.ps = s_ps[o];
                 dog.w = s_w[o];
                 dog.h = s_h[o];

@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """Instruction budget of a kernel's hot loop from the compiler's own ISA (no GPU needed).
 
-    tools/isa_count.py [--kernel k_descriptor] [--marker ds_add_u64] [--samples 2] [extra hipcc flags ...]
+    tools/isa_count.py [--src FILE.hip] [--kernel k_descriptor] [--marker ds_add_u64] [--samples 2] [--most] [extra hipcc flags ...]
 
-Compiles popsift_amd/csrc/keypoint.hip for gfx950 with the Makefile's flags plus -gline-tables-only, takes the
+Compiles popsift_amd/csrc/keypoint.hip (or --src FILE.hip) for gfx950 with the Makefile's flags plus -gline-tables-only, takes the
 innermost-but-one loop of <kernel> that contains <marker>, and counts its instructions
   - by kind: VALU (full rate), VALU quarter rate (transcendentals, 32-bit integer multiply), SALU, LDS, VMEM, waits;
   - by source group: the `.loc` line of every instruction is looked up in the `/* ISA: <group> */` markers of the
     source (a marker opens a group that lasts until the next marker or the end of the enclosing lambda / block given
     by `/* ISA: end */`).
 --samples N: the loop body handles N samples (software-pipelined unroll), counts are printed per sample.
+--kernel takes any part of the mangled name that ends where a capital letter follows, so one instance of a template is
+  named by its arguments: k_detectILi0ELi3ELb0ELb1E is k_detect<0, 3, false, true>.
+--most: of the loops that contain <marker>, take the one whose own blocks hold most of them (default: the first in
+  program order).
+The 64-bit vector address arithmetic of the loop (v_lshl_add_u64, v_mad_i64_i32, v_mad_u64_u32, v_add_co_u32 /
+v_addc_co_u32 pairs) is counted on a line of its own: a load with a wave-uniform base and a 32-bit lane offset needs none.
+
+    tools/isa_count.py --src popsift_amd/csrc/extrema.hip --kernel k_detectILi0ELi3ELb0ELb1E --marker global_load --most --samples 4
 """
 import collections
 import os
@@ -24,6 +32,7 @@ SRC = os.path.join(R, "popsift_amd", "csrc", "keypoint.hip")
 #   half rate 2.36 -- compares, v_cndmask, conversions, floor / fract / trunc, min / max / max3, v_bfi, shifts left, v_lshl_add /
 #                     v_add_lshl / v_lshl_or / v_add3, 24- and 32-bit multiplies and multiply-adds
 #   transcendental 4.64 -- sqrt, rcp, rsq, exp, log, sin, cos
+ADDR64 = ("v_lshl_add_u64", "v_mad_i64_i32", "v_mad_u64_u32", "v_add_co_u32", "v_addc_co_u32", "v_lshlrev_b64", "v_ashrrev_i64")
 TRANS = ("v_sqrt_f32", "v_rcp_f32", "v_rsq_f32", "v_exp_f32", "v_log_f32", "v_sin_f32", "v_cos_f32", "v_rcp_iflag_f32")
 FULL = ("v_fma_f32", "v_fmac_f32", "v_fmaak_f32", "v_fmamk_f32", "v_mul_f32", "v_add_f32", "v_sub_f32", "v_subrev_f32",
         "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32", "v_ashrrev_i32", "v_lshrrev_b32", "v_mov_b32",
@@ -43,7 +52,8 @@ def source_groups():
 
 def main():
     a = sys.argv[1:]
-    kernel, marker, samples = "k_descriptor", "ds_add_u64", 2
+    global SRC
+    kernel, marker, samples, most = "k_descriptor", "ds_add_u64", 2, False
     extra = []
     i = 0
     while i < len(a):
@@ -51,6 +61,10 @@ def main():
             kernel = a[i + 1]; i += 2
         elif a[i] == "--marker":
             marker = a[i + 1]; i += 2
+        elif a[i] == "--src":
+            SRC = os.path.abspath(a[i + 1]); i += 2
+        elif a[i] == "--most":
+            most = True; i += 1
         elif a[i] == "--samples":
             samples = int(a[i + 1]); i += 2
         else:
@@ -98,7 +112,14 @@ def main():
     marked = [n for n, b in blocks.items() if any(marker in x for x in b["ins"])]
     if not marked:
         sys.exit("marker %s not found in %s" % (marker, kernel))
-    hdr, depth = header_of(marked[0], blocks[marked[0]])
+    looped = [n for n in marked if header_of(n, blocks[n])[1] > 0]
+    if not looped:
+        sys.exit("marker %s is in no loop of %s" % (marker, kernel))
+    hits = collections.Counter()
+    for n in looped:
+        hits[header_of(n, blocks[n])[0]] += sum(marker in x for x in blocks[n]["ins"])
+    pick = max(looped, key=lambda n: hits[header_of(n, blocks[n])[0]]) if most else looped[0]
+    hdr, depth = header_of(pick, blocks[pick])
     # all blocks of that loop (including deeper child loops whose parent chain mentions the header)
     member = []
     for n, b in blocks.items():
@@ -109,9 +130,10 @@ def main():
     kp_files = set()
     for l in lines:
         m = re.match(r"\s*\.file\s+(\d+)\s+(.*)$", l)
-        if m and "keypoint.hip" in m.group(2):
+        if m and os.path.basename(SRC) in m.group(2):
             kp_files.add(int(m.group(1)))
     kinds = collections.Counter()
+    addr64 = collections.Counter()
     bygroup = collections.defaultdict(collections.Counter)
     loc = 0
     listing = []
@@ -130,6 +152,8 @@ def main():
             if op.startswith("v_"):
                 base = op[:-4] if op.endswith(("_e32", "_e64")) else op
                 base = base.replace("_sdwa", "").replace("_dpp", "")
+                if base in ADDR64:
+                    addr64[base] += 1
                 k = "valu_quarter" if base in TRANS else ("valu" if base in FULL else "valu_half")
             elif op.startswith("s_waitcnt") or op.startswith("s_nop"):
                 k = "wait_nop"
@@ -153,6 +177,8 @@ def main():
     print("per sample: VALU %.1f = %.1f full-rate + %.1f half-rate + %.1f transcendental => %.1f full-rate issue slots;  SALU %.1f  LDS %.1f  VMEM %.1f  waits/nops %.1f"
           % (tot_v / samples, kinds["valu"] / samples, kinds["valu_half"] / samples, kinds["valu_quarter"] / samples, cost / samples,
              kinds["salu"] / samples, kinds["lds"] / samples, kinds["vmem"] / samples, kinds["wait_nop"] / samples))
+    print("64-bit vector address arithmetic in the loop body: %d  (%s)" %
+          (sum(addr64.values()), ", ".join("%s %d" % kv for kv in sorted(addr64.items())) or "none"))
     print("\n%-22s %8s %8s %8s %8s %8s %8s %8s" % ("group (per sample)", "VALU", "half", "transc", "slots", "SALU", "LDS", "VMEM"))
     tv = lambda c: c["valu"] + c["valu_half"] + c["valu_quarter"]
     for g in sorted(bygroup, key=lambda g: -tv(bygroup[g])):

@@ -105,6 +105,30 @@ typedef float v2f __attribute__((ext_vector_type(2)));
         if (threadIdx.x == 0) out[1 + blockIdx.x] = t1 - t0;                                      \
     }
 PKKERNEL(k_pkfma, "v_pk_fma_f32 %0, %1, %1, %0") PKKERNEL(k_pkmul, "v_pk_mul_f32 %0, %1, %0") PKKERNEL(k_pkadd, "v_pk_add_f32 %0, %1, %0")
+// 64-bit address arithmetic on register pairs: what every load with a per-lane 64-bit address pays before it (k_detect
+// and k_refine formed base + offset this way per load until their bases moved to scalar registers)
+typedef unsigned long long u64;
+#define A64KERNEL(NAME, FMT)                                                                                                \
+    __global__ __launch_bounds__(64) void NAME(long long* out, float a, float b)                                             \
+    {                                                                                                                        \
+        u64       p0 = threadIdx.x, p1 = p0 + 1, p2 = p0 + 2, p3 = p0 + 3, p4 = p0 + 4, p5 = p0 + 5, p6 = p0 + 6, p7 = p0 + 7; \
+        const u64 qa = ((u64)__float_as_uint(b) << 32) | __float_as_uint(a);                                                 \
+        const int ia = __float_as_int(a), ib = __float_as_int(b);                                                            \
+        const long long t0 = __builtin_readcyclecounter();                                                                  \
+        for (int it = 0; it < ITERS; it++) {                                                                                 \
+            REP8(asm volatile(FMT(0) "\n" FMT(1) "\n" FMT(2) "\n" FMT(3) "\n" FMT(4) "\n" FMT(5) "\n" FMT(6) "\n" FMT(7)       \
+                              : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3), "+v"(p4), "+v"(p5), "+v"(p6), "+v"(p7)               \
+                              : "v"(qa), "v"(ia), "v"(ib)                                                                    \
+                              : "vcc");)                                                                                     \
+        }                                                                                                                    \
+        const long long t1 = __builtin_readcyclecounter();                                                                  \
+        if (p0 + p1 + p2 + p3 + p4 + p5 + p6 + p7 == 12345678ull) out[0] = 1;                                                \
+        if (threadIdx.x == 0) out[1 + blockIdx.x] = t1 - t0;                                                                 \
+    }
+#define F_LSHLADD64(i) "v_lshl_add_u64 %" #i ", %8, 0, %" #i
+#define F_LSHLADD64S(i) "v_lshl_add_u64 %" #i ", %" #i ", 2, %8"
+#define F_MAD64(i) "v_mad_i64_i32 %" #i ", vcc, %9, %10, %" #i
+A64KERNEL(k_lshl_add64, F_LSHLADD64) A64KERNEL(k_lshl_add64s, F_LSHLADD64S) A64KERNEL(k_mad64, F_MAD64)
 // a typical mix: compare -> select (vcc dependency inside the wave)
 KERNEL(k_cmp_cnd, F_CMP(0), F_CNDM(0), F_CMP(1), F_CNDM(1), F_CMP(2), F_CNDM(2), F_CMP(3), F_CNDM(3))
 KERNEL(k_fma_int, F_FMA(0), F_ADDU(1), F_FMA(2), F_ADDU(3), F_FMA(4), F_ADDU(5), F_FMA(6), F_ADDU(7))
@@ -131,6 +155,7 @@ int main()
         {"v_fract_f32", k_fract}, {"v_trunc_f32", k_trunc}, {"v_cvt_rpi_i32_f32", k_cvtrpi}, {"v_cvt_flr_i32_f32", k_cvtflr},
         {"v_cvt_f32_ubyte0", k_cvtub}, {"v_cndmask_b32 (sgpr mask)", k_cnds}, {"v_bfe_u32", k_bfe}, {"v_mul_u32_u24", k_mulu24},
         {"v_not_b32", k_not}, {"v_med3_f32", k_med3}, {"v_ldexp_f32", k_ldexp}, {"v_mov_b32 dpp quad_perm", k_movdpp},
+        {"v_lshl_add_u64 (shift 0)", k_lshl_add64}, {"v_lshl_add_u64 (shift 2)", k_lshl_add64s}, {"v_mad_i64_i32", k_mad64},
         {"v_pk_fma_f32 (dependent chain)", k_pkfma}, {"v_pk_mul_f32 (dependent chain)", k_pkmul}, {"v_pk_add_f32 (dependent chain)", k_pkadd}};
     const long long n_ins = (long long)ITERS * 64;
     printf("%-30s %s\n", "instruction", "SIMD cycles per wave64 instruction at 1 / 2 / 4 / 8 waves per SIMD");
