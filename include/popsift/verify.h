@@ -1,12 +1,14 @@
 /*
- * popsift/verify.h -- extension: geometric verification of correspondences on the GPU (popsift_hip_ransac and
- * popsift_hip_epipolar, include/popsift_hip.h, which states the rules).  No counterpart in the reference, whose matching demo stops at the
+ * popsift/verify.h -- extension: geometric verification of correspondences on the GPU (popsift_hip_ransac,
+ * popsift_hip_epipolar and popsift_hip_refit, include/popsift_hip.h, which states the rules).  No counterpart in the reference, whose matching demo stops at the
  * descriptor pairs.
  *
  *     std::vector<FeaturesDev::Pair> pairs = l->matchPairs(r, opts);
  *     popsift::Verifier              verifier;
  *     popsift::RansacResult          fit = verifier.ransac(l->pairPoints(r, pairs), popsift::RansacOptions());
  *     popsift::RansacResult          two = verifier.epipolar(l->pairPoints(r, pairs), popsift::EpipolarOptions());
+ *     popsift::RefitResult           best = verifier.refit(l->pairPoints(r, pairs),
+ *                                                          popsift::RefitOptions(fit, popsift::RefitOptions::Homography, 2.0f));
  */
 #pragma once
 
@@ -42,6 +44,33 @@ struct RansacResult {
     std::vector<unsigned char> mask;            /* one byte per pair: 1 = inlier of H */
 };
 
+/* Least squares on the inliers: the model of a minimal sample carries that sample's noise; the refit fits the kind's model
+ * to all inliers of the current model and repeats on the new model's inliers while their number does not drop. */
+struct RefitOptions {
+    enum Kind { Homography = 0, Affine = 1, Epipolar = 2 };
+    Kind  kind = Homography;
+    int   rounds = 4;     /* 1 .. 16 */
+    float maxErr = 2.0f;  /* the kind's inlier limit, as in the call the model came from */
+    float M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; /* the start model, row major */
+
+    RefitOptions() {}
+    /* start from the winner of Verifier::ransac / Verifier::epipolar */
+    RefitOptions(const RansacResult& start, Kind k, float max_err) : kind(k), maxErr(max_err)
+    {
+        for (int i = 0; i < 9; i++) M[i] = start.H[i];
+    }
+};
+
+struct RefitResult {
+    enum Stop { Rounds = 0, Converged = 1, NotBetter = 2, NoFit = 3, NoSupport = 4 };
+    float                      M[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; /* the refitted model, row major */
+    int                        inliers = 0;                        /* >= start */
+    int                        start = 0;                          /* inliers of the start model */
+    int                        rounds = 0;                         /* accepted rounds */
+    Stop                       stop = NoSupport;
+    std::vector<unsigned char> mask;                               /* one byte per pair: 1 = inlier of M */
+};
+
 /* A stream and grow-only scratch on one GPU; one call at a time.  The result is a function of (points, options) alone. */
 class Verifier {
     popsift_hip_verifier* _v;
@@ -59,6 +88,8 @@ public:
     /* the same points; the result's H holds F and its mask the pairs within maxErr of their epipolar lines */
     RansacResult epipolar(const std::vector<float>& pts, const EpipolarOptions& opts);
     RansacResult epipolar(const std::vector<float>& pts) { return epipolar(pts, EpipolarOptions()); }
+    /* the same points and the model to start from */
+    RefitResult refit(const std::vector<float>& pts, const RefitOptions& opts);
 };
 
 }  // namespace popsift

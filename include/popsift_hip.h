@@ -667,6 +667,100 @@ int  popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n
                                 int32_t* samples, float* models, int32_t* counts);
 
 /*
+ * Least-squares refit on the inliers (the step OpenCV's findHomography / findFundamentalMat take after their RANSAC, and
+ * LO-RANSAC repeats): popsift_hip_ransac and popsift_hip_epipolar return a model solved from a minimal sample, which carries
+ * the noise of those 3, 4 or 8 pairs.  popsift_hip_refit starts from such a model M (or any other), fits the kind's model to
+ * ALL inliers of the current model by the normal equations in double, and repeats on the new model's inliers for up to
+ * `rounds` rounds, as long as the inlier count does not drop.  A third kind of call on the verifier: the two above, their
+ * options, records and bytes do not change, and calls of all kinds may alternate on one verifier.  The result is a function
+ * of (points, options) alone.  m = 4 (homography), 3 (affine map) or 8 (epipolar) pairs; every line one IEEE operation, fma /
+ * fmaf fused:
+ *
+ * 1. Normalise.  Step 2 of popsift_hip_ransac over all n pairs: (cx, cy, k) left, (cx', cy', s', k') right.
+ * 2. Start.  cur = M; c_cur = the number of inliers of cur under the kind's test, operation for operation: step 4 of
+ *    popsift_hip_ransac (homography, affine map), step 6 of popsift_hip_epipolar (epipolar).  n_start = c_cur.  c_cur < m:
+ *    stop with NO_SUPPORT.
+ * 3. Round r = 0 .. rounds - 1:
+ *    a. Terms, of the pairs that are inliers of cur only, from the normalised doubles (x, y) -> (u, v) of step 1.  45 slots;
+ *       a slot a kind does not list is the constant +0.0.
+ *       Homography -- the normal equations of the rows a = [x y 1 0 0 0 p6 p7 | u], b = [0 0 0 x y 1 q6 q7 | v] of step 3
+ *       of popsift_hip_ransac, p6 = (-u) * x, p7 = (-u) * y, q6 = (-v) * x, q7 = (-v) * y; N[j][k] = sum a_j a_k + b_j b_k,
+ *       c[j] = sum a_j u + b_j v, a term with one structurally non-zero product is that product:
+ *         0 x*x   1 x*y   2 x   3 y*y   4 y   5 1.0          N00 N01 N02 N11 N12 N22, and N[3+j][3+k] = N[j][k], formed once
+ *         6 x*p6  7 x*p7  8 y*p6  9 y*p7  10 p6  11 p7       N06 N07 N16 N17 N26 N27
+ *         12 x*q6 13 x*q7 14 y*q6 15 y*q7 16 q6  17 q7       N36 N37 N46 N47 N56 N57
+ *         18 fma(p6, p6, q6*q6)  19 fma(p6, p7, q6*q7)  20 fma(p7, p7, q7*q7)       N66 N67 N77
+ *         21 x*u  22 y*u  23 u  24 x*v  25 y*v  26 v  27 fma(p6, u, q6*v)  28 fma(p7, u, q7*v)       c0 .. c7
+ *       N[j][3+k] = 0 for j, k < 3.  Affine map -- slots 0 .. 5 and 21 .. 26 of the above: the 3 x 3 matrix of [x y 1] and its
+ *       two right-hand sides.  Epipolar -- the row a = [u*x, u*y, u, v*x, v*y, v, x, y, 1.0] of step 3 of
+ *       popsift_hip_epipolar; slot 9j - j(j-1)/2 + (k - j) = a_j * a_k for j <= k: the upper triangle of the 9 x 9 N, row by
+ *       row.
+ *    b. Sum.  Each slot is the root of a pairwise tree over the pair index: tree(a, 1) = term + 0.0 for a pair a < n that
+ *       is an inlier of cur (so a term of -0.0 enters as +0.0), else +0.0; tree(a, 2L) = tree(a, L) + tree(a + L, L); the
+ *       root is tree(0, P), P the smallest power of two >= n.  No node is -0.0, so adding +0.0 changes no bit: padding
+ *       further, or not at all, gives the same root.  The order is a function of the index alone, not of a launch shape.
+ *    c. Solve, in double.  N is mirrored.  Homography: the 8 x 8 system [N | c] by the elimination, back substitution and
+ *       denormalisation of step 3 of popsift_hip_ransac, unchanged.  Affine map: the 3 x 3 system with its two right-hand
+ *       sides, the same way.  Epipolar: eight steps k = 0 .. 7 of the complete-pivoting elimination of step 3 of
+ *       popsift_hip_epipolar on the 9 x 9 N, rows k .. 8 and columns k .. 8 in the search (the same order: columns, within a
+ *       column rows, '>' decides) and in the update, column swaps in all nine rows; row 8 is then dropped, z[8] = 1, back
+ *       substitution and f[perm[j]] = z[j] as there: the least-squares F with the coefficient the pivoting leaves over fixed
+ *       to 1.  Then that rule's rank-2 step 4 and its denormalisation and scaling step 5.  The nine values rounded to float
+ *       are the candidate.  It is invalid iff a pivot is exactly 0, the scaling divisor is 0 or a value is not finite: stop
+ *       with NO_FIT.
+ *    d. Decide.  c' = the inlier count of the candidate (step 2's test).  The candidate equals cur as bytes: stop with
+ *       CONVERGED.  c' < c_cur: stop with NOT_BETTER.  Otherwise cur = candidate, c_cur = c', the round is accepted.
+ * 4. No stop in `rounds` rounds: stop = ROUNDS.
+ * 5. Result: M = cur, n_inliers = c_cur, n_start, rounds = the accepted rounds, stop, and the mask of cur.  Hence
+ *    n_inliers >= n_start, and a start model the fit cannot improve comes back unchanged.
+ *
+ * ERR_INVALID, before any GPU call: a NULL verifier, opts or result; pts NULL with n > 0; n < 0 or n > 2^24; an unknown model;
+ * rounds outside 1 .. 16; max_err not finite or <= 0; an entry of M that is not finite; reserved != 0.  n < m: OK, answered
+ * on the host: M = the caller's M, n_inliers = n_start = rounds = 0, stop = NO_SUPPORT, the mask zeros.
+ *
+ * A call is one upload of the points, every launch of every round enqueued up front (ransac.hip: a state record on the
+ * device carries cur, c_cur and a `done` flag that the later rounds' kernels read and return on), one download and one
+ * synchronisation.  The accumulating kernel gives a workgroup POPSIFT_HIP_REFIT_CHUNK pairs; results do not depend on it.
+ *
+ * popsift_hip_refit_trace is the parity hook: the same call, returning for each of opts->rounds rounds its 45 sums, its
+ * candidate (zeros when invalid), c' (-1 when invalid) and whether it was accepted; a round that did not run is zeros with
+ * count -1.  Any of the four may be NULL.
+ */
+enum { POPSIFT_HIP_REFIT_HOMOGRAPHY = 0, POPSIFT_HIP_REFIT_AFFINE = 1, POPSIFT_HIP_REFIT_EPIPOLAR = 2 };
+enum {
+    POPSIFT_HIP_REFIT_STOP_ROUNDS = 0,      /* every round ran and was accepted                        */
+    POPSIFT_HIP_REFIT_STOP_CONVERGED = 1,   /* a round returned the model it started from              */
+    POPSIFT_HIP_REFIT_STOP_NOT_BETTER = 2,  /* a round's candidate has fewer inliers                   */
+    POPSIFT_HIP_REFIT_STOP_NO_FIT = 3,      /* a round's system is singular or its solution not finite */
+    POPSIFT_HIP_REFIT_STOP_NO_SUPPORT = 4   /* the start model has fewer than m inliers                */
+};
+#define POPSIFT_HIP_REFIT_CHUNK 1024
+#define POPSIFT_HIP_REFIT_MAX_ROUNDS 16
+#define POPSIFT_HIP_REFIT_SLOTS 45
+typedef struct popsift_hip_refit_opts {     /* 64 bytes */
+    int32_t model;         /* POPSIFT_HIP_REFIT_*                                         */
+    int32_t rounds;        /* 1 .. POPSIFT_HIP_REFIT_MAX_ROUNDS                           */
+    float   max_err;       /* the kind's inlier limit (px), as in the call M came from    */
+    float   M[9];          /* the start model, row major                                  */
+    int32_t reserved[4];   /* must be 0 */
+} popsift_hip_refit_opts;
+typedef struct popsift_hip_refit_result {   /* 52 bytes */
+    float   M[9];          /* the refitted model, row major                               */
+    int32_t n_inliers;
+    int32_t n_start;       /* inliers of the start model                                  */
+    int32_t rounds;        /* accepted rounds                                             */
+    int32_t stop;          /* POPSIFT_HIP_REFIT_STOP_*                                    */
+} popsift_hip_refit_result;
+void popsift_hip_default_refit_opts(popsift_hip_refit_opts* o);   /* {HOMOGRAPHY, 4, 2.0f, identity, {0, 0, 0, 0}} */
+/* pts, inlier: as popsift_hip_ransac */
+int  popsift_hip_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
+                       popsift_hip_refit_result* res, uint8_t* inlier);
+/* sums: rounds x 45 doubles, models: rounds x 9, counts: rounds, accepted: rounds; any may be NULL */
+int  popsift_hip_refit_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
+                             popsift_hip_refit_result* res, uint8_t* inlier, double* sums, float* models, int32_t* counts,
+                             int32_t* accepted);
+
+/*
  * Guided matching: nearest neighbours under a known model (the expectation SiftGPU's GetGuidedSiftMatch(.., H, F, distmax,
  * ratiomax, hsearch_thresh, fsearch_thresh, mutual) sets).  With the homography or the fundamental matrix of an image pair
  * known -- from popsift_hip_ransac / popsift_hip_epipolar, or from anywhere else -- each left descriptor is searched for only

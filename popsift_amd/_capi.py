@@ -88,6 +88,12 @@ class EpipolarOpts(C.Structure):
     _fields_ = [("hypotheses", C.c_int32), ("max_err", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_int32 * 3)]
 
 
+class RefitOpts(C.Structure):
+    """popsift_hip_refit_opts"""
+    _fields_ = [("model", C.c_int32), ("rounds", C.c_int32), ("max_err", C.c_float), ("M", C.c_float * 9),
+                ("reserved", C.c_int32 * 4)]
+
+
 FEATURE_DTYPE = np.dtype([
     ("debug_octave", np.int32), ("xpos", np.float32), ("ypos", np.float32),
     ("sigma", np.float32), ("num_ori", np.int32),
@@ -100,6 +106,15 @@ PAIR_DTYPE = np.dtype([("l", np.int32), ("r", np.int32), ("dist_best", np.float3
 # popsift_hip_ransac_result: what Verifier.ransac returns beside the mask
 RANSAC_RESULT_DTYPE = np.dtype([("H", np.float32, (9,)), ("n_inliers", np.int32), ("hypothesis", np.int32),
                                 ("n_valid", np.int32), ("reserved", np.int32)])
+# popsift_hip_refit_result: what Verifier.refit returns beside the mask
+REFIT_RESULT_DTYPE = np.dtype([("M", np.float32, (9,)), ("n_inliers", np.int32), ("n_start", np.int32), ("rounds", np.int32),
+                               ("stop", np.int32)])
+REFIT_HOMOGRAPHY, REFIT_AFFINE, REFIT_EPIPOLAR = 0, 1, 2     # POPSIFT_HIP_REFIT_*: the kind of model of Verifier.refit
+REFITS = {"homography": REFIT_HOMOGRAPHY, "affine": REFIT_AFFINE, "epipolar": REFIT_EPIPOLAR}
+# POPSIFT_HIP_REFIT_STOP_*: why Verifier.refit stopped
+REFIT_STOP_ROUNDS, REFIT_STOP_CONVERGED, REFIT_STOP_NOT_BETTER, REFIT_STOP_NO_FIT, REFIT_STOP_NO_SUPPORT = range(5)
+# POPSIFT_HIP_REFIT_*: pairs per workgroup of the accumulating kernel, the most rounds, sums per round of the trace
+REFIT_CHUNK, REFIT_MAX_ROUNDS, REFIT_SLOTS = 1024, 16, 45
 MODEL_HOMOGRAPHY, MODEL_AFFINE = 0, 1
 MODELS = {"homography": MODEL_HOMOGRAPHY, "affine": MODEL_AFFINE}
 RANSAC_CHUNK, RANSAC_HYP_BLOCK = 1024, 64  # POPSIFT_HIP_RANSAC_*: pairs / hypotheses per workgroup of the scoring kernel
@@ -191,6 +206,9 @@ SYMBOLS = [
     ("popsift_hip_default_epipolar_opts", None, [C.POINTER(EpipolarOpts)]),
     ("popsift_hip_epipolar", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp]),
     ("popsift_hip_epipolar_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(EpipolarOpts), _vp, _vp, _vp]),
+    ("popsift_hip_default_refit_opts", None, [C.POINTER(RefitOpts)]),
+    ("popsift_hip_refit", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RefitOpts), _vp, _vp]),
+    ("popsift_hip_refit_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RefitOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
     ("popsift_hip_default_guided_opts", None, [C.POINTER(GuidedOpts)]),
     ("popsift_hip_match_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp]),
     ("popsift_hip_match_pairs_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp, C.c_size_t, _ip]),
@@ -543,6 +561,21 @@ def epipolar_opts(hypotheses=None, max_err=None, seed=None):
     return o
 
 
+def refit_opts(model="homography", M=None, max_err=None, rounds=None):
+    """popsift_hip_refit_opts: the library's defaults with the given fields replaced; model by name or number, M any array
+    of nine numbers in row-major order"""
+    o = RefitOpts()
+    lib().popsift_hip_default_refit_opts(C.byref(o))
+    o.model = REFITS.get(model, model)
+    if M is not None:
+        o.M[:] = [float(v) for v in np.asarray(M, np.float32).reshape(9)]
+    if max_err is not None:
+        o.max_err = max_err
+    if rounds is not None:
+        o.rounds = rounds
+    return o
+
+
 class Verifier:
     """popsift_hip_verifier: RANSAC over point pairs on one GPU (a stream and grow-only scratch; one call at a time)."""
 
@@ -615,6 +648,39 @@ class Verifier:
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_epipolar_trace")
         return samples, models, counts
+
+    def refit(self, pts, model="homography", M=None, max_err=None, rounds=None, want_mask=True):
+        """popsift_hip_refit -> (result, mask): the model M (of ransac() / epipolar(), or any other) fitted by least squares
+        to its inliers, for up to `rounds` rounds; result a REFIT_RESULT_DTYPE record (M row major, n_inliers, n_start,
+        rounds, stop), mask n bytes (None with want_mask=False)"""
+        pts = self._points(pts)
+        n = len(pts)
+        res = np.zeros(1, REFIT_RESULT_DTYPE)
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        o = refit_opts(model, M, max_err, rounds)
+        rc = lib().popsift_hip_refit(self._h, pts.ctypes.data if n else None, n, C.byref(o), res.ctypes.data,
+                                     mask.ctypes.data if want_mask and n else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_refit")
+        return res[0], mask
+
+    def refit_trace(self, pts, model="homography", M=None, max_err=None, rounds=None):
+        """popsift_hip_refit_trace -> (result, mask, sums (rounds, 45) float64, models (rounds, 9) float32, counts (rounds,)
+        int32, accepted (rounds,) int32)"""
+        pts = self._points(pts)
+        n = len(pts)
+        res = np.zeros(1, REFIT_RESULT_DTYPE)
+        mask = np.zeros(n, np.uint8)
+        o = refit_opts(model, M, max_err, rounds)
+        R = max(int(o.rounds), 0)
+        sums, models = np.zeros((R, REFIT_SLOTS), np.float64), np.zeros((R, 9), np.float32)
+        counts, accepted = np.zeros(R, np.int32), np.zeros(R, np.int32)
+        rc = lib().popsift_hip_refit_trace(self._h, pts.ctypes.data if n else None, n, C.byref(o), res.ctypes.data,
+                                           mask.ctypes.data if n else None, sums.ctypes.data, models.ctypes.data,
+                                           counts.ctypes.data, accepted.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_refit_trace")
+        return res[0], mask, sums, models, counts, accepted
 
     def close(self):
         if self._h:

@@ -18,10 +18,21 @@
  *   k_ransac_select   arg-max under (count, -t) in one workgroup, writes the result record
  *   k_ransac_mask     the winner's inlier bytes, four pairs per lane
  *   k_pair_points     (x, y, x', y') of descriptor pairs through the sets' descriptor -> feature maps
+ *
+ * popsift_hip_refit, the least-squares refit of such a model on its inliers (tests/refit_ref.c), enqueues all its rounds up
+ * front; a state record on the device carries the current model and a `done` flag between them:
+ *
+ *   k_refit_init        the state record from the caller's model
+ *   k_refit_count       the inliers of one model, by ballots and one integer atomic per wave
+ *   k_refit_accumulate  the terms of the normal equations over the current model's inliers in float64, summed as a
+ *                       pairwise tree over the pair index up to one block of sums per chunk of 1024 pairs
+ *   k_refit_solve       the rest of the tree over the chunks, then one lane solves and writes the round's candidate
+ *   k_refit_decide      accept the candidate or stop
  */
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <new>
 
@@ -608,6 +619,431 @@ __global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts
     mask[q] = word;
 }
 
+/* ---- popsift_hip_refit: least squares on the inliers, every round enqueued up front.  The state record starts like a
+ * popsift_hip_ransac_result, so that k_ransac_mask writes the final mask from it. */
+
+constexpr int F_SLOTS = POPSIFT_HIP_REFIT_SLOTS;
+constexpr int F_ROUNDS = POPSIFT_HIP_REFIT_MAX_ROUNDS;
+constexpr int F_CHUNK = POPSIFT_HIP_REFIT_CHUNK;
+static_assert(F_CHUNK == 256 * 4, "a chunk is 256 lanes x 4 consecutive pairs");
+
+struct RefitState {
+    float H[9];       /* cur */
+    int   n_inliers;  /* c_cur; the start count is added up here */
+    int   hypothesis; /* 0: k_ransac_mask takes the record for a winner */
+    int   n_start, rounds, stop;
+    int   done;       /* the kernels of the rounds still enqueued return at once */
+    int   pad;
+};
+static_assert(sizeof(RefitState) == 64 && offsetof(RefitState, n_inliers) == offsetof(popsift_hip_ransac_result, n_inliers) &&
+                  offsetof(RefitState, hypothesis) == offsetof(popsift_hip_ransac_result, hypothesis),
+              "the front of the state is a popsift_hip_ransac_result");
+
+/* the trace of a call, one block on the device and in the pinned buffer */
+struct RefitTrace {
+    double sums[F_ROUNDS][F_SLOTS];
+    float  models[F_ROUNDS][9];
+    int    counts[F_ROUNDS];
+    int    accepted[F_ROUNDS];
+};
+
+template <int KIND> struct RefitKind;
+template <> struct RefitKind<POPSIFT_HIP_REFIT_HOMOGRAPHY> { typedef Transfer Rule; static constexpr int slots = 29, m = 4; };
+template <> struct RefitKind<POPSIFT_HIP_REFIT_AFFINE> { typedef Transfer Rule; static constexpr int slots = 12, m = 3; };
+template <> struct RefitKind<POPSIFT_HIP_REFIT_EPIPOLAR> { typedef Sampson Rule; static constexpr int slots = 45, m = 8; };
+
+struct RefitStart {
+    float M[9];
+};
+
+/* one lane: cur = M, the counters of the trace to "did not run" (the rest of the trace is zeroed by a memset) */
+__global__ __launch_bounds__(64) void k_refit_init(RefitStart start, RefitState* __restrict__ st, RefitTrace* __restrict__ tr)
+{
+    if (threadIdx.x != 0) return;
+    for (int i = 0; i < 9; i++) st->H[i] = start.M[i];
+    st->n_inliers = 0;
+    st->hypothesis = 0;
+    st->n_start = 0;
+    st->rounds = 0;
+    st->stop = POPSIFT_HIP_REFIT_STOP_ROUNDS;
+    st->done = 0;
+    st->pad = 0;
+    for (int r = 0; r < F_ROUNDS; r++) tr->counts[r] = -1;
+}
+
+/* the inliers of one model among all pairs, four per lane; an invalid candidate is all zeros and counts nothing */
+template <class Rule>
+__global__ __launch_bounds__(256) void k_refit_count(const v4f* __restrict__ pts, int n, const float* __restrict__ model,
+                                                     float max_err2, int* __restrict__ counter, const int* __restrict__ done)
+{
+    if (*done) return;
+    float H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) H[i] = model[i];
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    int       c = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int  i = 4 * q + r;
+        const bool in = i < n && Rule::inlier(H, pts[i < n ? i : 0], max_err2);
+        c += __popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63) == 0 && c != 0) atomicAdd(counter, c);
+}
+
+/* rule 3a: the terms of one pair, +0.0 for a pair that is no inlier; t + 0.0 turns a term of -0.0 into +0.0 */
+template <int KIND>
+__device__ __forceinline__ void refit_terms(v4f p, bool in, const Norm& L, const Norm& Rn, double (&t)[RefitKind<KIND>::slots])
+{
+    const double x = ((double)p[0] - L.cx) * L.k;
+    const double y = ((double)p[1] - L.cy) * L.k;
+    const double u = ((double)p[2] - Rn.cx) * Rn.k;
+    const double v = ((double)p[3] - Rn.cy) * Rn.k;
+    if (KIND == POPSIFT_HIP_REFIT_EPIPOLAR) {
+        const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
+        int          s = 0;
+#pragma unroll
+        for (int j = 0; j < 9; j++) {
+#pragma unroll
+            for (int k = j; k < 9; k++) t[s++] = a[j] * a[k];
+        }
+    } else {
+        t[0] = x * x; t[1] = x * y; t[2] = x; t[3] = y * y; t[4] = y; t[5] = 1.0;
+        constexpr int c0 = KIND == POPSIFT_HIP_REFIT_AFFINE ? 6 : 21; /* the affine map's right-hand sides follow its matrix */
+        t[c0] = x * u; t[c0 + 1] = y * u; t[c0 + 2] = u; t[c0 + 3] = x * v; t[c0 + 4] = y * v; t[c0 + 5] = v;
+        if (KIND == POPSIFT_HIP_REFIT_HOMOGRAPHY) {
+            const double p6 = -u * x, p7 = -u * y, q6 = -v * x, q7 = -v * y;
+            t[6] = x * p6; t[7] = x * p7; t[8] = y * p6; t[9] = y * p7; t[10] = p6; t[11] = p7;
+            t[12] = x * q6; t[13] = x * q7; t[14] = y * q6; t[15] = y * q7; t[16] = q6; t[17] = q7;
+            t[18] = fma(p6, p6, q6 * q6);
+            t[19] = fma(p6, p7, q6 * q7);
+            t[20] = fma(p7, p7, q7 * q7);
+            t[27] = fma(p6, u, q6 * v);
+            t[28] = fma(p7, u, q7 * v);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < RefitKind<KIND>::slots; j++) t[j] = in ? t[j] + 0.0 : 0.0;
+}
+
+/* where register j of a kind's sums lies among the 45 slots: only the affine map's right-hand sides move */
+template <int KIND>
+__device__ __forceinline__ constexpr int refit_slot(int j)
+{
+    return KIND == POPSIFT_HIP_REFIT_AFFINE && j >= 6 ? j + 15 : j;
+}
+
+/* the sum of one value per lane over the workgroup's 256 lanes in the order of the tree: xor 1, 2, .. 32 inside a wave,
+ * then (w0 + w1) + (w2 + w3); valid in the first SLOTS lanes as out[lane].  s_wave: [4][SLOTS] */
+template <int SLOTS>
+__device__ __forceinline__ double refit_block_tree(double (&v)[SLOTS], double (*s_wave)[SLOTS])
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < SLOTS; j++) {
+#pragma unroll
+        for (int d = 1; d <= 32; d <<= 1) v[j] = v[j] + __shfl_xor(v[j], d);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < SLOTS; j++) s_wave[wave][j] = v[j];
+    }
+    __syncthreads();
+    double r = 0.0;
+    if ((int)threadIdx.x < SLOTS) {
+        const int j = threadIdx.x;
+        r = (s_wave[0][j] + s_wave[1][j]) + (s_wave[2][j] + s_wave[3][j]);
+    }
+    return r;
+}
+
+/* rules 3a and 3b up to a chunk: one workgroup per F_CHUNK pairs, a lane takes 4 consecutive pairs; blocks[j * chunks +
+ * chunk] = tree(chunk * F_CHUNK, F_CHUNK) of the kind's register j */
+template <int KIND>
+__global__ __launch_bounds__(256) void k_refit_accumulate(const v4f* __restrict__ pts, int n, const uint32_t* __restrict__ bounds,
+                                                          const RefitState* __restrict__ st, float max_err2,
+                                                          double* __restrict__ blocks)
+{
+    typedef RefitKind<KIND> K;
+    constexpr int    S = K::slots;
+    __shared__ double s_wave[4][S];
+    if (st->done) return; /* the same in every lane */
+    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    float      H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) H[i] = st->H[i];
+    const int i0 = blockIdx.x * F_CHUNK + 4 * threadIdx.x;
+    double    acc[S];
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        double t0[S], t1[S];
+        const int  ia = i0 + 2 * half, ib = ia + 1;
+        const v4f  pa = pts[ia < n ? ia : 0], pb = pts[ib < n ? ib : 0];
+        refit_terms<KIND>(pa, ia < n && K::Rule::inlier(H, pa, max_err2), L, Rn, t0);
+        refit_terms<KIND>(pb, ib < n && K::Rule::inlier(H, pb, max_err2), L, Rn, t1);
+#pragma unroll
+        for (int j = 0; j < S; j++) {
+            const double s = t0[j] + t1[j];
+            acc[j] = half == 0 ? s : acc[j] + s;
+        }
+    }
+    const double r = refit_block_tree<S>(acc, s_wave);
+    if ((int)threadIdx.x < S) blocks[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = r;
+}
+
+/* rule 3c for the homography and the affine map: partial pivoting on the R x (R + NB) system in LDS, one lane */
+__device__ bool refit_eliminate(double (*a)[10], int R, int NB)
+{
+    const int C = R + NB;
+    bool      ok = true;
+    for (int c = 0; c < R; c++) {
+        int    p = c;
+        double best = fabs(a[c][c]);
+        for (int r = c + 1; r < R; r++) {
+            const double v = fabs(a[r][c]);
+            if (v > best) {
+                best = v;
+                p = r;
+            }
+        }
+        if (p != c)
+            for (int j = 0; j < C; j++) {
+                const double tmp = a[c][j];
+                a[c][j] = a[p][j];
+                a[p][j] = tmp;
+            }
+        ok = ok && !(a[c][c] == 0.0);
+        for (int r = c + 1; r < R; r++) {
+            const double f = a[r][c] / a[c][c];
+            for (int j = c + 1; j < C; j++) a[r][j] = fma(-f, a[c][j], a[r][j]);
+        }
+    }
+    for (int b = 0; b < NB; b++)
+        for (int i = R - 1; i >= 0; i--) {
+            double s = a[i][R + b];
+            for (int j = i + 1; j < R; j++) s = fma(-a[i][j], a[j][R + b], s);
+            a[i][R + b] = s / a[i][i];
+        }
+    return ok;
+}
+
+/* rule 3c for the epipolar kind: eight steps of complete pivoting on the 9 x 9 matrix in LDS; f in column 9 of a */
+__device__ bool refit_null_vector(double (*a)[10], int* perm)
+{
+    bool ok = true;
+    for (int j = 0; j < 9; j++) perm[j] = j;
+    for (int k = 0; k < 8; k++) {
+        int    pr = k, pc = k;
+        double best = fabs(a[k][k]);
+        for (int c = k; c < 9; c++)
+            for (int r = k; r < 9; r++) {
+                const double v = fabs(a[r][c]);
+                if (v > best) {
+                    best = v;
+                    pr = r;
+                    pc = c;
+                }
+            }
+        if (pr != k)
+            for (int j = 0; j < 9; j++) {
+                const double tmp = a[k][j];
+                a[k][j] = a[pr][j];
+                a[pr][j] = tmp;
+            }
+        if (pc != k) {
+            for (int r = 0; r < 9; r++) {
+                const double tmp = a[r][k];
+                a[r][k] = a[r][pc];
+                a[r][pc] = tmp;
+            }
+            const int tmp = perm[k];
+            perm[k] = perm[pc];
+            perm[pc] = tmp;
+        }
+        ok = ok && !(a[k][k] == 0.0);
+        for (int r = k + 1; r < 9; r++) {
+            const double q = a[r][k] / a[k][k];
+            for (int j = k + 1; j < 9; j++) a[r][j] = fma(-q, a[k][j], a[r][j]);
+        }
+    }
+    /* row 8 is dropped; z in row 8, then f[perm[j]] = z[j] into column 9 */
+    a[8][8] = 1.0;
+    for (int i = 7; i >= 0; i--) {
+        double s = -a[i][8];
+        for (int j = i + 1; j < 8; j++) s = fma(-a[i][j], a[8][j], s);
+        a[8][i] = s / a[i][i];
+    }
+    for (int j = 0; j < 9; j++) a[perm[j]][9] = a[8][j];
+    return ok;
+}
+
+/* rule 3b above the chunks, then rule 3c on one lane.  One workgroup.  blocks: [slot][chunks] as k_refit_accumulate left
+ * them; spare: room for [slot][(chunks + 1) / 2], used when there are more than 256 chunks */
+template <int KIND>
+__global__ __launch_bounds__(256) void k_refit_solve(double* blocks, double* spare, int chunks,
+                                                     const uint32_t* __restrict__ bounds, const RefitState* __restrict__ st,
+                                                     RefitTrace* __restrict__ tr, int round)
+{
+    typedef RefitKind<KIND> K;
+    constexpr int    S = K::slots;
+    __shared__ double s_wave[4][S];
+    __shared__ double s_sum[F_SLOTS];
+    __shared__ double s_a[9][10];
+    __shared__ int    s_perm[9];
+    if (st->done) return;
+    /* level by level, pairs (2i, 2i + 1) of chunk sums, until one value per lane is left */
+    double* src = blocks;
+    double* dst = spare;
+    int     cnt = chunks, stride = chunks;
+    while (cnt > 256) {
+        const int half = (cnt + 1) / 2;
+        for (int e = threadIdx.x; e < S * half; e += 256) {
+            const int     j = e / half, i = e - j * half;
+            const double* p = src + (size_t)j * stride;
+            dst[(size_t)j * half + i] = p[2 * i] + (2 * i + 1 < cnt ? p[2 * i + 1] : 0.0);
+        }
+        __syncthreads(); /* the next level reads what other lanes of this workgroup wrote */
+        double* const tmp = src;
+        src = dst;
+        dst = tmp;
+        cnt = stride = half;
+    }
+    double v[S];
+#pragma unroll
+    for (int j = 0; j < S; j++) v[j] = (int)threadIdx.x < cnt ? src[(size_t)j * stride + threadIdx.x] : 0.0;
+    const double r = refit_block_tree<S>(v, s_wave);
+    if (threadIdx.x < F_SLOTS) s_sum[threadIdx.x] = 0.0;
+    __syncthreads();
+    if ((int)threadIdx.x < S) s_sum[refit_slot<KIND>(threadIdx.x)] = r;
+    __syncthreads();
+    if (threadIdx.x < F_SLOTS) tr->sums[round][threadIdx.x] = s_sum[threadIdx.x];
+    if (threadIdx.x != 0) return;
+
+    const Norm    L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    const double* s = s_sum;
+    double        h[9];
+    bool          ok;
+    if (KIND == POPSIFT_HIP_REFIT_EPIPOLAR) {
+        int k = 0;
+        for (int i = 0; i < 9; i++)
+            for (int j = i; j < 9; j++) s_a[i][j] = s_a[j][i] = s[k++];
+        ok = refit_null_vector(s_a, s_perm);
+        double f[9], g[9];
+        for (int i = 0; i < 9; i++) f[i] = s_a[i][9];
+        rank2(f);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            g[3 * i] = f[3 * i] * L.k;
+            g[3 * i + 1] = f[3 * i + 1] * L.k;
+            g[3 * i + 2] = fma(-g[3 * i], L.cx, fma(-g[3 * i + 1], L.cy, f[3 * i + 2]));
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            h[j] = g[j] * Rn.k;
+            h[3 + j] = g[3 + j] * Rn.k;
+            h[6 + j] = fma(-h[j], Rn.cx, fma(-h[3 + j], Rn.cy, g[6 + j]));
+        }
+        double d = h[0], best = fabs(h[0]);
+#pragma unroll
+        for (int i = 1; i < 9; i++) {
+            const double a = fabs(h[i]);
+            const bool   gt = a > best;
+            best = gt ? a : best;
+            d = gt ? h[i] : d;
+        }
+        ok = ok && !(d == 0.0);
+#pragma unroll
+        for (int i = 0; i < 9; i++) h[i] = h[i] / d;
+    } else {
+        double g[9];
+        for (int i = 0; i < 8; i++)
+            for (int j = 0; j < 10; j++) s_a[i][j] = 0.0;
+        const double n3[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
+        if (KIND == POPSIFT_HIP_REFIT_AFFINE) {
+            for (int i = 0; i < 3; i++) {
+                for (int j = 0; j < 3; j++) s_a[i][j] = n3[i][j];
+                s_a[i][3] = s[21 + i];
+                s_a[i][4] = s[24 + i];
+            }
+            ok = refit_eliminate(s_a, 3, 2);
+            for (int i = 0; i < 3; i++) {
+                g[i] = s_a[i][3];
+                g[3 + i] = s_a[i][4];
+            }
+            g[6] = 0.0;
+            g[7] = 0.0;
+        } else {
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) s_a[i][j] = s_a[3 + i][3 + j] = n3[i][j];
+            for (int i = 0; i < 3; i++) {
+                s_a[i][6] = s_a[6][i] = s[6 + 2 * i];
+                s_a[i][7] = s_a[7][i] = s[7 + 2 * i];
+                s_a[3 + i][6] = s_a[6][3 + i] = s[12 + 2 * i];
+                s_a[3 + i][7] = s_a[7][3 + i] = s[13 + 2 * i];
+            }
+            s_a[6][6] = s[18];
+            s_a[6][7] = s_a[7][6] = s[19];
+            s_a[7][7] = s[20];
+            for (int i = 0; i < 8; i++) s_a[i][8] = s[21 + i];
+            ok = refit_eliminate(s_a, 8, 1);
+            for (int i = 0; i < 8; i++) g[i] = s_a[i][8];
+        }
+        g[8] = 1.0;
+        double mm[9];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            mm[3 * i] = g[3 * i] * L.k;
+            mm[3 * i + 1] = g[3 * i + 1] * L.k;
+            mm[3 * i + 2] = fma(-mm[3 * i], L.cx, fma(-mm[3 * i + 1], L.cy, g[3 * i + 2]));
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            h[j] = fma(Rn.s, mm[j], Rn.cx * mm[6 + j]);
+            h[3 + j] = fma(Rn.s, mm[3 + j], Rn.cy * mm[6 + j]);
+            h[6 + j] = mm[6 + j];
+        }
+    }
+    float M[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        M[i] = (float)h[i];
+        ok = ok && isfinite(M[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) tr->models[round][i] = ok ? M[i] : 0.0f;
+    tr->counts[round] = ok ? 0 : -1;
+}
+
+/* rules 2 and 3d on the state record, one lane.  round -1: the start count has been added up in st->n_inliers */
+__global__ __launch_bounds__(64) void k_refit_decide(RefitState* __restrict__ st, RefitTrace* __restrict__ tr, int round, int m)
+{
+    if (threadIdx.x != 0 || st->done) return;
+    if (round < 0) {
+        st->n_start = st->n_inliers;
+        if (st->n_inliers < m) {
+            st->stop = POPSIFT_HIP_REFIT_STOP_NO_SUPPORT;
+            st->done = 1;
+        }
+        return;
+    }
+    const int c = tr->counts[round];
+    bool      same = true;
+    for (int i = 0; i < 9; i++) same = same && __float_as_uint(tr->models[round][i]) == __float_as_uint(st->H[i]);
+    int stop = -1;
+    if (c < 0) stop = POPSIFT_HIP_REFIT_STOP_NO_FIT;
+    else if (same) stop = POPSIFT_HIP_REFIT_STOP_CONVERGED;
+    else if (c < st->n_inliers) stop = POPSIFT_HIP_REFIT_STOP_NOT_BETTER;
+    if (stop >= 0) {
+        st->stop = stop;
+        st->done = 1;
+        return;
+    }
+    for (int i = 0; i < 9; i++) st->H[i] = tr->models[round][i];
+    st->n_inliers = c;
+    st->rounds = st->rounds + 1;
+    tr->accepted[round] = 1;
+}
+
 /* ---- pair_points */
 
 /* *bad = 1 when a descriptor has no feature behind it (map entry outside 0 .. n_feat - 1) */
@@ -787,9 +1223,140 @@ int run(popsift_hip_verifier* v, const float* pts, int n, const Fit& fit, popsif
     return ok.rc;
 }
 
+bool refit_opts_valid(const popsift_hip_refit_opts* o)
+{
+    if (!o || o->model < POPSIFT_HIP_REFIT_HOMOGRAPHY || o->model > POPSIFT_HIP_REFIT_EPIPOLAR || o->rounds < 1 ||
+        o->rounds > F_ROUNDS || !std::isfinite(o->max_err) || !(o->max_err > 0.0f))
+        return false;
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(o->M[i])) return false;
+    return o->reserved[0] == 0 && o->reserved[1] == 0 && o->reserved[2] == 0 && o->reserved[3] == 0;
+}
+
+template <int KIND>
+void launch_refit(hipStream_t s, const v4f* d_pts, int n, const uint32_t* d_bounds, RefitState* d_st, RefitTrace* d_tr,
+                  double* d_blocks, double* d_spare, int rounds, float max_err2, uint32_t* d_mask)
+{
+    typedef typename RefitKind<KIND>::Rule Rule;
+    const int  chunks = (n + F_CHUNK - 1) / F_CHUNK, m = RefitKind<KIND>::m;
+    const dim3 g_quads((n + 1023) / 1024);
+    hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, dim3(256), 0, s, d_pts, n, d_st->H, max_err2, &d_st->n_inliers, &d_st->done);
+    hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, -1, m);
+    for (int r = 0; r < rounds; r++) {
+        hipLaunchKernelGGL(k_refit_accumulate<KIND>, dim3(chunks), dim3(256), 0, s, d_pts, n, d_bounds, d_st, max_err2, d_blocks);
+        hipLaunchKernelGGL(k_refit_solve<KIND>, dim3(1), dim3(256), 0, s, d_blocks, d_spare, chunks, d_bounds, d_st, d_tr, r);
+        hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, dim3(256), 0, s, d_pts, n, d_tr->models[r], max_err2, &d_tr->counts[r],
+                           &d_st->done);
+        hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, r, m);
+    }
+    hipLaunchKernelGGL(k_ransac_mask<Rule>, g_quads, dim3(256), 0, s, d_pts, n, (const popsift_hip_ransac_result*)d_st, max_err2,
+                       d_mask);
+}
+
+/* popsift_hip_refit and its trace.  As in run() the layout of the scratch is a function of the arguments, and every byte
+ * the call reads it has written before. */
+int run_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o, popsift_hip_refit_result* res,
+              uint8_t* inlier, bool trace, double* sums, float* models, int32_t* counts, int32_t* accepted)
+{
+    if (!refit_opts_valid(o) || !v || !res || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
+    const int R = o->rounds;
+    const int m = o->model == POPSIFT_HIP_REFIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : o->model == POPSIFT_HIP_REFIT_AFFINE ? 3 : 4;
+    if (n < m) { /* no model of this kind has support */
+        memcpy(res->M, o->M, sizeof res->M);
+        res->n_inliers = res->n_start = res->rounds = 0;
+        res->stop = POPSIFT_HIP_REFIT_STOP_NO_SUPPORT;
+        if (inlier && n > 0) memset(inlier, 0, (size_t)n);
+        if (sums) memset(sums, 0, sizeof(double) * F_SLOTS * (size_t)R);
+        if (models) memset(models, 0, sizeof(float) * 9 * (size_t)R);
+        if (counts) memset(counts, 0xff, sizeof(int32_t) * (size_t)R);
+        if (accepted) memset(accepted, 0, sizeof(int32_t) * (size_t)R);
+        return POPSIFT_HIP_OK;
+    }
+    if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status       ok;
+    const size_t chunks = ((size_t)n + F_CHUNK - 1) / F_CHUNK;
+    const size_t b_pts = sizeof(float) * 4 * (size_t)n, b_mask = round16((size_t)n), b_trace = round16(sizeof(RefitTrace)),
+                 b_blocks = round16(sizeof(double) * F_SLOTS * chunks), b_spare = round16(sizeof(double) * F_SLOTS * ((chunks + 1) / 2));
+    /* device: [bounds 32][state 64][mask][points][trace][chunk sums][spare]; the state and the mask come down together */
+    const size_t o_head = 32, o_mask = o_head + HEAD, o_pts = o_mask + b_mask, o_trace = o_pts + b_pts, o_blocks = o_trace + b_trace,
+                 o_spare = o_blocks + b_blocks, d_need = o_spare + b_spare;
+    /* pinned: [points][state + mask][trace] */
+    const size_t g_down = b_pts, g_trace = g_down + HEAD + b_mask, h_need = g_trace + b_trace;
+    if (!grow(ok, v, d_need, h_need)) return ok.rc;
+    hipStream_t const s = v->stream;
+    char* const       d = v->d_buf;
+    auto* const       d_bounds = (uint32_t*)d;
+    auto* const       d_st = (RefitState*)(d + o_head);
+    auto* const       d_pts = (const v4f*)(d + o_pts);
+    auto* const       d_tr = (RefitTrace*)(d + o_trace);
+    auto* const       d_blocks = (double*)(d + o_blocks);
+    auto* const       d_spare = (double*)(d + o_spare);
+    auto* const       d_mask = (uint32_t*)(d + o_mask);
+    const float       max_err2 = o->max_err * o->max_err;
+
+    memcpy(v->h_buf, pts, b_pts);
+    ok(hipMemcpyAsync(d + o_pts, v->h_buf, b_pts, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, 32, s)) &&
+        ok(hipMemsetAsync(d_tr, 0, b_trace, s));
+    if (ok.good()) {
+        RefitStart start;
+        memcpy(start.M, o->M, sizeof start.M);
+        hipLaunchKernelGGL(k_ransac_bounds, dim3(std::min((n + 255) / 256, 512)), dim3(256), 0, s, d_pts, n, d_bounds);
+        hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, start, d_st, d_tr);
+        if (o->model == POPSIFT_HIP_REFIT_HOMOGRAPHY)
+            launch_refit<POPSIFT_HIP_REFIT_HOMOGRAPHY>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
+        else if (o->model == POPSIFT_HIP_REFIT_AFFINE)
+            launch_refit<POPSIFT_HIP_REFIT_AFFINE>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
+        else
+            launch_refit<POPSIFT_HIP_REFIT_EPIPOLAR>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
+        ok(hipGetLastError());
+    }
+    const size_t down = HEAD + (inlier ? (size_t)n : 0);
+    ok.good() && ok(hipMemcpyAsync(v->h_buf + g_down, d + o_head, down, hipMemcpyDeviceToHost, s));
+    if (ok.good() && trace) ok(hipMemcpyAsync(v->h_buf + g_trace, d + o_trace, sizeof(RefitTrace), hipMemcpyDeviceToHost, s));
+    if (ok.good() && ok(hipStreamSynchronize(s))) {
+        RefitState st;
+        memcpy(&st, v->h_buf + g_down, sizeof st);
+        memcpy(res->M, st.H, sizeof res->M);
+        res->n_inliers = st.n_inliers;
+        res->n_start = st.n_start;
+        res->rounds = st.rounds;
+        res->stop = st.stop;
+        if (inlier) memcpy(inlier, v->h_buf + g_down + HEAD, (size_t)n);
+        const RefitTrace* tr = (const RefitTrace*)(v->h_buf + g_trace);
+        if (sums) memcpy(sums, tr->sums, sizeof(double) * F_SLOTS * (size_t)R);
+        if (models) memcpy(models, tr->models, sizeof(float) * 9 * (size_t)R);
+        if (counts) memcpy(counts, tr->counts, sizeof(int32_t) * (size_t)R);
+        if (accepted) memcpy(accepted, tr->accepted, sizeof(int32_t) * (size_t)R);
+    }
+    return ok.rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+void popsift_hip_default_refit_opts(popsift_hip_refit_opts* o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->model = POPSIFT_HIP_REFIT_HOMOGRAPHY;
+    o->rounds = 4;
+    o->max_err = 2.0f;
+    o->M[0] = o->M[4] = o->M[8] = 1.0f;
+}
+
+int popsift_hip_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
+                      popsift_hip_refit_result* res, uint8_t* inlier)
+{
+    return run_refit(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr, nullptr);
+}
+
+int popsift_hip_refit_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
+                            popsift_hip_refit_result* res, uint8_t* inlier, double* sums, float* models, int32_t* counts,
+                            int32_t* accepted)
+{
+    return run_refit(v, pts, n, o, res, inlier, true, sums, models, counts, accepted);
+}
 
 int popsift_hip_verifier_create(int device, popsift_hip_verifier** out)
 {

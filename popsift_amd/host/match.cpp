@@ -9,6 +9,8 @@
  * the fundamental matrix of two views of a 3-D scene.
  * Extension: --guided [--guided-err E] with --verify matches again under the model just found (FeaturesDev::matchGuided)
  * and prints those pairs after the model block.
+ * Extension: --refit [--refit-rounds N] with --verify refits the model RANSAC found to all its inliers by least squares
+ * (Verifier::refit) and prints the refitted model under the RANSAC block; with --guided the refitted model is the guide.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -45,6 +47,8 @@ static popsift::RansacOptions verify_opts;
 static bool verify_epipolar = false;
 static bool guided_pairs = false;
 static float guided_err = 0.0f; /* 0: --max-err */
+static bool refit_model = false;
+static int refit_rounds = 4;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -128,6 +132,12 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
            "--cross-check as given; prints those pairs after the model, then their count",
            [&] { guided_pairs = true; });
     o.fval("guided-err", "Matching", "With --guided: the distance in pixels (default: --max-err)", [&](float f) { guided_err = f; });
+    o.flag("refit", 0, "Matching",
+           "With --verify: refit the model to all its inliers by least squares, again on the new model's inliers while\n"
+           "their number does not drop; prints the refitted model, its inliers, the rounds and why it stopped under the\n"
+           "RANSAC lines; --guided then matches under the refitted model",
+           [&] { refit_model = true; });
+    o.ival("refit-rounds", "Matching", "With --refit: the most rounds, 1 .. 16 (default 4)", [&](int v) { refit_rounds = v; });
     o.val("feature-order", 0, "Extensions",
           "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
           "pixel column, level: the same bytes on every run)",
@@ -143,6 +153,14 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     }
     if (guided_pairs && !verify_pairs) {
         cerr << "--guided matches under the model --verify finds: add --verify" << endl;
+        exit(-1);
+    }
+    if (refit_model && !verify_pairs) {
+        cerr << "--refit refits the model --verify finds: add --verify" << endl;
+        exit(-1);
+    }
+    if (refit_rounds < 1 || refit_rounds > 16) {
+        cerr << "--refit-rounds: 1 .. 16, not " << refit_rounds << endl;
         exit(-1);
     }
     if (guided_pairs && match_bytes) {
@@ -178,11 +196,27 @@ static void print_verification(popsift::FeaturesDev* lf, popsift::FeaturesDev* r
     printf("Model (%s):\n", verify_epipolar ? "epipolar" : verify_opts.model == popsift::RansacOptions::Affine ? "affine" : "homography");
     for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", fit.H[3 * i], fit.H[3 * i + 1], fit.H[3 * i + 2]);
     printf("Number of inliers:     %d of %zu\n", fit.inliers, pairs.size());
+    float guide[9];
+    for (int i = 0; i < 9; i++) guide[i] = fit.H[i];
+    if (refit_model) {
+        popsift::RefitOptions ro(fit, verify_epipolar ? popsift::RefitOptions::Epipolar
+                                      : verify_opts.model == popsift::RansacOptions::Affine ? popsift::RefitOptions::Affine
+                                                                                            : popsift::RefitOptions::Homography,
+                                 verify_opts.maxErr);
+        ro.rounds = refit_rounds;
+        const popsift::RefitResult again = verifier.refit(pts, ro);
+        static const char* const why[] = {"all rounds ran", "converged", "no more inliers", "no fit", "no support"};
+        printf("Refitted model:\n");
+        for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", again.M[3 * i], again.M[3 * i + 1], again.M[3 * i + 2]);
+        printf("Refit inliers:         %d -> %d of %zu, %d rounds (%s)\n", again.start, again.inliers, pairs.size(), again.rounds,
+               why[again.stop]);
+        for (int i = 0; i < 9; i++) guide[i] = again.M[i];
+    }
     if (!guided_pairs) return;
     /* --guided: the search again, among the right descriptors that agree with the model */
     popsift::FeaturesDev::GuidedOptions g;
     g.model = verify_epipolar ? popsift::FeaturesDev::GuidedOptions::Epipolar : popsift::FeaturesDev::GuidedOptions::Homography;
-    for (int i = 0; i < 9; i++) g.M[i] = fit.H[i];
+    for (int i = 0; i < 9; i++) g.M[i] = guide[i];
     g.maxErr = guided_err > 0.0f ? guided_err : verify_opts.maxErr;
     g.ratio = pair_opts.ratio;
     g.maxDist2 = pair_opts.maxDist2;

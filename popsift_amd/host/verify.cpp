@@ -1,4 +1,4 @@
-/* popsift::Verifier on top of popsift_hip_ransac and popsift_hip_epipolar (include/popsift/verify.h) */
+/* popsift::Verifier on top of popsift_hip_ransac, popsift_hip_epipolar and popsift_hip_refit (include/popsift/verify.h) */
 #include "popsift/verify.h"
 
 #include <cstdlib>
@@ -65,6 +65,28 @@ RansacResult Verifier::epipolar(const std::vector<float>& pts, const EpipolarOpt
     const int rc = popsift_hip_epipolar(_v, n ? pts.data() : 0, n, &o, &res, n ? out.mask.data() : 0);
     if (rc != POPSIFT_HIP_OK) verify_fatal("epipolar verification failed", rc);
     take(out, res);
+    return out;
+}
+
+RefitResult Verifier::refit(const std::vector<float>& pts, const RefitOptions& opts)
+{
+    RefitResult              out;
+    const int                n = (int)(pts.size() / 4);
+    popsift_hip_refit_opts   o;
+    popsift_hip_refit_result res;
+    popsift_hip_default_refit_opts(&o);
+    o.model = (int)opts.kind;
+    o.rounds = opts.rounds;
+    o.max_err = opts.maxErr;
+    memcpy(o.M, opts.M, sizeof o.M);
+    out.mask.resize((size_t)n);
+    const int rc = popsift_hip_refit(_v, n ? pts.data() : 0, n, &o, &res, n ? out.mask.data() : 0);
+    if (rc != POPSIFT_HIP_OK) verify_fatal("refit failed", rc);
+    memcpy(out.M, res.M, sizeof out.M);
+    out.inliers = res.n_inliers;
+    out.start = res.n_start;
+    out.rounds = res.rounds;
+    out.stop = (RefitResult::Stop)res.stop;
     return out;
 }
 
