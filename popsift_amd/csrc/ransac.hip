@@ -28,6 +28,12 @@
  *                       pairwise tree over the pair index up to one block of sums per chunk of 1024 pairs
  *   k_refit_solve       the rest of the tree over the chunks, then one lane solves and writes the round's candidate
  *   k_refit_decide      accept the candidate or stop
+ *
+ * Each numeric step has one text, used by the sampler's model kernels and by the refit: normalise (a pair), eliminate<R, NB>
+ * (partial pivoting), null_vector<ROWS> (complete pivoting), rank2, denormalise_transfer, denormalise_fundamental and
+ * round_model; all of them work on register arrays with compile-time indices.  Kind<> gives per kind the inlier rule, the
+ * pairs per sample, the ints per sample row and the refit's sums.  On the host the two call bodies, run and run_refit,
+ * share their frame: args_valid, Frame (the offsets both lay out alike), grow, upload and download.
  */
 #include <hip/hip_runtime.h>
 
@@ -50,6 +56,24 @@ constexpr int S_CHUNK = POPSIFT_HIP_RANSAC_CHUNK;  /* pairs per workgroup */
 constexpr int S_HYP = POPSIFT_HIP_RANSAC_HYP_BLOCK; /* hypotheses per workgroup */
 static_assert(S_CHUNK == S_BLOCK * S_PER_LANE, "chunk = lanes x pairs per lane");
 static_assert(S_HYP <= S_BLOCK, "one lane per hypothesis merges the waves' counts");
+
+/* what a call fits: the run-time value, equal to the model of popsift_hip_ransac_opts and of popsift_hip_refit_opts */
+enum { FIT_HOMOGRAPHY = 0, FIT_AFFINE = 1, FIT_EPIPOLAR = 2 };
+static_assert(FIT_HOMOGRAPHY == POPSIFT_HIP_MODEL_HOMOGRAPHY && FIT_AFFINE == POPSIFT_HIP_MODEL_AFFINE &&
+                  FIT_HOMOGRAPHY == POPSIFT_HIP_REFIT_HOMOGRAPHY && FIT_AFFINE == POPSIFT_HIP_REFIT_AFFINE &&
+                  FIT_EPIPOLAR == POPSIFT_HIP_REFIT_EPIPOLAR,
+              "one numbering of the kinds");
+
+/* per kind: the inlier rule (rule 4 below), m pairs per sample, `row` ints per row of the samples, `slots` sums of the
+ * refit's normal equations held in registers */
+struct Transfer;
+struct Sampson;
+template <int KIND> struct Kind;
+template <> struct Kind<FIT_HOMOGRAPHY> { typedef Transfer Rule; static constexpr int m = 4, row = 4, slots = 29; };
+template <> struct Kind<FIT_AFFINE> { typedef Transfer Rule; static constexpr int m = 3, row = 4, slots = 12; };
+template <> struct Kind<FIT_EPIPOLAR> { typedef Sampson Rule; static constexpr int m = 8, row = 8, slots = 45; };
+static_assert(Kind<FIT_EPIPOLAR>::m == POPSIFT_HIP_EPIPOLAR_SAMPLE && Kind<FIT_EPIPOLAR>::slots == POPSIFT_HIP_REFIT_SLOTS,
+              "the header's sample size and trace slots");
 
 /* ---- rule 1: sample */
 
@@ -134,6 +158,20 @@ __device__ __forceinline__ Norm normaliser(const uint32_t* __restrict__ bounds, 
     return q;
 }
 
+/* a pair in the normalised coordinates of its two sides */
+struct Pair {
+    double x, y, u, v;
+};
+__device__ __forceinline__ Pair normalise(v4f p, const Norm& L, const Norm& Rn)
+{
+    Pair q;
+    q.x = ((double)p[0] - L.cx) * L.k;
+    q.y = ((double)p[1] - L.cy) * L.k;
+    q.u = ((double)p[2] - Rn.cx) * Rn.k;
+    q.v = ((double)p[3] - Rn.cy) * Rn.k;
+    return q;
+}
+
 __global__ __launch_bounds__(256) void k_ransac_bounds(const v4f* __restrict__ pts, int n, uint32_t* __restrict__ bounds)
 {
     uint32_t m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -206,36 +244,61 @@ __device__ __forceinline__ bool eliminate(double (&a)[R][R + NB])
     return ok;
 }
 
+/* a transfer model out of the normalised coordinates: M = G * Tl, then H = Tr^-1 * M */
+__device__ __forceinline__ void denormalise_transfer(const double (&g)[9], const Norm& L, const Norm& Rn, double (&h)[9])
+{
+    double mm[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        mm[3 * i] = g[3 * i] * L.k;
+        mm[3 * i + 1] = g[3 * i + 1] * L.k;
+        mm[3 * i + 2] = fma(-mm[3 * i], L.cx, fma(-mm[3 * i + 1], L.cy, g[3 * i + 2]));
+    }
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        h[j] = fma(Rn.s, mm[j], Rn.cx * mm[6 + j]);
+        h[3 + j] = fma(Rn.s, mm[3 + j], Rn.cy * mm[6 + j]);
+        h[6 + j] = mm[6 + j];
+    }
+}
+
+/* a model's nine float64 values rounded to float32; true when all nine are finite.  A caller without a valid model
+ * writes zeros and -1 instead */
+__device__ __forceinline__ bool round_model(const double (&h)[9], float (&M)[9])
+{
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        M[i] = (float)h[i];
+        ok = ok && isfinite(M[i]);
+    }
+    return ok;
+}
+
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
                                                       const uint32_t* __restrict__ bounds, float* __restrict__ models,
                                                       int* __restrict__ samples, int* __restrict__ counts)
 {
-    constexpr int M = MODEL == POPSIFT_HIP_MODEL_AFFINE ? 3 : 4;
+    constexpr int M = Kind<MODEL>::m, ROW = Kind<MODEL>::row;
     const int     t = blockIdx.x * 64 + threadIdx.x;
     if (t >= T) return;
     const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
-    int        idx[4];
+    int        idx[ROW];
     bool       ok = sample<M>(seed, t, n, idx);
-    double     x[M], y[M], u[M], v[M];
+    Pair       q[M];
 #pragma unroll
-    for (int i = 0; i < M; i++) {
-        const v4f p = pts[ok ? idx[i] : 0];
-        x[i] = ((double)p[0] - L.cx) * L.k;
-        y[i] = ((double)p[1] - L.cy) * L.k;
-        u[i] = ((double)p[2] - Rn.cx) * Rn.k;
-        v[i] = ((double)p[3] - Rn.cy) * Rn.k;
-    }
+    for (int i = 0; i < M; i++) q[i] = normalise(pts[ok ? idx[i] : 0], L, Rn);
     double g[9];
-    if (MODEL == POPSIFT_HIP_MODEL_AFFINE) {
+    if (MODEL == FIT_AFFINE) {
         double a[3][5];
 #pragma unroll
         for (int i = 0; i < 3; i++) {
-            a[i][0] = x[i];
-            a[i][1] = y[i];
+            a[i][0] = q[i].x;
+            a[i][1] = q[i].y;
             a[i][2] = 1.0;
-            a[i][3] = u[i];
-            a[i][4] = v[i];
+            a[i][3] = q[i].u;
+            a[i][4] = q[i].v;
         }
         ok = eliminate<3, 2>(a) && ok;
 #pragma unroll
@@ -249,50 +312,37 @@ __global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pt
         double a[8][9];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
+            const double x = q[i].x, y = q[i].y, u = q[i].u, v = q[i].v;
             double(&r0)[9] = a[2 * i];
             double(&r1)[9] = a[2 * i + 1];
-            r0[0] = x[i]; r0[1] = y[i]; r0[2] = 1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0;
-            r0[6] = -u[i] * x[i]; r0[7] = -u[i] * y[i]; r0[8] = u[i];
-            r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = x[i]; r1[4] = y[i]; r1[5] = 1.0;
-            r1[6] = -v[i] * x[i]; r1[7] = -v[i] * y[i]; r1[8] = v[i];
+            r0[0] = x; r0[1] = y; r0[2] = 1.0; r0[3] = 0.0; r0[4] = 0.0; r0[5] = 0.0;
+            r0[6] = -u * x; r0[7] = -u * y; r0[8] = u;
+            r1[0] = 0.0; r1[1] = 0.0; r1[2] = 0.0; r1[3] = x; r1[4] = y; r1[5] = 1.0;
+            r1[6] = -v * x; r1[7] = -v * y; r1[8] = v;
         }
         ok = eliminate<8, 1>(a) && ok;
 #pragma unroll
         for (int i = 0; i < 8; i++) g[i] = a[i][8];
     }
     g[8] = 1.0;
-    /* denormalise: M = G * Tl, then H = Tr^-1 * M */
-    double mm[9], h[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        mm[3 * i] = g[3 * i] * L.k;
-        mm[3 * i + 1] = g[3 * i + 1] * L.k;
-        mm[3 * i + 2] = fma(-mm[3 * i], L.cx, fma(-mm[3 * i + 1], L.cy, g[3 * i + 2]));
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        h[j] = fma(Rn.s, mm[j], Rn.cx * mm[6 + j]);
-        h[3 + j] = fma(Rn.s, mm[3 + j], Rn.cy * mm[6 + j]);
-        h[6 + j] = mm[6 + j];
-    }
-    float H[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        H[i] = (float)h[i];
-        ok = ok && isfinite(H[i]);
-    }
+    double h[9];
+    float  H[9];
+    denormalise_transfer(g, L, Rn, h);
+    ok = round_model(h, H) && ok;
 #pragma unroll
     for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? H[i] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < 4; i++) samples[4 * (size_t)t + i] = idx[i];
+    for (int i = 0; i < ROW; i++) samples[ROW * (size_t)t + i] = idx[i];
     counts[t] = ok ? 0 : -1;
 }
 
 /* ---- popsift_hip_epipolar, rules 3 to 5: one fundamental matrix per lane.  As above every index is a compile-time
  * constant after unrolling; row and column swaps are selects. */
 
-/* rule 3: the null vector of the 8 x 9 system, complete pivoting; false when a pivot is exactly 0 */
-__device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
+/* rule 3: the null vector by eight steps of complete pivoting; false when a pivot is exactly 0.  ROWS 8: the sampler's
+ * 8 x 9 system.  ROWS 9: the refit's 9 x 9 normal matrix, whose row 8 takes part in the pivoting and is then dropped */
+template <int ROWS>
+__device__ __forceinline__ bool null_vector(double (&a)[ROWS][9], double (&f)[9])
 {
     bool ok = true;
     int  perm[9];
@@ -305,7 +355,7 @@ __device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
 #pragma unroll
         for (int c = k; c < 9; c++) { /* column-major: the lowest column, then the lowest row, wins a tie */
 #pragma unroll
-            for (int r = (c == k ? k + 1 : k); r < 8; r++) {
+            for (int r = (c == k ? k + 1 : k); r < ROWS; r++) {
                 const double v = fabs(a[r][c]);
                 const bool   g = v > best;
                 best = g ? v : best;
@@ -314,7 +364,7 @@ __device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
             }
         }
 #pragma unroll
-        for (int r = k + 1; r < 8; r++) {
+        for (int r = k + 1; r < ROWS; r++) {
             const bool sw = pr == r;
 #pragma unroll
             for (int j = k; j < 9; j++) { /* the columns before k of these rows are not read again */
@@ -327,7 +377,7 @@ __device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
         for (int c = k + 1; c < 9; c++) {
             const bool sw = pc == c;
 #pragma unroll
-            for (int r = 0; r < 8; r++) { /* the rows above k too: back substitution reads them */
+            for (int r = 0; r < ROWS; r++) { /* the rows above k too: back substitution reads them */
                 const double lo = a[r][k], hi = a[r][c];
                 a[r][k] = sw ? hi : lo;
                 a[r][c] = sw ? lo : hi;
@@ -338,7 +388,7 @@ __device__ __forceinline__ bool null_vector(double (&a)[8][9], double (&f)[9])
         }
         ok = ok && !(a[k][k] == 0.0);
 #pragma unroll
-        for (int r = k + 1; r < 8; r++) {
+        for (int r = k + 1; r < ROWS; r++) {
             const double q = a[r][k] / a[k][k];
 #pragma unroll
             for (int j = k + 1; j < 9; j++) a[r][j] = fma(-q, a[k][j], a[r][j]);
@@ -427,32 +477,11 @@ __device__ __forceinline__ void rank2(double (&f)[9])
     }
 }
 
-__global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
-                                                        const uint32_t* __restrict__ bounds, float* __restrict__ models,
-                                                        int* __restrict__ samples, int* __restrict__ counts)
+/* rule 5: a fundamental matrix out of the normalised coordinates, G = Fn * Tl, then H = Tr^T * G, scaled so that its
+ * entry of largest magnitude is 1; false when that entry is 0 */
+__device__ __forceinline__ bool denormalise_fundamental(const double (&f)[9], const Norm& L, const Norm& Rn, double (&h)[9])
 {
-    constexpr int M = POPSIFT_HIP_EPIPOLAR_SAMPLE;
-    const int     t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= T) return;
-    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
-    int        idx[M];
-    bool       ok = sample<M>(seed, t, n, idx);
-    double     a[M][9], f[9];
-#pragma unroll
-    for (int i = 0; i < M; i++) {
-        const v4f    p = pts[ok ? idx[i] : 0];
-        const double x = ((double)p[0] - L.cx) * L.k;
-        const double y = ((double)p[1] - L.cy) * L.k;
-        const double u = ((double)p[2] - Rn.cx) * Rn.k;
-        const double v = ((double)p[3] - Rn.cy) * Rn.k;
-        a[i][0] = u * x; a[i][1] = u * y; a[i][2] = u;
-        a[i][3] = v * x; a[i][4] = v * y; a[i][5] = v;
-        a[i][6] = x; a[i][7] = y; a[i][8] = 1.0;
-    }
-    ok = null_vector(a, f) && ok;
-    rank2(f);
-    /* rule 5, denormalise: G = Fn * Tl, then H = Tr^T * G */
-    double g[9], h[9];
+    double g[9];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         g[3 * i] = f[3 * i] * L.k;
@@ -465,7 +494,6 @@ __global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ 
         h[3 + j] = g[3 + j] * Rn.k;
         h[6 + j] = fma(-h[j], Rn.cx, fma(-h[3 + j], Rn.cy, g[6 + j]));
     }
-    /* scale: the entry of largest magnitude becomes 1 */
     double d = h[0], best = fabs(h[0]);
 #pragma unroll
     for (int i = 1; i < 9; i++) {
@@ -474,13 +502,34 @@ __global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ 
         best = gt ? v : best;
         d = gt ? h[i] : d;
     }
-    ok = ok && !(d == 0.0);
-    float F[9];
 #pragma unroll
-    for (int i = 0; i < 9; i++) {
-        F[i] = (float)(h[i] / d);
-        ok = ok && isfinite(F[i]);
+    for (int i = 0; i < 9; i++) h[i] = h[i] / d;
+    return !(d == 0.0);
+}
+
+__global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
+                                                        const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                        int* __restrict__ samples, int* __restrict__ counts)
+{
+    constexpr int M = Kind<FIT_EPIPOLAR>::m;
+    const int     t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= T) return;
+    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    int        idx[M];
+    bool       ok = sample<M>(seed, t, n, idx);
+    double     a[M][9], f[9], h[9];
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const Pair q = normalise(pts[ok ? idx[i] : 0], L, Rn);
+        a[i][0] = q.u * q.x; a[i][1] = q.u * q.y; a[i][2] = q.u;
+        a[i][3] = q.v * q.x; a[i][4] = q.v * q.y; a[i][5] = q.v;
+        a[i][6] = q.x; a[i][7] = q.y; a[i][8] = 1.0;
     }
+    ok = null_vector<M>(a, f) && ok;
+    rank2(f);
+    ok = denormalise_fundamental(f, L, Rn, h) && ok;
+    float F[9];
+    ok = round_model(h, F) && ok;
 #pragma unroll
     for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? F[i] : 0.0f;
 #pragma unroll
@@ -647,11 +696,6 @@ struct RefitTrace {
     int    accepted[F_ROUNDS];
 };
 
-template <int KIND> struct RefitKind;
-template <> struct RefitKind<POPSIFT_HIP_REFIT_HOMOGRAPHY> { typedef Transfer Rule; static constexpr int slots = 29, m = 4; };
-template <> struct RefitKind<POPSIFT_HIP_REFIT_AFFINE> { typedef Transfer Rule; static constexpr int slots = 12, m = 3; };
-template <> struct RefitKind<POPSIFT_HIP_REFIT_EPIPOLAR> { typedef Sampson Rule; static constexpr int slots = 45, m = 8; };
-
 struct RefitStart {
     float M[9];
 };
@@ -693,12 +737,10 @@ __global__ __launch_bounds__(256) void k_refit_count(const v4f* __restrict__ pts
 
 /* rule 3a: the terms of one pair, +0.0 for a pair that is no inlier; t + 0.0 turns a term of -0.0 into +0.0 */
 template <int KIND>
-__device__ __forceinline__ void refit_terms(v4f p, bool in, const Norm& L, const Norm& Rn, double (&t)[RefitKind<KIND>::slots])
+__device__ __forceinline__ void refit_terms(v4f p, bool in, const Norm& L, const Norm& Rn, double (&t)[Kind<KIND>::slots])
 {
-    const double x = ((double)p[0] - L.cx) * L.k;
-    const double y = ((double)p[1] - L.cy) * L.k;
-    const double u = ((double)p[2] - Rn.cx) * Rn.k;
-    const double v = ((double)p[3] - Rn.cy) * Rn.k;
+    const Pair   q = normalise(p, L, Rn);
+    const double x = q.x, y = q.y, u = q.u, v = q.v;
     if (KIND == POPSIFT_HIP_REFIT_EPIPOLAR) {
         const double a[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1.0};
         int          s = 0;
@@ -723,7 +765,7 @@ __device__ __forceinline__ void refit_terms(v4f p, bool in, const Norm& L, const
         }
     }
 #pragma unroll
-    for (int j = 0; j < RefitKind<KIND>::slots; j++) t[j] = in ? t[j] + 0.0 : 0.0;
+    for (int j = 0; j < Kind<KIND>::slots; j++) t[j] = in ? t[j] + 0.0 : 0.0;
 }
 
 /* where register j of a kind's sums lies among the 45 slots: only the affine map's right-hand sides move */
@@ -764,7 +806,7 @@ __global__ __launch_bounds__(256) void k_refit_accumulate(const v4f* __restrict_
                                                           const RefitState* __restrict__ st, float max_err2,
                                                           double* __restrict__ blocks)
 {
-    typedef RefitKind<KIND> K;
+    typedef Kind<KIND> K;
     constexpr int    S = K::slots;
     __shared__ double s_wave[4][S];
     if (st->done) return; /* the same in every lane */
@@ -791,105 +833,18 @@ __global__ __launch_bounds__(256) void k_refit_accumulate(const v4f* __restrict_
     if ((int)threadIdx.x < S) blocks[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = r;
 }
 
-/* rule 3c for the homography and the affine map: partial pivoting on the R x (R + NB) system in LDS, one lane */
-__device__ bool refit_eliminate(double (*a)[10], int R, int NB)
-{
-    const int C = R + NB;
-    bool      ok = true;
-    for (int c = 0; c < R; c++) {
-        int    p = c;
-        double best = fabs(a[c][c]);
-        for (int r = c + 1; r < R; r++) {
-            const double v = fabs(a[r][c]);
-            if (v > best) {
-                best = v;
-                p = r;
-            }
-        }
-        if (p != c)
-            for (int j = 0; j < C; j++) {
-                const double tmp = a[c][j];
-                a[c][j] = a[p][j];
-                a[p][j] = tmp;
-            }
-        ok = ok && !(a[c][c] == 0.0);
-        for (int r = c + 1; r < R; r++) {
-            const double f = a[r][c] / a[c][c];
-            for (int j = c + 1; j < C; j++) a[r][j] = fma(-f, a[c][j], a[r][j]);
-        }
-    }
-    for (int b = 0; b < NB; b++)
-        for (int i = R - 1; i >= 0; i--) {
-            double s = a[i][R + b];
-            for (int j = i + 1; j < R; j++) s = fma(-a[i][j], a[j][R + b], s);
-            a[i][R + b] = s / a[i][i];
-        }
-    return ok;
-}
-
-/* rule 3c for the epipolar kind: eight steps of complete pivoting on the 9 x 9 matrix in LDS; f in column 9 of a */
-__device__ bool refit_null_vector(double (*a)[10], int* perm)
-{
-    bool ok = true;
-    for (int j = 0; j < 9; j++) perm[j] = j;
-    for (int k = 0; k < 8; k++) {
-        int    pr = k, pc = k;
-        double best = fabs(a[k][k]);
-        for (int c = k; c < 9; c++)
-            for (int r = k; r < 9; r++) {
-                const double v = fabs(a[r][c]);
-                if (v > best) {
-                    best = v;
-                    pr = r;
-                    pc = c;
-                }
-            }
-        if (pr != k)
-            for (int j = 0; j < 9; j++) {
-                const double tmp = a[k][j];
-                a[k][j] = a[pr][j];
-                a[pr][j] = tmp;
-            }
-        if (pc != k) {
-            for (int r = 0; r < 9; r++) {
-                const double tmp = a[r][k];
-                a[r][k] = a[r][pc];
-                a[r][pc] = tmp;
-            }
-            const int tmp = perm[k];
-            perm[k] = perm[pc];
-            perm[pc] = tmp;
-        }
-        ok = ok && !(a[k][k] == 0.0);
-        for (int r = k + 1; r < 9; r++) {
-            const double q = a[r][k] / a[k][k];
-            for (int j = k + 1; j < 9; j++) a[r][j] = fma(-q, a[k][j], a[r][j]);
-        }
-    }
-    /* row 8 is dropped; z in row 8, then f[perm[j]] = z[j] into column 9 */
-    a[8][8] = 1.0;
-    for (int i = 7; i >= 0; i--) {
-        double s = -a[i][8];
-        for (int j = i + 1; j < 8; j++) s = fma(-a[i][j], a[8][j], s);
-        a[8][i] = s / a[i][i];
-    }
-    for (int j = 0; j < 9; j++) a[perm[j]][9] = a[8][j];
-    return ok;
-}
-
-/* rule 3b above the chunks, then rule 3c on one lane.  One workgroup.  blocks: [slot][chunks] as k_refit_accumulate left
- * them; spare: room for [slot][(chunks + 1) / 2], used when there are more than 256 chunks */
+/* rule 3b above the chunks, then rule 3c on one lane: the sums go from LDS into the register system of the sampler's
+ * solver.  One workgroup.  blocks: [slot][chunks] as k_refit_accumulate left them; spare: room for
+ * [slot][(chunks + 1) / 2], used when there are more than 256 chunks */
 template <int KIND>
 __global__ __launch_bounds__(256) void k_refit_solve(double* blocks, double* spare, int chunks,
                                                      const uint32_t* __restrict__ bounds, const RefitState* __restrict__ st,
                                                      RefitTrace* __restrict__ tr, int round)
 {
-    typedef RefitKind<KIND> K;
+    typedef Kind<KIND> K;
     constexpr int    S = K::slots;
     __shared__ double s_wave[4][S];
     __shared__ double s_sum[F_SLOTS];
-    __shared__ double s_a[9][10];
-    __shared__ int    s_perm[9];
     if (st->done) return;
     /* level by level, pairs (2i, 2i + 1) of chunk sums, until one value per lane is left */
     double* src = blocks;
@@ -923,92 +878,65 @@ __global__ __launch_bounds__(256) void k_refit_solve(double* blocks, double* spa
     const double* s = s_sum;
     double        h[9];
     bool          ok;
-    if (KIND == POPSIFT_HIP_REFIT_EPIPOLAR) {
-        int k = 0;
-        for (int i = 0; i < 9; i++)
-            for (int j = i; j < 9; j++) s_a[i][j] = s_a[j][i] = s[k++];
-        ok = refit_null_vector(s_a, s_perm);
-        double f[9], g[9];
-        for (int i = 0; i < 9; i++) f[i] = s_a[i][9];
+    if (KIND == FIT_EPIPOLAR) {
+        double a[9][9], f[9];
+        int    k = 0;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+#pragma unroll
+            for (int j = i; j < 9; j++) a[i][j] = a[j][i] = s[k++];
+        }
+        ok = null_vector<9>(a, f);
         rank2(f);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            g[3 * i] = f[3 * i] * L.k;
-            g[3 * i + 1] = f[3 * i + 1] * L.k;
-            g[3 * i + 2] = fma(-g[3 * i], L.cx, fma(-g[3 * i + 1], L.cy, f[3 * i + 2]));
-        }
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            h[j] = g[j] * Rn.k;
-            h[3 + j] = g[3 + j] * Rn.k;
-            h[6 + j] = fma(-h[j], Rn.cx, fma(-h[3 + j], Rn.cy, g[6 + j]));
-        }
-        double d = h[0], best = fabs(h[0]);
-#pragma unroll
-        for (int i = 1; i < 9; i++) {
-            const double a = fabs(h[i]);
-            const bool   gt = a > best;
-            best = gt ? a : best;
-            d = gt ? h[i] : d;
-        }
-        ok = ok && !(d == 0.0);
-#pragma unroll
-        for (int i = 0; i < 9; i++) h[i] = h[i] / d;
+        ok = denormalise_fundamental(f, L, Rn, h) && ok;
     } else {
-        double g[9];
-        for (int i = 0; i < 8; i++)
-            for (int j = 0; j < 10; j++) s_a[i][j] = 0.0;
+        double       g[9];
         const double n3[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
-        if (KIND == POPSIFT_HIP_REFIT_AFFINE) {
+        if (KIND == FIT_AFFINE) {
+            double a[3][5];
+#pragma unroll
             for (int i = 0; i < 3; i++) {
-                for (int j = 0; j < 3; j++) s_a[i][j] = n3[i][j];
-                s_a[i][3] = s[21 + i];
-                s_a[i][4] = s[24 + i];
+#pragma unroll
+                for (int j = 0; j < 3; j++) a[i][j] = n3[i][j];
+                a[i][3] = s[21 + i];
+                a[i][4] = s[24 + i];
             }
-            ok = refit_eliminate(s_a, 3, 2);
+            ok = eliminate<3, 2>(a);
+#pragma unroll
             for (int i = 0; i < 3; i++) {
-                g[i] = s_a[i][3];
-                g[3 + i] = s_a[i][4];
+                g[i] = a[i][3];
+                g[3 + i] = a[i][4];
             }
             g[6] = 0.0;
             g[7] = 0.0;
         } else {
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) s_a[i][j] = s_a[3 + i][3 + j] = n3[i][j];
+            double a[8][9];
+#pragma unroll
             for (int i = 0; i < 3; i++) {
-                s_a[i][6] = s_a[6][i] = s[6 + 2 * i];
-                s_a[i][7] = s_a[7][i] = s[7 + 2 * i];
-                s_a[3 + i][6] = s_a[6][3 + i] = s[12 + 2 * i];
-                s_a[3 + i][7] = s_a[7][3 + i] = s[13 + 2 * i];
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    a[i][j] = a[3 + i][3 + j] = n3[i][j];
+                    a[i][3 + j] = a[3 + i][j] = 0.0;
+                }
+                a[i][6] = a[6][i] = s[6 + 2 * i];
+                a[i][7] = a[7][i] = s[7 + 2 * i];
+                a[3 + i][6] = a[6][3 + i] = s[12 + 2 * i];
+                a[3 + i][7] = a[7][3 + i] = s[13 + 2 * i];
             }
-            s_a[6][6] = s[18];
-            s_a[6][7] = s_a[7][6] = s[19];
-            s_a[7][7] = s[20];
-            for (int i = 0; i < 8; i++) s_a[i][8] = s[21 + i];
-            ok = refit_eliminate(s_a, 8, 1);
-            for (int i = 0; i < 8; i++) g[i] = s_a[i][8];
+            a[6][6] = s[18];
+            a[6][7] = a[7][6] = s[19];
+            a[7][7] = s[20];
+#pragma unroll
+            for (int i = 0; i < 8; i++) a[i][8] = s[21 + i];
+            ok = eliminate<8, 1>(a);
+#pragma unroll
+            for (int i = 0; i < 8; i++) g[i] = a[i][8];
         }
         g[8] = 1.0;
-        double mm[9];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            mm[3 * i] = g[3 * i] * L.k;
-            mm[3 * i + 1] = g[3 * i + 1] * L.k;
-            mm[3 * i + 2] = fma(-mm[3 * i], L.cx, fma(-mm[3 * i + 1], L.cy, g[3 * i + 2]));
-        }
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            h[j] = fma(Rn.s, mm[j], Rn.cx * mm[6 + j]);
-            h[3 + j] = fma(Rn.s, mm[3 + j], Rn.cy * mm[6 + j]);
-            h[6 + j] = mm[6 + j];
-        }
+        denormalise_transfer(g, L, Rn, h);
     }
     float M[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        M[i] = (float)h[i];
-        ok = ok && isfinite(M[i]);
-    }
+    ok = round_model(h, M) && ok;
 #pragma unroll
     for (int i = 0; i < 9; i++) tr->models[round][i] = ok ? M[i] : 0.0f;
     tr->counts[round] = ok ? 0 : -1;
@@ -1112,15 +1040,39 @@ bool epipolar_opts_valid(const popsift_hip_epipolar_opts* o)
            o->reserved[0] == 0 && o->reserved[1] == 0 && o->reserved[2] == 0;
 }
 
-/* what a call fits: the two models of popsift_hip_ransac_opts, or a fundamental matrix */
-enum { FIT_HOMOGRAPHY = POPSIFT_HIP_MODEL_HOMOGRAPHY, FIT_AFFINE = POPSIFT_HIP_MODEL_AFFINE, FIT_EPIPOLAR };
+/* the sampler's options, from popsift_hip_ransac_opts or popsift_hip_epipolar_opts */
 struct Fit {
-    int      what, hypotheses;
+    int      hypotheses;
     float    max_err;
     uint32_t seed;
-    int      m() const { return what == FIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : what == FIT_AFFINE ? 3 : 4; } /* pairs per sample */
-    int      slots() const { return what == FIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : 4; } /* ints per row of the samples */
 };
+
+/* ---- the frame that run() and run_refit() share around their own launches */
+
+bool args_valid(const popsift_hip_verifier* v, const float* pts, int n)
+{
+    return v && n >= 0 && n <= MAX_PAIRS && (n == 0 || pts);
+}
+
+/* device: [bounds 32][record 64][mask][points], then the call's own arrays from d_own; the record and the mask come down
+ * together.  pinned: [points][record + mask], then the call's trace from h_own */
+struct Frame {
+    size_t b_pts, o_head, o_mask, o_pts, d_own, g_down, h_own;
+};
+
+Frame frame(int n)
+{
+    const size_t b_mask = round16((size_t)n);
+    Frame        f;
+    f.b_pts = sizeof(float) * 4 * (size_t)n;
+    f.o_head = 32;
+    f.o_mask = f.o_head + HEAD;
+    f.o_pts = f.o_mask + b_mask;
+    f.d_own = f.o_pts + f.b_pts;
+    f.g_down = f.b_pts;
+    f.h_own = f.g_down + HEAD + b_mask;
+    return f;
+}
 
 bool grow(Status& ok, popsift_hip_verifier* v, size_t d_need, size_t h_need)
 {
@@ -1139,88 +1091,110 @@ bool grow(Status& ok, popsift_hip_verifier* v, size_t d_need, size_t h_need)
     return ok.good();
 }
 
-/* the four entry points: the same launches but for the model kernel and the inlier rule; a trace downloads three more
- * arrays.  The layout of the scratch is a function of (n, T, fit) and every byte a call reads it has written before, so
- * nothing of an earlier call, whatever its kind, reaches a later one. */
+/* the points go up through the pinned block, then k_ransac_bounds on zeroed bounds.  The launch is checked by the
+ * hipGetLastError() that follows the caller's own launches */
+bool upload(Status& ok, popsift_hip_verifier* v, const Frame& f, const float* pts, int n)
+{
+    auto* const d_pts = (const v4f*)(v->d_buf + f.o_pts);
+    auto* const d_bounds = (uint32_t*)v->d_buf;
+    memcpy(v->h_buf, pts, f.b_pts);
+    if (ok(hipMemcpyAsync(v->d_buf + f.o_pts, v->h_buf, f.b_pts, hipMemcpyHostToDevice, v->stream)) &&
+        ok(hipMemsetAsync(d_bounds, 0, 32, v->stream)))
+        hipLaunchKernelGGL(k_ransac_bounds, dim3(std::min((n + 255) / 256, 512)), dim3(256), 0, v->stream, d_pts, n, d_bounds);
+    return ok.good();
+}
+
+/* the record, the mask for a caller that takes it, and b_own bytes of the call's own arrays from o_own come down.  True
+ * when they have arrived: the record at h_buf + g_down, the own bytes at h_buf + h_own, the mask in the caller's array */
+bool download(Status& ok, popsift_hip_verifier* v, const Frame& f, int n, uint8_t* inlier, size_t o_own, size_t b_own)
+{
+    const size_t down = HEAD + (inlier ? (size_t)n : 0);
+    ok.good() && ok(hipMemcpyAsync(v->h_buf + f.g_down, v->d_buf + f.o_head, down, hipMemcpyDeviceToHost, v->stream));
+    if (ok.good() && b_own) ok(hipMemcpyAsync(v->h_buf + f.h_own, v->d_buf + o_own, b_own, hipMemcpyDeviceToHost, v->stream));
+    if (!ok.good() || !ok(hipStreamSynchronize(v->stream))) return false;
+    if (inlier) memcpy(inlier, v->h_buf + f.g_down + HEAD, (size_t)n);
+    return true;
+}
+
+/* popsift_hip_ransac, popsift_hip_epipolar and their traces: the same launches but for the model kernel and the inlier
+ * rule; a trace downloads three more arrays.  The layout of the scratch is a function of (n, T, kind) and every byte a
+ * call reads it has written before, so nothing of an earlier call, whatever its kind, reaches a later one. */
+template <int KIND>
 int run(popsift_hip_verifier* v, const float* pts, int n, const Fit& fit, popsift_hip_ransac_result* res, uint8_t* inlier,
         bool trace, int32_t* samples, float* models, int32_t* counts)
 {
-    if (!v || (!trace && !res) || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
+    typedef Kind<KIND>        K;
+    typedef typename K::Rule Rule;
+    if (!args_valid(v, pts, n) || (!trace && !res)) return POPSIFT_HIP_ERR_INVALID;
     const int T = fit.hypotheses;
-    const int m = fit.m();
-    if (n < m) { /* no sample exists */
+    if (n < K::m) { /* no sample exists */
         if (res) {
             memset(res, 0, sizeof *res);
             res->hypothesis = -1;
         }
         if (inlier && n > 0) memset(inlier, 0, (size_t)n);
-        if (samples) memset(samples, 0xff, sizeof(int32_t) * fit.slots() * (size_t)T);
+        if (samples) memset(samples, 0xff, sizeof(int32_t) * K::row * (size_t)T);
         if (models) memset(models, 0, sizeof(float) * 9 * (size_t)T);
         if (counts) memset(counts, 0xff, sizeof(int32_t) * (size_t)T);
         return POPSIFT_HIP_OK;
     }
     if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     Status       ok;
-    const size_t b_pts = sizeof(float) * 4 * (size_t)n, b_mask = round16((size_t)n);
-    const size_t b_models = round16(sizeof(float) * 9 * (size_t)T), b_samples = sizeof(int) * fit.slots() * (size_t)T,
-                 b_counts = round16(sizeof(int) * (size_t)T);
-    /* device: [bounds 32][record 64][mask][points][models][samples][counts]; the record and the mask come down together,
-     * the last three are contiguous for the trace */
-    const size_t o_head = 32, o_mask = o_head + HEAD, o_pts = o_mask + b_mask, o_models = o_pts + b_pts,
-                 o_samples = o_models + b_models, o_counts = o_samples + b_samples, d_need = o_counts + b_counts;
-    const size_t b_trace = b_models + b_samples + b_counts;
-    /* pinned: [points][record + mask][trace] */
-    const size_t g_down = b_pts, g_trace = g_down + HEAD + b_mask, h_need = g_trace + b_trace;
-    if (!grow(ok, v, d_need, h_need)) return ok.rc;
+    const Frame  f = frame(n);
+    const size_t b_models = round16(sizeof(float) * 9 * (size_t)T), b_samples = sizeof(int) * K::row * (size_t)T,
+                 b_counts = round16(sizeof(int) * (size_t)T), b_trace = b_models + b_samples + b_counts;
+    /* the call's own arrays: [models][samples][counts], contiguous for the trace */
+    const size_t o_models = f.d_own, o_samples = o_models + b_models, o_counts = o_samples + b_samples;
+    if (!grow(ok, v, o_counts + b_counts, f.h_own + b_trace)) return ok.rc;
     hipStream_t const s = v->stream;
     char* const       d = v->d_buf;
     auto* const       d_bounds = (uint32_t*)d;
-    auto* const       d_res = (popsift_hip_ransac_result*)(d + o_head);
-    auto* const       d_pts = (const v4f*)(d + o_pts);
+    auto* const       d_res = (popsift_hip_ransac_result*)(d + f.o_head);
+    auto* const       d_mask = (uint32_t*)(d + f.o_mask);
+    auto* const       d_pts = (const v4f*)(d + f.o_pts);
     auto* const       d_models = (float*)(d + o_models);
     auto* const       d_samples = (int*)(d + o_samples);
     auto* const       d_counts = (int*)(d + o_counts);
     const float       max_err2 = fit.max_err * fit.max_err;
 
-    memcpy(v->h_buf, pts, b_pts);
-    ok(hipMemcpyAsync(d + o_pts, v->h_buf, b_pts, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, 32, s));
-    if (ok.good()) {
-        const int blocks = std::min((n + 255) / 256, 512);
-        hipLaunchKernelGGL(k_ransac_bounds, dim3(blocks), dim3(256), 0, s, d_pts, n, d_bounds);
+    if (upload(ok, v, f, pts, n)) {
         const dim3 g_models((T + 63) / 64), g_score((T + S_HYP - 1) / S_HYP, (n + S_CHUNK - 1) / S_CHUNK), g_mask((n + 1023) / 1024);
-        auto* const d_mask = (uint32_t*)(d + o_mask);
-        if (fit.what == FIT_AFFINE)
-            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_AFFINE>, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed, d_bounds,
-                               d_models, d_samples, d_counts);
-        else if (fit.what == FIT_HOMOGRAPHY)
-            hipLaunchKernelGGL(k_ransac_models<POPSIFT_HIP_MODEL_HOMOGRAPHY>, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed,
-                               d_bounds, d_models, d_samples, d_counts);
-        else
+        if constexpr (KIND == FIT_EPIPOLAR)
             hipLaunchKernelGGL(k_epipolar_models, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed, d_bounds, d_models, d_samples,
                                d_counts);
-        if (fit.what == FIT_EPIPOLAR)
-            hipLaunchKernelGGL(k_ransac_score<Sampson>, g_score, dim3(S_BLOCK), 0, s, d_pts, n, d_models, T, max_err2, d_counts);
         else
-            hipLaunchKernelGGL(k_ransac_score<Transfer>, g_score, dim3(S_BLOCK), 0, s, d_pts, n, d_models, T, max_err2, d_counts);
-        hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, s, d_counts, d_models, T, m, d_res);
-        if (fit.what == FIT_EPIPOLAR)
-            hipLaunchKernelGGL(k_ransac_mask<Sampson>, g_mask, dim3(256), 0, s, d_pts, n, d_res, max_err2, d_mask);
-        else
-            hipLaunchKernelGGL(k_ransac_mask<Transfer>, g_mask, dim3(256), 0, s, d_pts, n, d_res, max_err2, d_mask);
+            hipLaunchKernelGGL(k_ransac_models<KIND>, g_models, dim3(64), 0, s, d_pts, n, T, fit.seed, d_bounds, d_models,
+                               d_samples, d_counts);
+        hipLaunchKernelGGL(k_ransac_score<Rule>, g_score, dim3(S_BLOCK), 0, s, d_pts, n, d_models, T, max_err2, d_counts);
+        hipLaunchKernelGGL(k_ransac_select, dim3(1), dim3(256), 0, s, d_counts, d_models, T, K::m, d_res);
+        hipLaunchKernelGGL(k_ransac_mask<Rule>, g_mask, dim3(256), 0, s, d_pts, n, d_res, max_err2, d_mask);
         ok(hipGetLastError());
     }
-    const size_t down = HEAD + (inlier ? (size_t)n : 0);
-    ok.good() && ok(hipMemcpyAsync(v->h_buf + g_down, d + o_head, down, hipMemcpyDeviceToHost, s));
-    if (ok.good() && trace) ok(hipMemcpyAsync(v->h_buf + g_trace, d + o_models, b_trace, hipMemcpyDeviceToHost, s));
-    if (ok.good() && ok(hipStreamSynchronize(s))) {
-        if (res) memcpy(res, v->h_buf + g_down, sizeof *res);
-        if (inlier) memcpy(inlier, v->h_buf + g_down + HEAD, (size_t)n);
-        const char* tr = v->h_buf + g_trace;
+    if (download(ok, v, f, n, inlier, o_models, trace ? b_trace : 0)) {
+        if (res) memcpy(res, v->h_buf + f.g_down, sizeof *res);
+        const char* tr = v->h_buf + f.h_own;
         if (models) memcpy(models, tr, sizeof(float) * 9 * (size_t)T);
         if (samples) memcpy(samples, tr + b_models, b_samples);
         if (counts) memcpy(counts, tr + b_models + b_samples, sizeof(int) * (size_t)T);
     }
     return ok.rc;
+}
+
+/* popsift_hip_ransac and its trace: the model of the options becomes the kind here */
+int run_ransac(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, popsift_hip_ransac_result* res,
+               uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+{
+    if (!opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    const Fit fit{o->hypotheses, o->max_err, o->seed};
+    return o->model == FIT_AFFINE ? run<FIT_AFFINE>(v, pts, n, fit, res, inlier, trace, samples, models, counts)
+                                  : run<FIT_HOMOGRAPHY>(v, pts, n, fit, res, inlier, trace, samples, models, counts);
+}
+
+int run_epipolar(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
+                 popsift_hip_ransac_result* res, uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+{
+    if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return run<FIT_EPIPOLAR>(v, pts, n, Fit{o->hypotheses, o->max_err, o->seed}, res, inlier, trace, samples, models, counts);
 }
 
 bool refit_opts_valid(const popsift_hip_refit_opts* o)
@@ -1233,34 +1207,16 @@ bool refit_opts_valid(const popsift_hip_refit_opts* o)
     return o->reserved[0] == 0 && o->reserved[1] == 0 && o->reserved[2] == 0 && o->reserved[3] == 0;
 }
 
+/* popsift_hip_refit and its trace for one kind.  As in run() the layout of the scratch is a function of the arguments, and
+ * every byte the call reads it has written before. */
 template <int KIND>
-void launch_refit(hipStream_t s, const v4f* d_pts, int n, const uint32_t* d_bounds, RefitState* d_st, RefitTrace* d_tr,
-                  double* d_blocks, double* d_spare, int rounds, float max_err2, uint32_t* d_mask)
-{
-    typedef typename RefitKind<KIND>::Rule Rule;
-    const int  chunks = (n + F_CHUNK - 1) / F_CHUNK, m = RefitKind<KIND>::m;
-    const dim3 g_quads((n + 1023) / 1024);
-    hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, dim3(256), 0, s, d_pts, n, d_st->H, max_err2, &d_st->n_inliers, &d_st->done);
-    hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, -1, m);
-    for (int r = 0; r < rounds; r++) {
-        hipLaunchKernelGGL(k_refit_accumulate<KIND>, dim3(chunks), dim3(256), 0, s, d_pts, n, d_bounds, d_st, max_err2, d_blocks);
-        hipLaunchKernelGGL(k_refit_solve<KIND>, dim3(1), dim3(256), 0, s, d_blocks, d_spare, chunks, d_bounds, d_st, d_tr, r);
-        hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, dim3(256), 0, s, d_pts, n, d_tr->models[r], max_err2, &d_tr->counts[r],
-                           &d_st->done);
-        hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, r, m);
-    }
-    hipLaunchKernelGGL(k_ransac_mask<Rule>, g_quads, dim3(256), 0, s, d_pts, n, (const popsift_hip_ransac_result*)d_st, max_err2,
-                       d_mask);
-}
-
-/* popsift_hip_refit and its trace.  As in run() the layout of the scratch is a function of the arguments, and every byte
- * the call reads it has written before. */
 int run_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o, popsift_hip_refit_result* res,
               uint8_t* inlier, bool trace, double* sums, float* models, int32_t* counts, int32_t* accepted)
 {
-    if (!refit_opts_valid(o) || !v || !res || n < 0 || n > MAX_PAIRS || (n > 0 && !pts)) return POPSIFT_HIP_ERR_INVALID;
+    typedef typename Kind<KIND>::Rule Rule;
+    constexpr int                     m = Kind<KIND>::m;
+    if (!args_valid(v, pts, n) || !res) return POPSIFT_HIP_ERR_INVALID;
     const int R = o->rounds;
-    const int m = o->model == POPSIFT_HIP_REFIT_EPIPOLAR ? POPSIFT_HIP_EPIPOLAR_SAMPLE : o->model == POPSIFT_HIP_REFIT_AFFINE ? 3 : 4;
     if (n < m) { /* no model of this kind has support */
         memcpy(res->M, o->M, sizeof res->M);
         res->n_inliers = res->n_start = res->rounds = 0;
@@ -1274,61 +1230,66 @@ int run_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hi
     }
     if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     Status       ok;
-    const size_t chunks = ((size_t)n + F_CHUNK - 1) / F_CHUNK;
-    const size_t b_pts = sizeof(float) * 4 * (size_t)n, b_mask = round16((size_t)n), b_trace = round16(sizeof(RefitTrace)),
-                 b_blocks = round16(sizeof(double) * F_SLOTS * chunks), b_spare = round16(sizeof(double) * F_SLOTS * ((chunks + 1) / 2));
-    /* device: [bounds 32][state 64][mask][points][trace][chunk sums][spare]; the state and the mask come down together */
-    const size_t o_head = 32, o_mask = o_head + HEAD, o_pts = o_mask + b_mask, o_trace = o_pts + b_pts, o_blocks = o_trace + b_trace,
-                 o_spare = o_blocks + b_blocks, d_need = o_spare + b_spare;
-    /* pinned: [points][state + mask][trace] */
-    const size_t g_down = b_pts, g_trace = g_down + HEAD + b_mask, h_need = g_trace + b_trace;
-    if (!grow(ok, v, d_need, h_need)) return ok.rc;
+    const Frame  f = frame(n);
+    const int    chunks = (n + F_CHUNK - 1) / F_CHUNK;
+    const size_t b_trace = round16(sizeof(RefitTrace)), b_blocks = round16(sizeof(double) * F_SLOTS * (size_t)chunks),
+                 b_spare = round16(sizeof(double) * F_SLOTS * (((size_t)chunks + 1) / 2));
+    /* the call's own arrays: [trace][chunk sums][spare] */
+    const size_t o_trace = f.d_own, o_blocks = o_trace + b_trace, o_spare = o_blocks + b_blocks;
+    if (!grow(ok, v, o_spare + b_spare, f.h_own + b_trace)) return ok.rc;
     hipStream_t const s = v->stream;
     char* const       d = v->d_buf;
     auto* const       d_bounds = (uint32_t*)d;
-    auto* const       d_st = (RefitState*)(d + o_head);
-    auto* const       d_pts = (const v4f*)(d + o_pts);
+    auto* const       d_st = (RefitState*)(d + f.o_head);
+    auto* const       d_mask = (uint32_t*)(d + f.o_mask);
+    auto* const       d_pts = (const v4f*)(d + f.o_pts);
     auto* const       d_tr = (RefitTrace*)(d + o_trace);
     auto* const       d_blocks = (double*)(d + o_blocks);
     auto* const       d_spare = (double*)(d + o_spare);
-    auto* const       d_mask = (uint32_t*)(d + o_mask);
     const float       max_err2 = o->max_err * o->max_err;
 
-    memcpy(v->h_buf, pts, b_pts);
-    ok(hipMemcpyAsync(d + o_pts, v->h_buf, b_pts, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, 32, s)) &&
-        ok(hipMemsetAsync(d_tr, 0, b_trace, s));
-    if (ok.good()) {
+    if (upload(ok, v, f, pts, n) && ok(hipMemsetAsync(d_tr, 0, b_trace, s))) {
         RefitStart start;
         memcpy(start.M, o->M, sizeof start.M);
-        hipLaunchKernelGGL(k_ransac_bounds, dim3(std::min((n + 255) / 256, 512)), dim3(256), 0, s, d_pts, n, d_bounds);
+        const dim3 g_quads((n + 1023) / 1024), g_chunks(chunks), wg(256);
         hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, start, d_st, d_tr);
-        if (o->model == POPSIFT_HIP_REFIT_HOMOGRAPHY)
-            launch_refit<POPSIFT_HIP_REFIT_HOMOGRAPHY>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
-        else if (o->model == POPSIFT_HIP_REFIT_AFFINE)
-            launch_refit<POPSIFT_HIP_REFIT_AFFINE>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
-        else
-            launch_refit<POPSIFT_HIP_REFIT_EPIPOLAR>(s, d_pts, n, d_bounds, d_st, d_tr, d_blocks, d_spare, R, max_err2, d_mask);
+        hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, wg, 0, s, d_pts, n, d_st->H, max_err2, &d_st->n_inliers, &d_st->done);
+        hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, -1, m);
+        for (int r = 0; r < R; r++) {
+            hipLaunchKernelGGL(k_refit_accumulate<KIND>, g_chunks, wg, 0, s, d_pts, n, d_bounds, d_st, max_err2, d_blocks);
+            hipLaunchKernelGGL(k_refit_solve<KIND>, dim3(1), wg, 0, s, d_blocks, d_spare, chunks, d_bounds, d_st, d_tr, r);
+            hipLaunchKernelGGL(k_refit_count<Rule>, g_quads, wg, 0, s, d_pts, n, d_tr->models[r], max_err2, &d_tr->counts[r],
+                               &d_st->done);
+            hipLaunchKernelGGL(k_refit_decide, dim3(1), dim3(64), 0, s, d_st, d_tr, r, m);
+        }
+        hipLaunchKernelGGL(k_ransac_mask<Rule>, g_quads, wg, 0, s, d_pts, n, (const popsift_hip_ransac_result*)d_st, max_err2, d_mask);
         ok(hipGetLastError());
     }
-    const size_t down = HEAD + (inlier ? (size_t)n : 0);
-    ok.good() && ok(hipMemcpyAsync(v->h_buf + g_down, d + o_head, down, hipMemcpyDeviceToHost, s));
-    if (ok.good() && trace) ok(hipMemcpyAsync(v->h_buf + g_trace, d + o_trace, sizeof(RefitTrace), hipMemcpyDeviceToHost, s));
-    if (ok.good() && ok(hipStreamSynchronize(s))) {
+    if (download(ok, v, f, n, inlier, o_trace, trace ? sizeof(RefitTrace) : 0)) {
         RefitState st;
-        memcpy(&st, v->h_buf + g_down, sizeof st);
+        memcpy(&st, v->h_buf + f.g_down, sizeof st);
         memcpy(res->M, st.H, sizeof res->M);
         res->n_inliers = st.n_inliers;
         res->n_start = st.n_start;
         res->rounds = st.rounds;
         res->stop = st.stop;
-        if (inlier) memcpy(inlier, v->h_buf + g_down + HEAD, (size_t)n);
-        const RefitTrace* tr = (const RefitTrace*)(v->h_buf + g_trace);
+        const RefitTrace* tr = (const RefitTrace*)(v->h_buf + f.h_own);
         if (sums) memcpy(sums, tr->sums, sizeof(double) * F_SLOTS * (size_t)R);
         if (models) memcpy(models, tr->models, sizeof(float) * 9 * (size_t)R);
         if (counts) memcpy(counts, tr->counts, sizeof(int32_t) * (size_t)R);
         if (accepted) memcpy(accepted, tr->accepted, sizeof(int32_t) * (size_t)R);
     }
     return ok.rc;
+}
+
+/* popsift_hip_refit and its trace: the model of the options becomes the kind here */
+int refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o, popsift_hip_refit_result* res,
+          uint8_t* inlier, bool trace, double* sums, float* models, int32_t* counts, int32_t* accepted)
+{
+    if (!refit_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
+    return o->model == FIT_HOMOGRAPHY ? run_refit<FIT_HOMOGRAPHY>(v, pts, n, o, res, inlier, trace, sums, models, counts, accepted)
+           : o->model == FIT_AFFINE   ? run_refit<FIT_AFFINE>(v, pts, n, o, res, inlier, trace, sums, models, counts, accepted)
+                                      : run_refit<FIT_EPIPOLAR>(v, pts, n, o, res, inlier, trace, sums, models, counts, accepted);
 }
 
 }  // namespace
@@ -1348,14 +1309,14 @@ void popsift_hip_default_refit_opts(popsift_hip_refit_opts* o)
 int popsift_hip_refit(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
                       popsift_hip_refit_result* res, uint8_t* inlier)
 {
-    return run_refit(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr, nullptr);
+    return refit(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr, nullptr);
 }
 
 int popsift_hip_refit_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
                             popsift_hip_refit_result* res, uint8_t* inlier, double* sums, float* models, int32_t* counts,
                             int32_t* accepted)
 {
-    return run_refit(v, pts, n, o, res, inlier, true, sums, models, counts, accepted);
+    return refit(v, pts, n, o, res, inlier, true, sums, models, counts, accepted);
 }
 
 int popsift_hip_verifier_create(int device, popsift_hip_verifier** out)
@@ -1401,15 +1362,13 @@ void popsift_hip_default_ransac_opts(popsift_hip_ransac_opts* o)
 int popsift_hip_ransac(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o,
                        popsift_hip_ransac_result* res, uint8_t* inlier)
 {
-    if (!opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
-    return run(v, pts, n, Fit{o->model, o->hypotheses, o->max_err, o->seed}, res, inlier, false, nullptr, nullptr, nullptr);
+    return run_ransac(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr);
 }
 
 int popsift_hip_ransac_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_ransac_opts* o, int32_t* samples,
                              float* models, int32_t* counts)
 {
-    if (!opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
-    return run(v, pts, n, Fit{o->model, o->hypotheses, o->max_err, o->seed}, nullptr, nullptr, true, samples, models, counts);
+    return run_ransac(v, pts, n, o, nullptr, nullptr, true, samples, models, counts);
 }
 
 void popsift_hip_default_epipolar_opts(popsift_hip_epipolar_opts* o)
@@ -1424,15 +1383,13 @@ void popsift_hip_default_epipolar_opts(popsift_hip_epipolar_opts* o)
 int popsift_hip_epipolar(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
                          popsift_hip_ransac_result* res, uint8_t* inlier)
 {
-    if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
-    return run(v, pts, n, Fit{FIT_EPIPOLAR, o->hypotheses, o->max_err, o->seed}, res, inlier, false, nullptr, nullptr, nullptr);
+    return run_epipolar(v, pts, n, o, res, inlier, false, nullptr, nullptr, nullptr);
 }
 
 int popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_epipolar_opts* o,
                                int32_t* samples, float* models, int32_t* counts)
 {
-    if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
-    return run(v, pts, n, Fit{FIT_EPIPOLAR, o->hypotheses, o->max_err, o->seed}, nullptr, nullptr, true, samples, models, counts);
+    return run_epipolar(v, pts, n, o, nullptr, nullptr, true, samples, models, counts);
 }
 
 int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r, const popsift_hip_pair* pairs,
