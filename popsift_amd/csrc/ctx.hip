@@ -15,7 +15,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstddef>
@@ -23,7 +22,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <type_traits>
 #include <vector>
 
 #include "devfeatures.h"
@@ -1781,23 +1779,10 @@ int popsift_hip_devfeatures_free(popsift_hip_devfeatures* f)
 {
     if (!f) return POPSIFT_HIP_OK;
     (void)hipSetDevice(f->device);
-    if (f->d_feat) (void)hipFree(f->d_feat);
-    if (f->d_desc) (void)hipFree(f->d_desc);
-    if (f->d_rev) (void)hipFree(f->d_rev);
-    if (f->m_stream) (void)hipStreamDestroy((hipStream_t)f->m_stream);
-    if (f->m_partial) (void)hipFree(f->m_partial);
-    if (f->m_out) (void)hipFree(f->m_out);
-    if (f->m_host) (void)hipHostFree(f->m_host);
-    if (f->m_redo) (void)hipFree(f->m_redo);
-    if (f->d_norm) (void)hipFree(f->d_norm);
-    if (f->m_rnorm) (void)hipFree(f->m_rnorm);
-    if (f->p_pairs) (void)hipFree(f->p_pairs);
-    if (f->p_host) (void)hipHostFree(f->p_host);
-    if (f->p_idx) (void)hipFree(f->p_idx);
-    if (f->p_back) (void)hipFree(f->p_back);
-    if (f->v_buf) (void)hipFree(f->v_buf);
+    f->release();
+    for (void* p : {(void*)f->d_feat, (void*)f->d_desc, (void*)f->d_rev, (void*)f->d_norm, (void*)f->m_redo, f->v_buf, f->g_buf})
+        if (p) (void)hipFree(p);
     if (f->v_host) (void)hipHostFree(f->v_host);
-    if (f->g_buf) (void)hipFree(f->g_buf);
     if (f->g_host) (void)hipHostFree(f->g_host);
     delete f;
     return POPSIFT_HIP_OK;
@@ -1946,12 +1931,9 @@ int popsift_hip_bytefeatures_free(popsift_hip_bytefeatures* f)
 {
     if (!f) return POPSIFT_HIP_OK;
     (void)hipSetDevice(f->device);
-    if (f->m_stream) (void)hipStreamDestroy((hipStream_t)f->m_stream);
-    for (void* p : {(void*)f->d_desc, (void*)f->d_rev, f->m_partial, f->m_out, (void*)f->d_norm, (void*)f->m_rnorm, f->p_pairs,
-                    (void*)f->p_idx, f->p_back})
+    f->release();
+    for (void* p : {(void*)f->d_desc, (void*)f->d_rev, (void*)f->d_norm})
         if (p) (void)hipFree(p);
-    if (f->m_host) (void)hipHostFree(f->m_host);
-    if (f->p_host) (void)hipHostFree(f->p_host);
     delete f;
     return POPSIFT_HIP_OK;
 }
@@ -2065,328 +2047,6 @@ int popsift_hip_bytefeatures_download(const popsift_hip_bytefeatures* f, uint8_t
     if (rev && hipMemcpy(rev, f->d_rev, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
         return POPSIFT_HIP_ERR_DEVICE;
     return POPSIFT_HIP_OK;
-}
-
-static std::atomic<int> g_match_path{POPSIFT_HIP_MATCH_AUTO};
-
-int popsift_hip_match_set_path(int path)
-{
-    if (path < POPSIFT_HIP_MATCH_AUTO || path > POPSIFT_HIP_MATCH_SCREEN) return POPSIFT_HIP_ERR_INVALID;
-    g_match_path.store(path);
-    return POPSIFT_HIP_OK;
-}
-
-} /* extern "C" */
-
-namespace {
-
-/* the first failing HIP call of a match decides its status; the calls after it are skipped */
-struct MatchStatus {
-    int  rc = POPSIFT_HIP_OK;
-    bool good() const { return rc == POPSIFT_HIP_OK; }
-    bool operator()(hipError_t e)
-    {
-        if (e != hipSuccess && rc == POPSIFT_HIP_OK) rc = (e == hipErrorOutOfMemory) ? POPSIFT_HIP_ERR_OOM : POPSIFT_HIP_ERR_DEVICE;
-        return e == hipSuccess;
-    }
-};
-
-/* grow-only scratch of a left set: `cap` counts units of `unit` bytes */
-template <class T>
-bool match_grow(MatchStatus& ok, T*& p, size_t& cap, size_t need, size_t unit)
-{
-    if (!ok.good()) return false;
-    if (need <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (ok(hipMalloc((void**)&p, need * unit))) cap = need;
-    return ok.good();
-}
-
-/* large problems: matrix-core screening + exact re-rank (match_mfma.hip); small ones and POPSIFT_HIP_MATCH_EXACT: the
- * exact brute-force kernel alone (match.hip) */
-bool match_screens(int path, int l_len, int r_len)
-{
-    return path == POPSIFT_HIP_MATCH_SCREEN || (path == POPSIFT_HIP_MATCH_AUTO && (double)l_len * (double)r_len >= 4.0e6);
-}
-
-/* |x|^2 of the set's own descriptors (and launch_norms' flag behind them), computed on first use */
-void match_own_norms(MatchStatus& ok, popsift_hip_devfeatures* f, hipStream_t s)
-{
-    if (ok.good() && !f->d_norm && ok(hipMalloc((void**)&f->d_norm, sizeof(float) * ((size_t)f->n_desc + 1))))
-        ok(launch_norms(f->d_desc, f->n_desc, f->d_norm, s));
-}
-
-/* One 2-NN sweep of l_len descriptors against r_len on stream s: d_out[l_len] on the device.  The candidate buffer is
- * `own`'s; with screening the norms of both sides are ready and redo = [count, rows the screening pass leaves to the
- * exact kernel ...] has room for l_len rows. */
-void match_sweep(MatchStatus& ok, popsift_hip_devfeatures* own, bool screen, const float* ldesc, int l_len, const float* lnorm,
-                 const float* rdesc, int r_len, const float* rnorm, popsift_hip_match* d_out, int* redo, hipStream_t s)
-{
-    const int n_split = match_splits(l_len, r_len);
-    const int s_split = screen ? screen_splits(l_len, r_len) : 1;
-    /* rows the screening pass cannot decide are few: the first REDO_CAP of them are matched with the right set split
-     * over many workgroups, a second launch (normally empty) covers the rest of the list */
-    const int REDO_CAP = 2048;
-    const int redo_split = std::min(256, std::max((r_len + 63) / 64, 1));
-    size_t    need = match_partial_bytes(l_len, n_split);
-    if (screen) need = std::max(need, screen_partial_bytes(l_len, s_split));
-    if (screen) need = std::max(need, match_partial_bytes(REDO_CAP, redo_split));
-    if (!match_grow(ok, own->m_partial, own->m_partial_cap, need, 1)) return;
-    if (screen) {
-        ok(launch_match_screen(ldesc, l_len, rdesc, r_len, lnorm, rnorm, s_split, own->m_partial, d_out, redo + 1, redo, s)) &&
-            ok(launch_match(ldesc, l_len, rdesc, r_len, redo_split, own->m_partial, d_out, redo + 1, redo, 0, REDO_CAP, s)) &&
-            ok(launch_match(ldesc, l_len, rdesc, r_len, n_split, own->m_partial, d_out, redo + 1, redo, REDO_CAP, l_len, s));
-    } else {
-        ok(launch_match(ldesc, l_len, rdesc, r_len, n_split, own->m_partial, d_out, nullptr, nullptr, 0, 0, s));
-    }
-}
-
-/* The sweep of l against r into l->m_out, enqueued on l's stream (l->n_desc > 0, l's GPU current).  *rdesc: r's
- * descriptors on l's GPU; when that is a copy, *r_copy is the caller's to free. */
-void match_forward(MatchStatus& ok, popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, int path, const float** rdesc,
-                   float** r_copy)
-{
-    *rdesc = r->d_desc;
-    *r_copy = nullptr;
-    /* the scratch buffers live in the left set (one match at a time per left set, like one image at a time per context) */
-    if (!l->m_stream) {
-        hipStream_t s = nullptr;
-        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
-    }
-    if (ok.good() && !l->m_out) ok(hipMalloc(&l->m_out, sizeof(popsift_hip_match) * (size_t)l->n_desc));
-    if (ok.good() && r->device != l->device && r->n_desc > 0) {
-        /* images of one PopSift object may have been extracted on different GPUs: bring the right set over (xGMI) */
-        const size_t bytes = sizeof(float) * 128 * (size_t)r->n_desc;
-        if (ok(hipMalloc((void**)r_copy, bytes)) && ok(hipMemcpyPeer(*r_copy, l->device, r->d_desc, r->device, bytes)))
-            *rdesc = *r_copy;
-    }
-    hipStream_t s = (hipStream_t)l->m_stream;
-    const bool  screen = match_screens(path, l->n_desc, r->n_desc);
-    if (ok.good() && screen) {
-        if (!l->m_redo) ok(hipMalloc((void**)&l->m_redo, sizeof(int) * ((size_t)l->n_desc + 1)));
-        match_own_norms(ok, l, s);
-        /* the right set may be the left set of another thread's match: its norms go to a buffer of this call */
-        if (match_grow(ok, l->m_rnorm, l->m_rnorm_cap, (size_t)r->n_desc + 1, sizeof(float)))
-            ok(launch_norms(*rdesc, r->n_desc, l->m_rnorm, s));
-    }
-    if (ok.good())
-        match_sweep(ok, l, screen, l->d_desc, l->n_desc, l->d_norm, *rdesc, r->n_desc, l->m_rnorm, (popsift_hip_match*)l->m_out,
-                    l->m_redo, s);
-}
-
-/* The reverse sweep of the cross-check: the n_list right descriptors of `list` (ascending) against all of l, on l's
- * stream; returns their rows, in list order, in l's p_back. */
-const popsift_hip_match* match_reverse(MatchStatus& ok, popsift_hip_devfeatures* l, const float* rdesc, const int* list,
-                                       int n_list, int path)
-{
-    const int    l_len = l->n_desc;
-    hipStream_t  s = (hipStream_t)l->m_stream;
-    /* per member of J: 128 floats, a result row, a norm and a redo slot (+ the norms' flag and the redo count) */
-    const size_t per = sizeof(float) * 128 + sizeof(popsift_hip_match) + sizeof(float) + sizeof(int);
-    if (!match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list + 1, per)) return nullptr;
-    float* const gdesc = (float*)l->p_back;
-    auto* const  rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
-    float* const gnorm = (float*)(rows + n_list);
-    int* const   redo = (int*)(gnorm + n_list + 1);
-    const bool   screen = match_screens(path, n_list, l_len);
-    ok(launch_gather_rows(rdesc, list, n_list, gdesc, s));
-    if (screen) {
-        match_own_norms(ok, l, s);
-        if (ok.good()) ok(launch_norms(gdesc, n_list, gnorm, s));
-    }
-    if (ok.good()) match_sweep(ok, l, screen, gdesc, n_list, gnorm, l->d_desc, l_len, l->d_norm, rows, redo, s);
-    return rows;
-}
-
-/* ---- the same three steps for byte sets (match_u8.hip): one exact kernel, no path choice */
-
-void match_own_norms(MatchStatus& ok, popsift_hip_bytefeatures* f, hipStream_t s)
-{
-    if (ok.good() && !f->d_norm && ok(hipMalloc((void**)&f->d_norm, sizeof(int) * (size_t)f->n_desc)))
-        ok(launch_norms_u8(f->d_desc, f->n_desc, f->d_norm, s));
-}
-
-void match_sweep_u8(MatchStatus& ok, popsift_hip_bytefeatures* own, const uint8_t* ldesc, int l_len, const int* lnorm,
-                    const uint8_t* rdesc, int r_len, const int* rnorm, popsift_hip_match* d_out, hipStream_t s)
-{
-    const int n_split = match_u8_splits(l_len, r_len);
-    if (!match_grow(ok, own->m_partial, own->m_partial_cap, match_u8_partial_bytes(l_len, n_split), 1)) return;
-    ok(launch_match_u8(ldesc, l_len, lnorm, rdesc, r_len, rnorm, n_split, own->m_partial, d_out, s));
-}
-
-void match_forward(MatchStatus& ok, popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, int /*path*/,
-                   const uint8_t** rdesc, uint8_t** r_copy)
-{
-    *rdesc = r->d_desc;
-    *r_copy = nullptr;
-    if (!l->m_stream) {
-        hipStream_t s = nullptr;
-        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
-    }
-    if (ok.good() && !l->m_out) ok(hipMalloc(&l->m_out, sizeof(popsift_hip_match) * (size_t)l->n_desc));
-    if (ok.good() && r->device != l->device && r->n_desc > 0) {
-        const size_t bytes = (size_t)128 * (size_t)r->n_desc;
-        if (ok(hipMalloc((void**)r_copy, bytes)) && ok(hipMemcpyPeer(*r_copy, l->device, r->d_desc, r->device, bytes)))
-            *rdesc = *r_copy;
-    }
-    hipStream_t s = (hipStream_t)l->m_stream;
-    match_own_norms(ok, l, s);
-    /* the right set may be the left set of another thread's match: its norms go to a buffer of this call */
-    if (match_grow(ok, l->m_rnorm, l->m_rnorm_cap, (size_t)r->n_desc, sizeof(int)))
-        ok(launch_norms_u8(*rdesc, r->n_desc, l->m_rnorm, s));
-    if (ok.good())
-        match_sweep_u8(ok, l, l->d_desc, l->n_desc, l->d_norm, *rdesc, r->n_desc, l->m_rnorm, (popsift_hip_match*)l->m_out, s);
-}
-
-const popsift_hip_match* match_reverse(MatchStatus& ok, popsift_hip_bytefeatures* l, const uint8_t* rdesc, const int* list,
-                                       int n_list, int /*path*/)
-{
-    hipStream_t  s = (hipStream_t)l->m_stream;
-    /* per member of J: 128 bytes, a result row and a norm */
-    const size_t per = 128 + sizeof(popsift_hip_match) + sizeof(int);
-    if (!match_grow(ok, l->p_back, l->p_back_cap, (size_t)n_list, per)) return nullptr;
-    uint8_t* const gdesc = (uint8_t*)l->p_back;
-    auto* const    rows = (popsift_hip_match*)(gdesc + 128 * (size_t)n_list);
-    int* const     gnorm = (int*)(rows + n_list);
-    ok(launch_gather_rows_u8(rdesc, list, n_list, gdesc, s)) && ok(launch_norms_u8(gdesc, n_list, gnorm, s));
-    if (ok.good()) match_sweep_u8(ok, l, gdesc, n_list, gnorm, l->d_desc, l->n_desc, l->d_norm, rows, s);
-    return rows;
-}
-
-/* popsift_hip_match_sets / popsift_hip_match_bytes */
-template <class Set>
-int match_rows(const Set* lc, const Set* r, popsift_hip_match* out, int path)
-{
-    if (!lc || !r || (lc->n_desc > 0 && !out)) return POPSIFT_HIP_ERR_INVALID;
-    if (lc->n_desc == 0) return POPSIFT_HIP_OK;
-    Set* l = const_cast<Set*>(lc);
-    if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    typedef typename std::remove_pointer<decltype(l->d_desc)>::type Elem;
-    MatchStatus  ok;
-    const Elem*  rdesc = nullptr;
-    Elem*        r_copy = nullptr;
-    const size_t out_bytes = sizeof(popsift_hip_match) * (size_t)l->n_desc;
-    match_forward(ok, l, r, path, &rdesc, &r_copy);
-    if (ok.good() && !l->m_host) ok(hipHostMalloc(&l->m_host, out_bytes, hipHostMallocDefault));
-    hipStream_t s = (hipStream_t)l->m_stream;
-    if (ok.good() && ok(hipMemcpyAsync(l->m_host, l->m_out, out_bytes, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s)))
-        memcpy(out, l->m_host, out_bytes);
-    if (r_copy) (void)hipFree(r_copy);
-    return ok.rc;
-}
-
-/* popsift_hip_match_pairs / popsift_hip_match_pairs_bytes */
-template <class Set>
-int match_pairs(const Set* lc, const Set* r, const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap,
-                int* n_pairs, int path)
-{
-    if (!lc || !r || !opts || !n_pairs || (cap > 0 && !pairs)) return POPSIFT_HIP_ERR_INVALID;
-    if (!(opts->ratio >= 0.0f) || std::isinf(opts->ratio) || std::isnan(opts->max_dist2) || opts->reserved != 0 ||
-        (opts->cross_check != 0 && opts->cross_check != 1))
-        return POPSIFT_HIP_ERR_INVALID;
-    *n_pairs = 0;
-    if (lc->n_desc == 0 || r->n_desc == 0) return POPSIFT_HIP_OK;
-    Set* l = const_cast<Set*>(lc);
-    if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    typedef typename std::remove_pointer<decltype(l->d_desc)>::type Elem;
-    const int    l_len = l->n_desc, r_len = r->n_desc;
-    MatchStatus  ok;
-    const Elem*  rdesc = nullptr;
-    Elem*        r_copy = nullptr;
-    match_forward(ok, l, r, path, &rdesc, &r_copy);
-    hipStream_t  s = (hipStream_t)l->m_stream;
-    const auto*  fwd = (const popsift_hip_match*)l->m_out;
-    /* device block and its pinned twin: the two counts, then the pairs */
-    const size_t head = sizeof(popsift_hip_pair), block = head + sizeof(popsift_hip_pair) * (size_t)l_len;
-    if (ok.good() && !l->p_pairs) ok(hipMalloc(&l->p_pairs, block));
-    if (ok.good() && !l->p_host) ok(hipHostMalloc(&l->p_host, block, hipHostMallocDefault));
-    int* const   d_count = (int*)l->p_pairs; /* [0] pairs, [1] |J| */
-    const size_t n_counts = (size_t)std::max(pair_count_blocks(l_len), pair_count_blocks(r_len));
-    match_grow(ok, l->p_idx, l->p_idx_cap, n_counts + (opts->cross_check ? 3 * (size_t)r_len : 0), sizeof(int));
-    int*                     counts = l->p_idx;
-    const popsift_hip_match* back = nullptr;
-    const int*               rank = nullptr;
-    size_t                   most = std::min(cap, (size_t)l_len); /* pairs the download has to cover */
-    if (ok.good() && opts->cross_check) {
-        /* J: the right descriptors a passing row points to.  Only their nearest left neighbours matter. */
-        int* const flags = l->p_idx + n_counts;
-        int* const list = flags + 2 * (size_t)r_len;
-        rank = flags + r_len;
-        int n_list = 0;
-        /* |J| sizes the reverse sweep's launches and buffers: one 4-byte read-back between the sweeps */
-        if (ok(launch_pair_targets(fwd, l_len, r_len, opts->ratio, opts->max_dist2, flags, counts, list, (int*)rank,
-                                   d_count + 1, s)) &&
-            ok(hipMemcpyAsync(l->p_host, d_count + 1, sizeof(int), hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s)))
-            n_list = *(const int*)l->p_host;
-        if (ok.good() && n_list == 0) { /* no row passes */
-            if (r_copy) (void)hipFree(r_copy);
-            return POPSIFT_HIP_OK;
-        }
-        back = match_reverse(ok, l, rdesc, list, n_list, path);
-        most = std::min(most, (size_t)n_list); /* every member of J has one nearest left descriptor */
-    }
-    auto* const d_pairs = (popsift_hip_pair*)((char*)l->p_pairs + head);
-    if (ok.good() &&
-        ok(launch_pair_emit(fwd, l_len, opts->ratio, opts->max_dist2, back, rank, counts, d_pairs, d_count, s)) &&
-        ok(hipMemcpyAsync(l->p_host, l->p_pairs, head + sizeof(popsift_hip_pair) * most, hipMemcpyDeviceToHost, s)) &&
-        ok(hipStreamSynchronize(s))) {
-        const int total = *(const int*)l->p_host;
-        *n_pairs = total;
-        const size_t n = std::min((size_t)total, cap);
-        if (n > 0) memcpy(pairs, (const char*)l->p_host + head, sizeof(popsift_hip_pair) * n);
-        if ((size_t)total > cap) ok.rc = POPSIFT_HIP_ERR_TOO_SMALL;
-    }
-    if (r_copy) (void)hipFree(r_copy);
-    return ok.rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int popsift_hip_match_sets(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, popsift_hip_match* out)
-{
-    return match_rows(l, r, out, g_match_path.load());
-}
-
-int popsift_hip_devfeatures_debug_redo_count(const popsift_hip_devfeatures* l, int* count)
-{
-    if (!l || !count) return POPSIFT_HIP_ERR_INVALID;
-    *count = -1;
-    if (!l->m_redo) return POPSIFT_HIP_OK;
-    if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    if (hipStreamSynchronize((hipStream_t)l->m_stream) != hipSuccess ||
-        hipMemcpy(count, l->m_redo, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-        return POPSIFT_HIP_ERR_DEVICE;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_match_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r, popsift_hip_match* out)
-{
-    return match_rows(l, r, out, 0);
-}
-
-void popsift_hip_default_match_opts(popsift_hip_match_opts* o)
-{
-    if (!o) return;
-    o->ratio = 0.8f;
-    o->max_dist2 = INFINITY;
-    o->cross_check = 0;
-    o->reserved = 0;
-}
-
-int popsift_hip_match_pairs(const popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r,
-                            const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs)
-{
-    return match_pairs(l, r, opts, pairs, cap, n_pairs, g_match_path.load());
-}
-
-int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsift_hip_bytefeatures* r,
-                                  const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs)
-{
-    return match_pairs(l, r, opts, pairs, cap, n_pairs, 0);
 }
 
 void* popsift_hip_host_alloc(size_t bytes)

@@ -1,5 +1,12 @@
-/* devfeatures.h -- device-resident result set (internal; the C ABI sees an opaque pointer). */
+/* devfeatures.h -- device-resident result sets (internal; the C ABI sees opaque pointers), the scratch record a set keeps
+ * for the calls that have it on the left, and the host helpers those calls share (match_sets.hip, match_guided.hip,
+ * ransac.hip). */
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+
 #include "sift_types.h"
 
 /* popsift::Feature as laid out on an LP64 host (features.h:22-34): 72 bytes, the four
@@ -14,29 +21,43 @@ struct DevFeature {
 };
 static_assert(sizeof(DevFeature) == 72, "popsift::Feature layout");
 
-struct popsift_hip_devfeatures {
+/* Scratch of the matchers with this set on the left, kept between calls (one match at a time per left set, like one image
+ * at a time per context).  Both set types embed it; release() is the one place that frees it. */
+struct MatchScratch {
+    void*  m_stream = nullptr;  /* hipStream_t */
+    void*  m_partial = nullptr; /* the sweeps' per-split candidates */
+    size_t m_partial_cap = 0;   /* bytes */
+    void*  m_out = nullptr;     /* popsift_hip_match[n_desc] */
+    void*  m_host = nullptr;    /* pinned staging of the same size */
+    void*  m_rnorm = nullptr;   /* norms of the right set of the current call, in the set's norm type */
+    size_t m_rnorm_cap = 0;     /* bytes */
+    /* of popsift_hip_match_pairs* */
+    void*  p_pairs = nullptr;   /* a 16-byte header ([0] = pair count, [1] = |J|, [2] = the guided matcher's map flag) and
+                                   popsift_hip_pair[n_desc] */
+    void*  p_host = nullptr;    /* pinned staging of the same size */
+    int*   p_idx = nullptr;     /* over the right set: flags, ranks, the list J; and the compaction's block counts */
+    size_t p_idx_cap = 0;       /* ints */
+    void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows (and its redo list) */
+    size_t p_back_cap = 0;      /* rows */
+
+    void release()
+    {
+        if (m_stream) (void)hipStreamDestroy((hipStream_t)m_stream);
+        for (void* p : {m_partial, m_out, m_rnorm, p_pairs, (void*)p_idx, p_back})
+            if (p) (void)hipFree(p);
+        if (m_host) (void)hipHostFree(m_host);
+        if (p_host) (void)hipHostFree(p_host);
+    }
+};
+
+struct popsift_hip_devfeatures : MatchScratch {
     int         device = 0;
     int         n_feat = 0, n_desc = 0;
     DevFeature* d_feat = nullptr; /* n_feat      */
     float*      d_desc = nullptr; /* n_desc * 128 */
     int*        d_rev = nullptr;  /* n_desc: descriptor -> feature (feat_to_ext_map) */
-    /* scratch of popsift_hip_match_sets with this set on the left, kept between calls */
-    void*  m_stream = nullptr;  /* hipStream_t */
-    void*  m_partial = nullptr;
-    size_t m_partial_cap = 0;
-    void*  m_out = nullptr;     /* popsift_hip_match[n_desc] */
-    void*  m_host = nullptr;    /* pinned staging of the same size */
-    int*   m_redo = nullptr;    /* [0] = count, [1 ..] = rows the screening pass left to the exact kernel */
-    float* d_norm = nullptr;    /* |x|^2 per descriptor, computed on first use by a match */
-    float* m_rnorm = nullptr;   /* norms of the right set of the current call */
-    size_t m_rnorm_cap = 0;
-    /* scratch of popsift_hip_match_pairs with this set on the left */
-    void*  p_pairs = nullptr;   /* a 16-byte header ([0] = pair count, [1] = |J|) and popsift_hip_pair[n_desc] */
-    void*  p_host = nullptr;    /* pinned staging of the same size */
-    int*   p_idx = nullptr;     /* over the right set: flags, ranks, the list J; and the compaction's block counts */
-    size_t p_idx_cap = 0;       /* ints */
-    void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows and its redo list */
-    size_t p_back_cap = 0;      /* rows */
+    float*      d_norm = nullptr; /* |x|^2 per descriptor, computed on first use by a match */
+    int*        m_redo = nullptr; /* [0] = count, [1 ..] = rows the screening pass left to the exact kernel */
     /* scratch of popsift_hip_pair_points with this set on the left: a flag, the pairs, the points */
     void*  v_buf = nullptr;
     void*  v_host = nullptr;    /* pinned twin */
@@ -48,25 +69,115 @@ struct popsift_hip_devfeatures {
     void*  g_host = nullptr;    /* pinned twin of the header and the forward rows */
 };
 
-/* A set of byte descriptors (popsift_hip_bytefeatures).  The scratch members mean what their namesakes above mean; a
- * zero-filled block reads as an empty set. */
-struct popsift_hip_bytefeatures {
+/* A set of byte descriptors (popsift_hip_bytefeatures); a zero-filled block reads as an empty set. */
+struct popsift_hip_bytefeatures : MatchScratch {
     int      device = 0;
     int      n_desc = 0;
     uint8_t* d_desc = nullptr; /* n_desc * 128, the caller's bytes */
     int*     d_rev = nullptr;  /* n_desc: descriptor -> feature, -1 = none */
-    void*    m_stream = nullptr;
-    void*    m_partial = nullptr;
-    size_t   m_partial_cap = 0;
-    void*    m_out = nullptr;
-    void*    m_host = nullptr;
-    int*     d_norm = nullptr;  /* |x - 128|^2 per descriptor, computed on first use by a match */
-    int*     m_rnorm = nullptr;
-    size_t   m_rnorm_cap = 0;
-    void*    p_pairs = nullptr;
-    void*    p_host = nullptr;
-    int*     p_idx = nullptr;
-    size_t   p_idx_cap = 0;
-    void*    p_back = nullptr; /* of J: gathered descriptors, the reverse sweep's rows, their norms */
-    size_t   p_back_cap = 0;
+    int*     d_norm = nullptr; /* |x - 128|^2 per descriptor, computed on first use by a match */
 };
+
+namespace popsift_hip {
+
+/* the first failing HIP call decides the status; the calls after it are skipped */
+struct Status {
+    int  rc = POPSIFT_HIP_OK;
+    bool good() const { return rc == POPSIFT_HIP_OK; }
+    bool operator()(hipError_t e)
+    {
+        if (e != hipSuccess && rc == POPSIFT_HIP_OK) rc = (e == hipErrorOutOfMemory) ? POPSIFT_HIP_ERR_OOM : POPSIFT_HIP_ERR_DEVICE;
+        return e == hipSuccess;
+    }
+};
+
+inline size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+/* grow-only device scratch: `cap` counts units of `unit` bytes */
+template <class T>
+bool grow(Status& ok, T*& p, size_t& cap, size_t need, size_t unit)
+{
+    if (!ok.good()) return false;
+    if (need <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (ok(hipMalloc((void**)&p, need * unit))) cap = need;
+    return ok.good();
+}
+
+/* the set's own non-blocking stream, created on first use */
+inline hipStream_t stream_of(Status& ok, MatchScratch& m)
+{
+    if (!m.m_stream) {
+        hipStream_t s = nullptr;
+        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) m.m_stream = s;
+    }
+    return (hipStream_t)m.m_stream;
+}
+
+/* Arrays of a right set on the left set's GPU for the length of one call (images of one PopSift object may have been
+ * extracted on different GPUs; xGMI): one allocation, one hipMemcpyPeer per array, freed with the object. */
+struct PeerCopy {
+    struct Part {
+        const void* src;
+        size_t      bytes;
+    };
+    char* at[3] = {nullptr, nullptr, nullptr}; /* the copy of part k (16-byte aligned); at[0] is the allocation */
+
+    PeerCopy() = default;
+    PeerCopy(const PeerCopy&) = delete;
+    PeerCopy& operator=(const PeerCopy&) = delete;
+    ~PeerCopy()
+    {
+        if (at[0]) (void)hipFree(at[0]);
+    }
+    /* true: every part has arrived on dst_device.  False: the devices are the same, or a call failed (see ok) */
+    template <size_t N>
+    bool fetch(Status& ok, int dst_device, int src_device, const Part (&parts)[N])
+    {
+        static_assert(N <= 3, "at[] holds three parts");
+        if (!ok.good() || dst_device == src_device) return false;
+        size_t off[N + 1] = {0};
+        for (size_t k = 0; k < N; k++) off[k + 1] = off[k] + round16(parts[k].bytes);
+        if (!ok(hipMalloc((void**)&at[0], off[N]))) return false;
+        for (size_t k = 0; k < N; k++) {
+            at[k] = at[0] + off[k];
+            if (!ok(hipMemcpyPeer(at[k], dst_device, parts[k].src, src_device, parts[k].bytes))) return false;
+        }
+        return true;
+    }
+};
+
+/* the pair block of a left set of l_len descriptors and its pinned twin, allocated on first use */
+inline void pair_block(Status& ok, MatchScratch& m, int l_len)
+{
+    const size_t block = sizeof(popsift_hip_pair) * ((size_t)l_len + 1); /* the header has the size of a pair */
+    if (ok.good() && !m.p_pairs) ok(hipMalloc(&m.p_pairs, block));
+    if (ok.good() && !m.p_host) ok(hipHostMalloc(&m.p_host, block, hipHostMallocDefault));
+}
+
+/* The pair block of a set ([16-byte header][popsift_hip_pair ...], MatchScratch::p_pairs) comes down through its pinned
+ * twin: the header and the `most` pairs the call can need.  Header int [0] is the number of pairs found; header int
+ * [bad_at] != 0 (bad_at < 0: the call has no such flag) says that a map entry names no feature.  min(found, cap) pairs are
+ * copied out; more found than cap is POPSIFT_HIP_ERR_TOO_SMALL. */
+inline void download_pairs(Status& ok, MatchScratch& m, size_t most, int bad_at, popsift_hip_pair* pairs, size_t cap,
+                           int* n_pairs, hipStream_t s)
+{
+    const size_t head = sizeof(popsift_hip_pair);
+    if (!ok.good() || !ok(hipMemcpyAsync(m.p_host, m.p_pairs, head + sizeof(popsift_hip_pair) * most, hipMemcpyDeviceToHost, s)) ||
+        !ok(hipStreamSynchronize(s)))
+        return;
+    const int* h = (const int*)m.p_host;
+    if (bad_at >= 0 && h[bad_at] != 0) {
+        ok.rc = POPSIFT_HIP_ERR_INVALID;
+        return;
+    }
+    const int total = h[0];
+    *n_pairs = total;
+    const size_t n = std::min((size_t)total, cap);
+    if (n > 0) memcpy(pairs, (const char*)m.p_host + head, sizeof(popsift_hip_pair) * n);
+    if ((size_t)total > cap) ok.rc = POPSIFT_HIP_ERR_TOO_SMALL;
+}
+
+}  // namespace popsift_hip

@@ -150,41 +150,39 @@ hipError_t launch_filter(int n_oct, const SiftConsts& sc, const BatchDesc& bd, i
 size_t     order_rows(const PyrDesc& pd);
 hipError_t launch_order(const PyrDesc& pd, const SiftConsts& sc, int coarse, const OrderBatch& ob, int nb, hipStream_t s);
 
+/* The matchers.  A sweep's n_split comes from splits() (top2.h) with the sweep's shape: rows per workgroup, searched rows
+ * per tile and the workgroups to aim at; `partial` holds partial_bytes(l_len, n_split, record) bytes. */
+constexpr int M_LT = 32, M_RT = 64, M_GROUPS = 2048;    /* match.hip; >= 8 workgroups per CU; records: Top2<float> */
+constexpr int S_LB = 128, S_RB = 128, S_GROUPS = 1024;  /* match_mfma.hip; >= 2 resident workgroups per CU x 2 rounds */
+constexpr int U_LB = 128, U_RB = 128, U_GROUPS = 1024;  /* match_u8.hip; as S_*; records: Top2<int> */
+constexpr size_t S_CAND_BYTES = 32;                     /* match_mfma.hip's record */
 /* match.hip: brute-force 2-NN (features.cu:157-300) */
-int        match_splits(int l_len, int r_len);
-size_t     match_partial_bytes(int l_len, int n_split);
 hipError_t launch_match(const float* ldesc, int l_len, const float* rdesc, int r_len, int n_split, void* partial,
                         popsift_hip_match* out, const int* rows, const int* n_rows, int first_row, int row_end,
                         hipStream_t s);
 /* match_mfma.hip: matrix-core screening + exact re-rank of the survivors */
-int        screen_splits(int l_len, int r_len);
-size_t     screen_partial_bytes(int l_len, int n_split);
 hipError_t launch_norms(const float* desc, int n, float* out, hipStream_t s);
 hipError_t launch_match_screen(const float* ldesc, int l_len, const float* rdesc, int r_len, const float* lnorm,
                                const float* rnorm, int n_split, void* partial, popsift_hip_match* out, int* redo_list,
                                int* redo_count, hipStream_t s);
-/* match_pairs.hip: 2-NN rows -> pair list.  fwd: the forward sweep's rows, back: the reverse sweep's rows of the flagged
- * right descriptors in the order of `list` (null without the cross-check), counts: pair_count_blocks(n) ints of scratch
- * for a compaction over n elements.  l_len and r_len >= 1. */
+/* match_pairs.hip: 2-NN rows -> pair list.  fwd: the forward sweep's rows; a row without a candidate (best < 0, the guided
+ * matcher's) yields no pair.  back: the reverse sweep's rows (null without the cross-check): of the flagged right
+ * descriptors in the order of `list`, found through rank; or, with rank == null, one row per right descriptor.  counts:
+ * pair_count_blocks(n) ints of scratch for a compaction over n elements.  l_len and r_len >= 1. */
 int        pair_count_blocks(int n);
 hipError_t launch_pair_targets(const popsift_hip_match* fwd, int l_len, int r_len, float ratio, float max_dist2, int* flags,
                                int* counts, int* list, int* rank, int* n_list, hipStream_t s);
-hipError_t launch_gather_rows(const float* desc, const int* list, int n, float* out, hipStream_t s);
 hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
                             const popsift_hip_match* back, const int* rank, int* counts, popsift_hip_pair* pairs, int* n_pairs,
                             hipStream_t s);
-/* the same over the guided matcher's rows (match_guided.hip): a row without a candidate has best = -1; back: a row per
- * right descriptor, or null without the cross-check */
-hipError_t launch_pair_emit_guided(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
-                                   const popsift_hip_match* back, int* counts, popsift_hip_pair* pairs, int* n_pairs, hipStream_t s);
+/* the rows of a list into a contiguous buffer, for T = float and T = uint8_t (descriptors of 128 T, 16-byte aligned) */
+template <class T>
+hipError_t launch_gather_rows(const T* desc, const int* list, int n, T* out, hipStream_t s);
 /* match_u8.hip: exact integer 2-NN of byte descriptors (128 bytes each, 16-byte aligned) on the i8 matrix instructions.
  * Norms are |x - 128|^2 as int; `out` receives l_len rows whose distances are integers held in floats. */
-int        match_u8_splits(int l_len, int r_len);
-size_t     match_u8_partial_bytes(int l_len, int n_split);
 hipError_t launch_norms_u8(const uint8_t* desc, int n, int* out, hipStream_t s);
 hipError_t launch_match_u8(const uint8_t* ldesc, int l_len, const int* lnorm, const uint8_t* rdesc, int r_len,
                            const int* rnorm, int n_split, void* partial, popsift_hip_match* out, hipStream_t s);
-hipError_t launch_gather_rows_u8(const uint8_t* desc, const int* list, int n, uint8_t* out, hipStream_t s);
 /* Feature records (72-byte popsift::Feature layout) with device descriptor pointers for a cloned set */
 hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, float* desc_base, void* out, hipStream_t s);
 

@@ -19,38 +19,17 @@
  */
 #include "devfeatures.h"
 #include "kernels.h"
+#include "top2.h"
 
 namespace popsift_hip {
 namespace {
 
-constexpr int M_LT = 32;    /* left descriptors per workgroup */
-constexpr int M_RT = 64;    /* right descriptors per LDS tile */
 constexpr int M_ROW = 132;  /* floats per LDS row: 128 + 4 padding (conflict-free ds_read_b128) */
 constexpr int M_LPT = 4;    /* left rows per lane  */
 constexpr int M_RPT = 2;    /* right rows per lane */
 constexpr int M_PAIRS = M_LPT * M_RPT;
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-struct Top2 {
-    float v1, v2;
-    int   i1, i2;
-};
-
-__device__ __forceinline__ bool lex_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void top2_insert(Top2& t, float d, int i)
-{
-    if (lex_less(d, i, t.v1, t.i1)) {
-        t.v2 = t.v1;
-        t.i2 = t.i1;
-        t.v1 = d;
-        t.i1 = i;
-    } else if (lex_less(d, i, t.v2, t.i2)) {
-        t.v2 = d;
-        t.i2 = i;
-    }
-}
 
 struct Acc {
     float v[M_PAIRS];
@@ -121,7 +100,7 @@ __device__ __forceinline__ Acc pair_distances(const float* __restrict__ lrow, co
  */
 __global__ __launch_bounds__(256, 2) void k_match(const float* __restrict__ ldesc, int l_len,
                                                const float* __restrict__ rdesc, int r_len, int n_split,
-                                               Top2* __restrict__ partial, const int* __restrict__ rows,
+                                               Top2<float>* __restrict__ partial, const int* __restrict__ rows,
                                                const int* __restrict__ n_rows, int first_row, int row_end)
 {
     /* rows != null: only the left descriptors rows[first_row .. min(*n_rows, row_end)) -- the list the screening
@@ -142,9 +121,9 @@ __global__ __launch_bounds__(256, 2) void k_match(const float* __restrict__ ldes
         *(v4f*)(s_l + row * M_ROW + 4 * ch) = v;
     }
 
-    Top2 best[M_LPT];
+    Top2<float> best[M_LPT];
 #pragma unroll
-    for (int a = 0; a < M_LPT; a++) best[a] = Top2{INFINITY, INFINITY, 0, 0}; /* features.cu:185-188 */
+    for (int a = 0; a < M_LPT; a++) best[a] = Top2<float>{INFINITY, INFINITY, 0, 0}; /* features.cu:185-188 */
 
     const int n_tiles = (r_len + M_RT - 1) / M_RT;
     v4f       stage[8]; /* this lane's share of the next right tile (64 rows x 32 chunks / 256 lanes) */
@@ -183,42 +162,19 @@ __global__ __launch_bounds__(256, 2) void k_match(const float* __restrict__ ldes
 
     /* merge the 32 lanes that share a left row */
     __syncthreads();
-    Top2* s_top = (Top2*)s_r; /* [32 left rows][32 lanes] = 16 KB */
+    Top2<float>* s_top = (Top2<float>*)s_r; /* [32 left rows][32 lanes] = 16 KB */
 #pragma unroll
     for (int a = 0; a < M_LPT; a++) s_top[(M_LPT * lg + a) * 32 + rg] = best[a];
     __syncthreads();
     if (tid < M_LT && l0 + tid < l_len) {
-        Top2 t = s_top[tid * 32];
+        Top2<float> t = s_top[tid * 32];
         for (int k = 1; k < 32; k++) {
-            const Top2 o = s_top[tid * 32 + k];
+            const Top2<float> o = s_top[tid * 32 + k];
             top2_insert(t, o.v1, o.i1);
             top2_insert(t, o.v2, o.i2);
         }
         partial[(size_t)(l0 + tid) * n_split + blockIdx.y] = t;
     }
-}
-
-/* merge the per-split candidates; accept as in features.cu:217-218 */
-__global__ __launch_bounds__(256) void k_match_finish(const Top2* __restrict__ partial, int l_len, int n_split,
-                                                      popsift_hip_match* __restrict__ out, const int* __restrict__ rows,
-                                                      const int* __restrict__ n_rows, int first_row, int row_end)
-{
-    const int l = first_row + blockIdx.x * 256 + threadIdx.x;
-    if (rows) l_len = min(min(*n_rows, row_end), l_len);
-    if (l >= l_len) return;
-    Top2 t = partial[(size_t)l * n_split];
-    for (int k = 1; k < n_split; k++) {
-        const Top2 o = partial[(size_t)l * n_split + k];
-        top2_insert(t, o.v1, o.i1);
-        top2_insert(t, o.v2, o.i2);
-    }
-    popsift_hip_match m;
-    m.best = t.i1;
-    m.second = t.i2;
-    m.accept = (__fdiv_rn(t.v1, t.v2) < 0.8f) ? 1 : 0;
-    m.dist_best = t.v1;
-    m.dist_second = t.v2;
-    out[rows ? rows[l] : l] = m;
 }
 
 /* prep_features writing into a FeaturesDev (sift_pyramid.cu:323-345): indices -> device pointers */
@@ -253,15 +209,6 @@ hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, f
     return hipGetLastError();
 }
 
-int match_splits(int l_len, int r_len)
-{
-    const int l_blocks = (l_len + M_LT - 1) / M_LT;
-    const int tiles = (r_len + M_RT - 1) / M_RT;
-    int       s = (2048 + l_blocks - 1) / std::max(l_blocks, 1); /* aim at >= 8 workgroups per CU */
-    s = std::min(s, std::max(tiles, 1));
-    return std::max(s, 1);
-}
-
 hipError_t launch_match(const float* ldesc, int l_len, const float* rdesc, int r_len, int n_split, void* partial,
                         popsift_hip_match* out, const int* rows, const int* n_rows, int first_row, int row_end,
                         hipStream_t s)
@@ -273,12 +220,9 @@ hipError_t launch_match(const float* ldesc, int l_len, const float* rdesc, int r
     if (end <= begin) return hipSuccess;
     const int cover = end - begin;
     hipLaunchKernelGGL(k_match, dim3((cover + M_LT - 1) / M_LT, n_split), dim3(256), 0, s, ldesc, l_len, rdesc, r_len, n_split,
-                       (Top2*)partial, rows, n_rows, begin, end);
-    hipLaunchKernelGGL(k_match_finish, dim3((cover + 255) / 256), dim3(256), 0, s, (const Top2*)partial, l_len, n_split, out,
-                       rows, n_rows, begin, end);
+                       (Top2<float>*)partial, rows, n_rows, begin, end);
+    launch_top2_finish((const Top2<float>*)partial, l_len, n_split, out, rows, n_rows, begin, end, s);
     return hipGetLastError();
 }
-
-size_t match_partial_bytes(int l_len, int n_split) { return (size_t)std::max(l_len, 1) * n_split * sizeof(Top2); }
 
 }  // namespace popsift_hip

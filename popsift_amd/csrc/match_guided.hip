@@ -19,12 +19,12 @@
  *                    in the reference's own shape -- and the lane that keeps the pair's row inserts under (d, j).  "The
  *                    two smallest under lexicographic (d, j)" does not depend on the order of insertion, which is what
  *                    lets waves that share rows (the candidate side split over gridDim.y for small row counts) keep
- *                    private candidates; k_guided_finish merges them and writes the rows.
+ *                    private candidates; k_top2_finish (top2.h) merges them and writes the rows.
  *                    One wave per workgroup: no barrier couples waves whose queues fill at different times.
  *   SWAP             The cross-check's search the other way round is the same kernel with the right descriptors as rows
  *                    and the left ones as candidates; the test itself stays left -> right.  It runs over all of r: on
  *                    positions that is as cheap as the forward sweep, and it needs no read-back between the sweeps.
- *   pairs            match_pairs.hip's order-preserving compaction over the forward rows (launch_pair_emit_guided).
+ *   pairs            match_pairs.hip's order-preserving compaction over the forward rows (launch_pair_emit without a rank).
  */
 #include <hip/hip_runtime.h>
 
@@ -34,6 +34,7 @@
 
 #include "devfeatures.h"
 #include "kernels.h"
+#include "top2.h"
 
 namespace popsift_hip {
 namespace {
@@ -53,26 +54,6 @@ struct Model {
     float m[9];
     float max_err2; /* max_err * max_err */
 };
-
-struct Top2 {
-    float v1, v2;
-    int   i1, i2;
-};
-
-__device__ __forceinline__ bool lex_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void top2_insert(Top2& t, float d, int i)
-{
-    if (lex_less(d, i, t.v1, t.i1)) {
-        t.v2 = t.v1;
-        t.i2 = t.i1;
-        t.v1 = d;
-        t.i1 = i;
-    } else if (lex_less(d, i, t.v2, t.i2)) {
-        t.v2 = d;
-        t.i2 = i;
-    }
-}
 
 /* what the test needs of the left point alone.  Homography (step 4 of popsift_hip_ransac): u, v, w, lim.  Epipolar (step 6
  * of popsift_hip_epipolar): a, b, c. */
@@ -129,10 +110,10 @@ __global__ __launch_bounds__(256) void k_guided_pos(const DevFeature* __restrict
 }
 
 /* the queued pairs' distances, two at a time: lanes 0 .. 31 take s_q[q], lanes 32 .. 63 s_q[q + 1], one float4 chunk a
- * lane.  p(c) and the shuffle tree are l2_in_t0's (match.hip states them); (l - r)^2 and (r - l)^2 are the same bits, so
+ * lane.  p(c) and the shuffle tree are l2_in_t0's (top2.h); (l - r)^2 and (r - l)^2 are the same bits, so
  * rows minus candidates serves both directions.  Lane i of the wave keeps row r0 + i. */
 __device__ __forceinline__ void drain(const int2* s_q, int qn, const float* __restrict__ row_desc, int r0,
-                                      const float* __restrict__ col_desc, Top2& top)
+                                      const float* __restrict__ col_desc, Top2<float>& top)
 {
     __syncthreads(); /* the queue's entries are written (a one-wave workgroup: this orders LDS, nothing waits) */
     const int lane = threadIdx.x, half = lane >> 5, ch = lane & 31;
@@ -141,13 +122,7 @@ __device__ __forceinline__ void drain(const int2* s_q, int qn, const float* __re
         const int2 e = half ? e1 : e0;
         const v4f  a = *(const v4f*)(row_desc + (size_t)(r0 + e.x) * 128 + 4 * ch);
         const v4f  b = *(const v4f*)(col_desc + (size_t)e.y * 128 + 4 * ch);
-        const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z, w = a.w - b.w;
-        float       p = fmaf(w, w, fmaf(z, z, fmaf(y, y, x * x)));
-        p = p + __shfl_down(p, 16, 32);
-        p = p + __shfl_down(p, 8, 32);
-        p = p + __shfl_down(p, 4, 32);
-        p = p + __shfl_down(p, 2, 32);
-        p = p + __shfl_down(p, 1, 32);
+        const float p = l2_in_t0(a, b);
         const float d0 = __shfl(p, 0), d1 = __shfl(p, 32);
         /* d < +inf: a NaN or an overflowed distance is no candidate */
         if (lane == e0.x && d0 < INFINITY) top2_insert(top, d0, e0.y);
@@ -164,7 +139,7 @@ __device__ __forceinline__ void drain(const int2* s_q, int qn, const float* __re
 template <int MODEL, bool SWAP>
 __global__ __launch_bounds__(64) void k_guided(Model M, const v2f* __restrict__ row_pos, int n_rows,
                                                const float* __restrict__ row_desc, const v2f* __restrict__ col_pos, int n_cols,
-                                               const float* __restrict__ col_desc, int n_split, Top2* __restrict__ partial)
+                                               const float* __restrict__ col_desc, int n_split, Top2<float>* __restrict__ partial)
 {
     __shared__ v4f  s_row[G_ROWS];
     __shared__ int2 s_q[G_QUEUE];
@@ -177,7 +152,7 @@ __global__ __launch_bounds__(64) void k_guided(Model M, const v2f* __restrict__ 
     }
     __syncthreads();
 
-    Top2                     top = {INFINITY, INFINITY, -1, -1};
+    Top2<float>              top = {INFINITY, INFINITY, -1, -1};
     int                      qn = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
     const int                n_steps = (n_cols + G_STEP - 1) / G_STEP;
@@ -217,56 +192,15 @@ __global__ __launch_bounds__(64) void k_guided(Model M, const v2f* __restrict__ 
     if (r0 + lane < n_rows) partial[(size_t)(r0 + lane) * n_split + blockIdx.y] = top;
 }
 
-/* merge the splits' candidates and write the rows; accept as k_match_finish forms it */
-__global__ __launch_bounds__(256) void k_guided_finish(const Top2* __restrict__ partial, int n_rows, int n_split,
-                                                       popsift_hip_match* __restrict__ out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_rows) return;
-    Top2 t = partial[(size_t)i * n_split];
-    for (int k = 1; k < n_split; k++) {
-        const Top2 o = partial[(size_t)i * n_split + k];
-        if (o.i1 >= 0) top2_insert(t, o.v1, o.i1);
-        if (o.i2 >= 0) top2_insert(t, o.v2, o.i2);
-    }
-    popsift_hip_match m;
-    m.best = t.i1;
-    m.second = t.i2;
-    m.accept = (__fdiv_rn(t.v1, t.v2) < 0.8f) ? 1 : 0;
-    m.dist_best = t.v1;
-    m.dist_second = t.v2;
-    out[i] = m;
-}
-
-/* at least 4096 waves where the candidate side has the steps for it */
-int guided_splits(int n_rows, int n_cols)
-{
-    const int blocks = (n_rows + G_ROWS - 1) / G_ROWS, steps = (n_cols + G_STEP - 1) / G_STEP;
-    return std::max(std::min((4096 + blocks - 1) / std::max(blocks, 1), steps), 1);
-}
-
 template <int MODEL, bool SWAP>
 hipError_t launch_sweep(const Model& M, const v2f* row_pos, int n_rows, const float* row_desc, const v2f* col_pos, int n_cols,
-                        const float* col_desc, int n_split, Top2* partial, popsift_hip_match* out, hipStream_t s)
+                        const float* col_desc, int n_split, Top2<float>* partial, popsift_hip_match* out, hipStream_t s)
 {
     hipLaunchKernelGGL((k_guided<MODEL, SWAP>), dim3((n_rows + G_ROWS - 1) / G_ROWS, n_split), dim3(64), 0, s, M, row_pos, n_rows,
                        row_desc, col_pos, n_cols, col_desc, n_split, partial);
-    hipLaunchKernelGGL(k_guided_finish, dim3((n_rows + 255) / 256), dim3(256), 0, s, (const Top2*)partial, n_rows, n_split, out);
+    launch_top2_finish(partial, n_rows, n_split, out, nullptr, nullptr, 0, n_rows, s);
     return hipGetLastError();
 }
-
-/* the first failing HIP call decides the status; the calls after it are skipped */
-struct Status {
-    int  rc = POPSIFT_HIP_OK;
-    bool good() const { return rc == POPSIFT_HIP_OK; }
-    bool operator()(hipError_t e)
-    {
-        if (e != hipSuccess && rc == POPSIFT_HIP_OK) rc = (e == hipErrorOutOfMemory) ? POPSIFT_HIP_ERR_OOM : POPSIFT_HIP_ERR_DEVICE;
-        return e == hipSuccess;
-    }
-};
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 bool opts_valid(const popsift_hip_guided_opts* o)
 {
@@ -289,11 +223,7 @@ int run(popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, const pops
     const int  nl = l->n_desc, nr = r->n_desc;
     const bool cross = !rows && o->cross_check;
     Status     ok;
-    if (!l->m_stream) {
-        hipStream_t s = nullptr;
-        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
-    }
-    hipStream_t const s = (hipStream_t)l->m_stream;
+    hipStream_t const s = stream_of(ok, *l);
 
     /* l's block: header, forward rows | positions of l, of r | reverse rows | the compaction's counts */
     const size_t b_head = 16, b_rows = round16(sizeof(popsift_hip_match) * (size_t)nl);
@@ -301,43 +231,26 @@ int run(popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, const pops
     const size_t b_back = cross ? round16(sizeof(popsift_hip_match) * (size_t)nr) : 0;
     const size_t b_counts = round16(sizeof(int) * (size_t)pair_count_blocks(nl));
     const size_t need = b_head + b_rows + b_lpos + b_rpos + b_back + b_counts;
-    if (ok.good() && need > l->g_cap) {
-        if (l->g_buf) (void)hipFree(l->g_buf);
-        l->g_buf = nullptr;
-        l->g_cap = 0;
-        if (ok(hipMalloc(&l->g_buf, need))) l->g_cap = need;
-    }
+    grow(ok, l->g_buf, l->g_cap, need, 1);
     if (ok.good() && !l->g_host) ok(hipHostMalloc(&l->g_host, b_head + b_rows, hipHostMallocDefault));
-    const int    split_f = guided_splits(nl, nr), split_b = cross ? guided_splits(nr, nl) : 1;
-    const size_t b_partial = sizeof(Top2) * std::max((size_t)nl * split_f, cross ? (size_t)nr * split_b : 0);
-    if (ok.good() && b_partial > l->m_partial_cap) {
-        if (l->m_partial) (void)hipFree(l->m_partial);
-        l->m_partial = nullptr;
-        l->m_partial_cap = 0;
-        if (ok(hipMalloc(&l->m_partial, b_partial))) l->m_partial_cap = b_partial;
-    }
-    /* the pairs' block and its pinned twin are popsift_hip_match_pairs': [0] the count, [2] the map flag, then the pairs */
-    const size_t p_head = sizeof(popsift_hip_pair), p_block = p_head + sizeof(popsift_hip_pair) * (size_t)nl;
-    if (!rows) {
-        if (ok.good() && !l->p_pairs) ok(hipMalloc(&l->p_pairs, p_block));
-        if (ok.good() && !l->p_host) ok(hipHostMalloc(&l->p_host, p_block, hipHostMallocDefault));
-    }
+    /* at least 4096 waves where the candidate side has the steps for it */
+    const int split_f = splits(nl, nr, G_ROWS, G_STEP, 4096), split_b = cross ? splits(nr, nl, G_ROWS, G_STEP, 4096) : 1;
+    grow(ok, l->m_partial, l->m_partial_cap,
+         std::max(partial_bytes(nl, split_f, sizeof(Top2<float>)), cross ? partial_bytes(nr, split_b, sizeof(Top2<float>)) : 0), 1);
+    /* the pairs' block is popsift_hip_match_pairs'; its header int [2] is the map flag */
+    if (!rows) pair_block(ok, *l, nl);
     /* a right set on another GPU: its feature records, its map and its descriptors come over for the call */
     const DevFeature* rf = r->d_feat;
     const int*        rrev = r->d_rev;
     const float*      rdesc = r->d_desc;
-    char*             r_copy = nullptr;
-    if (ok.good() && r->device != l->device) {
-        const size_t bf = round16(sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1)), br = round16(sizeof(int) * (size_t)nr);
-        const size_t bd = sizeof(float) * 128 * (size_t)nr;
-        if (ok(hipMalloc((void**)&r_copy, bf + br + bd)) &&
-            ok(hipMemcpyPeer(r_copy, l->device, r->d_feat, r->device, sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1))) &&
-            ok(hipMemcpyPeer(r_copy + bf, l->device, r->d_rev, r->device, sizeof(int) * (size_t)nr)) &&
-            ok(hipMemcpyPeer(r_copy + bf + br, l->device, r->d_desc, r->device, bd))) {
-            rf = (const DevFeature*)r_copy;
-            rrev = (const int*)(r_copy + bf);
-            rdesc = (const float*)(r_copy + bf + br);
-        }
+    PeerCopy          peer;
+    if (peer.fetch(ok, l->device, r->device,
+                   {{r->d_feat, sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1)},
+                    {r->d_rev, sizeof(int) * (size_t)nr},
+                    {r->d_desc, sizeof(float) * 128 * (size_t)nr}})) {
+        rf = (const DevFeature*)peer.at[0];
+        rrev = (const int*)peer.at[1];
+        rdesc = (const float*)peer.at[2];
     }
     if (ok.good()) {
         char* const d = (char*)l->g_buf;
@@ -348,7 +261,7 @@ int run(popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, const pops
         int* const  counts = (int*)(d + b_head + b_rows + b_lpos + b_rpos + b_back);
         int* const  head = rows ? (int*)d : (int*)l->p_pairs;
         int* const  bad = rows ? head : head + 2;
-        Top2* const partial = (Top2*)l->m_partial;
+        auto* const partial = (Top2<float>*)l->m_partial;
         Model       M;
         memcpy(M.m, o->M, sizeof M.m);
         M.max_err2 = o->max_err * o->max_err;
@@ -376,26 +289,12 @@ int run(popsift_hip_devfeatures* l, const popsift_hip_devfeatures* r, const pops
                 else memcpy(rows, (const char*)l->g_host + b_head, sizeof(popsift_hip_match) * (size_t)nl);
             }
         } else {
-            auto* const  d_pairs = (popsift_hip_pair*)((char*)l->p_pairs + p_head);
-            const size_t most = std::min(cap, (size_t)nl); /* pairs the download has to cover */
-            if (ok.good() &&
-                ok(launch_pair_emit_guided(d_fwd, nl, o->ratio, o->max_dist2, cross ? d_back : nullptr, counts, d_pairs, head, s)) &&
-                ok(hipMemcpyAsync(l->p_host, l->p_pairs, p_head + sizeof(popsift_hip_pair) * most, hipMemcpyDeviceToHost, s)) &&
-                ok(hipStreamSynchronize(s))) {
-                const int* h = (const int*)l->p_host;
-                if (h[2] != 0) {
-                    ok.rc = POPSIFT_HIP_ERR_INVALID;
-                } else {
-                    const int total = h[0];
-                    *n_pairs = total;
-                    const size_t n = std::min((size_t)total, cap);
-                    if (n > 0) memcpy(pairs, (const char*)l->p_host + p_head, sizeof(popsift_hip_pair) * n);
-                    if ((size_t)total > cap) ok.rc = POPSIFT_HIP_ERR_TOO_SMALL;
-                }
-            }
+            /* no rank: d_back holds a row for every right descriptor */
+            if (ok.good() && ok(launch_pair_emit(d_fwd, nl, o->ratio, o->max_dist2, cross ? d_back : nullptr, nullptr, counts,
+                                                 (popsift_hip_pair*)l->p_pairs + 1, head, s)))
+                download_pairs(ok, *l, std::min(cap, (size_t)nl), 2, pairs, cap, n_pairs, s);
         }
     }
-    if (r_copy) (void)hipFree(r_copy);
     return ok.rc;
 }
 

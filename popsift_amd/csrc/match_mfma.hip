@@ -23,6 +23,7 @@
  */
 #include "devfeatures.h"
 #include "kernels.h"
+#include "top2.h"
 
 namespace popsift_hip {
 namespace {
@@ -30,8 +31,8 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 
-constexpr int S_LB = 128;   /* left descriptors per workgroup: 32 per wave (the N dimension of its MFMA tiles) */
-constexpr int S_RB = 128;   /* right descriptors per LDS tile: 4 row blocks of 32 (the M dimension)            */
+/* S_LB left descriptors per workgroup: 32 per wave (the N dimension of its MFMA tiles); S_RB right descriptors per LDS
+ * tile: 4 row blocks of 32 (the M dimension) */
 constexpr int S_ROW = 132;  /* floats per LDS row: +4 keeps the 16 rows of a ds_read_b128 group on distinct slots */
 constexpr int S_K = 4;      /* screened candidates kept per left descriptor */
 
@@ -39,18 +40,17 @@ struct Cand {
     float d[S_K];
     int   i[S_K];
 };
-
-__device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
+static_assert(sizeof(Cand) == S_CAND_BYTES, "the driver sizes the candidate buffer");
 
 /* sorted insert into the 4 smallest (ascending; ties to the lower index) */
 __device__ __forceinline__ void cand_insert(Cand& c, float d, int i)
 {
-    if (!cand_less(d, i, c.d[S_K - 1], c.i[S_K - 1])) return;
+    if (!lex_less(d, i, c.d[S_K - 1], c.i[S_K - 1])) return;
     c.d[S_K - 1] = d;
     c.i[S_K - 1] = i;
 #pragma unroll
     for (int k = S_K - 1; k > 0; k--) {
-        if (cand_less(c.d[k], c.i[k], c.d[k - 1], c.i[k - 1])) {
+        if (lex_less(c.d[k], c.i[k], c.d[k - 1], c.i[k - 1])) {
             const float td = c.d[k];
             const int   ti = c.i[k];
             c.d[k] = c.d[k - 1];
@@ -184,20 +184,6 @@ __global__ __launch_bounds__(256, 2) void k_match_screen(const float* __restrict
     if (half == 0 && l < l_len) partial[(size_t)l * n_split + blockIdx.y] = best;
 }
 
-/* the reference's distance of one pair, 32 lanes per pair (two pairs per wave): features.cu:157-176 */
-__device__ __forceinline__ float exact_distance(const float* __restrict__ lrow, const float* __restrict__ rrow, int t)
-{
-    const v4f a = *(const v4f*)(lrow + 4 * t), b = *(const v4f*)(rrow + 4 * t);
-    const float x = a.x - b.x, y = a.y - b.y, z = a.z - b.z, w = a.w - b.w;
-    float       res = fmaf(w, w, fmaf(z, z, fmaf(y, y, x * x)));
-    res += __shfl_down(res, 16, 32);
-    res += __shfl_down(res, 8, 32);
-    res += __shfl_down(res, 4, 32);
-    res += __shfl_down(res, 2, 32);
-    res += __shfl_down(res, 1, 32);
-    return res; /* valid in lane t == 0 of each 32-lane group */
-}
-
 /* one wave per left descriptor */
 __global__ __launch_bounds__(256) void k_match_select(const float* __restrict__ ldesc, int l_len,
                                                       const float* __restrict__ rdesc, int r_len,
@@ -248,51 +234,22 @@ __global__ __launch_bounds__(256) void k_match_select(const float* __restrict__ 
     for (int k = 0; k < S_K; k += 2) {
         const int   idx = c.i[k + grp];
         const bool  valid = c.d[k + grp] < INFINITY;
-        const float e = exact_distance(lrow, rdesc + (size_t)(valid ? idx : 0) * 128, t);
+        /* 32 lanes per pair, two pairs per wave; valid in lane t == 0 of each group */
+        const float e = l2_in_t0(*(const v4f*)(lrow + 4 * t), *(const v4f*)(rdesc + (size_t)(valid ? idx : 0) * 128 + 4 * t));
         const float e0 = __shfl(e, 0), e1 = __shfl(e, 32);
         ed[k] = (c.d[k] < INFINITY) ? e0 : INFINITY;
         ed[k + 1] = (c.d[k + 1] < INFINITY) ? e1 : INFINITY;
     }
     if (lane == 0) {
-        float v1 = INFINITY, v2 = INFINITY;
-        int   i1 = 0, i2 = 0; /* features.cu:185-188 */
+        Top2<float> top = {INFINITY, INFINITY, 0, 0}; /* features.cu:185-188 */
 #pragma unroll
-        for (int k = 0; k < S_K; k++) {
-            if (!(c.d[k] < INFINITY)) continue;
-            const float d = ed[k];
-            const int   i = c.i[k];
-            if (cand_less(d, i, v1, i1)) {
-                v2 = v1;
-                i2 = i1;
-                v1 = d;
-                i1 = i;
-            } else if (cand_less(d, i, v2, i2)) {
-                v2 = d;
-                i2 = i;
-            }
-        }
-        popsift_hip_match m;
-        m.best = i1;
-        m.second = i2;
-        m.accept = (__fdiv_rn(v1, v2) < 0.8f) ? 1 : 0;
-        m.dist_best = v1;
-        m.dist_second = v2;
-        out[l] = m;
+        for (int k = 0; k < S_K; k++)
+            if (c.d[k] < INFINITY) top2_insert(top, ed[k], c.i[k]);
+        out[l] = top2_row(top);
     }
 }
 
 }  // namespace
-
-int screen_splits(int l_len, int r_len)
-{
-    const int l_blocks = (l_len + S_LB - 1) / S_LB;
-    const int tiles = (r_len + S_RB - 1) / S_RB;
-    int       s = (1024 + l_blocks - 1) / std::max(l_blocks, 1); /* >= 2 resident workgroups per CU x 2 rounds */
-    s = std::min(s, std::max(tiles, 1));
-    return std::max(s, 1);
-}
-
-size_t screen_partial_bytes(int l_len, int n_split) { return (size_t)std::max(l_len, 1) * n_split * sizeof(Cand); }
 
 /* out: n norms and, in out[n], the flag "one of them is not finite" */
 hipError_t launch_norms(const float* desc, int n, float* out, hipStream_t s)

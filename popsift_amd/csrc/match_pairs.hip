@@ -1,6 +1,6 @@
 /*
- * match_pairs.hip -- from the 2-NN rows of a sweep (match.hip / match_mfma.hip) to a list of pairs:
- * ratio test, distance cap and mutual-nearest-neighbour check (popsift_hip_match_pairs, include/popsift_hip.h).
+ * match_pairs.hip -- from the 2-NN rows of a sweep (match.hip / match_mfma.hip / match_u8.hip / match_guided.hip) to a list
+ * of pairs: ratio test, distance cap and mutual-nearest-neighbour check (popsift_hip_match_pairs, include/popsift_hip.h).
  *
  * The sweeps are the expensive part and are not touched.  Everything here is one pass over 20-byte rows:
  *   k_pair_mark     with the cross-check: flag the nearest right descriptor of every row that passes the ratio test
@@ -22,7 +22,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 constexpr int C_BLOCK = 256; /* elements (= lanes) per workgroup of the compaction kernels */
 
-/* conditions 2 and 3 of the rule; __fdiv_rn and '<' as k_match_finish / k_match_select form `accept`: a NaN quotient
+/* conditions 2 and 3 of the rule; __fdiv_rn and '<' as top2_row (top2.h) forms `accept`: a NaN quotient
  * (0 / 0, inf / inf) fails */
 __device__ __forceinline__ bool row_passes(const popsift_hip_match& m, float ratio, float max_dist2)
 {
@@ -35,33 +35,20 @@ struct Flagged {
     __device__ bool operator()(int j) const { return flags[j] != 0; }
 };
 
-/* row i yields a pair: it passes, and with the cross-check it is the nearest left descriptor of its best right one.
- * back[rank[j]] is the reverse sweep's row of right descriptor j; rank is defined for every flagged j, and a passing
- * row's best is flagged. */
+/* row i yields a pair: it has a candidate (the guided matcher's rows may have none: best = -1; the other sweeps' always
+ * do), it passes, and with the cross-check it is the nearest left descriptor of its best right one.  With a rank,
+ * back[rank[j]] is the reverse sweep's row of right descriptor j: rank is defined for every flagged j, and a passing
+ * row's best is flagged.  Without one, `back` holds a row for every right descriptor. */
 struct PairKept {
     const popsift_hip_match* fwd;
     const popsift_hip_match* back; /* null: no cross-check */
-    const int*               rank;
-    float                    ratio, max_dist2;
-    __device__ bool operator()(int i) const
-    {
-        const popsift_hip_match m = fwd[i];
-        if (!row_passes(m, ratio, max_dist2)) return false;
-        return !back || back[rank[m.best]].best == i;
-    }
-};
-
-/* the same for the guided matcher's rows (match_guided.hip): a row without a candidate has best = -1, and `back` holds a
- * row for every right descriptor */
-struct GuidedPairKept {
-    const popsift_hip_match* fwd;
-    const popsift_hip_match* back; /* null: no cross-check */
+    const int*               rank; /* null: back[j] is the row of j */
     float                    ratio, max_dist2;
     __device__ bool operator()(int i) const
     {
         const popsift_hip_match m = fwd[i];
         if (m.best < 0 || !row_passes(m, ratio, max_dist2)) return false;
-        return !back || back[m.best].best == i;
+        return !back || back[rank ? rank[m.best] : m.best].best == i;
     }
 };
 
@@ -145,14 +132,16 @@ __global__ __launch_bounds__(256) void k_pair_mark(const popsift_hip_match* __re
     if (row_passes(m, ratio, max_dist2)) flags[m.best] = 1;
 }
 
-/* one float4 per lane, 32 lanes per row */
-__global__ __launch_bounds__(256) void k_gather_rows(const float* __restrict__ desc, const int* __restrict__ list, int n,
-                                                     float* __restrict__ out)
+/* one 16-byte chunk per lane */
+template <int ROW_BYTES>
+__global__ __launch_bounds__(256) void k_gather_rows(const char* __restrict__ desc, const int* __restrict__ list, int n,
+                                                     char* __restrict__ out)
 {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n * 32) return;
-    const int row = c >> 5, ch = c & 31;
-    *(v4f*)(out + (size_t)row * 128 + 4 * ch) = *(const v4f*)(desc + (size_t)list[row] * 128 + 4 * ch);
+    constexpr int CHUNKS = ROW_BYTES / 16;
+    const int     c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n * CHUNKS) return;
+    const int row = c / CHUNKS, ch = c % CHUNKS;
+    *(v4f*)(out + (size_t)row * ROW_BYTES + 16 * ch) = *(const v4f*)(desc + (size_t)list[row] * ROW_BYTES + 16 * ch);
 }
 
 int blocks_of(int n) { return (n + C_BLOCK - 1) / C_BLOCK; }
@@ -174,12 +163,17 @@ hipError_t launch_pair_targets(const popsift_hip_match* fwd, int l_len, int r_le
     return hipGetLastError();
 }
 
-hipError_t launch_gather_rows(const float* desc, const int* list, int n, float* out, hipStream_t s)
+template <class T>
+hipError_t launch_gather_rows(const T* desc, const int* list, int n, T* out, hipStream_t s)
 {
+    constexpr int ROW_BYTES = 128 * sizeof(T);
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_gather_rows, dim3((n * 32 + 255) / 256), dim3(256), 0, s, desc, list, n, out);
+    hipLaunchKernelGGL(k_gather_rows<ROW_BYTES>, dim3((n * (ROW_BYTES / 16) + 255) / 256), dim3(256), 0, s, (const char*)desc, list,
+                       n, (char*)out);
     return hipGetLastError();
 }
+template hipError_t launch_gather_rows<float>(const float*, const int*, int, float*, hipStream_t);
+template hipError_t launch_gather_rows<uint8_t>(const uint8_t*, const int*, int, uint8_t*, hipStream_t);
 
 hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
                             const popsift_hip_match* back, const int* rank, int* counts, popsift_hip_pair* pairs, int* n_pairs,
@@ -188,16 +182,6 @@ hipError_t launch_pair_emit(const popsift_hip_match* fwd, int l_len, float ratio
     const PairKept keep{fwd, back, rank, ratio, max_dist2};
     hipLaunchKernelGGL(k_count<PairKept>, dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep, l_len, counts);
     hipLaunchKernelGGL((k_compact<PairKept, WritePair>), dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep,
-                       WritePair{fwd, pairs}, l_len, counts, n_pairs);
-    return hipGetLastError();
-}
-
-hipError_t launch_pair_emit_guided(const popsift_hip_match* fwd, int l_len, float ratio, float max_dist2,
-                                   const popsift_hip_match* back, int* counts, popsift_hip_pair* pairs, int* n_pairs, hipStream_t s)
-{
-    const GuidedPairKept keep{fwd, back, ratio, max_dist2};
-    hipLaunchKernelGGL(k_count<GuidedPairKept>, dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep, l_len, counts);
-    hipLaunchKernelGGL((k_compact<GuidedPairKept, WritePair>), dim3(blocks_of(l_len)), dim3(C_BLOCK), 0, s, keep,
                        WritePair{fwd, pairs}, l_len, counts, n_pairs);
     return hipGetLastError();
 }

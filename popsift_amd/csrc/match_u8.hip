@@ -25,13 +25,11 @@
  *               end) and its share of a min over the row block's 16 values; only when that minimum beats the lane's second
  *               best -- rare after the first tiles -- the 16 values are looked at one by one.  A lane meets its right rows
  *               in ascending index, so "ties go to the lower index" is a strict '<' there.
- *   k_match_u8_finish  merges the right-set splits under lexicographic (d, j) and writes popsift_hip_match rows.
- *   k_gather_rows_u8   the rows of a list into a contiguous buffer (the left operand of the cross-check's reverse sweep).
+ *   k_top2_finish<int> (top2.h) merges the right-set splits under lexicographic (d, j) and writes popsift_hip_match rows.
  */
-#include <climits>
-
 #include "devfeatures.h"
 #include "kernels.h"
+#include "top2.h"
 
 namespace popsift_hip {
 namespace {
@@ -39,31 +37,10 @@ namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-constexpr int U_LB = 128;          /* left descriptors per workgroup: 32 per wave (the N dimension of its MFMA tiles) */
-constexpr int U_RB = 128;          /* right descriptors per LDS tile: 4 row blocks of 32 (the M dimension)            */
+/* U_LB left descriptors per workgroup: 32 per wave (the N dimension of its MFMA tiles); U_RB right descriptors per LDS
+ * tile: 4 row blocks of 32 (the M dimension); U_NONE (top2.h): "no candidate yet" */
 constexpr int U_ROW = 144;         /* bytes per LDS row: +16 keeps the rows of a ds_read_b128 group on distinct banks   */
-constexpr int U_NONE = INT_MAX;    /* "no candidate yet": becomes +INFINITY in the row                                */
 constexpr int U_FAR = INT_MAX / 2; /* norm of a row past the end: U_FAR - 2 dot cannot overflow and beats no real row  */
-
-struct Top2i {
-    int d1, d2; /* the two smallest distances (U_NONE: none) */
-    int j1, j2; /* their right indices                       */
-};
-
-__device__ __forceinline__ bool lex_less(int d, int i, int e, int j) { return d < e || (d == e && i < j); }
-
-__device__ __forceinline__ void top2_insert(Top2i& t, int d, int j)
-{
-    if (lex_less(d, j, t.d1, t.j1)) {
-        t.d2 = t.d1;
-        t.j2 = t.j1;
-        t.d1 = d;
-        t.j1 = j;
-    } else if (lex_less(d, j, t.d2, t.j2)) {
-        t.d2 = d;
-        t.j2 = j;
-    }
-}
 
 /* x - 128 for the sixteen bytes of v, as signed bytes */
 __device__ __forceinline__ v4i to_signed(v4i v)
@@ -102,7 +79,7 @@ __global__ __launch_bounds__(256) void k_norms_u8(const uint8_t* __restrict__ de
 __global__ __launch_bounds__(256, 2) void k_match_u8(const uint8_t* __restrict__ ldesc, int l_len,
                                                      const int* __restrict__ lnorm, const uint8_t* __restrict__ rdesc,
                                                      int r_len, const int* __restrict__ rnorm, int n_split,
-                                                     Top2i* __restrict__ partial)
+                                                     Top2<int>* __restrict__ partial)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_r[U_RB * U_ROW];
     __shared__ __attribute__((aligned(16))) int     s_rn[U_RB];
@@ -197,59 +174,16 @@ __global__ __launch_bounds__(256, 2) void k_match_u8(const uint8_t* __restrict__
         }
     }
     const int ln = lnorm[lc];
-    Top2i     best{e1 == U_NONE ? U_NONE : e1 + ln, e2 == U_NONE ? U_NONE : e2 + ln, j1, j2};
+    Top2<int> best{e1 == U_NONE ? U_NONE : e1 + ln, e2 == U_NONE ? U_NONE : e2 + ln, j1, j2};
     /* the two halves hold different right rows of the same left descriptor */
-    const int od1 = __shfl_xor(best.d1, 32), od2 = __shfl_xor(best.d2, 32);
-    const int oj1 = __shfl_xor(best.j1, 32), oj2 = __shfl_xor(best.j2, 32);
+    const int od1 = __shfl_xor(best.v1, 32), od2 = __shfl_xor(best.v2, 32);
+    const int oj1 = __shfl_xor(best.i1, 32), oj2 = __shfl_xor(best.i2, 32);
     top2_insert(best, od1, oj1);
     top2_insert(best, od2, oj2);
     if (half == 0 && l < l_len) partial[(size_t)l * n_split + blockIdx.y] = best;
 }
 
-__device__ __forceinline__ float as_dist(int d) { return d == U_NONE ? INFINITY : (float)d; }
-
-/* merge the per-split candidates; accept as k_match_finish forms it */
-__global__ __launch_bounds__(256) void k_match_u8_finish(const Top2i* __restrict__ partial, int l_len, int n_split,
-                                                         popsift_hip_match* __restrict__ out)
-{
-    const int l = blockIdx.x * 256 + threadIdx.x;
-    if (l >= l_len) return;
-    Top2i t = partial[(size_t)l * n_split];
-    for (int k = 1; k < n_split; k++) {
-        const Top2i o = partial[(size_t)l * n_split + k];
-        top2_insert(t, o.d1, o.j1);
-        top2_insert(t, o.d2, o.j2);
-    }
-    popsift_hip_match m;
-    m.best = t.j1;
-    m.second = t.j2;
-    m.dist_best = as_dist(t.d1);
-    m.dist_second = as_dist(t.d2);
-    m.accept = (__fdiv_rn(m.dist_best, m.dist_second) < 0.8f) ? 1 : 0;
-    out[l] = m;
-}
-
-__global__ __launch_bounds__(256) void k_gather_rows_u8(const uint8_t* __restrict__ desc, const int* __restrict__ list, int n,
-                                                        uint8_t* __restrict__ out)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n * 8) return;
-    const int row = c >> 3, ch = c & 7;
-    *(v4i*)(out + (size_t)row * 128 + 16 * ch) = *(const v4i*)(desc + (size_t)list[row] * 128 + 16 * ch);
-}
-
 }  // namespace
-
-int match_u8_splits(int l_len, int r_len)
-{
-    const int l_blocks = (l_len + U_LB - 1) / U_LB;
-    const int tiles = (r_len + U_RB - 1) / U_RB;
-    int       s = (1024 + l_blocks - 1) / std::max(l_blocks, 1); /* >= 2 resident workgroups per CU x 2 rounds */
-    s = std::min(s, std::max(tiles, 1));
-    return std::max(s, 1);
-}
-
-size_t match_u8_partial_bytes(int l_len, int n_split) { return (size_t)std::max(l_len, 1) * n_split * sizeof(Top2i); }
 
 hipError_t launch_norms_u8(const uint8_t* desc, int n, int* out, hipStream_t s)
 {
@@ -263,16 +197,8 @@ hipError_t launch_match_u8(const uint8_t* ldesc, int l_len, const int* lnorm, co
 {
     if (l_len <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_match_u8, dim3((l_len + U_LB - 1) / U_LB, n_split), dim3(256), 0, s, ldesc, l_len, lnorm, rdesc, r_len,
-                       rnorm, n_split, (Top2i*)partial);
-    hipLaunchKernelGGL(k_match_u8_finish, dim3((l_len + 255) / 256), dim3(256), 0, s, (const Top2i*)partial, l_len, n_split,
-                       out);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather_rows_u8(const uint8_t* desc, const int* list, int n, uint8_t* out, hipStream_t s)
-{
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_gather_rows_u8, dim3((n * 8 + 255) / 256), dim3(256), 0, s, desc, list, n, out);
+                       rnorm, n_split, (Top2<int>*)partial);
+    launch_top2_finish((const Top2<int>*)partial, l_len, n_split, out, nullptr, nullptr, 0, l_len, s);
     return hipGetLastError();
 }
 

@@ -992,19 +992,6 @@ __global__ __launch_bounds__(256) void k_pair_points(const popsift_hip_pair* __r
     out[i] = v4f{lf[fl].xpos, lf[fl].ypos, rf[fr].xpos, rf[fr].ypos};
 }
 
-/* the first failing HIP call decides the status; the calls after it are skipped */
-struct Status {
-    int  rc = POPSIFT_HIP_OK;
-    bool good() const { return rc == POPSIFT_HIP_OK; }
-    bool operator()(hipError_t e)
-    {
-        if (e != hipSuccess && rc == POPSIFT_HIP_OK) rc = (e == hipErrorOutOfMemory) ? POPSIFT_HIP_ERR_OOM : POPSIFT_HIP_ERR_DEVICE;
-        return e == hipSuccess;
-    }
-};
-
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace
 }  // namespace popsift_hip
 
@@ -1401,11 +1388,8 @@ int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip
     if (n == 0) return POPSIFT_HIP_OK;
     popsift_hip_devfeatures* l = const_cast<popsift_hip_devfeatures*>(lc);
     if (hipSetDevice(l->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    Status ok;
-    if (!l->m_stream) {
-        hipStream_t s = nullptr;
-        if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) l->m_stream = s;
-    }
+    Status            ok;
+    hipStream_t const s = stream_of(ok, *l);
     /* device block and its pinned twin: a flag, the pairs, the points */
     const size_t b_pairs = sizeof(popsift_hip_pair) * (size_t)n, b_pts = sizeof(float) * 4 * (size_t)n, need = 16 + b_pairs + b_pts;
     if (ok.good() && need > l->v_cap) {
@@ -1418,19 +1402,15 @@ int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip
     /* a right set on another GPU: its feature records and its map come over for the call */
     const DevFeature* rf = r->d_feat;
     const int*        rrev = r->d_rev;
-    char*             r_copy = nullptr;
-    if (ok.good() && r->device != l->device) {
-        const size_t bf = sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1), br = sizeof(int) * (size_t)r->n_desc;
-        if (ok(hipMalloc((void**)&r_copy, bf + br)) && ok(hipMemcpyPeer(r_copy, l->device, r->d_feat, r->device, bf)) &&
-            ok(hipMemcpyPeer(r_copy + bf, l->device, r->d_rev, r->device, br))) {
-            rf = (const DevFeature*)r_copy;
-            rrev = (const int*)(r_copy + bf);
-        }
+    PeerCopy          peer;
+    if (peer.fetch(ok, l->device, r->device,
+                   {{r->d_feat, sizeof(DevFeature) * (size_t)std::max(r->n_feat, 1)}, {r->d_rev, sizeof(int) * (size_t)r->n_desc}})) {
+        rf = (const DevFeature*)peer.at[0];
+        rrev = (const int*)peer.at[1];
     }
     if (ok.good()) {
-        hipStream_t const s = (hipStream_t)l->m_stream;
-        char* const       d = (char*)l->v_buf;
-        char* const       h = (char*)l->v_host;
+        char* const d = (char*)l->v_buf;
+        char* const h = (char*)l->v_host;
         memset(h, 0, 16);
         memcpy(h + 16, pairs, b_pairs);
         if (ok(hipMemcpyAsync(d, h, 16 + b_pairs, hipMemcpyHostToDevice, s))) {
@@ -1445,7 +1425,6 @@ int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip
             else memcpy(pts, h + 16 + b_pairs, b_pts);
         }
     }
-    if (r_copy) (void)hipFree(r_copy);
     return ok.rc;
 }
 
