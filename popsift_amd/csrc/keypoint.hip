@@ -262,55 +262,36 @@ __device__ __forceinline__ void sincos_cr(float ang, float& s, float& c)
 }
 
 /* ISA: magnitude + angle */
-/* t = atan(min / max) * 4/pi in [0, 1] -> the angle of (x, y) in (-4, 4], without compares and selects (half rate on
- * gfx950; and / xor / add / sub are full rate, tools/ubench/valu_rate.hip):
- *   2 - sx * (1 + sd * (1 - t)),   sd = -1 where |y| > |x|, sx = -1 where x < 0
- * (2 - t where the roles of x and y were swapped, then 4 - that where x < 0), each sign applied by an XOR with the sign
- * bit of |x| - |y| resp. of x; the sign of y is copied last (one v_bfi).  1 - (1 - t) differs from t by < 6e-8. */
-__device__ __forceinline__ float octants(float t, float x, float y, float ax, float ay)
+/* The angle of the gradient (x, y) from the tangent of HALF the angle, which needs no octant reduction: with
+ * theta' = the angle of (|x|, y), in [-pi/2, pi/2],
+ *   tan(theta' / 2) = y / (|x| + |g|),   |g| = mod = sqrt(x^2 + y^2), which both callers have for their weight,
+ * lies in [-1, 1], where the odd degree-11 minimax polynomial of atan(t) * 8/pi (the one of atan(r) * 4/pi on [0, 1],
+ * max error 2.2e-6 there, fitted offline, every coefficient doubled) gives theta' in units of pi / 4 ("bins"): no min,
+ * no max, no swap, no quadrant signs -- compares, selects and min / max are half rate on gfx950
+ * (tools/ubench/valu_rate.hip).  x < 0 mirrors: theta = 4 - theta' bins, one v_bfi for the sign and the caller's scale
+ * and offset in the same two FMAs:
+ *   returns  scale * theta + k0 - 2 * scale   for x >= 0,  that plus 8 * scale where x < 0 and y < 0,
+ * i.e. the angle in [-2, 6] bins where atan2 gives (-4, 4]: equal mod 8.  `scale` and `k0` are wave-uniform.
+ * 1e-18 in the denominator keeps |t| <= 1 for EVERY gradient: a zero one gives t = 0, not 0 * inf, and one below
+ * 1.1e-19, whose squares underflow so that mod comes out as 0 although y is not, gives |y| / (|x| + 1e-18) < 1 -- with
+ * 1e-30 there it gave t = 1e4, the polynomial overflowed and the NaN fraction went into the histogram words of a sample
+ * whose weight is zero (planes with a black background have such tails: a bright edge blurred level after level).  Such
+ * a sample's angle is then wrong and harmless, its weight being 0 in fixed point below |g| = 1e-6; above that 1e-18 is
+ * less than 1e-12 of the denominator.  Error against the float64 atan2 with v_sqrt and v_rcp one ulp off either way:
+ * 4.9e-6 bins for |g| >= 1e-6 (tests/test_half_angle.py).  v_rcp instead of a division, as before. */
+__device__ __forceinline__ float half_angle_bins(float y, float x, float mod, float scale, float k0)
 {
-    const unsigned int sgn = 0x80000000u;
-    const float a = __uint_as_float(__float_as_uint(1.0f - t) ^ (__float_as_uint(ax - ay) & sgn));
-    const float b = __uint_as_float(__float_as_uint(1.0f + a) ^ (__float_as_uint(x) & sgn));
-    return copysignf(2.0f - b, y);
-}
-
-/* atan2(y, x) * 4/pi in (-4, 4]: octant reduction + odd degree-11 minimax polynomial of
- * atan(r) * 4/pi on [0, 1] (max error 2.2e-6 bins = 1.7e-6 rad, fitted offline), v_rcp instead of
- * a division.  Only used for the descriptor's SOFT orientation binning, which is continuous in
- * the angle (the reference uses fast intrinsics there too, s_desc_loop.cu:48,97). */
-/* ISA: magnitude + angle */
-__device__ __forceinline__ float atan2_bins(float y, float x)
-{
-    const float ax = fabsf(x), ay = fabsf(y);
-    /* the larger magnitude is kept off zero inside the v_max3 (0 / 1e-30 = 0: the same result as the test for a zero
-     * gradient it replaces), the sign of y is copied with one v_bfi (t >= 0; y = -0 gives -t, the same angle mod 8) */
-    const float mx = fmaxf(fmaxf(ax, ay), 1e-30f), mn = fminf(ax, ay);
-    const float r = mn * __builtin_amdgcn_rcpf(mx);
-    const float s = r * r;
-    float       p = fmaf(-0.01492126751691103f, s, 0.06703268736600876f);
-    p = fmaf(p, s, -0.14823880791664124f);
-    p = fmaf(p, s, 0.24642325937747955f);
-    p = fmaf(p, s, -0.42350852489471436f);
-    p = fmaf(p, s, 1.2732105255126953f);
-    return octants(p * r, x, y, ax, ay);
-}
-
-/* The same with a degree-9 polynomial (max error 1.5e-5 bins = 1.2e-5 rad, fitted offline as a minimax problem) for the
- * descriptor's soft binning alone: the angle only splits a sample's weight between two neighbouring bins, so 1e-5 bins
- * moves 1e-5 of a weight.  The largest magnitude is kept off zero inside the v_max3 (a zero gradient has zero weight
- * whatever its angle), the sign of y is copied with one v_bfi. */
-__device__ __forceinline__ float atan2_bins9(float y, float x)
-{
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(fmaxf(ax, ay), 1e-30f), mn = fminf(ax, ay);
-    const float r = mn * __builtin_amdgcn_rcpf(mx);
-    const float s = r * r;
-    float       p = fmaf(0.026540832594037056f, s, -0.1084246039390564f);
-    p = fmaf(p, s, 0.22938621044158936f);
-    p = fmaf(p, s, -0.4205572307109833f);
-    p = fmaf(p, s, 1.2730693817138672f);
-    return octants(p * r, x, y, ax, ay);
+    const float d = (fabsf(x) + 1e-18f) + mod;
+    const float t = y * __builtin_amdgcn_rcpf(d);
+    const float s = t * t;
+    float       p = fmaf(-0.02984253503382206f, s, 0.13406537473201752f);
+    p = fmaf(p, s, -0.2964776158332825f);
+    p = fmaf(p, s, 0.4928465187549591f);
+    p = fmaf(p, s, -0.8470170497894287f);
+    p = fmaf(p, s, 2.5464210510253906f);
+    const float th = t * p;
+    const float sg = copysignf(scale, x);
+    return fmaf(th, sg, fmaf(-2.0f, sg, k0));
 }
 
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -341,9 +322,10 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
     const InitExt* __restrict__ iext = filtered ? bd.s[blockIdx.y].iext2 : bd.s[blockIdx.y].iext;
     float* __restrict__         ohist = bd.s[blockIdx.y].ohist;
     const int n_oct = pdp->n_oct, L = pdp->L;
-    /* bin 36 is bin 0 (the histogram is circular): a sample that rounds up to 36 is added there and joins bin 0 at the
-     * read-out, so the loop needs no wrap-around select */
-    constexpr int    NB = PS_ORI_NBINS + 2;
+    /* The histogram is circular and the loop's bin coordinate runs from 9 to 45 (half_angle_bins: the angle in [-pi/2,
+     * 3pi/2]; next to a bin edge from 0 to 36, atan2_acc): bin b + 36 is bin b.  A sample is added where it falls and
+     * the bins 36 .. 45 join the bins 0 .. 9 at the read-out, so the loop needs no wrap-around select. */
+    constexpr int    NB = PS_ORI_NBINS + 10;
     __shared__ fix64 s_hist[KP_NW][ORI_COPIES][NB];
     const int        wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     fix64*           hall = &s_hist[wave][0][0];
@@ -413,17 +395,19 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
             if (live && sq_dist <= (float)sq_thres) {
                 /* hypotf * expf(sq_dist * factor) * 2^20 (the fixed-point scale of to_fix): the scale and log2(e) go into
                  * the exponent, so the window weight is one FMA and one v_exp */
-                const float wfix = __builtin_amdgcn_sqrtf(fmaf(gdx, gdx, gdy * gdy)) * __builtin_amdgcn_exp2f(fmaf(sq_dist, factor2, 20.0f));
+                const float mod = __builtin_amdgcn_sqrtf(fmaf(gdx, gdx, gdy * gdy));
+                const float wfix = mod * __builtin_amdgcn_exp2f(fmaf(sq_dist, factor2, 20.0f));
                 /* The bin is a HARD decision, so the angle needs libm-grade accuracy -- but only when it lies next to a
-                 * bin edge: the cheap atan2 (the descriptor's one-reciprocal degree-11 polynomial in units of pi / 4:
-                 * error < 1.7e-6 rad = 1e-5 of these bins) decides every sample farther than 1e-4 bins from an edge
-                 * identically to the accurate one, which the others (1 in 5000) then take. */
-                float fb = fmaf(atan2_bins(gdy, gdx), (float)PS_ORI_NBINS / 8.0f, (float)PS_ORI_NBINS / 2.0f);
+                 * bin edge: the cheap arctangent (the descriptor's: one reciprocal, a degree-11 polynomial in units of
+                 * pi / 4, error < 4.9e-6 of those = 2.2e-5 of these bins) decides every sample farther than 1e-4 bins
+                 * from an edge identically to the accurate one, which the others (1 in 5000) then take.  Scale and
+                 * offset ride in its last FMA: theta * 36 / 8 + 18, up to a multiple of 36 (NB above). */
+                float fb = half_angle_bins(gdy, gdx, mod, (float)PS_ORI_NBINS / 8.0f, 0.75f * (float)PS_ORI_NBINS);
                 /* next to an edge the value is formed exactly as the oracle forms it (product, then IEEE quotient): gradients
                  * of exactly 45 degrees -- frequent in level 0 of the up-scaled octave -- sit ON the edge 22.5, 31.5, ...,
                  * where the two formulas round to different sides */
                 if (fabsf((fb - floorf(fb)) - 0.5f) < 1e-4f) fb = (float)PS_ORI_NBINS * (atan2_acc(gdy, gdx) + F_PI) / F_PI2;
-                /* roundf(fb) for fb in [0, 36]: floor(fb + 0.5), one instruction; 36 is bin 0 (NB above) */
+                /* roundf(fb) for fb in [0, 45]: floor(fb + 0.5), one instruction; 36 .. 45 are bins 0 .. 9 (NB above) */
                 int bidx;
                 asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(bidx) : "v"(fb));
                 atomicAdd(&hist[bidx], (fix64)(unsigned int)wfix);
@@ -452,7 +436,8 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
         if (lane < PS_ORI_NBINS) {
             fix64 acc = 0ull;
 #pragma unroll
-            for (int k = 0; k < ORI_COPIES; k++) acc += hall[k * NB + lane] + (lane == 0 ? hall[k * NB + PS_ORI_NBINS] : 0ull);
+            for (int k = 0; k < ORI_COPIES; k++)
+                acc += hall[k * NB + lane] + (lane < NB - PS_ORI_NBINS ? hall[k * NB + PS_ORI_NBINS + lane] : 0ull);
             ohist[(size_t)g * PS_ORI_NBINS + lane] = from_fix(acc);
         }
         wave_lds_sync();
@@ -896,7 +881,8 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
         const u4           q0 = rp[0], q1 = rp[1], q2 = rp[2];
         const float        x = uniformf(__uint_as_float(q0.x)), y = uniformf(__uint_as_float(q0.y));
         const float        crsbp = uniformf(__uint_as_float(q0.z)), srsbp = uniformf(__uint_as_float(q0.w));
-        const float        ang_bins = uniformf(__uint_as_float(q1.x));
+        /* the keypoint orientation in bins enters the angle's last FMA as 2 - ang_bins (half_angle_bins) */
+        const float        ang_k0 = 2.0f - uniformf(__uint_as_float(q1.x));
         const float        inv_c = uniformf(__uint_as_float(q1.y)), inv_s = uniformf(__uint_as_float(q2.w));
         const int          pmin = uniform((int)q1.z), pmax = uniform((int)q1.w);
         const unsigned int misc = (unsigned int)uniform((int)q2.z);
@@ -1102,7 +1088,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                     const float  wm = __builtin_amdgcn_exp2f(fmaf(-0.18033688011112042f, fmaf(u, u, v * v), ffbits)) * mod;
                     /* gradient angle relative to the keypoint orientation in units of one bin; any multiple of 8 may be
                      * missing: floor / fraction / (& 7) below do not care */
-                    const float tth = atan2_bins9(gy, gx) - ang_bins;
+                    const float tth = half_angle_bins(gy, gx, mod, 1.0f, ang_k0);
                     const float ffo = floorf(tth);
                     const float do0 = tth - ffo;
 
