@@ -889,6 +889,39 @@ hipError_t enqueue_order(popsift_hip_ctx* c, bool filtered)
     return launch_order(c->pd, c->sc, c->order_coarse, ob, c->nb, c->stream);
 }
 
+/* What extraction and describe end with: orientation -> scan -> descriptors -> the counters to the host, with their stage
+ * marks.  lb: the slot table the scan writes its records through; with_ori: k_orientation and k_scan_local run (otherwise
+ * the Ext records and the partial sums are there already, k_frame_place); fb: the frames of a describe, whose records
+ * k_frame_out moves to caller order after the descriptor kernel, or null. */
+int enqueue_descriptor_stages(popsift_hip_ctx* c, const BatchDesc& lb, bool filtered, bool with_ori, const FrameBatch* fb)
+{
+    const bool stages = (c->profile == 2);
+    auto       mark = [&](int k) -> hipError_t { return stages ? hipEventRecord(c->ev_stage[k], c->stream) : hipSuccess; };
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_ORIENTATION));
+    if (with_ori) {
+        HIP_TRY(c, launch_orientation(c->d_pd, c->bd, c->nb, c->sc, filtered, (int)c->ohist_cap, c->kp_waves, c->stream));
+        SYNC_CHK(c, "k_orientation");
+    }
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_SCAN));
+    const int n_chunks = std::max((int)(((size_t)c->pd.n_oct * c->sc.max_extrema + scan_chunk() - 1) / scan_chunk()), 1);
+    if (with_ori)
+        HIP_TRY(c, launch_scan(c->d_pd, lb, c->nb, c->sc, filtered, (int)c->ohist_cap, n_chunks, c->desc_cap, c->stream));
+    else
+        HIP_TRY(c, launch_scan_apply(c->d_pd, lb, c->nb, c->sc, n_chunks, c->desc_cap, c->stream));
+    SYNC_CHK(c, "k_scan_local / k_scan_apply");
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DESCRIPTOR));
+    HIP_TRY(c, launch_descriptors(c->d_pd, c->bd, c->nb, c->sc, c->desc_cap, c->kp_waves, c->stream));
+    SYNC_CHK(c, "descriptor kernel");
+    if (fb) {
+        /* after the descriptor kernel: k_descriptor_grid / _notile read ext + map[d] with the list positions */
+        HIP_TRY(c, launch_frame_out(c->bd, *fb, c->nb, c->desc_cap, c->frames_max, c->stream));
+        SYNC_CHK(c, "k_frame_out");
+    }
+    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_COUNT));
+    HIP_TRY(c, hipMemcpyAsync(c->h_ct, c->d_ct, sizeof(Counters) * (size_t)c->nb, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
 /* counters_cleared: the level-0 launch of this batch has zeroed the counters (submit); re-runs clear them here */
 int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
 {
@@ -917,19 +950,7 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
             SYNC_CHK(c, "k_order (filtered list)");
         }
     }
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_ORIENTATION));
-    HIP_TRY(c, launch_orientation(c->d_pd, c->bd, c->nb, c->sc, filtered, (int)c->ohist_cap, c->kp_waves, c->stream));
-    SYNC_CHK(c, "k_orientation");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_SCAN));
-    const int n_chunks = (int)(((size_t)c->pd.n_oct * c->sc.max_extrema + scan_chunk() - 1) / scan_chunk());
-    HIP_TRY(c, launch_scan(c->d_pd, c->bd, c->nb, c->sc, filtered, (int)c->ohist_cap, std::max(n_chunks, 1), c->desc_cap, c->stream));
-    SYNC_CHK(c, "k_scan_local / k_scan_apply");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DESCRIPTOR));
-    HIP_TRY(c, launch_descriptors(c->d_pd, c->bd, c->nb, c->sc, c->desc_cap, c->kp_waves, c->stream));
-    SYNC_CHK(c, "descriptor kernel");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_COUNT));
-    HIP_TRY(c, hipMemcpyAsync(c->h_ct, c->d_ct, sizeof(Counters) * (size_t)c->nb, hipMemcpyDeviceToHost, c->stream));
-    return 0;
+    return enqueue_descriptor_stages(c, c->bd, filtered, true, nullptr);
 }
 
 /* The keypoint stages of a describe (describe.hip): the frames instead of detection and refinement, then orientation (or
@@ -959,27 +980,7 @@ int enqueue_describe_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     SYNC_CHK(c, "k_frame_count");
     HIP_TRY(c, launch_frame_place(c->d_pd, c->bd, fb, c->nb, c->sc, c->ori_given, c->frames_max, c->stream));
     SYNC_CHK(c, "k_frame_place");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_ORIENTATION));
-    if (!c->ori_given) {
-        HIP_TRY(c, launch_orientation(c->d_pd, c->bd, c->nb, c->sc, false, (int)c->ohist_cap, c->kp_waves, c->stream));
-        SYNC_CHK(c, "k_orientation");
-    }
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_SCAN));
-    const int n_chunks = std::max((int)(((size_t)c->pd.n_oct * c->sc.max_extrema + scan_chunk() - 1) / scan_chunk()), 1);
-    if (!c->ori_given)
-        HIP_TRY(c, launch_scan(c->d_pd, lb, c->nb, c->sc, false, (int)c->ohist_cap, n_chunks, c->desc_cap, c->stream));
-    else
-        HIP_TRY(c, launch_scan_apply(c->d_pd, lb, c->nb, c->sc, n_chunks, c->desc_cap, c->stream));
-    SYNC_CHK(c, "k_scan_local / k_scan_apply");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DESCRIPTOR));
-    HIP_TRY(c, launch_descriptors(c->d_pd, c->bd, c->nb, c->sc, c->desc_cap, c->kp_waves, c->stream));
-    SYNC_CHK(c, "descriptor kernel");
-    /* after the descriptor kernel: k_descriptor_grid / _notile read ext + map[d] with the list positions */
-    HIP_TRY(c, launch_frame_out(c->bd, fb, c->nb, c->desc_cap, c->frames_max, c->stream));
-    SYNC_CHK(c, "k_frame_out");
-    HIP_TRY(c, mark(POPSIFT_HIP_STAGE_COUNT));
-    HIP_TRY(c, hipMemcpyAsync(c->h_ct, c->d_ct, sizeof(Counters) * (size_t)c->nb, hipMemcpyDeviceToHost, c->stream));
-    return 0;
+    return enqueue_descriptor_stages(c, lb, false, !c->ori_given, &fb);
 }
 
 /* the frames of a describe (popsift_hip_describe_batch); null for an extraction */

@@ -124,6 +124,10 @@ hipError_t launch_scan(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const S
 hipError_t launch_descriptors(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
                               hipStream_t s);
 
+/* desc_modes.hip: the descriptor kernel of desc_mode GRID, NOTILE, IGRID or ILOOP (launch_descriptors calls it for those) */
+hipError_t launch_desc_modes(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
+                             hipStream_t s);
+
 /* k_scan_apply alone, for lists whose Ext records and local partial sums were written elsewhere (k_frame_place) */
 hipError_t launch_scan_apply(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
                              hipStream_t s);

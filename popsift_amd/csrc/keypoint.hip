@@ -1,6 +1,8 @@
 /*
- * keypoint.hip -- orientation assignment, orientation prefix sum, the 128-D descriptors
- * (loop, grid, notile / igrid, iloop) + normalisation, Feature assembly.  All kernels size themselves
+ * keypoint.hip -- orientation assignment, orientation prefix sum, the 128-D loop descriptor + normalisation, Feature
+ * assembly: the kernels of every benchmark step.  The descriptors of the other DescModes (grid, notile / igrid,
+ * iloop) are in desc_modes.hip, the device helpers both files use (wave sums, wave-uniform values, the work
+ * distribution KP_CHUNK, atan2_acc) in keypoint_dev.h.  All kernels size themselves
  * from the device-resident counters (grid-stride), so the host never has to
  * read a count back between stages (the reference blocks on the counters twice
  * per image: s_orientation.cu:351, sift_desc.cu:60-61).
@@ -9,45 +11,20 @@
  *   ori_par               s_orientation.cu:60-242   -> k_orientation (1 wave / extremum)
  *   ori_prefix_sum        s_orientation.cu:303-345  -> k_scan_local + k_scan_apply (256 extrema / workgroup)
  *   ext_desc_loop(+_sub)  s_desc_loop.cu:19-161     -> k_descriptor (1 wave / descriptor)
- *   ext_desc_grid         s_desc_grid.cu:19-147     -> k_descriptor_grid
- *   ext_desc_notile/igrid s_desc_notile.cu:28-166, s_desc_igrid.cu:20-109 -> k_descriptor_notile<false>
- *   ext_desc_iloop        s_desc_iloop.cu:18-154    -> k_descriptor_notile<true>
  *   normalize_histogram   s_desc_normalize.h:14-33, s_desc_norm_rs.h, s_desc_norm_l2.h
- *                                                   -> fused into the descriptor kernels
+ *                                                   -> fused into k_descriptor
  *   prep_features         sift_pyramid.cu:249-279   -> fused into k_scan_apply
  */
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "keypoint_dev.h"
 #include "sift_types.h"
 
 namespace popsift_hip {
 namespace {
 
-/* sift_constants.h:22-29: float constants */
-constexpr float F_PI = 3.14159265358979323846f;
-constexpr float F_PI2 = 2.0f * 3.14159265358979323846f;
-constexpr float            ORI_WINFACTOR = 1.5f;
-constexpr float            DESC_MAGNIFY = 3.0f;
-
-/*
- * Histogram accumulation: on gfx950 an LDS float atomic add (ds_add_f32) costs
- * ~200 cycles per wave instruction whatever the address pattern, an integer one
- * ~6 (tools/ubench/lds_atomic.hip).  Bins are therefore 64-bit fixed point
- * (2^-32 resolution, exact and order-independent sums => bit-reproducible
- * histograms, unlike the reference's float atomicAdd, s_orientation.cu:136).
- */
-typedef unsigned long long fix64;
-/* one sample weighs < 2^11 (|gradient| <= 255*2*sqrt2, window weights <= 1): w * 2^20 fits 32 bits */
-__device__ __forceinline__ fix64 to_fix(float w) { return (fix64)(unsigned int)(w * 1048576.0f); }
-__device__ __forceinline__ float from_fix(fix64 v) { return (float)((double)v * (1.0 / 1048576.0)); }
-
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+constexpr float ORI_WINFACTOR = 1.5f; /* sift_constants.h:22-29 */
 
 /* Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15
  * and row_bcast:31 carry the row totals across), register to register -- no LDS round trips as with six shuffles. */
@@ -62,36 +39,6 @@ __device__ __forceinline__ int wave_incl_scan(int v)
     return v;
 }
 
-
-/* The sum over the 64 lanes, in every lane: four DPP adds inside the rows of 16 (quad butterflies, then the two mirrors),
- * the four row sums through scalar registers.  Register to register -- six __shfl_xor are six dependent ds_bpermute round
- * trips through the LDS queue (~150 cycles each behind whatever the wave has queued there), three times per descriptor
- * with the L2 normalisation.  A fixed order of additions like the butterfly's, so results stay reproducible. */
-__device__ __forceinline__ float wave_allsum(float v)
-{
-#define PS_DPP_ADD(CTRL) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false))
-    PS_DPP_ADD(0xB1);  /* quad_perm [1,0,3,2] */
-    PS_DPP_ADD(0x4E);  /* quad_perm [2,3,0,1] */
-    PS_DPP_ADD(0x141); /* row_half_mirror     */
-    PS_DPP_ADD(0x140); /* row_mirror          */
-#undef PS_DPP_ADD
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
-/* a value every lane of the wave holds identically, moved to scalar registers */
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float uniformf(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ long long uniform64(long long v)
-{
-    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)(v & 0xffffffffll));
-    const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
 /* The four gradient taps around plane element `off` (>= pitch + 1, so every tap is in the plane).  `layer` and
  * `pitch` are wave-uniform: with an UNSIGNED 32-bit byte offset the loads take the scalar-base + vector-offset
  * form (three scalar bases: the row, the row below, the row above) instead of 64-bit vector address arithmetic
@@ -103,7 +50,7 @@ struct Taps {
     const char* up;
     __device__ __forceinline__ Taps(const float* layer, int pitch)
         : row((const char*)layer), dn((const char*)(layer + pitch)), up((const char*)(layer - pitch)) {}
-    /* the same with the BYTE offset of the element */
+    /* b: the BYTE offset of the element */
     __device__ __forceinline__ void load_b(unsigned int b, float& xp, float& xm, float& yp, float& ym) const
     {
         xp = *(const float*)(row + (size_t)b + 4);
@@ -111,63 +58,9 @@ struct Taps {
         yp = *(const float*)(dn + (size_t)b);
         ym = *(const float*)(up + (size_t)b);
     }
-    __device__ __forceinline__ void load(int off, float& xp, float& xm, float& yp, float& ym) const
-    {
-        const size_t b = (unsigned int)off * 4u;
-        xp = *(const float*)(row + b + 4);
-        xm = *(const float*)(row + b - 4);
-        yp = *(const float*)(dn + b);
-        ym = *(const float*)(up + b);
-    }
 };
 
 /* ISA: end */
-/* element `idx` >= 0 of a wave-uniform plane through an unsigned 32-bit byte offset (scalar base + vector offset) */
-__device__ __forceinline__ float plane_at(const float* pl, int idx)
-{
-    return *(const float*)((const char*)pl + (size_t)((unsigned int)idx * 4u));
-}
-
-/*
- * Work distribution of the keypoint kernels.  Workgroups b and b + 8 share an XCD and its 4 MiB L2 (round-robin
- * dispatch -- relied on for speed only, never for correctness).  The lists come out of refinement grouped by image
- * region (extrema.hip: a detection sub-queue is a region, refinement appends one sub-queue batch at a time), so they
- * are cut into chunks of KP_CHUNK consecutive keypoints, chunk c goes to XCD c mod 8, and the workgroups of an XCD
- * walk its chunks front to back: the patches of the waves in flight on one XCD overlap, while every XCD still gets
- * the same mix of levels and octaves (the work per keypoint grows with sigma^2; handing each XCD one contiguous
- * eighth of a level-major list left the XCD with the coarse levels running 35 % longer than the others).
- * gridDim.x is a multiple of 8; NW = waves per workgroup.  Position s of XCD x is list element
- * ((s / KP_CHUNK) * 8 + x) * KP_CHUNK + s % KP_CHUNK.
- * (Tried and dropped, round 2: resident waves pulling positions from work queues in device memory -- one returning
- * atomicAdd per keypoint on 32 padded heads, next position requested ahead of time.  592 us against 505 us for the
- * descriptor kernel, 164 against 106 for orientation: the hardware dispatcher already balances 65536 single-wave
- * workgroups, and it does so without a memory round trip in the wave's in-order load queue.  Round 3 repeated it with
- * FEWER resident waves -- 8 .. 32 per CU, one counter per XCD, one descriptor / four histograms per fetch -- so that wave
- * slots, registers and LDS stay free for the other images' bandwidth-bound kernels: at 32 per CU it equals this
- * distribution (k_descriptor 421 us, 2.90 Gpix/s), at 24 / 16 / 12 / 8 it loses (2.89 / 2.77 / 2.58 / 2.47 Gpix/s), and
- * the level launches of the other images take as long in the mix as before (107 us against 108 us per octave-0 level,
- * profiles/r03_timeline_resident16.txt): what slows them beside a descriptor kernel is the shared vector issue, LDS and
- * L2, not the lack of a free slot.  DESIGN 6.4.)
- */
-#ifndef KP_CHUNK
-#define KP_CHUNK 256
-#endif
-struct XcdSlice {
-    int x, s, step;
-    __device__ __forceinline__ int index() const { return ((s / KP_CHUNK) * 8 + x) * KP_CHUNK + (s % KP_CHUNK); }
-    /* positions whose element lies beyond the list are skipped: later chunks of the same XCD may still be inside */
-    __device__ __forceinline__ bool more(int total) const { return (s / KP_CHUNK) * 8 * KP_CHUNK < total; }
-};
-template <int NW>
-__device__ __forceinline__ XcdSlice xcd_slice()
-{
-    XcdSlice sl;
-    sl.x = blockIdx.x & 7;
-    sl.s = (int)(blockIdx.x >> 3) * NW + (int)(threadIdx.x >> 6);
-    sl.step = (int)(gridDim.x >> 3) * NW;
-    return sl;
-}
-
 /* clamped extrema counts -> exclusive prefix (uniform, <= 20 entries) */
 __device__ __forceinline__ int ext_prefix(const Counters* ct, const SiftConsts& sc, int n_oct, int* ps)
 {
@@ -180,45 +73,7 @@ __device__ __forceinline__ int ext_prefix(const Counters* ct, const SiftConsts& 
     return acc;
 }
 
-/* s_gradiant.h:55-69; the caller keeps (x, y) inside [1,w-2]x[1,h-2] */
-__device__ __forceinline__ void get_gradiant(float& grad, float& theta, int x, int y, const float* pl, int pitch)
-{
-    const float* c = pl + (size_t)y * pitch + x;
-    const float  dx = c[1] - c[-1];
-    const float  dy = c[pitch] - c[-pitch];
-    grad = hypotf(dx, dy);
-    theta = atan2f(dy, dx);
-}
-
 /* ------------------------------------------------------------ orientation */
-
-/* atan2 for the HARD 36-bin orientation histogram (s_orientation.cu:129): needs libm-grade
- * accuracy, because an error of e rad moves a sample across a bin edge with probability
- * e / 0.1745.  Cephes atanf scheme (|error| ~ 1.5e-7 rad, about 1 ulp at pi/2 -- the level at
- * which device and host libm already disagree) with Newton-refined v_rcp quotients instead of
- * the ~12-instruction IEEE division sequence of the library routine. */
-__device__ __forceinline__ float div_nr(float a, float b)
-{
-    const float r = __builtin_amdgcn_rcpf(b);
-    const float q = a * r;
-    return fmaf(fmaf(-b, q, a), r, q);
-}
-__device__ __forceinline__ float atan2_acc(float y, float x)
-{
-    const float ax = fabsf(x), ay = fabsf(y);
-    const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float       a = (mx == 0.0f) ? 0.0f : div_nr(mn, mx);
-    const bool  big = a > 0.4142135623730950f; /* tan(pi/8) */
-    const float t = big ? div_nr(a - 1.0f, a + 1.0f) : a;
-    const float z = t * t;
-    const float p = fmaf(fmaf(fmaf(8.05374449538e-2f, z, -1.38776856032e-1f), z, 1.99777106478e-1f), z,
-                         -3.33329491539e-1f);
-    float       r = fmaf(p * z, t, t);
-    r = big ? r + 0.7853981633974483f : r;
-    r = (ay > ax) ? 1.5707963267948966f - r : r;
-    r = (x < 0.0f) ? 3.14159265358979323846f - r : r;
-    return (y < 0.0f) ? -r : r;
-}
 
 /*
  * cos / sin of the keypoint orientation, evaluated in double and rounded once: the same two floats as the oracle's
@@ -294,7 +149,6 @@ __device__ __forceinline__ float half_angle_bins(float y, float x, float mod, fl
     return fmaf(th, sg, fmaf(-2.0f, sg, k0));
 }
 
-typedef float v2f __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) fix64 lds_fix64;
 typedef __attribute__((address_space(3))) unsigned int lds_u32;
 typedef __attribute__((address_space(3))) short lds_i16;
@@ -393,7 +247,7 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
              * comparison with rad^2 and the product with `factor` give what the int round trip gives) */
             const float sq_dist = truncf(dx * dx + dy * dy);
             if (live && sq_dist <= (float)sq_thres) {
-                /* hypotf * expf(sq_dist * factor) * 2^20 (the fixed-point scale of to_fix): the scale and log2(e) go into
+                /* hypotf * expf(sq_dist * factor) * 2^20 (the fixed-point scale of from_fix): the scale and log2(e) go into
                  * the exponent, so the window weight is one FMA and one v_exp */
                 const float mod = __builtin_amdgcn_sqrtf(fmaf(gdx, gdx, gdy * gdy));
                 const float wfix = mod * __builtin_amdgcn_exp2f(fmaf(sq_dist, factor2, 20.0f));
@@ -621,13 +475,6 @@ constexpr int SCAN_CHUNK = 256 * SCAN_ITEMS;
 constexpr int SCAN_LT = 256;
 constexpr int SCAN_LCHUNK = SCAN_LT / 4;
 constexpr int SCAN_SUB = SCAN_CHUNK / SCAN_LCHUNK;
-
-__device__ __forceinline__ int clamped_total(const Counters* ct, const SiftConsts& sc, int n_oct)
-{
-    int acc = 0;
-    for (int o = 0; o < n_oct; o++) acc += min(ct->ext_ct[o], sc.max_extrema);
-    return acc;
-}
 
 __global__ __launch_bounds__(SCAN_LT) void k_scan_local(const PyrDesc* __restrict__ pdp, SiftConsts sc, BatchDesc bd,
                                                      int filtered, int hist_cap)
@@ -1213,8 +1060,8 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
          * correctly rounded roots.  Here the quotient is the hardware reciprocal (1 ulp, like __fdividef's 2 ulp) and the
          * roots are v_sqrt_f32 / v_rsq_f32: 1 ulp where the reference rounds correctly, and a denormal quotient (a bin
          * below 1e-38 of the sum) comes out as 0 -- a divergence of one unit in the last place of single bins, seven orders
-         * below the 1e-3 bar, recorded in DESIGN 4; the notile / iloop / grid kernels keep sqrtf and "/".  It replaced 50
-         * instructions per descriptor. */
+         * below the 1e-3 bar, recorded in DESIGN 4.  It replaced 50 instructions per descriptor; the version with sqrtf
+         * and "/" is normalize_store (desc_modes.hip). */
         if (sc.norm_mode == POPSIFT_HIP_NORM_ROOTSIFT) {
             float sum = v0 + v1;
             sum = wave_allsum(sum);
@@ -1239,330 +1086,6 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
     }
 }
 
-/* --------------------------------------------------------- descriptor: grid */
-
-/*
- * DescMode Grid (s_desc_grid.cu:19-147): every cell samples a FIXED 16 x 16 grid of points of its
- * own rotated unit square, each snapped to the nearest pixel, and bins only into its own 8
- * orientation bins.  The reference runs a (16,4,4) block per descriptor: 16 lanes per cell, each
- * looping over 16 rows.  Here one wave owns a descriptor and visits the cells one after the other
- * with all 64 lanes (4 grid rows x 16 columns per step); bins are accumulated in registers with
- * predicated adds and summed over the wave by a butterfly -- no atomics, fixed summation order.
- * The position arithmetic follows the reference operation by operation (the float -> int
- * truncation of "pt + (round(pt + pix) - pt)" included), so the sampled pixels are the oracle's.
- */
-__global__ __launch_bounds__(256) void k_descriptor_grid(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc,
-                                                         int desc_cap)
-{
-    const float* __restrict__    arena = bd.s[blockIdx.y].arena;
-    const Counters* __restrict__ ct = bd.s[blockIdx.y].ct;
-    const Ext* __restrict__      ext = bd.s[blockIdx.y].ext;
-    const int* __restrict__      map = bd.s[blockIdx.y].map;
-    const float2* __restrict__   rot = bd.s[blockIdx.y].rot;
-    float* __restrict__          desc = bd.s[blockIdx.y].desc;
-    __shared__ float s_feat[4][128];
-    const int        lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float*           feat = s_feat[wave];
-    const int        total = min(ct->ori_total, desc_cap);
-    const int        L = pdp->L;
-    const float      M_4RPI = 4.0f / F_PI;
-    const int        xd = lane & 15, ysub = lane >> 4;
-
-    for (XcdSlice sl = xcd_slice<4>(); sl.more(total); sl.s += sl.step) {
-        const int d = sl.index();
-        if (d >= total) continue;
-        const Ext*     e = ext + map[d];
-        const float    x = uniformf(e->xpos), y = uniformf(e->ypos), sigma = uniformf(e->sigma);
-        const int      ko = min(max(d - e->idx_ori, 0), POPSIFT_HIP_ORI_MAX - 1);
-        const float    ang = e->orientation[ko];
-        const OctDesc* od = &pdp->o[e->octave];
-        const int      width = uniform(od->w), height = uniform(od->h), pitch = uniform(od->pitch);
-        const int      lvl = min(max(e->lpos, 0), L - 1);
-        const float*   layer = arena + uniform64(od->data_off + lvl * od->plane_stride);
-        const float    SBP = fabsf(DESC_MAGNIFY * sigma);
-
-        feat[lane] = 0.0f;
-        feat[lane + 64] = 0.0f;
-        if (SBP != 0.0f) {
-            float sin_t, cos_t;
-            cos_t = uniformf(rot[d].x);
-            sin_t = uniformf(rot[d].y);
-            const float csbp = cos_t * SBP, ssbp = sin_t * SBP;
-            const float ldx = -cos_t + sin_t, ldy = -cos_t - sin_t; /* lft_dn  */
-            const float rsx = cos_t / 8.0f, rsy = sin_t / 8.0f;     /* rgt_stp */
-            const float usx = -sin_t / 8.0f, usy = cos_t / 8.0f;    /* up__stp */
-            for (int cell = 0; cell < 16; cell++) {
-                const int   ix = cell & 3, iy = cell >> 2;
-                const float offx = ix - 1.5f, offy = iy - 1.5f;
-                const float ptx = fmaf(csbp, offx, fmaf(-ssbp, offy, x));
-                const float pty = fmaf(csbp, offy, fmaf(ssbp, offx, y));
-                float       acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int step = 0; step < 4; step++) {
-                    const int yd = step * 4 + ysub;
-                    float     pixox = ldx + (xd + 0.5f) * rsx + (yd + 0.5f) * usx;
-                    float     pixoy = ldy + (xd + 0.5f) * rsy + (yd + 0.5f) * usy;
-                    float     pixx = pixox * SBP, pixy = pixoy * SBP;
-                    pixx = roundf(ptx + pixx) - ptx;
-                    pixy = roundf(pty + pixy) - pty;
-                    pixox = pixx / SBP;
-                    pixoy = pixy / SBP;
-                    const int    gx = (int)(ptx + pixx), gy = (int)(pty + pixy);
-                    /* point texture, clamp addressing */
-                    const int    xc = min(max(gx, 0), width - 1), yc = min(max(gy, 0), height - 1);
-                    const int    xl = min(max(gx - 1, 0), width - 1), xr = min(max(gx + 1, 0), width - 1);
-                    const int    yu = min(max(gy - 1, 0), height - 1), yl = min(max(gy + 1, 0), height - 1);
-                    const int    rowc = __mul24(yc, pitch);
-                    const float  dxv = plane_at(layer, rowc + xr) - plane_at(layer, rowc + xl);
-                    const float  dyv = plane_at(layer, __mul24(yl, pitch) + xc) - plane_at(layer, __mul24(yu, pitch) + xc);
-                    const float  mod = __builtin_amdgcn_sqrtf(dxv * dxv + dyv * dyv);
-                    float        th = atan2_acc(dyv, dxv);
-                    const float  npx = fmaf(cos_t, pixox, sin_t * pixoy);
-                    const float  npy = fmaf(cos_t, pixoy, -sin_t * pixox);
-                    const float  dnx = npx + offx, dny = npy + offy;
-                    const float  ww = __expf(-0.125f * (dnx * dnx + dny * dny));
-                    const float  wx_ = 1.0f - fabsf(npx), wy_ = 1.0f - fabsf(npy);
-                    const float  wgt = (wx_ < 0.0f || wy_ < 0.0f) ? 0.0f : ww * wx_ * wy_ * mod;
-                    th -= ang;
-                    th += (th < 0.0f ? F_PI2 : 0.0f);
-                    th -= (th >= F_PI2 ? F_PI2 : 0.0f);
-                    const float tth = th * M_4RPI;
-                    const float ffo = floorf(tth);
-                    const float do0 = tth - ffo;
-                    const int   b0 = (int)ffo & 7, b1 = (b0 + 1) & 7;
-                    const float w1 = do0 * wgt, w0 = wgt - w1;
-#pragma unroll
-                    for (int b = 0; b < 8; b++) acc[b] += (b == b0 ? w0 : 0.0f) + (b == b1 ? w1 : 0.0f);
-                }
-#pragma unroll
-                for (int b = 0; b < 8; b++) {
-                    const float v = wave_allsum(acc[b]);
-                    if (lane == 0) feat[(cell << 3) + b] = v;
-                }
-            }
-        }
-        wave_lds_sync();
-
-        /* normalisation (s_desc_norm_rs.h:44-79, s_desc_norm_l2.h:87-134), whole wave */
-        float v0 = feat[lane], v1 = feat[lane + 64];
-        if (sc.norm_mode == POPSIFT_HIP_NORM_ROOTSIFT) {
-            float sum = v0 + v1;
-            sum = wave_allsum(sum);
-            v0 = scalbnf(sqrtf(v0 / sum), sc.norm_multi);
-            v1 = scalbnf(sqrtf(v1 / sum), sc.norm_multi);
-        } else {
-            float sq = v0 * v0 + v1 * v1;
-            sq = wave_allsum(sq);
-            const float norm = sqrtf(sq);
-            v0 = fminf(v0, 0.2f * norm);
-            v1 = fminf(v1, 0.2f * norm);
-            sq = v0 * v0 + v1 * v1;
-            sq = wave_allsum(sq);
-            float rn = 1.0f / sqrtf(sq);
-            rn = scalbnf(rn, sc.norm_multi);
-            v0 = v0 * rn;
-            v1 = v1 * rn;
-        }
-        desc[(size_t)d * 128 + lane] = v0;
-        desc[(size_t)d * 128 + 64 + lane] = v1;
-        wave_lds_sync();
-    }
-}
-
-/* ------------------------------------------------------- descriptor: notile */
-
-/* linear-filter read at pixel-centre coordinates, clamp addressing, 1.8 fixed-point weights
- * (what tex2DLayered on the reference's linear texture returns, common/assist.h:66-81) */
-__device__ __forceinline__ float tex_linear(const float* pl, int w, int h, int pitch, float x, float y)
-{
-    const float fx = floorf(x), fy = floorf(y);
-    float       a = x - fx, b = y - fy;
-    a = floorf(a * 256.0f + 0.5f) * (1.0f / 256.0f);
-    b = floorf(b * 256.0f + 0.5f) * (1.0f / 256.0f);
-    const int    i = (int)fx, j = (int)fy;
-    const int    x0 = min(max(i, 0), w - 1), x1 = min(max(i + 1, 0), w - 1);
-    const int    r0 = __mul24(min(max(j, 0), h - 1), pitch);
-    const int    r1 = __mul24(min(max(j + 1, 0), h - 1), pitch);
-    const float  top = (1.0f - a) * plane_at(pl, r0 + x0) + a * plane_at(pl, r0 + x1);
-    const float  bot = (1.0f - a) * plane_at(pl, r1 + x0) + a * plane_at(pl, r1 + x1);
-    return (1.0f - b) * top + b * bot;
-}
-
-/*
- * DescMode NoTile (s_desc_notile.cu:28-128): a 40 x 40 grid of sample points at 1/8-cell pitch in
- * the keypoint's rotated frame; at each point the gradient is taken along the rotated axes from
- * four bilinearly interpolated reads (s_gradiant.h:71-87), weighted by a Gaussian table
- * (desc_gauss, sift_constants.cu:33-41) and by tent weights over the 16 x 16 points of every cell
- * that covers it (desc_tile, :43-46).  The reference evaluates each point once per covering
- * cell (up to four times); here one wave owns the descriptor, evaluates each of the 1600 points
- * once and spreads it to its <= 2 x 2 cells with the packed fixed-point LDS atomics of the loop
- * kernel.
- */
-template <bool ILOOP>
-__global__ __launch_bounds__(256) void k_descriptor_notile(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc,
-                                                           int desc_cap)
-{
-    const float* __restrict__    arena = bd.s[blockIdx.y].arena;
-    const Counters* __restrict__ ct = bd.s[blockIdx.y].ct;
-    const Ext* __restrict__      ext = bd.s[blockIdx.y].ext;
-    const int* __restrict__      map = bd.s[blockIdx.y].map;
-    const float2* __restrict__   rot = bd.s[blockIdx.y].rot;
-    float* __restrict__          desc = bd.s[blockIdx.y].desc;
-    constexpr int    DCOPY = 2;
-    /* notile: 256 points per cell, iloop: up to 1024, each <= 361 * 1: low halves stay below 2^32 */
-    constexpr int    FBITS = ILOOP ? 13 : 14;
-    __shared__ fix64 s_hist[4][DCOPY][128];
-    const int        lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    fix64*           hist = s_hist[wave][lane & (DCOPY - 1)];
-    fix64*           hall = s_hist[wave][0];
-    const int        total = min(ct->ori_total, desc_cap);
-    const int        L = pdp->L;
-    const float      M_4RPI = 4.0f / F_PI;
-    const float      stepbase = -2.5f + 1.0f / 16.0f;
-    const float      fscale = (float)(1 << FBITS);
-
-    for (XcdSlice sl = xcd_slice<4>(); sl.more(total); sl.s += sl.step) {
-        const int d = sl.index();
-        if (d >= total) continue;
-        const Ext*     e = ext + map[d];
-        const float    x = uniformf(e->xpos), y = uniformf(e->ypos), sigma = uniformf(e->sigma);
-        const OctDesc* od = &pdp->o[e->octave];
-        const int      width = uniform(od->w), height = uniform(od->h), pitch = uniform(od->pitch);
-        const int      lvl = min(max(e->lpos, 0), L - 1);
-        const float*   layer = arena + uniform64(od->data_off + lvl * od->plane_stride);
-        const float    SBP = fabsf(DESC_MAGNIFY * sigma);
-
-#pragma unroll
-        for (int k = 0; k < 2 * DCOPY; k++) hall[lane + 64 * k] = 0ull;
-        wave_lds_sync();
-
-        if (sigma != 0.0f) {
-            float sin_t, cos_t;
-            cos_t = uniformf(rot[d].x);
-            sin_t = uniformf(rot[d].y);
-            if (ILOOP) {
-                /* DescMode ILoop (s_desc_iloop.cu:18-133): every cell samples a FIXED 32 x 32 lattice over the
-                 * bounding box of its rotated two-cell square and keeps the points inside the square; the
-                 * gradient is the interpolated, rotated one of notile, the weights are the loop descriptor's.
-                 * The reference gives a cell 32 lanes x 32 steps; a wave here takes two lattice rows a step. */
-                const float csbp = cos_t * SBP, ssbp = sin_t * SBP;
-                const float bsz = fabsf(cos_t) + fabsf(sin_t);
-                const int   j = lane & 31;
-                for (int cell = 0; cell < 16; cell++) {
-                    const float offx = (float)(cell & 3) - 1.5f, offy = (float)(cell >> 2) - 1.5f;
-                    const float ptx = fmaf(csbp, offx, -ssbp * offy);
-                    const float pty = fmaf(csbp, offy, ssbp * offx);
-                    for (int it = 0; it < 16; it++) {
-                        const int   i = 2 * it + (lane >> 5);
-                        const float dx = -bsz + (float)j * bsz / 16.0f;
-                        const float dy = -bsz + (float)i * bsz / 16.0f;
-                        const float nx = fmaf(cos_t, dx, sin_t * dy);
-                        const float ny = fmaf(cos_t, dy, -sin_t * dx);
-                        const float nnx = fabsf(nx), nny = fabsf(ny);
-                        if (nnx < 1.0f && nny < 1.0f) {
-                            const float px = x + ptx + dx * SBP, py = y + pty + dy * SBP;
-                            const float dxv = tex_linear(layer, width, height, pitch, px + cos_t, py + sin_t) -
-                                              tex_linear(layer, width, height, pitch, px - cos_t, py - sin_t);
-                            const float dyv = tex_linear(layer, width, height, pitch, px - sin_t, py + cos_t) -
-                                              tex_linear(layer, width, height, pitch, px + sin_t, py - cos_t);
-                            const float mod = __builtin_amdgcn_sqrtf(dxv * dxv + dyv * dyv);
-                            float       th = atan2_acc(dyv, dxv);
-                            th += (th < 0.0f ? F_PI2 : 0.0f);
-                            th -= (th >= F_PI2 ? F_PI2 : 0.0f);
-                            const float tth = th * M_4RPI;
-                            const float ffo = floorf(tth);
-                            const float do0 = tth - ffo;
-                            const int   b0 = (int)ffo & 7;
-                            const float dnx = nx + offx, dny = ny + offy;
-                            const float ww = __expf(-0.125f * (dnx * dnx + dny * dny));
-                            const float wgt = ww * (1.0f - nnx) * (1.0f - nny) * mod * fscale;
-                            const float a1 = do0 * wgt, a0 = wgt - a1;
-                            atomicAdd(&hist[(cell << 3) + b0],
-                                      ((fix64)(unsigned int)(a1 + 0.5f) << 32) | (unsigned int)(a0 + 0.5f));
-                        }
-                    }
-                }
-            } else
-            for (int p = lane; p < 1600; p += 64) {
-                const int   newy = p / 40, newx = p - newy * 40;
-                const float stepx = stepbase + 0.125f * (float)newx;
-                const float stepy = stepbase + 0.125f * (float)newy;
-                const float ptx = cos_t * stepx + -sin_t * stepy;
-                const float pty = cos_t * stepy + sin_t * stepx;
-                const float px = x + ptx * SBP, py = y + pty * SBP;
-                const float dxv = tex_linear(layer, width, height, pitch, px + cos_t, py + sin_t) -
-                                  tex_linear(layer, width, height, pitch, px - cos_t, py - sin_t);
-                const float dyv = tex_linear(layer, width, height, pitch, px - sin_t, py + cos_t) -
-                                  tex_linear(layer, width, height, pitch, px + sin_t, py - cos_t);
-                const float mod = __builtin_amdgcn_sqrtf(dxv * dxv + dyv * dyv);
-                float       th = atan2_acc(dyv, dxv);
-                th += (th < 0.0f ? F_PI2 : 0.0f);
-                const float tth = th * M_4RPI;
-                const float ffo = floorf(tth);
-                const float do0 = tth - ffo;
-                const int   b0 = (int)ffo & 7;
-                /* desc_gauss[newy][newx]: exp(-(dnx^2 + dny^2) / 8), dn = step position */
-                const float ww = __expf(-0.125f * (stepx * stepx + stepy * stepy)) * mod * fscale;
-                const float a1 = do0 * ww, a0 = ww - a1;
-                /* cells cx with 8cx <= newx <= 8cx+15, tent weight desc_tile[newx - 8cx] */
-#pragma unroll
-                for (int jy = 0; jy < 2; jy++) {
-                    const int cy = (newy >> 3) - jy;
-                    if (cy < 0 || cy > 3) continue;
-                    const float wy = 1.0f - fabsf(-1.0f + 1.0f / 16.0f + 0.125f * (float)(newy - 8 * cy));
-#pragma unroll
-                    for (int jx = 0; jx < 2; jx++) {
-                        const int cx = (newx >> 3) - jx;
-                        if (cx < 0 || cx > 3) continue;
-                        const float wx = 1.0f - fabsf(-1.0f + 1.0f / 16.0f + 0.125f * (float)(newx - 8 * cx));
-                        const float wgt = wx * wy;
-                        const unsigned int lo = (unsigned int)fmaf(a0, wgt, 0.5f);
-                        const unsigned int hi = (unsigned int)fmaf(a1, wgt, 0.5f);
-                        atomicAdd(&hist[((((cy << 2) + cx) << 3)) + b0], ((fix64)hi << 32) | lo);
-                    }
-                }
-            }
-        }
-        wave_lds_sync();
-
-        /* bin b of a cell = low half of word b + high half of word b-1 (mod 8), over the copies */
-        fix64     a0 = 0ull, a1 = 0ull;
-        const int prevw = (lane & ~7) | ((lane + 7) & 7);
-#pragma unroll
-        for (int k = 0; k < DCOPY; k++) {
-            a0 += (hall[k * 128 + lane] & 0xffffffffull) + (hall[k * 128 + prevw] >> 32);
-            a1 += (hall[k * 128 + lane + 64] & 0xffffffffull) + (hall[k * 128 + prevw + 64] >> 32);
-        }
-        float v0 = (float)a0 * (1.0f / (float)(1 << FBITS)), v1 = (float)a1 * (1.0f / (float)(1 << FBITS));
-
-        /* normalisation (s_desc_norm_rs.h:44-79, s_desc_norm_l2.h:87-134), whole wave */
-        if (sc.norm_mode == POPSIFT_HIP_NORM_ROOTSIFT) {
-            float sum = v0 + v1;
-            sum = wave_allsum(sum);
-            v0 = scalbnf(sqrtf(v0 / sum), sc.norm_multi);
-            v1 = scalbnf(sqrtf(v1 / sum), sc.norm_multi);
-        } else {
-            float sq = v0 * v0 + v1 * v1;
-            sq = wave_allsum(sq);
-            const float norm = sqrtf(sq);
-            v0 = fminf(v0, 0.2f * norm);
-            v1 = fminf(v1, 0.2f * norm);
-            sq = v0 * v0 + v1 * v1;
-            sq = wave_allsum(sq);
-            float rn = 1.0f / sqrtf(sq);
-            rn = scalbnf(rn, sc.norm_multi);
-            v0 = v0 * rn;
-            v1 = v1 * rn;
-        }
-        desc[(size_t)d * 128 + lane] = v0;
-        desc[(size_t)d * 128 + 64 + lane] = v1;
-        wave_lds_sync();
-    }
-}
-
-/* --------------------------------------------------------------- features */
-
-
 }  // namespace
 
 hipError_t launch_orientation(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, bool filtered, int hist_cap,
@@ -1578,9 +1101,7 @@ hipError_t launch_scan(const PyrDesc* pd, const BatchDesc& bd, int nb, const Sif
     /* n_chunks is the capacity of the lists; a 1080p image fills ~300 chunks */
     hipLaunchKernelGGL(k_scan_local, dim3(std::min(n_chunks * SCAN_SUB, 512 * SCAN_SUB), nb), dim3(SCAN_LT), 0, s, pd, sc, bd,
                        filtered ? 1 : 0, hist_cap);
-    hipLaunchKernelGGL(k_scan_apply, dim3(std::min(n_chunks, 1024), nb), dim3(256), 0, s, pd, sc, bd,
-                       sc.desc_mode == POPSIFT_HIP_DESC_LOOP ? 1 : 0, desc_cap);
-    return hipGetLastError();
+    return launch_scan_apply(pd, bd, nb, sc, n_chunks, desc_cap, s);
 }
 
 hipError_t launch_scan_apply(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
@@ -1597,19 +1118,11 @@ int scan_partials_per_chunk() { return SCAN_SUB; }
 hipError_t launch_descriptors(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
                               hipStream_t s)
 {
-    /* IGrid (s_desc_igrid.cu:20-83) evaluates the same 40 x 40 point lattice with the same weights as NoTile,
-     * cell by cell (each point up to four times); the two differ only in summation order (6e-7 relative in the
-     * oracle), so both run the one-evaluation-per-point kernel */
-    if (sc.desc_mode == POPSIFT_HIP_DESC_NOTILE || sc.desc_mode == POPSIFT_HIP_DESC_IGRID)
-        hipLaunchKernelGGL(k_descriptor_notile<false>, dim3(blocks / 4, nb), dim3(256), 0, s, pd, bd, sc, desc_cap);
-    else if (sc.desc_mode == POPSIFT_HIP_DESC_ILOOP)
-        hipLaunchKernelGGL(k_descriptor_notile<true>, dim3(blocks / 4, nb), dim3(256), 0, s, pd, bd, sc, desc_cap);
-    else if (sc.desc_mode == POPSIFT_HIP_DESC_GRID)
-        hipLaunchKernelGGL(k_descriptor_grid, dim3(blocks / 4, nb), dim3(256), 0, s, pd, bd, sc, desc_cap);
-    else
-        hipLaunchKernelGGL(k_descriptor, dim3(blocks / KP_NW, nb), dim3(64 * KP_NW), 0, s, bd, sc, desc_cap);
+    if (sc.desc_mode == POPSIFT_HIP_DESC_NOTILE || sc.desc_mode == POPSIFT_HIP_DESC_IGRID ||
+        sc.desc_mode == POPSIFT_HIP_DESC_ILOOP || sc.desc_mode == POPSIFT_HIP_DESC_GRID)
+        return launch_desc_modes(pd, bd, nb, sc, desc_cap, blocks, s);
+    hipLaunchKernelGGL(k_descriptor, dim3(blocks / KP_NW, nb), dim3(64 * KP_NW), 0, s, bd, sc, desc_cap);
     return hipGetLastError();
 }
-
 
 }  // namespace popsift_hip

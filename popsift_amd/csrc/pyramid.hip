@@ -32,23 +32,6 @@ namespace {
 
 constexpr int TW = BLUR_TW; /* tile width  (outputs) */
 
-template <typename T>
-__device__ __forceinline__ float texel(const T* img, int w, int h, int pitch, int x, int y);
-template <>
-__device__ __forceinline__ float texel<uint8_t>(const uint8_t* img, int w, int h, int pitch, int x, int y)
-{
-    x = clampi(x, 0, w - 1);
-    y = clampi(y, 0, h - 1);
-    return (float)img[(size_t)y * pitch + x] / 255.0f;
-}
-template <>
-__device__ __forceinline__ float texel<float>(const float* img, int w, int h, int pitch, int x, int y)
-{
-    x = clampi(x, 0, w - 1);
-    y = clampi(y, 0, h - 1);
-    return img[(size_t)y * pitch + x];
-}
-
 /*
  * MODE 0: level l >= 1 from plane l-1 (centre tap first in the H pass, DoG out)
  * MODE 1: octave 0 level 0 from the u8 input image (bilinear upscale on the fly)

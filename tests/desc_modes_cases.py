@@ -41,6 +41,7 @@ FRAMES = {
     "igrid-frames_noise2-rootsift": ("igrid", "noise2", dict(), "crafted"),
     "grid-frames_noise2-rootsift": ("grid", "noise2", dict(), "crafted"),
     "iloop-frames_noise2-rootsift": ("iloop", "noise2", dict(), "crafted"),
+    "iloop-frames_noise2-classic9": ("iloop", "noise2", CLASSIC, "crafted"),
     "notile-step": ("notile", "step", dict(), "step"),
     "iloop-step": ("iloop", "step", dict(), "step"),
 }

@@ -6,7 +6,7 @@ Rule it uses unchanged and whose offender_rows its format_offenders shares.
     ILOOP   desc_mode 1                descriptor_iloop_one                            k_descriptor_notile<true>
     GRID    desc_mode 2                descriptor_grid_one                             k_descriptor_grid
 
-These descriptors are step functions of their inputs (texture weights in steps of 1/256, samples snapped to pixels, an
+(the kernels: popsift_amd/csrc/desc_modes.hip).  These descriptors are step functions of their inputs (texture weights in steps of 1/256, samples snapped to pixels, an
 inclusion test), but every step is a function of the POSITION alone, and kernel and oracle form the positions with the
 same float32 operations (both are built with -ffp-contract=off).  So the rule needs no decision margins: `samples`
 restates every integer or step decision in float32, operation by operation (numpy float32 arithmetic rounds every
@@ -35,7 +35,7 @@ Bin b of a cell receives weight * hat(circular distance of t and b): the (1 - d,
 Each raw element carries delta = A + F + G + W + S + T, by how much a correct implementation may differ:
 
   A  arctangent.  e * sum of weight over the samples whose t lies within 1 + 1e-4 of b.  e = A_ACC = 2e-7 bins, the stated
-     error of atan2_acc (keypoint.hip: "|error| ~ 1.5e-7 rad" = 1.9e-7 bins), a device-only term, plus desc_rule.A_FLOAT =
+     error of atan2_acc (keypoint_dev.h: "|error| ~ 1.5e-7 rad" = 1.9e-7 bins), a device-only term, plus desc_rule.A_FLOAT =
      1.5e-6 bins for float32 angle arithmetic on either side (th + 2 pi and th - angle rounded at up to 2 pi, t at up to
      8, rounded UP by the oracle's mul_up, atan2f itself), which stays on for the oracle.
   F  fixed point (device only; none for GRID, which sums floats).  k_descriptor_notile adds (unsigned)(share * weight *

@@ -15,7 +15,7 @@ delta, the amount by which one SMOOTHED bin of a correct implementation may diff
   U               the total weight of the samples whose t lies within EDGE_EPS = 1e-4 of a bin edge k + 0.5: such a
                   sample may fall into either bin (1e-4 is 45 times the 2.2e-6 bins of the device's cheap arctangent,
                   which hands every sample nearer than 1e-4 to an edge to its accurate one; keypoint.hip, atan2_bins);
-  n * 2^-20       the device's fixed-point resolution (to_fix, keypoint.hip): each of the n samples inside the circle
+  n * 2^-20       the device's fixed-point resolution (from_fix, keypoint_dev.h): each of the n samples inside the circle
                   is truncated to a multiple of 2^-20, losing less than one unit;
   TAU * max(H)    float32 rounding of the weights and the sums, TAU = 1e-5, relative to the largest SMOOTHED bin: a
                   relative error TAU * raw[i] per raw bin averages to TAU * H[b] <= TAU * max(H).  The oracle needs

@@ -1,5 +1,5 @@
-"""k_descriptor_notile<false> (notile, igrid), k_descriptor_notile<true> (iloop) and k_descriptor_grid, descriptor by
-descriptor, against the float64 rules of tests/desc_modes_rule.py (cases: tests/desc_modes_cases.py).
+"""k_descriptor_notile<false> (notile, igrid), k_descriptor_notile<true> (iloop) and k_descriptor_grid (desc_modes.hip),
+descriptor by descriptor, against the float64 rules of tests/desc_modes_rule.py (cases: tests/desc_modes_cases.py).
 
 util.descriptor_parity holds these modes to 1e-3 relative L2 against the float32 oracle with max(1, n // 5000)
 descriptors beyond it; one lattice point dropped, a tent weight one index off or fixed-point rounding turned into
@@ -8,7 +8,7 @@ device's own frame (its sigma, its angles), lies inside the interval the rule de
 allowance.  The crafted frames go through the describe path with a given orientation: sigma up to the largest accepted
 one, angles of exactly +-0, pi/2 and +-pi, a corner, x = w - 1 and y = h - 1, and frames on a 0 -> 255 step.
 
-Largest error / bound per case as printed on an MI355X, and which temporary mutations of keypoint.hip fail this test where
+Largest error / bound per case as printed on an MI355X, and which temporary mutations of desc_modes.hip fail this test where
 test_hip_matches_oracle passes: DESIGN 4.3."""
 import numpy as np
 import pytest

@@ -16,8 +16,7 @@ import sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = os.path.join(R, "popsift_amd", "csrc")
 OUT = os.path.join(R, "build_variants")
-BASE = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-        "-Wno-unused-function"]
+BASE = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 
 
 def main():

@@ -3,7 +3,8 @@
 
     tools/isa_count.py [--src FILE.hip] [--kernel k_descriptor] [--marker ds_add_u64] [--samples 2] [--most] [extra hipcc flags ...]
 
-Compiles popsift_amd/csrc/keypoint.hip (or --src FILE.hip) for gfx950 with the Makefile's flags plus -gline-tables-only, takes the
+Compiles popsift_amd/csrc/keypoint.hip, the benchmarked kernels (or --src FILE.hip: desc_modes.hip for the other descriptor
+modes, extrema.hip), for gfx950 with the Makefile's flags plus -gline-tables-only, takes the
 innermost-but-one loop of <kernel> that contains <marker>, and counts its instructions
   - by kind: VALU (full rate), VALU quarter rate (transcendentals, 32-bit integer multiply), SALU, LDS, VMEM, waits;
   - by source group: the `.loc` line of every instruction is looked up in the `/* ISA: <group> */` markers of the
@@ -71,7 +72,7 @@ def main():
             extra.append(a[i]); i += 1
     out = "/tmp/isa_count.s"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-slp-vectorize", "-Wno-unused-function", "-gline-tables-only", "-S", "--cuda-device-only",
+                           "-fno-slp-vectorize", "-gline-tables-only", "-S", "--cuda-device-only",
                            SRC, "-o", out] + extra, stderr=subprocess.DEVNULL)
     lines = open(out).read().split("\n")
     # the function body
