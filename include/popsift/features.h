@@ -56,6 +56,7 @@ class FeaturesHost : public FeaturesBase {
     Descriptor*      _ori;
     unsigned char*   _bytes = 0;   /* byte format: num_ori x 128 bytes, a pinned block like the others */
     std::vector<int> _desc_idx;    /* byte format: ORIENTATION_MAX_COUNT descriptor indices per feature, -1 = none */
+    std::vector<float> _responses; /* Config::setKeepStrongest only: one DoG response per feature */
 
 public:
     FeaturesHost();
@@ -90,6 +91,12 @@ public:
     const unsigned char* descriptorBytes(int feature, int ori) const;
     /* ORIENTATION_MAX_COUNT descriptor indices per feature (byte format; filled by PopSift's workers) */
     inline int* getDescriptorIndices() { return _desc_idx.data(); }
+
+    /* Extension, Config::setKeepStrongest(n > 0): the DoG response of every feature (the strength the selection ranks by,
+     * include/popsift_hip.h), in feature order; null when the setting is off (and for an image without features) */
+    inline const float* getResponses() const { return _responses.empty() ? 0 : _responses.data(); }
+    /* room for one response per feature (filled by PopSift's workers) */
+    inline float* resetResponses() { _responses.assign((size_t)size(), 0.0f); return _responses.data(); }
 
     /* one line per (feature, orientation): x y 1/s^2 0 1/s^2 d0 .. d127; the byte format writes the bytes as
      * integers (the layout of write_as_uchar) */

@@ -60,6 +60,15 @@ struct Config {
      * Verifier::ransac on two extractions of an image pair repeat exactly. */
     enum FeatureOrder { ArrivalOrder, RasterOrder };
 
+    /* Extension: keep the n keypoints of every image with the largest DoG response (OpenCV's nfeatures; the rule, ties
+     * at the cut included, is stated in include/popsift_hip.h, popsift_hip_set_keep_strongest), thinned on the GPU before
+     * orientation, and return every feature's response: FeaturesHost::getResponses().  0 (default): off.  A huge n
+     * (INT_MAX) thins nothing and still returns the responses.  Does not chain with the grid filter
+     * (setFilterMaxExtrema > 0: fatal).  A job takes the value the configuration has when it is enqueued; jobs with
+     * frames (describe) and MatchingMode results carry no responses. */
+    void setKeepStrongest(int n) { _keep_strongest = n; }
+    int  getKeepStrongest() const { return _keep_strongest; }
+
     /* ---- setters (sift_conf.cu:51-258) -------------------------------------- */
     void setGaussMode(const std::string& m);
     void setGaussMode(GaussMode m) { _gauss_mode = m; }
@@ -125,7 +134,7 @@ struct Config {
     FeatureOrder     getFeatureOrder() const { return _feature_order; }
 
     /* compares the 14 fields that decide whether tables must be rebuilt (sift_conf.cu:285-303), and the descriptor
-     * format and the feature order */
+     * format, the feature order and the keep-strongest count */
     bool equal(const Config& other) const;
 
     /* ---- public data members, as in the reference ------------------------------ */
@@ -154,6 +163,7 @@ private:
     bool           _print_gauss_tables;
     DescriptorFormat _descriptor_format;
     FeatureOrder     _feature_order;
+    int              _keep_strongest;
 };
 
 inline bool operator==(const Config& l, const Config& r) { return l.equal(r); }

@@ -165,7 +165,7 @@ typedef struct popsift_hip_report {
 } popsift_hip_report;
 enum { POPSIFT_HIP_STAGE_PYRAMID = 0,     /* every k_blur_tile launch                              */
        POPSIFT_HIP_STAGE_DETECT = 1,      /* k_detect (both passes)                                */
-       POPSIFT_HIP_STAGE_REFINE = 2,      /* k_refine (+ the grid filter when enabled)             */
+       POPSIFT_HIP_STAGE_REFINE = 2,      /* k_refine (+ grid filter / keep-strongest pass when on) */
        POPSIFT_HIP_STAGE_ORIENTATION = 3, /* k_orientation                                         */
        POPSIFT_HIP_STAGE_SCAN = 4,        /* k_scan_local + k_scan_apply                           */
        POPSIFT_HIP_STAGE_DESCRIPTOR = 5,  /* the descriptor kernel                                 */
@@ -277,6 +277,54 @@ int popsift_hip_results_dev_item(popsift_hip_ctx* ctx, int k, const void** d_fea
  * submit the next batch, then ONE popsift_hip_fetch_end waits for all the downloads */
 int popsift_hip_fetch_begin_item(popsift_hip_ctx* ctx, int k, popsift_hip_feature* feats, size_t feats_cap, float* desc,
                                  size_t desc_cap);
+
+/*
+ * Keep the n strongest keypoints of every image (OpenCV's nfeatures, KeyPointsFilter::retainBest) and hand out every
+ * feature's strength (OpenCV's KeyPoint::response).  A setting of the context, off by default; the pass (strongest.hip)
+ * runs on the GPU between refinement and orientation, so orientation and the descriptors see the thinned lists only.
+ *
+ * The response of a refined extremum record (xpos, ypos, lpos, sigma) of octave o, planes w x h, `levels` search levels:
+ *     xi = clamp((int)floorf(xpos + 0.5f), 0, w - 1)     a non-finite xpos or ypos: response = NaN
+ *     yi = clamp((int)floorf(ypos + 0.5f), 0, h - 1)
+ *     di = clamp(lpos, 1, levels)
+ *     response = fabsf(D(xi, yi, di))
+ * D(x, y, d) is the DoG value as refinement reads it: the stored plane d of the octave with params.store_dog = 1,
+ * otherwise G[d+1] - G[d] formed on the fly, which is bit-identical (popsift_hip_download_plane, kind 1, gives it either
+ * way).  So the response is the magnitude of the DoG at the sample nearest to the refined position, in the pyramid's
+ * 0 .. 255 units: one load, or one IEEE subtraction, and an absolute value.  (Not the interpolated contrast of the
+ * refinement, which mixes the first iteration's centre value with the last iteration's derivatives and cannot be
+ * recomputed from a record.)
+ *
+ * Selection, per image, over all octaves together:
+ *     key = 0 if the response is NaN, else the response's bit pattern as uint32 (responses are >= 0: bit order is
+ *           numeric order)
+ *     total = the records after the max_extrema clamp, n = the setting
+ *     total <= n: every record stays.  Otherwise t = the n-th largest key, and a record stays iff key >= t.
+ * Every record that ties with the n-th stays (retainBest's rule), so the surviving SET is a function of the records alone,
+ * in either feature order and on every run; its size is >= n, and exactly n without a tie at the cut.  Survivors stay in
+ * their octave and keep their relative list order: with POPSIFT_HIP_ORDER_RASTER the results are, byte for byte, those of
+ * the unthinned run with the dropped records removed (desc_idx renumbered).
+ *
+ * popsift_hip_set_keep_strongest: n = 0 off; n > 0 on, from the next submit or popsift_hip_rerun_keypoint_stages (the
+ * grow-and-rerun paths of popsift_hip_wait include the pass).  A huge n (INT32_MAX) thins nothing and still delivers the
+ * responses.  ERR_INVALID: null context, n < 0, or a context whose params enable the grid filter (filter_max_extrema > 0;
+ * the two do not chain).  ERR_STATE while a batch is in flight.  popsift_hip_describe_batch ignores the setting: frames
+ * are never thinned.  After the pass popsift_hip_download_extrema returns the survivors and popsift_hip_get_report their
+ * per-octave counts.  The pass's time counts into POPSIFT_HIP_STAGE_REFINE.  While the setting has never been on, a
+ * context allocates and launches nothing for the pass.
+ *
+ * popsift_hip_fetch_responses_item: the n_features[k] responses of image k of the finished batch, out[i] belonging to
+ * feature i; popsift_hip_responses_dev_item: the device array, valid as long as popsift_hip_results_dev_item's pointers.
+ * State rules as for popsift_hip_fetch_item; ERR_STATE also when the batch ran with the setting off and for the results
+ * of a describe; ERR_TOO_SMALL when cap < n_features[k].
+ *
+ * A workgroup of the pass's per-record kernels takes POPSIFT_HIP_STRONGEST_CHUNK records of a list (stated here for the
+ * tests of its edges; results do not depend on it).
+ */
+#define POPSIFT_HIP_STRONGEST_CHUNK 1024
+int popsift_hip_set_keep_strongest(popsift_hip_ctx* ctx, int n);
+int popsift_hip_fetch_responses_item(popsift_hip_ctx* ctx, int k, float* out, size_t cap);
+int popsift_hip_responses_dev_item(popsift_hip_ctx* ctx, int k, const void** d_resp);
 
 /*
  * Describe caller-supplied keypoints (vl_sift's 'frames' / 'orientations' options, OpenCV's SIFT::compute): the pyramid

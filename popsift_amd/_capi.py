@@ -27,6 +27,7 @@ NORM_ROOTSIFT, NORM_CLASSIC = 0, 1
 SCALE_DEFAULT, SCALE_DIRECT = 0, 1  # params.scale_direct (not Config::ScalingMode's enum values)
 ORDER_ARRIVAL, ORDER_RASTER = 0, 1  # params.feature_order: POPSIFT_HIP_ORDER_* (tests/order_rule.py states the raster rule)
 ORDER_CHUNK = 1024  # POPSIFT_HIP_ORDER_CHUNK: records per workgroup of the ordering pass
+STRONGEST_CHUNK = 1024  # POPSIFT_HIP_STRONGEST_CHUNK: records per workgroup of the keep-strongest pass
 
 
 class Params(C.Structure):
@@ -164,6 +165,9 @@ SYMBOLS = [
     ("popsift_hip_fetch_item", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("popsift_hip_results_dev_item", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     ("popsift_hip_fetch_begin_item", C.c_int, [_vp, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t]),
+    ("popsift_hip_set_keep_strongest", C.c_int, [_vp, C.c_int]),
+    ("popsift_hip_fetch_responses_item", C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),
+    ("popsift_hip_responses_dev_item", C.c_int, [_vp, C.c_int, C.POINTER(C.c_void_p)]),
     ("popsift_hip_wait", C.c_int, [_vp, _ip, _ip]),
     ("popsift_hip_fetch", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
     ("popsift_hip_fetch_begin", C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t]),
@@ -952,6 +956,21 @@ class Context:
     def set_profile(self, mode):
         """0 off, 1 (True): every blur launch timed, 2: stage times (report().ms_stage)"""
         self._chk(lib().popsift_hip_set_profile(self._h, int(mode)), "popsift_hip_set_profile")
+
+    def set_keep_strongest(self, n):
+        """popsift_hip_set_keep_strongest: from the next submit (or rerun_keypoint_stages) keep the n keypoints of every
+        image with the largest DoG response, ties with the n-th included (tests/strongest_rule.py states the rule);
+        0 = off.  A huge n (2**31 - 1) thins nothing and still makes fetch_responses work."""
+        self._chk(lib().popsift_hip_set_keep_strongest(self._h, int(n)), "popsift_hip_set_keep_strongest")
+        return self
+
+    def fetch_responses(self, k=0):
+        """the response of every feature of image k of the finished batch (float32, feature order); needs
+        set_keep_strongest(n > 0) at the submit"""
+        nf = self.wait_batch()[k][0]
+        out = np.zeros(nf, np.float32)
+        self._chk(lib().popsift_hip_fetch_responses_item(self._h, k, out.ctypes.data, nf), "popsift_hip_fetch_responses_item")
+        return out
 
     def octave_dims(self, o):
         w, h = C.c_int(), C.c_int()

@@ -82,6 +82,11 @@ struct ImageSlot {
     DevBuf<int>         fhist;
     DevBuf<InitExt>     otmp;  /* raster feature order only (order.hip): scratch list, never the filter's iext2 */
     DevBuf<int>         orows; /* ... and the row counters */
+    /* keep-strongest pass only (strongest.hip; its output list is iext2): responses before / after thinning in flattened
+     * list order, the selection's state, the chunk offsets */
+    DevBuf<float>       sresp_in, sresp;
+    DevBuf<StrongState> sstate;
+    DevBuf<int>         schunk;
     DevBuf<Ext>         ext;
     DevBuf<float, PS_ORI_NBINS> ohist; /* raw orientation histograms, one per extremum (k_orientation -> k_scan_local) */
     DevBuf<popsift_hip_feature> feats;
@@ -118,7 +123,7 @@ struct ImageSlot {
     void release()
     {
         auto each = [](auto&... b) { ((void)b.release(), ...); };
-        each(input, arena, iext, iext2, fstate, fhist, otmp, orows, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
+        each(input, arena, iext, iext2, fstate, fhist, otmp, orows, sresp_in, sresp, sstate, schunk, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
              alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats);
         if (h_input) (void)hipHostFree(h_input);
         if (h_frames) (void)hipHostFree(h_frames);
@@ -160,6 +165,8 @@ struct popsift_hip_ctx {
     int       desc_rows = 1 << 30;
     int       desc_list = 1 << 30;
     BlurTune  blur_tune{0, 0}; /* BLUR_PATH / BLUR_SEG debug switches */
+    int       keep_strongest = 0; /* popsift_hip_set_keep_strongest: 0 off, n: the next enqueue keeps the n strongest */
+    int       batch_keep = 0;     /* ... and what the keypoint stages of the batch in the context were enqueued with */
     int       order_coarse = 0; /* ORDER_COARSE: row bits the ordering pass drops from its bucket key */
     int       pyr_tail = 0;    /* PYR_TAIL: 0 the smallest octaves in one launch where they fit, 1 level launches only */
     int       cand_cap_init = 1 << 20;
@@ -872,7 +879,8 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
 /* Pyramid::step2 + prep_features: extrema -> orientation -> scan -> descriptors -> features */
 InitExt* final_iext(popsift_hip_ctx* c, int k = 0)
 {
-    return c->sc.filter_max > 0 && !c->describe ? c->slot[k].iext2.p : c->slot[k].iext.p; /* frames are not grid-filtered */
+    /* frames are neither grid-filtered nor thinned */
+    return (c->sc.filter_max > 0 || c->batch_keep > 0) && !c->describe ? c->slot[k].iext2.p : c->slot[k].iext.p;
 }
 
 /* POPSIFT_HIP_ORDER_RASTER: the lists `filtered ? iext2 : iext` of the batch into the header's order */
@@ -887,6 +895,37 @@ hipError_t enqueue_order(popsift_hip_ctx* c, bool filtered)
         ob.s[k].ct = c->d_ct + k;
     }
     return launch_order(c->pd, c->sc, c->order_coarse, ob, c->nb, c->stream);
+}
+
+/* popsift_hip_set_keep_strongest: the buffers of the pass for the slots of the batch, grown on the first use */
+int prepare_strongest(popsift_hip_ctx* c)
+{
+    const size_t need = std::max<size_t>(c->ext_cap, 1);
+    return ensure_cap(c, [&](ImageSlot& s) {
+        if (int rc = grow(c, s.iext2, need)) return rc;
+        if (int rc = grow(c, s.sresp_in, need)) return rc;
+        if (int rc = grow(c, s.sresp, need)) return rc;
+        if (int rc = grow(c, s.sstate, 1)) return rc;
+        return grow(c, s.schunk, (size_t)PS_MAX_OCT * strongest_chunks(c->sc.max_extrema));
+    });
+}
+
+/* the pass on the refined (and ordered) lists iext of the batch -> iext2 */
+hipError_t enqueue_strongest(popsift_hip_ctx* c)
+{
+    StrongBatch sb{};
+    for (int k = 0; k < c->nb; k++) {
+        const ImageSlot& sl = c->slot[k];
+        sb.s[k].arena = sl.arena.p;
+        sb.s[k].ct = c->d_ct + k;
+        sb.s[k].in = sl.iext.p;
+        sb.s[k].out = sl.iext2.p;
+        sb.s[k].resp_in = sl.sresp_in.p;
+        sb.s[k].resp_out = sl.sresp.p;
+        sb.s[k].state = sl.sstate.p;
+        sb.s[k].chunk_off = sl.schunk.p;
+    }
+    return launch_strongest(c->pd, c->d_pd, c->sc, c->batch_keep, sb, c->nb, c->stream);
 }
 
 /* What extraction and describe end with: orientation -> scan -> descriptors -> the counters to the host, with their stage
@@ -927,7 +966,10 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
 {
     POPSIFT_RANGE("popsift_hip: keypoint stages");
     const bool stages = (c->profile == 2);
-    const bool filtered = c->sc.filter_max > 0;
+    c->batch_keep = c->keep_strongest;
+    if (c->batch_keep > 0)
+        if (int rc = prepare_strongest(c)) return rc;
+    const bool filtered = c->sc.filter_max > 0 || c->batch_keep > 0; /* the later stages read iext2 */
     auto       mark = [&](int k) -> hipError_t { return stages ? hipEventRecord(c->ev_stage[k], c->stream) : hipSuccess; };
     if (!counters_cleared) HIP_TRY(c, hipMemsetAsync(c->d_ct, 0, sizeof(Counters) * (size_t)c->nb, c->stream));
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DETECT)); /* = end of the pyramid stage */
@@ -940,7 +982,12 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
         HIP_TRY(c, enqueue_order(c, false));
         SYNC_CHK(c, "k_order (refined list)");
     }
-    if (filtered) {
+    if (c->batch_keep > 0) {
+        /* stable: a raster-ordered list stays one */
+        HIP_TRY(c, enqueue_strongest(c));
+        SYNC_CHK(c, "keep-strongest pass");
+    }
+    if (c->sc.filter_max > 0) {
         /* Pyramid::orientation's filter hook (s_orientation.cu:353-367); the 10 % test is taken on the device */
         HIP_TRY(c, launch_filter(c->pd.n_oct, c->sc, c->bd, c->nb, c->stream));
         SYNC_CHK(c, "grid filter");
@@ -961,6 +1008,7 @@ int enqueue_describe_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     POPSIFT_RANGE("popsift_hip: describe stages");
     const bool stages = (c->profile == 2);
     auto       mark = [&](int k) -> hipError_t { return stages ? hipEventRecord(c->ev_stage[k], c->stream) : hipSuccess; };
+    c->batch_keep = 0; /* frames are never thinned */
     FrameBatch fb{};
     BatchDesc  lb = c->bd; /* k_scan_apply writes its feature records in list order, k_frame_out moves them */
     for (int k = 0; k < c->nb; k++) {
@@ -2074,6 +2122,39 @@ int popsift_hip_set_profile(popsift_hip_ctx* c, int profile)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     c->profile = (profile == 2) ? 2 : (profile ? 1 : 0);
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_set_keep_strongest(popsift_hip_ctx* c, int n)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (n < 0) return fail(c, POPSIFT_HIP_ERR_INVALID, "keep_strongest: 0 (off) or a positive count");
+    if (c->sc.filter_max > 0)
+        return fail(c, POPSIFT_HIP_ERR_INVALID, "keep_strongest and the grid filter (filter_max_extrema > 0) do not chain");
+    if (c->have_image && c->batch_ok && !c->finished) return fail(c, POPSIFT_HIP_ERR_STATE, "a batch is in flight");
+    c->keep_strongest = n;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_responses_dev_item(popsift_hip_ctx* c, int k, const void** d_resp)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (int rc = results_here(c, k)) return rc;
+    if (c->describe || c->batch_keep <= 0)
+        return fail(c, POPSIFT_HIP_ERR_STATE, "no responses: the batch was not run with popsift_hip_set_keep_strongest on");
+    if (d_resp) *d_resp = c->slot[k].sresp.p;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_fetch_responses_item(popsift_hip_ctx* c, int k, float* out, size_t cap)
+{
+    const void* d_resp = nullptr;
+    if (int rc = popsift_hip_responses_dev_item(c, k, &d_resp)) return rc;
+    const size_t nf = (size_t)c->n_feat[k];
+    if (nf && !out) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
+    if (cap < nf) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (nf) HIP_TRY(c, hipMemcpy(out, d_resp, nf * sizeof(float), hipMemcpyDeviceToHost));
     return POPSIFT_HIP_OK;
 }
 

@@ -149,6 +149,13 @@ bool       filter_supported(int n_oct, int max_extrema, int grid_size);
 size_t     filter_hist_bytes(int grid_size);
 hipError_t launch_filter(int n_oct, const SiftConsts& sc, const BatchDesc& bd, int nb, hipStream_t s);
 
+/* strongest.hip: the keep-strongest pass between refinement and orientation, the rule of include/popsift_hip.h: the lists
+ * of `sb` (counts ext_ct, capped by max_extrema) thinned to the `keep` >= 1 largest responses per image, stably, into the
+ * second lists; ext_ct becomes the survivors'.  strongest_chunks: chunk offsets a slot needs per octave */
+int        strongest_chunks(int max_extrema);
+hipError_t launch_strongest(const PyrDesc& pd, const PyrDesc* d_pd, const SiftConsts& sc, int keep, const StrongBatch& sb, int nb,
+                            hipStream_t s);
+
 /* order.hip: the per-octave extrema lists of `ob` (counts ext_ct, capped by max_extrema) into raster order, the rule of
  * include/popsift_hip.h.  order_rows: row counters a slot needs for this pyramid; coarse: ORDER_COARSE, 0 .. 15 */
 size_t     order_rows(const PyrDesc& pd);

@@ -188,6 +188,35 @@ struct OrderSlot {
 struct OrderBatch {
     OrderSlot s[PS_MAX_BATCH];
 };
+/* Keep-strongest pass (strongest.hip), when popsift_hip_set_keep_strongest is on.  A slot table of its own, like OrderBatch:
+ * the refined lists, the thinned lists (the slot's iext2), the responses before and after thinning in flattened list order
+ * (octave after octave), the selection's state and the exclusive survivor count of every chunk within its octave. */
+struct StrongState {
+    unsigned int t;     /* the n-th largest key, 0: every record stays */
+    int          total; /* records of all octaves before the pass */
+    int          pad[2];
+    int          old_ct[PS_MAX_OCT], old_ps[PS_MAX_OCT]; /* per-octave counts (capped) and their exclusive prefix before ... */
+    int          new_ct[PS_MAX_OCT], new_ps[PS_MAX_OCT]; /* ... and after the pass */
+};
+struct StrongSlot {
+    const float*   arena;
+    Counters*      ct;
+    const InitExt* in;
+    InitExt*       out;
+    float*         resp_in;
+    float*         resp_out;
+    StrongState*   state;
+    int*           chunk_off;
+};
+struct StrongBatch {
+    StrongSlot s[PS_MAX_BATCH];
+};
+struct StrongArgs {
+    int n_oct, max_extrema, keep;
+    int chunks; /* chunks per octave = ceil(max_extrema / POPSIFT_HIP_STRONGEST_CHUNK) */
+    int levels; /* DoG search levels */
+};
+
 struct OrderArgs {
     int n_oct, coarse, max_extrema;
     int chunks;     /* workgroups per octave = ceil(max_extrema / POPSIFT_HIP_ORDER_CHUNK) */

@@ -18,6 +18,7 @@
 #include <popsift/sift_conf.h>
 
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
@@ -41,6 +42,7 @@ static bool   dont_write = false;
 static bool   pgmread_loading = false;
 static bool   float_mode = false;
 static string output_file = "output-features.txt";
+static string responses_file = ""; /* --write-responses */
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& inputFile)
 {
@@ -138,7 +140,20 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& in
             else opts.error("the argument ('" + s + "') for option '--feature-order' is invalid");
         });
 
+    ival("keep-strongest", "Extensions",
+         "Keep the N keypoints of every image with the largest DoG response (ties with the N-th included), thinned on\n"
+         "the GPU before orientation; 0 (default): off.  Does not combine with --filter-max-extrema",
+         [&](int n) {
+             if (n < 0) opts.error("the argument ('" + to_string(n) + "') for option '--keep-strongest' is invalid");
+             config.setKeepStrongest(n);
+         });
+    val("write-responses", 0, "Extensions",
+        "With --keep-strongest: write every feature's response to this file, one %.9g per line, in feature order",
+        [&](const string& s) { responses_file = s; });
+
     opts.parse(argc, argv);
+    if (!responses_file.empty() && config.getKeepStrongest() <= 0)
+        opts.error("option '--write-responses' needs '--keep-strongest'");
 }
 
 static void collectFilenames(list<string>& inputFiles, const filesystem::path& inputFile)
@@ -180,6 +195,17 @@ static void read_job(SiftJob* job, bool really_write)
     if (really_write) {
         std::ofstream of(output_file.c_str());
         feature_list->print(of, write_as_uchar);
+    }
+    if (!responses_file.empty()) {
+        /* like the feature file: the last image wins */
+        FILE*        f = fopen(responses_file.c_str(), "w");
+        const float* r = feature_list->getResponses();
+        if (!f) {
+            cerr << "cannot write " << responses_file << endl;
+            exit(-1);
+        }
+        for (int i = 0; r && i < feature_list->getFeatureCount(); i++) fprintf(f, "%.9g\n", r[i]);
+        fclose(f);
     }
     delete feature_list;
 }

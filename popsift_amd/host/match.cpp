@@ -146,6 +146,13 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
               else if (s == "raster") config.setFeatureOrder(popsift::Config::RasterOrder);
               else o.error("the argument ('" + s + "') for option '--feature-order' is invalid");
           });
+    o.ival("keep-strongest", "Extensions",
+           "Match only the N keypoints of every image with the largest DoG response (ties with the N-th included),\n"
+           "thinned on the GPU before orientation; 0 (default): off.  Does not combine with --filter-max-extrema",
+           [&](int n) {
+               if (n < 0) o.error("the argument ('" + to_string(n) + "') for option '--keep-strongest' is invalid");
+               config.setKeepStrongest(n);
+           });
     o.parse(argc, argv);
     if (verify_pairs && !print_pairs) {
         cerr << "--verify works on the pairs: add --pairs" << endl;

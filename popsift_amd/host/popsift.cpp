@@ -274,6 +274,9 @@ bool PopSift::configure(const popsift::Config& config, bool /*force*/)
         DIE("this build implements the Gauss modes 'vlfeat', 'vlfeat-direct' and 'opencv' only");
     if (_config.getFilterMaxExtrema() > 0 && (_config.getFilterGridSize() < 1 || _config.getFilterGridSize() > 64))
         DIE("the grid filter supports grid sizes 1..64");
+    if (_config.getKeepStrongest() < 0) DIE("setKeepStrongest: 0 (off) or a positive count");
+    if (_config.getKeepStrongest() > 0 && _config.getFilterMaxExtrema() > 0)
+        DIE("setKeepStrongest and the grid filter (setFilterMaxExtrema) do not chain");
     _shadow_config = _config;
     return true;
 }
@@ -310,6 +313,9 @@ void PopSift::start_workers(int w, int h)
             wk->cpus = node_cpus[d].second;
             const int rc = popsift_hip_ctx_create(d, &p, &wk->ctx);
             if (rc != POPSIFT_HIP_OK) DIE(string("cannot create extraction context: ") + popsift_hip_strerror(rc));
+            /* the configuration is fixed once the workers exist: every job takes the value of its enqueue */
+            if (_config.getKeepStrongest() > 0 && popsift_hip_set_keep_strongest(wk->ctx, _config.getKeepStrongest()) != POPSIFT_HIP_OK)
+                DIE(string("setKeepStrongest: ") + popsift_hip_last_error(wk->ctx));
             _workers.push_back(wk);
         }
     }
@@ -371,6 +377,16 @@ static popsift::FeaturesHost* new_features(const SiftJob* job, int nf, int nd)
 static void* desc_target(popsift::FeaturesHost* f)
 {
     return f->hasDescriptorBytes() ? (void*)f->getDescriptorBytes() : (void*)f->getDescriptors();
+}
+
+/* Config::setKeepStrongest: the responses of image k of the finished batch into the job's result block, before its
+ * download is started (popsift_hip_fetch_begin hands the slot's results on); a small blocking copy.  Describe jobs have
+ * none */
+static void fetch_responses(popsift_hip_ctx* ctx, int k, const SiftJob* job, popsift::FeaturesHost* features, int nf, int keep)
+{
+    if (keep <= 0 || job->isDescribe() || nf <= 0) return;
+    if (popsift_hip_fetch_responses_item(ctx, k, features->resetResponses(), (size_t)nf) != POPSIFT_HIP_OK)
+        DIE(string("download failed: ") + popsift_hip_last_error(ctx));
 }
 
 static_assert(sizeof(popsift::Frame) == sizeof(popsift_hip_frame) && offsetof(popsift::Frame, level) == offsetof(popsift_hip_frame, level),
@@ -491,6 +507,7 @@ void PopSift::worker_loop(Worker* me)
                     continue;
                 }
                 popsift_hip_feature* pod = pod_buffer((size_t)k, nfs[k]);
+                fetch_responses(me->ctx, k, jobs[(size_t)k], features, nfs[k], _config.getKeepStrongest());
                 if (features->hasDescriptorBytes())
                     rc = popsift_hip_fetch_begin_item_u8(me->ctx, k, pod, me->pods[(size_t)k].cap, features->getDescriptorBytes(),
                                                          (size_t)nds[k] * 128);
@@ -544,6 +561,7 @@ void PopSift::worker_loop(Worker* me)
         if (nd == 0) cerr << "Warning: no descriptors extracted" << endl; /* sift_desc.cu:88-92 */
         if (nf > 0) {
             popsift_hip_feature* pod = pod_buffer(0, nf);
+            fetch_responses(me->ctx, 0, job, features, nf, _config.getKeepStrongest());
             if (overlap) {
                 rc = bytes ? popsift_hip_fetch_begin_u8(me->ctx, pod, me->pods[0].cap, features->getDescriptorBytes(), (size_t)nd * 128)
                            : popsift_hip_fetch_begin(me->ctx, pod, me->pods[0].cap, (float*)desc_target(features), (size_t)nd * 128);

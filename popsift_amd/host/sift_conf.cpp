@@ -40,6 +40,7 @@ Config::Config()
     , _print_gauss_tables(false)
     , _descriptor_format(Config::FloatDescriptors)
     , _feature_order(Config::ArrivalOrder)
+    , _keep_strongest(0)
 {
 }
 
@@ -105,7 +106,8 @@ bool Config::equal(const Config& o) const
            _max_extrema == o._max_extrema && _gauss_mode == o._gauss_mode && _sift_mode == o._sift_mode &&
            _assume_initial_blur == o._assume_initial_blur && _initial_blur == o._initial_blur &&
            _normalization_mode == o._normalization_mode && _normalization_multiplier == o._normalization_multiplier &&
-           _descriptor_format == o._descriptor_format && _feature_order == o._feature_order;
+           _descriptor_format == o._descriptor_format && _feature_order == o._feature_order &&
+           _keep_strongest == o._keep_strongest;
 }
 
 }  // namespace popsift
