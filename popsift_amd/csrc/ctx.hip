@@ -1,7 +1,10 @@
 /*
  * ctx.hip -- C-ABI implementation of libpopsift_hip (include/popsift_hip.h):
- * per-GPU extraction context, Gauss / constant tables, HBM arena and the
- * per-image launch sequence.
+ * per-GPU extraction context, Gauss / constant tables, HBM arena, the
+ * per-image launch sequence and the ways its results leave the context
+ * (fetch, fetch_begin, device pointers, clones).  No device code.  The
+ * device-resident sets the clones make are sets.hip, the calls that match
+ * sets match_sets.hip; the set types are devfeatures.h.
  *
  * Replaces the host side of the reference's L3 layer:
  *   init_filter / init_constants      gauss_filter.cu:127-257, sift_constants.cu:22-53
@@ -1262,32 +1265,52 @@ int results_here(popsift_hip_ctx* c, int k = 0)
     return 0;
 }
 
-/* The byte buffer of a slot, sized for its slab.  Writers call this first: it waits for a pending fetch_begin*_u8 download
- * that still reads the buffer (the state of that download is left as it is: fetch_end still completes it). */
-int slot_u8_ready(popsift_hip_ctx* c, ImageSlot& sl)
+/* The first n descriptors of a slot as bytes in its desc_u8, by a pass on the compute stream.  The buffer is sized for the
+ * slab first, before anything is issued; a writer also waits for a pending fetch_begin*_u8 download that still reads the
+ * buffer (the state of that download is left as it is: fetch_end still completes it). */
+int slot_bytes(popsift_hip_ctx* c, ImageSlot& sl, int n)
 {
     if (sl.u8_read && c->copy_pending) HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
     sl.u8_read = false;
-    return grow(c, sl.desc_u8, std::max<size_t>(sl.desc_cap(), 1));
+    if (int rc = grow(c, sl.desc_u8, std::max<size_t>(sl.desc_cap(), 1))) return rc;
+    if (n > 0) {
+        HIP_TRY(c, launch_desc_bytes(sl.desc.p, n, sl.desc_u8.p, c->stream));
+        SYNC_CHK(c, "k_desc_bytes");
+    }
+    return 0;
 }
 
-/* image k's results into caller memory, descriptors as floats (u8 = false) or as bytes, on the compute stream */
-int fetch_sync(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap,
-               size_t nd, bool u8)
+/* What the blocking and the overlapped fetch share: the argument checks, then `prepare` (whatever the caller has to wait
+ * for or allocate), then image k's records and its descriptors -- floats, or the bytes of slot_bytes -- on their way to
+ * caller memory by copies on stream s.  s is read after prepare, where fetch_begin makes its stream. */
+template <typename F>
+int fetch_issue(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap, bool u8,
+                const hipStream_t& s, F prepare)
 {
-    const size_t nf = (size_t)c->n_feat[k];
+    const size_t nf = (size_t)c->n_feat[k], nd = (size_t)c->n_desc[k];
     if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
     if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
     HIP_TRY(c, hipSetDevice(c->device));
     ImageSlot& sl = c->slot[k];
-    if (u8 && nd) {
-        if (int rc = slot_u8_ready(c, sl)) return rc;
-        HIP_TRY(c, launch_desc_bytes(sl.desc.p, (int)nd, sl.desc_u8.p, c->stream));
-        SYNC_CHK(c, "k_desc_bytes");
-    }
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.feats.p, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->stream));
-    if (nd && u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc_u8.p, nd * 128, hipMemcpyDeviceToHost, c->stream));
-    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc.p, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = prepare(sl)) return rc;
+    /* Bytes: the pass runs on the compute stream -- idle now, and ahead of the next submit's kernels -- and a byte copy
+     * on another stream waits for it.  On the copy stream the pass would queue behind other contexts' kernels on a shared
+     * hardware queue (keypoint-sparse host to host 6.7-7.4 instead of 9.4-9.5 Gpix/s). */
+    const bool apart = u8 && nd && s != c->stream;
+    if (u8 && nd)
+        if (int rc = slot_bytes(c, sl, (int)nd)) return rc;
+    if (apart) HIP_TRY(c, hipEventRecord(c->ev_u8, c->stream));
+    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.feats.p, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, s));
+    if (apart) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_u8, 0));
+    if (nd && u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc_u8.p, nd * 128, hipMemcpyDeviceToHost, s));
+    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc.p, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+/* image k's results into caller memory, descriptors as floats (u8 = false) or as bytes, on the compute stream */
+int fetch_sync(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap, bool u8)
+{
+    if (int rc = fetch_issue(c, k, feats, feats_cap, desc, desc_cap, u8, c->stream, [](ImageSlot&) { return 0; })) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1295,39 +1318,26 @@ int fetch_sync(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t fea
 /* popsift_hip_fetch_begin_item(_u8) */
 int fetch_begin(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, void* desc, size_t desc_cap, bool u8)
 {
-    const size_t nf = (size_t)c->n_feat[k], nd = (size_t)c->n_desc[k];
-    if ((nf && !feats) || (nd && !desc)) return fail(c, POPSIFT_HIP_ERR_INVALID, "null output buffer");
-    if (feats_cap < nf || desc_cap < nd * 128) return fail(c, POPSIFT_HIP_ERR_TOO_SMALL, "output buffer too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    /* the other slabs may still be the source of the downloads of the batch before this one */
-    if (c->copy_pending && c->copy_seq != c->submit_seq)
-        if (int rc = drain_copy(c)) return rc;
-    /* The copy stream is made on first use: the runtime deals its few hardware queues to streams in the order they
-     * are created, so a second stream in EVERY context -- used or not -- takes queues from the streams that do the work
-     * (four active contexts next to sixteen idle ones: 7.8 -> 6.5 Gpix/s on the sparse workload). */
-    if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    /* nothing has been issued or swapped yet: a failed allocation leaves the results where they are (plain fetch works) */
+    auto prepare = [&](ImageSlot& sl) -> int {
+        /* the other slabs may still be the source of the downloads of the batch before this one */
+        if (c->copy_pending && c->copy_seq != c->submit_seq)
+            if (int rc = drain_copy(c)) return rc;
+        /* The copy stream is made on first use: the runtime deals its few hardware queues to streams in the order they
+         * are created, so a second stream in EVERY context -- used or not -- takes queues from the streams that do the work
+         * (four active contexts next to sixteen idle ones: 7.8 -> 6.5 Gpix/s on the sparse workload). */
+        if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        /* Nothing has been issued or swapped yet: a failed allocation leaves the results where they are (plain fetch works).
+         * That holds for the byte buffer too: slot_bytes, the first to issue anything, grows it before its launch. */
+        if (int rc = grow(c, sl.alt_feats, sl.feats.cap)) return rc;
+        if (int rc = grow(c, sl.alt_desc, sl.desc_cap())) return rc;
+        if (u8 && c->n_desc[k] && !c->ev_u8) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_u8, hipEventDisableTiming));
+        return 0;
+    };
+    /* finish() has synchronised the compute stream: the slab is complete, and copy_stream needs no event to wait on.  A
+     * byte pass reads the slab that becomes alt_desc below, which the next batch does not write. */
+    if (int rc = fetch_issue(c, k, feats, feats_cap, desc, desc_cap, u8, c->copy_stream, prepare)) return rc;
     ImageSlot& sl = c->slot[k];
-    if (int rc = grow(c, sl.alt_feats, sl.feats.cap)) return rc;
-    if (int rc = grow(c, sl.alt_desc, sl.desc_cap())) return rc;
-    if (u8 && nd) {
-        if (int rc = slot_u8_ready(c, sl)) return rc;
-        if (!c->ev_u8) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_u8, hipEventDisableTiming));
-    }
-    /* finish() has synchronised the compute stream: the slab is complete, and copy_stream needs no event to wait on.
-     * Bytes: the pass runs on the compute stream -- idle now, and ahead of the next submit's kernels -- and the byte copy
-     * waits for it.  On the copy stream it would queue behind other contexts' kernels on a shared hardware queue
-     * (keypoint-sparse host to host 6.7-7.4 instead of 9.4-9.5 Gpix/s).  It reads the slab that becomes
-     * alt_desc below, which the next batch does not write. */
-    if (nf) HIP_TRY(c, hipMemcpyAsync(feats, sl.feats.p, nf * sizeof(popsift_hip_feature), hipMemcpyDeviceToHost, c->copy_stream));
-    if (nd && u8) {
-        HIP_TRY(c, launch_desc_bytes(sl.desc.p, (int)nd, sl.desc_u8.p, c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_u8, c->stream));
-        HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_u8, 0));
-        HIP_TRY(c, hipMemcpyAsync(desc, sl.desc_u8.p, nd * 128, hipMemcpyDeviceToHost, c->copy_stream));
-        sl.u8_read = true;
-    }
-    if (nd && !u8) HIP_TRY(c, hipMemcpyAsync(desc, sl.desc.p, nd * 128 * sizeof(float), hipMemcpyDeviceToHost, c->copy_stream));
+    if (u8 && c->n_desc[k]) sl.u8_read = true;
     std::swap(sl.feats, sl.alt_feats);
     std::swap(sl.desc, sl.alt_desc); /* both hold desc_cap() descriptors now; map / rot / drec stay with the slot */
     refresh_caps(c);
@@ -1352,14 +1362,6 @@ int plane_ptr(popsift_hip_ctx* c, int octave, int kind, int level, float** p, co
         return fail(c, POPSIFT_HIP_ERR_INVALID, "bad plane kind/level");
     *odp = &od;
     return 0;
-}
-
-/* ERR_NO_DEVICE without a usable GPU, ERR_INVALID for an index out of range */
-int check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return POPSIFT_HIP_ERR_NO_DEVICE;
-    return device < 0 || device >= n ? POPSIFT_HIP_ERR_INVALID : POPSIFT_HIP_OK;
 }
 
 }  // namespace
@@ -1681,7 +1683,7 @@ int popsift_hip_fetch_item(popsift_hip_ctx* c, int k, popsift_hip_feature* feats
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c, k)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch");
-    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, (size_t)c->n_desc[k], false);
+    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, false);
 }
 
 int popsift_hip_fetch_item_u8(popsift_hip_ctx* c, int k, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc,
@@ -1690,7 +1692,7 @@ int popsift_hip_fetch_item_u8(popsift_hip_ctx* c, int k, popsift_hip_feature* fe
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = results_here(c, k)) return rc;
     POPSIFT_RANGE("popsift_hip: fetch_u8");
-    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, (size_t)c->n_desc[k], true);
+    return fetch_sync(c, k, feats, feats_cap, desc, desc_cap, true);
 }
 
 int popsift_hip_results_dev_item(popsift_hip_ctx* c, int k, const void** d_feats, const void** d_desc)
@@ -1708,32 +1710,27 @@ int popsift_hip_results_dev_item_u8(popsift_hip_ctx* c, int k, const void** d_fe
     if (int rc = results_here(c, k)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     ImageSlot& sl = c->slot[k];
-    if (int rc = slot_u8_ready(c, sl)) return rc;
-    if (c->n_desc[k] > 0) {
-        HIP_TRY(c, launch_desc_bytes(sl.desc.p, c->n_desc[k], sl.desc_u8.p, c->stream));
-        SYNC_CHK(c, "k_desc_bytes");
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
+    if (int rc = slot_bytes(c, sl, c->n_desc[k])) return rc;
+    if (c->n_desc[k] > 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (d_feats) *d_feats = sl.feats.p;
     if (d_desc_u8) *d_desc_u8 = sl.desc_u8.p;
     return POPSIFT_HIP_OK;
 }
+
+/* The single-image calls are the batch calls for image 0 (finish() sets the report's ori_total from n_desc[0]). */
 
 int popsift_hip_wait(popsift_hip_ctx* c, int* n_features, int* n_descriptors)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     if (int rc = finish(c)) return rc;
     if (n_features) *n_features = c->n_feat[0];
-    if (n_descriptors) *n_descriptors = c->rep.ori_total;
+    if (n_descriptors) *n_descriptors = c->n_desc[0];
     return POPSIFT_HIP_OK;
 }
 
 int popsift_hip_fetch(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t feats_cap, float* desc, size_t desc_cap)
 {
-    if (!c) return POPSIFT_HIP_ERR_INVALID;
-    if (int rc = results_here(c)) return rc;
-    POPSIFT_RANGE("popsift_hip: fetch");
-    return fetch_sync(c, 0, feats, feats_cap, desc, desc_cap, (size_t)c->rep.ori_total, false);
+    return popsift_hip_fetch_item(c, 0, feats, feats_cap, desc, desc_cap);
 }
 
 int popsift_hip_fetch_u8(popsift_hip_ctx* c, popsift_hip_feature* feats, size_t feats_cap, uint8_t* desc, size_t desc_cap)
@@ -1780,273 +1777,30 @@ int popsift_hip_fetch_end(popsift_hip_ctx* c)
 
 int popsift_hip_results_dev(popsift_hip_ctx* c, const void** d_feats, const void** d_desc)
 {
-    if (!c) return POPSIFT_HIP_ERR_INVALID;
-    if (int rc = results_here(c)) return rc;
-    if (d_feats) *d_feats = c->slot[0].feats.p;
-    if (d_desc) *d_desc = c->slot[0].desc.p;
-    return POPSIFT_HIP_OK;
+    return popsift_hip_results_dev_item(c, 0, d_feats, d_desc);
 }
 
-/* ------------------------------------------------------------------ MatchingMode (N3) */
+/* ------------------------------------------------------------------ MatchingMode (N3): a finished image as a set (sets.hip) */
 
 int popsift_hip_clone_results(popsift_hip_ctx* c, popsift_hip_devfeatures** out)
 {
     if (!c || !out) return POPSIFT_HIP_ERR_INVALID;
     *out = nullptr;
     if (int rc = results_here(c)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
-    if (!f) return fail(c, POPSIFT_HIP_ERR_OOM, "out of host memory");
-    f->device = c->device;
-    f->n_feat = c->n_feat[0];
-    f->n_desc = c->rep.ori_total;
-    int rc = [&]() -> int {
-        /* allocations of at least one element keep the pointers valid for empty results */
-        HIP_TRY(c, hipMalloc((void**)&f->d_feat, sizeof(DevFeature) * (size_t)std::max(f->n_feat, 1)));
-        HIP_TRY(c, hipMalloc((void**)&f->d_desc, sizeof(float) * 128 * (size_t)std::max(f->n_desc, 1)));
-        HIP_TRY(c, hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(f->n_desc, 1)));
+    const ImageSlot&         sl = c->slot[0];
+    const int                nf = c->n_feat[0], nd = c->n_desc[0];
+    popsift_hip_devfeatures* f = nullptr;
+    if (int rc = devfeatures_new(c->device, nf, nd, &f)) return fail(c, rc, "cannot allocate the set: %s", popsift_hip_strerror(rc));
+    return hand_over([&]() -> int {
         /* sift_pyramid.cu:323-345: prep_features into the clone, then the two device-to-device copies */
-        HIP_TRY(c, launch_clone_features(c->slot[0].feats.p, f->n_feat, f->d_desc, f->d_feat, c->stream));
-        if (f->n_desc > 0) {
-            HIP_TRY(c, hipMemcpyAsync(f->d_desc, c->slot[0].desc.p, sizeof(float) * 128 * (size_t)f->n_desc,
-                                      hipMemcpyDeviceToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(f->d_rev, c->slot[0].map.p, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToDevice,
-                                      c->stream));
+        HIP_TRY(c, launch_clone_features(sl.feats.p, nf, f->d_desc, f->d_feat, c->stream));
+        if (nd > 0) {
+            HIP_TRY(c, hipMemcpyAsync(f->d_desc, sl.desc.p, sizeof(float) * 128 * (size_t)nd, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(f->d_rev, sl.map.p, sizeof(int) * (size_t)nd, hipMemcpyDeviceToDevice, c->stream));
         }
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return 0;
-    }();
-    if (rc) {
-        popsift_hip_devfeatures_free(f);
-        return rc;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_free(popsift_hip_devfeatures* f)
-{
-    if (!f) return POPSIFT_HIP_OK;
-    (void)hipSetDevice(f->device);
-    f->release();
-    for (void* p : {(void*)f->d_feat, (void*)f->d_desc, (void*)f->d_rev, (void*)f->d_norm, (void*)f->m_redo, f->v_buf, f->g_buf})
-        if (p) (void)hipFree(p);
-    if (f->v_host) (void)hipHostFree(f->v_host);
-    if (f->g_host) (void)hipHostFree(f->g_host);
-    delete f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_info(const popsift_hip_devfeatures* f, int* device, int* n_features, int* n_descriptors)
-{
-    if (!f) return POPSIFT_HIP_ERR_INVALID;
-    if (device) *device = f->device;
-    if (n_features) *n_features = f->n_feat;
-    if (n_descriptors) *n_descriptors = f->n_desc;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_ptrs(const popsift_hip_devfeatures* f, void** d_features, void** d_descriptors,
-                                 void** d_reverse_map)
-{
-    if (!f) return POPSIFT_HIP_ERR_INVALID;
-    if (d_features) *d_features = f->d_feat;
-    if (d_descriptors) *d_descriptors = f->d_desc;
-    if (d_reverse_map) *d_reverse_map = f->d_rev;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_alloc(int device, int n_feat, int n_desc, popsift_hip_devfeatures** out)
-{
-    if (!out || n_feat < 0 || n_desc < 0) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
-    if (int rc = check_device(device)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
-    if (!f) return POPSIFT_HIP_ERR_OOM;
-    f->device = device;
-    f->n_feat = n_feat;
-    f->n_desc = n_desc;
-    const size_t bf = sizeof(DevFeature) * (size_t)std::max(n_feat, 1);
-    const size_t bd = sizeof(float) * 128 * (size_t)std::max(n_desc, 1);
-    const size_t br = sizeof(int) * (size_t)std::max(n_desc, 1);
-    const bool   ok = hipMalloc((void**)&f->d_feat, bf) == hipSuccess && hipMalloc((void**)&f->d_desc, bd) == hipSuccess &&
-                    hipMalloc((void**)&f->d_rev, br) == hipSuccess && hipMemset(f->d_feat, 0, bf) == hipSuccess &&
-                    hipMemset(f->d_desc, 0, bd) == hipSuccess && hipMemset(f->d_rev, 0, br) == hipSuccess;
-    if (!ok) {
-        popsift_hip_devfeatures_free(f);
-        return POPSIFT_HIP_ERR_OOM;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_from_host(int device, const float* desc, int n, popsift_hip_devfeatures** out)
-{
-    if (!out || n < 0 || (n > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
-    if (int rc = check_device(device)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
-    if (!f) return POPSIFT_HIP_ERR_OOM;
-    f->device = device;
-    f->n_feat = 0;
-    f->n_desc = n;
-    bool ok = hipMalloc((void**)&f->d_feat, sizeof(DevFeature)) == hipSuccess &&
-              hipMalloc((void**)&f->d_desc, sizeof(float) * 128 * (size_t)std::max(n, 1)) == hipSuccess &&
-              hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(n, 1)) == hipSuccess;
-    if (ok && n > 0) {
-        ok = hipMemcpy(f->d_desc, desc, sizeof(float) * 128 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemset(f->d_rev, 0xff, sizeof(int) * (size_t)n) == hipSuccess; /* -1: no feature behind it */
-    }
-    if (!ok) {
-        popsift_hip_devfeatures_free(f);
-        return POPSIFT_HIP_ERR_OOM;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_from_host_points(int device, const float* desc, const float* xy, int n, popsift_hip_devfeatures** out)
-{
-    if (!out || n < 0 || (n > 0 && (!desc || !xy))) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
-    if (int rc = check_device(device)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    popsift_hip_devfeatures* f = new (std::nothrow) popsift_hip_devfeatures();
-    if (!f) return POPSIFT_HIP_ERR_OOM;
-    f->device = device;
-    f->n_feat = n;
-    f->n_desc = n;
-    bool ok = hipMalloc((void**)&f->d_feat, sizeof(DevFeature) * (size_t)std::max(n, 1)) == hipSuccess &&
-              hipMalloc((void**)&f->d_desc, sizeof(float) * 128 * (size_t)std::max(n, 1)) == hipSuccess &&
-              hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(n, 1)) == hipSuccess;
-    if (ok && n > 0) {
-        /* the records are built here: one feature per descriptor, its desc[0] pointing into the device array */
-        std::vector<DevFeature> feat((size_t)n);
-        std::vector<int>        rev((size_t)n);
-        for (int i = 0; i < n; i++) {
-            DevFeature& o = feat[(size_t)i];
-            memset(&o, 0, sizeof o);
-            o.xpos = xy[2 * (size_t)i];
-            o.ypos = xy[2 * (size_t)i + 1];
-            o.num_ori = 1;
-            o.desc[0] = f->d_desc + (size_t)i * 128;
-            rev[(size_t)i] = i;
-        }
-        ok = hipMemcpy(f->d_desc, desc, sizeof(float) * 128 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(f->d_feat, feat.data(), sizeof(DevFeature) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(f->d_rev, rev.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) {
-        popsift_hip_devfeatures_free(f);
-        return POPSIFT_HIP_ERR_OOM;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_download(const popsift_hip_devfeatures* f, float* desc, int32_t* rev)
-{
-    if (!f) return POPSIFT_HIP_ERR_INVALID;
-    if (hipSetDevice(f->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    if (f->n_desc > 0) {
-        if (desc && hipMemcpy(desc, f->d_desc, sizeof(float) * 128 * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
-            return POPSIFT_HIP_ERR_DEVICE;
-        if (rev && hipMemcpy(rev, f->d_rev, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
-            return POPSIFT_HIP_ERR_DEVICE;
-    }
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_devfeatures_download_u8(const popsift_hip_devfeatures* f, uint8_t* desc)
-{
-    if (!f || (f->n_desc > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
-    if (f->n_desc <= 0) return POPSIFT_HIP_OK;
-    if (hipSetDevice(f->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    const size_t bytes = (size_t)f->n_desc * 128;
-    uint8_t*     d_u8 = nullptr;
-    if (hipMalloc((void**)&d_u8, bytes) != hipSuccess) return POPSIFT_HIP_ERR_OOM;
-    /* the null stream: the pass is ordered after whatever wrote the set, the blocking copy after the pass */
-    const bool ok = launch_desc_bytes(f->d_desc, f->n_desc, d_u8, nullptr) == hipSuccess &&
-                    hipMemcpy(desc, d_u8, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)hipFree(d_u8);
-    return ok ? POPSIFT_HIP_OK : POPSIFT_HIP_ERR_DEVICE;
-}
-
-/* ---- byte sets */
-
-int popsift_hip_bytefeatures_free(popsift_hip_bytefeatures* f)
-{
-    if (!f) return POPSIFT_HIP_OK;
-    (void)hipSetDevice(f->device);
-    f->release();
-    for (void* p : {(void*)f->d_desc, (void*)f->d_rev, (void*)f->d_norm})
-        if (p) (void)hipFree(p);
-    delete f;
-    return POPSIFT_HIP_OK;
-}
-
-} /* extern "C" */
-
-namespace {
-
-/* an uninitialised set of n descriptors on `device`, made current (allocations of at least one element keep the pointers
- * valid for empty sets) */
-int bytefeatures_new(int device, int n, popsift_hip_bytefeatures** out)
-{
-    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    popsift_hip_bytefeatures* f = new (std::nothrow) popsift_hip_bytefeatures();
-    if (!f) return POPSIFT_HIP_ERR_OOM;
-    f->device = device;
-    f->n_desc = n;
-    if (hipMalloc((void**)&f->d_desc, (size_t)128 * (size_t)std::max(n, 1)) != hipSuccess ||
-        hipMalloc((void**)&f->d_rev, sizeof(int) * (size_t)std::max(n, 1)) != hipSuccess) {
-        popsift_hip_bytefeatures_free(f);
-        return POPSIFT_HIP_ERR_OOM;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int popsift_hip_bytefeatures_from_host(int device, const uint8_t* desc, int n, popsift_hip_bytefeatures** out)
-{
-    if (!out || n < 0 || (n > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
-    if (int rc = check_device(device)) return rc;
-    popsift_hip_bytefeatures* f = nullptr;
-    if (int rc = bytefeatures_new(device, n, &f)) return rc;
-    if (n > 0 && (hipMemcpy(f->d_desc, desc, (size_t)128 * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-                  hipMemset(f->d_rev, 0xff, sizeof(int) * (size_t)n) != hipSuccess || /* -1: no feature behind it */
-                  hipDeviceSynchronize() != hipSuccess)) {
-        popsift_hip_bytefeatures_free(f);
-        return POPSIFT_HIP_ERR_DEVICE;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_bytefeatures_from_set(const popsift_hip_devfeatures* src, popsift_hip_bytefeatures** out)
-{
-    if (!src || !out) return POPSIFT_HIP_ERR_INVALID;
-    *out = nullptr;
-    popsift_hip_bytefeatures* f = nullptr;
-    if (int rc = bytefeatures_new(src->device, src->n_desc, &f)) return rc;
-    /* the null stream: ordered after whatever wrote the set; the set's own match stream does not wait for it, so the
-     * call returns with the bytes in place */
-    const int n = src->n_desc;
-    if (n > 0 && (launch_desc_bytes(src->d_desc, n, f->d_desc, nullptr) != hipSuccess ||
-                  hipMemcpyAsync(f->d_rev, src->d_rev, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, nullptr) != hipSuccess ||
-                  hipStreamSynchronize(nullptr) != hipSuccess)) {
-        popsift_hip_bytefeatures_free(f);
-        return POPSIFT_HIP_ERR_DEVICE;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
+    }(), f, out);
 }
 
 int popsift_hip_clone_results_u8(popsift_hip_ctx* c, int k, popsift_hip_bytefeatures** out)
@@ -2054,48 +1808,19 @@ int popsift_hip_clone_results_u8(popsift_hip_ctx* c, int k, popsift_hip_bytefeat
     if (!c || !out) return POPSIFT_HIP_ERR_INVALID;
     *out = nullptr;
     if (int rc = results_here(c, k)) return rc;
+    ImageSlot&                sl = c->slot[k];
     const int                 n = c->n_desc[k];
     popsift_hip_bytefeatures* f = nullptr;
-    if (int rc = bytefeatures_new(c->device, n, &f))
-        return fail(c, rc, "cannot allocate the byte set: %s", popsift_hip_strerror(rc));
-    ImageSlot& sl = c->slot[k];
-    const int  rc = [&]() -> int {
+    if (int rc = bytefeatures_new(c->device, n, &f)) return fail(c, rc, "cannot allocate the byte set: %s", popsift_hip_strerror(rc));
+    return hand_over([&]() -> int {
         if (n == 0) return 0;
         /* the bytes the byte fetch calls deliver: the slot's byte buffer, then device to device */
-        if (int e = slot_u8_ready(c, sl)) return e;
-        HIP_TRY(c, launch_desc_bytes(sl.desc.p, n, sl.desc_u8.p, c->stream));
-        SYNC_CHK(c, "k_desc_bytes");
+        if (int e = slot_bytes(c, sl, n)) return e;
         HIP_TRY(c, hipMemcpyAsync(f->d_desc, sl.desc_u8.p, (size_t)128 * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(f->d_rev, sl.map.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return 0;
-    }();
-    if (rc) {
-        popsift_hip_bytefeatures_free(f);
-        return rc;
-    }
-    *out = f;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_bytefeatures_info(const popsift_hip_bytefeatures* f, int* device, int* n_descriptors)
-{
-    if (!f) return POPSIFT_HIP_ERR_INVALID;
-    if (device) *device = f->device;
-    if (n_descriptors) *n_descriptors = f->n_desc;
-    return POPSIFT_HIP_OK;
-}
-
-int popsift_hip_bytefeatures_download(const popsift_hip_bytefeatures* f, uint8_t* desc, int32_t* rev)
-{
-    if (!f) return POPSIFT_HIP_ERR_INVALID;
-    if (f->n_desc <= 0) return POPSIFT_HIP_OK;
-    if (hipSetDevice(f->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
-    if (desc && hipMemcpy(desc, f->d_desc, (size_t)128 * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
-        return POPSIFT_HIP_ERR_DEVICE;
-    if (rev && hipMemcpy(rev, f->d_rev, sizeof(int) * (size_t)f->n_desc, hipMemcpyDeviceToHost) != hipSuccess)
-        return POPSIFT_HIP_ERR_DEVICE;
-    return POPSIFT_HIP_OK;
+    }(), f, out);
 }
 
 void* popsift_hip_host_alloc(size_t bytes)

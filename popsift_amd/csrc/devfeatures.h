@@ -1,11 +1,13 @@
 /* devfeatures.h -- device-resident result sets (internal; the C ABI sees opaque pointers), the scratch record a set keeps
- * for the calls that have it on the left, and the host helpers those calls share (match_sets.hip, match_guided.hip,
- * ransac.hip). */
+ * for the calls that have it on the left, and the host helpers those calls share (sets.hip, match_sets.hip,
+ * match_guided.hip, ransac.hip).  A set owns everything its fields point to: whichever file makes a buffer, the set's
+ * destructor here is the one place that frees it. */
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 
 #include "sift_types.h"
 
@@ -21,8 +23,17 @@ struct DevFeature {
 };
 static_assert(sizeof(DevFeature) == 72, "popsift::Feature layout");
 
+/* device and pinned buffers of a set go; its GPU is current (popsift_hip_*features_free) */
+inline void free_bufs(std::initializer_list<void*> dev, std::initializer_list<void*> pinned = {})
+{
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+    for (void* p : pinned)
+        if (p) (void)hipHostFree(p);
+}
+
 /* Scratch of the matchers with this set on the left, kept between calls (one match at a time per left set, like one image
- * at a time per context).  Both set types embed it; release() is the one place that frees it. */
+ * at a time per context).  Both set types embed it. */
 struct MatchScratch {
     void*  m_stream = nullptr;  /* hipStream_t */
     void*  m_partial = nullptr; /* the sweeps' per-split candidates */
@@ -40,13 +51,13 @@ struct MatchScratch {
     void*  p_back = nullptr;    /* of J: gathered descriptors, their norms, the reverse sweep's rows (and its redo list) */
     size_t p_back_cap = 0;      /* rows */
 
-    void release()
+    MatchScratch() = default;
+    MatchScratch(const MatchScratch&) = delete;
+    MatchScratch& operator=(const MatchScratch&) = delete;
+    ~MatchScratch()
     {
         if (m_stream) (void)hipStreamDestroy((hipStream_t)m_stream);
-        for (void* p : {m_partial, m_out, m_rnorm, p_pairs, (void*)p_idx, p_back})
-            if (p) (void)hipFree(p);
-        if (m_host) (void)hipHostFree(m_host);
-        if (p_host) (void)hipHostFree(p_host);
+        free_bufs({m_partial, m_out, m_rnorm, p_pairs, p_idx, p_back}, {m_host, p_host});
     }
 };
 
@@ -67,6 +78,8 @@ struct popsift_hip_devfeatures : MatchScratch {
     void*  g_buf = nullptr;
     size_t g_cap = 0;           /* bytes */
     void*  g_host = nullptr;    /* pinned twin of the header and the forward rows */
+
+    ~popsift_hip_devfeatures() { free_bufs({d_feat, d_desc, d_rev, d_norm, m_redo, v_buf, g_buf}, {v_host, g_host}); }
 };
 
 /* A set of byte descriptors (popsift_hip_bytefeatures); a zero-filled block reads as an empty set. */
@@ -76,6 +89,8 @@ struct popsift_hip_bytefeatures : MatchScratch {
     uint8_t* d_desc = nullptr; /* n_desc * 128, the caller's bytes */
     int*     d_rev = nullptr;  /* n_desc: descriptor -> feature, -1 = none */
     int*     d_norm = nullptr; /* |x - 128|^2 per descriptor, computed on first use by a match */
+
+    ~popsift_hip_bytefeatures() { free_bufs({d_desc, d_rev, d_norm}); }
 };
 
 namespace popsift_hip {
@@ -104,6 +119,34 @@ bool grow(Status& ok, T*& p, size_t& cap, size_t need, size_t unit)
     cap = 0;
     if (ok(hipMalloc((void**)&p, need * unit))) cap = need;
     return ok.good();
+}
+
+/* ... with a pinned host twin of the same size: one capacity, in bytes, for both */
+inline bool grow_twin(Status& ok, void*& dev, void*& host, size_t& cap, size_t need)
+{
+    if (!ok.good() || need <= cap) return ok.good();
+    if (host) (void)hipHostFree(host);
+    host = nullptr;
+    if (grow(ok, dev, cap, need, 1) && !ok(hipHostMalloc(&host, need, hipHostMallocDefault))) cap = 0;
+    return ok.good();
+}
+
+/* ERR_NO_DEVICE without a usable GPU, ERR_INVALID for an index out of range (sets.hip) */
+int check_device(int device);
+
+/* An uninitialised set on `device`, made current: n_feat feature records and n_desc descriptors with their map, or n
+ * byte descriptors with theirs.  Allocations of at least one element keep the pointers valid for empty sets.  A failure
+ * leaves nothing behind: ERR_DEVICE (the device cannot be made current) or ERR_OOM.  (sets.hip) */
+int devfeatures_new(int device, int n_feat, int n_desc, popsift_hip_devfeatures** out);
+int bytefeatures_new(int device, int n, popsift_hip_bytefeatures** out);
+
+/* what a constructor ends with (rc: the status of filling f): the set goes to the caller, or is freed */
+template <class Set>
+int hand_over(int rc, Set* f, Set** out)
+{
+    if (rc == POPSIFT_HIP_OK) *out = f;
+    else delete f;
+    return rc;
 }
 
 /* the set's own non-blocking stream, created on first use */

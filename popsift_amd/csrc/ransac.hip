@@ -1392,13 +1392,7 @@ int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip
     hipStream_t const s = stream_of(ok, *l);
     /* device block and its pinned twin: a flag, the pairs, the points */
     const size_t b_pairs = sizeof(popsift_hip_pair) * (size_t)n, b_pts = sizeof(float) * 4 * (size_t)n, need = 16 + b_pairs + b_pts;
-    if (ok.good() && need > l->v_cap) {
-        if (l->v_buf) (void)hipFree(l->v_buf);
-        if (l->v_host) (void)hipHostFree(l->v_host);
-        l->v_buf = l->v_host = nullptr;
-        l->v_cap = 0;
-        if (ok(hipMalloc(&l->v_buf, need)) && ok(hipHostMalloc(&l->v_host, need, hipHostMallocDefault))) l->v_cap = need;
-    }
+    grow_twin(ok, l->v_buf, l->v_host, l->v_cap, need);
     /* a right set on another GPU: its feature records and its map come over for the call */
     const DevFeature* rf = r->d_feat;
     const int*        rrev = r->d_rev;
