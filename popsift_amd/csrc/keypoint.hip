@@ -427,7 +427,8 @@ __device__ __forceinline__ DescRec make_desc_rec(const PyrDesc* __restrict__ pdp
     const float    x = e.xpos, y = e.ypos;
     const float    SBP = fabsf(DESC_MAGNIFY * e.sigma);
     const float    cell_px = (2.83f * SBP + 1.0f) * (2.83f * SBP + 1.0f);
-    /* ... and below 2^23 per sample (361 * 2^14 < 2^23): k_descriptor rounds by adding 2^23 */
+    /* ... and below 2^23 per sample (361 * 2^14 < 2^23): k_descriptor reads a word as the bits of a product scaled by
+     * 2^-149, which are the integer below 2^24 (PS_CELL) */
     const int      fbits = min(max(31 - (int)ceilf(log2f(361.0f * cell_px)), 2), 14);
     const float    csbp = cos_t * SBP, ssbp = sin_t * SBP;
     const float    bsz = fabsf(csbp) + fabsf(ssbp);
@@ -442,6 +443,10 @@ __device__ __forceinline__ DescRec make_desc_rec(const PyrDesc* __restrict__ pdp
     r.crsbp = cos_t / SBP;
     r.srsbp = sin_t / SBP;
     r.ang_bins = angle * (4.0f / F_PI);
+    /* Extraction's orientations lie within a bin of [-pi, pi], |ang_bins| <= 4.2, and stay the float they were.  The
+     * describe path accepts every finite angle: beyond two turns the bin count is brought back into [-4, 4] (any multiple
+     * of 8 bins may be missing), so that k_descriptor's slot sum has ONE bound for all of them (DESC_SLOT_BIAS). */
+    if (!(fabsf(r.ang_bins) <= 16.0f)) r.ang_bins = (float)remainder((double)angle * (4.0 / 3.14159265358979323846), 8.0);
     /* the hardware reciprocal, formed here once per descriptor instead of in all 64 lanes of its wave: the same
      * instruction on the same float, so the row spans of k_descriptor are what they were */
     r.inv_c = (fabsf(r.crsbp) > 1e-20f) ? __builtin_amdgcn_rcpf(r.crsbp) : 0.0f;
@@ -674,6 +679,13 @@ constexpr int DESC_MAXROWS = 96;
 constexpr int DESC_REC_WORDS = (((DESC_MAXROWS + 1) * 2 + 7) / 8) * 2; /* 50 words: the rows' records and the sentinel */
 constexpr int DESC_TAB64 = 55;                                          /* 64-bit words of the row-end bits */
 constexpr int DESC_LISTCAP = (DESC_TAB64 - 1) * 64;                     /* 3456 list positions per pass */
+/* k_descriptor reads the slot of a sample's lower bin from the BITS of the float (32 cx0 + 8 bin + 8 copy + BIAS) * 2^-149,
+ * which are that integer only while the sum is positive (a negative float is sign and magnitude).  cx0 >= -1 (the
+ * in-square test: u > -2.5); copy >= 0; the bin is floor(half_angle_bins(.., 1, 2 - ang_bins)), whose value lies in
+ * [-2, 6] + (2 - ang_bins) - 2 up to the polynomial's 5e-6, with |ang_bins| <= 16 (make_desc_rec): bin >= -19.  So the sum
+ * is at least -32 - 152 = -184 without the bias.  A multiple of 64: invisible to the `& 56` and the `^ 32` that use it. */
+constexpr int DESC_SLOT_BIAS = 512;
+static_assert(DESC_SLOT_BIAS % 64 == 0 && DESC_SLOT_BIAS > 32 + 8 * 19, "the slot sum stays positive and the bias drops out");
 /* The 64 lanes walk 64 CONSECUTIVE samples of the list, i.e. one and a half to two neighbouring patch rows, whose up /
  * down taps are each other's centre rows.  Round 2 ran four lane groups (16 lanes each, on four distant parts of the
  * patch: 61 % fewer LDS bank conflicts) while the kernel was bound by vector issue and LDS; once round 3 had slimmed the
@@ -706,12 +718,13 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
     short*        rec = (short*)s_lds[wave];
     unsigned int* tab = s_lds[wave] + DESC_REC_WORDS;
     fix64*        hall = (fix64*)(s_lds[wave] + ROW_WORDS);
-    /* 32-bit LDS addresses: the row records, the bit table, this lane's histogram copy (as a float: the cell addresses are
-     * formed by FMAs) */
+    /* 32-bit LDS addresses: the row records, the bit table, this lane's histogram copy -- as the float whose BITS are the
+     * address, n * 2^-149 (the cell addresses are formed by FMAs on that grid: "ISA: weights" below); the lane's copy
+     * number for the slot likewise, with the bias that keeps the slot sum positive */
     const unsigned int rbase32 = (unsigned int)(size_t)(lds_i16*)rec;
     const unsigned int tbase32 = (unsigned int)(size_t)(lds_u32*)tab;
-    const float        hbasef = (float)(unsigned int)(size_t)(lds_fix64*)(hall + cpy * DESC_CS);
-    const float        cpy8f = (float)(cpy << 3);
+    const float        hbasef = (float)(unsigned int)(size_t)(lds_fix64*)(hall + cpy * DESC_CS) * 0x1p-149f;
+    const float        cpy8f = (float)((cpy << 3) + DESC_SLOT_BIAS) * 0x1p-149f;
     const int     total = min(ct->ori_total, desc_cap);
     /* rows and list positions per pass: DESC_MAXROWS and DESC_LISTCAP, or fewer when a test asks for it
      * (popsift_hip_debug_set DESC_ROWS / DESC_LIST) */
@@ -946,15 +959,24 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                     const float tu = u + 1.5f, tv = v + 1.5f;
                     const float fcx = floorf(tu), fcy = floorf(tv);
                     const float fx = tu - fcx, fy = tv - fcy;
-                    const float wx0 = 1.0f - fx, wy0 = (1.0f - fy) * wm, wy1 = fy * wm;
-                    const float w0 = 1.0f - do0;
+                    /* The histogram words are read from the bits of products on the 2^-149 grid (PS_CELL): the bin shares
+                     * carry 2^-100 and the column weights 2^-49, every one of them a normal float.  A power of two commutes
+                     * with the rounding, so w0 is RN(1 - do0) * 2^-100 and wx0 is RN(1 - fx) * 2^-49 exactly. */
+                    const float wy0 = (1.0f - fy) * wm, wy1 = fy * wm;
+                    const float wx0 = fmaf(-fx, 0x1p-49f, 0x1p-49f), fxs = fx * 0x1p-49f;
+                    const float w0 = fmaf(-do0, 0x1p-100f, 0x1p-100f), do0s = do0 * 0x1p-100f;
                     /* Byte addresses of the four words: one base, the slot of the even and of the odd cell column, immediate
                      * offsets for the neighbours.  Slot of the lower bin: (bin + copy + 4 * (cx0 & 1)) mod 8 -- 4 * cx0 does
                      * for 4 * (cx0 & 1) under the mask, and the bin needs no mask of its own.  Cell indices and the bin are
-                     * small integers held in floats (the floors above), so both addresses are two FMAs and ONE conversion
-                     * each -- no conversion of the three floors, no integer multiply, no shift-adds. */
-                    const unsigned int s0 = (unsigned int)(int)fmaf(fcx, 32.0f, fmaf(ffo, 8.0f, cpy8f)) & 56u;
-                    const unsigned int cb = (unsigned int)(int)fmaf(fcy, (float)(DESC_RS * 8), fmaf(fcx, 64.0f, hbasef));
+                     * small integers held in floats (the floors above), so both addresses are two FMAs each and NO
+                     * conversion: for an integer 0 <= n < 2^24 the float n * 2^-149 has the bit pattern n (the denormals
+                     * and the first normal binade are one linear grid), so with the constants scaled by 2^-149 -- 8, 32 and
+                     * 64 of them are inline integer operands -- the exact sum leaves the integer in the result's bits.
+                     * Three conditions: f32 denormals are preserved (the kernels' mode; never a flush-denormals build,
+                     * csrc/Makefile), the sum is below 2^24 (an LDS address; a slot sum below 1024), and it is not
+                     * negative (cb: ROW_WORDS * 4 >= 352 above; s0: DESC_SLOT_BIAS). */
+                    const unsigned int s0 = __float_as_uint(fmaf(fcx, 0x1p-144f, fmaf(ffo, 0x1p-146f, cpy8f))) & 56u;
+                    const unsigned int cb = __float_as_uint(fmaf(fcy, (float)(DESC_RS * 8) * 0x1p-149f, fmaf(fcx, 0x1p-143f, hbasef)));
                     const unsigned int e0 = cb + s0;
                     const unsigned int e1 = (s0 ^ 32u) + cb;
                     /* A cell that does not exist (column / row -1 or 4) is skipped by the exec mask of its atomic -- the four
@@ -962,9 +984,13 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                      * zero (an add of zero is harmless): four compares per sample where there were eight and four selects. */
                     const bool x0 = tu >= 0.0f, x1 = tu < 3.0f, y0 = tv >= 0.0f, y1 = tv < 3.0f;
 /* ISA: atomics */
-/* round(w * wgt) for both halves of the word by the float trick: w * wgt + 2^23 holds the integer in its mantissa (the
- * products stay below 2^23: make_desc_rec keeps fbits <= 14), one v_and strips the exponent -- an FMA and an AND, both
- * full rate, where v_cvt_u32_f32 runs at half rate */
+/* round(w * wgt) for both halves of the word is ONE multiply each: w carries 2^-100 and wgt 2^-49 (above), the product's
+ * exact value is p * 2^-149 with p = w * wgt unscaled, and the hardware rounds it to the float grid there, whose step
+ * is 2^-149 up to 2^-125 -- to the nearest integer p, ties to even, the integer being the result's bit pattern.  The same
+ * three conditions as for the addresses: denormals preserved; p < 2^24 (make_desc_rec keeps fbits <= 14: a sample weighs
+ * at most 361 * 2^14 < 2^23); no negative operand (w0, do0s in [0, 2^-100], wgt a product of weights in [0, 1], the
+ * window and |g|).  Where wgt itself goes denormal and loses bits, p is below 2^-126 * 2^-100 * 2^149 = 2^-77: 0 either
+ * way.  Rounds as fma(w, wgt, 2^23) & 0x7fffff did (tests/test_desc_words.py), without the FMA's addend and the AND. */
 /* timing probes (results invalid): DESC_PROBE_NOATOMIC folds the words into a register instead of adding them to the LDS
  * histogram, DESC_PROBE_NOLOAD takes the taps from registers instead of memory (tools/build_variants.py) */
 #ifdef DESC_PROBE_NOATOMIC
@@ -977,17 +1003,17 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
 #define PS_CELL(ADDR, WGT)                                                                                     \
     {                                                                                                          \
         const float        wgt = (WGT);                                                                        \
-        const unsigned int lo = __float_as_uint(fmaf(w0, wgt, 8388608.0f)) & 0x7fffffu;                        \
-        const unsigned int hi = __float_as_uint(fmaf(do0, wgt, 8388608.0f)) & 0x7fffffu;                       \
+        const unsigned int lo = __float_as_uint(w0 * wgt);                                                     \
+        const unsigned int hi = __float_as_uint(do0s * wgt);                                                   \
         PS_CELL_ADD(ADDR, lo, hi)                                                                              \
     }
                     if (y0) {
                         if (x0) PS_CELL(e0, wy0 * wx0)
-                        if (x1) PS_CELL(e1 + 64u, wy0 * fx)
+                        if (x1) PS_CELL(e1 + 64u, wy0 * fxs)
                     }
                     if (y1) {
                         if (x0) PS_CELL(e0 + DESC_RS * 8u, wy1 * wx0)
-                        if (x1) PS_CELL(e1 + DESC_RS * 8u + 64u, wy1 * fx)
+                        if (x1) PS_CELL(e1 + DESC_RS * 8u + 64u, wy1 * fxs)
                     }
 #undef PS_CELL
 #undef PS_CELL_ADD

@@ -133,6 +133,35 @@ A64KERNEL(k_lshl_add64, F_LSHLADD64) A64KERNEL(k_lshl_add64s, F_LSHLADD64S) A64K
 KERNEL(k_cmp_cnd, F_CMP(0), F_CNDM(0), F_CMP(1), F_CNDM(1), F_CMP(2), F_CNDM(2), F_CMP(3), F_CNDM(3))
 KERNEL(k_fma_int, F_FMA(0), F_ADDU(1), F_FMA(2), F_ADDU(3), F_FMA(4), F_ADDU(5), F_FMA(6), F_ADDU(7))
 
+// f32 denormals (the kernels run with denormals preserved, .amdhsa_float_denorm_mode_32 3): k_descriptor forms its
+// histogram words and cell addresses as products scaled by 2^-149, whose bit pattern is the integer.  Does a denormal
+// result or input leave the full-rate class?  The operands are set inside the kernel (the launch passes 1.0001 / 0.9999)
+// and every instruction writes its register from the SAME three inputs, so the values stay what they are through all
+// 16384 instructions; the first row is the same form on normal numbers, to compare against.
+#define DKERNEL(NAME, INS, A, B, C)                                                                                        \
+    __global__ __launch_bounds__(64) void NAME(long long* out, float a, float b)                                          \
+    {                                                                                                                     \
+        float r0 = threadIdx.x, r1 = r0 + 1, r2 = r0 + 2, r3 = r0 + 3, r4 = r0 + 4, r5 = r0 + 5, r6 = r0 + 6, r7 = r0 + 7; \
+        const float da = a * (A), db = b * (B), dc = (C) + (float)(threadIdx.x & 7u) * 0x1p-149f;                          \
+        const long long t0 = __builtin_readcyclecounter();                                                               \
+        for (int it = 0; it < ITERS; it++) {                                                                             \
+            REP8(asm volatile(INS(0) "\n" INS(1) "\n" INS(2) "\n" INS(3) "\n" INS(4) "\n" INS(5) "\n" INS(6) "\n" INS(7)   \
+                              : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7)           \
+                              : "v"(da), "v"(db), "v"(dc));)                                                              \
+        }                                                                                                                 \
+        const long long t1 = __builtin_readcyclecounter();                                                               \
+        if (r1 + r2 + r3 + r4 + r5 + r6 + r7 == 12345.678f) out[0] = 1;                                                   \
+        if (threadIdx.x == 0) out[1 + blockIdx.x] = t1 - t0;                                                              \
+        if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = (long long)__float_as_uint(r0); /* the result's bits: printed */ \
+    }
+#define D_MUL(i) "v_mul_f32 %" #i ", %8, %9"
+#define D_FMA(i) "v_fma_f32 %" #i ", %8, %9, %10"
+DKERNEL(k_mul_nn, D_MUL, 0.75f, 1.5f, 0.0f)                      /* normal * normal -> normal */
+DKERNEL(k_mul_dres, D_MUL, 0x1.8p-100f, 0x1.2p-38f, 0.0f)        /* 2^-100-scaled weight * 2^-49-scaled weight -> about 2^-137 */
+DKERNEL(k_mul_din, D_MUL, 12345.0f * 0x1p-149f, 3.0f, 0.0f)      /* denormal * normal -> denormal */
+DKERNEL(k_fma_nn, D_FMA, 3.0f, 32.0f, 520.0f)                    /* the address FMA on normal numbers */
+DKERNEL(k_fma_den, D_FMA, 3.0f, 0x1p-144f, 520.0f * 0x1p-149f)   /* small integer * denormal constant + denormal -> denormal */
+
 typedef void (*kern_t)(long long*, float, float);
 
 int main()
@@ -156,11 +185,14 @@ int main()
         {"v_cvt_f32_ubyte0", k_cvtub}, {"v_cndmask_b32 (sgpr mask)", k_cnds}, {"v_bfe_u32", k_bfe}, {"v_mul_u32_u24", k_mulu24},
         {"v_not_b32", k_not}, {"v_med3_f32", k_med3}, {"v_ldexp_f32", k_ldexp}, {"v_mov_b32 dpp quad_perm", k_movdpp},
         {"v_lshl_add_u64 (shift 0)", k_lshl_add64}, {"v_lshl_add_u64 (shift 2)", k_lshl_add64s}, {"v_mad_i64_i32", k_mad64},
-        {"v_pk_fma_f32 (dependent chain)", k_pkfma}, {"v_pk_mul_f32 (dependent chain)", k_pkmul}, {"v_pk_add_f32 (dependent chain)", k_pkadd}};
+        {"v_pk_fma_f32 (dependent chain)", k_pkfma}, {"v_pk_mul_f32 (dependent chain)", k_pkmul}, {"v_pk_add_f32 (dependent chain)", k_pkadd},
+        {"v_mul_f32 d = a * b, normal", k_mul_nn}, {"v_mul_f32 denormal result", k_mul_dres}, {"v_mul_f32 denormal input", k_mul_din},
+        {"v_fma_f32 d = a * b + c, normal", k_fma_nn}, {"v_fma_f32 denormal b, c, result", k_fma_den}};
     const long long n_ins = (long long)ITERS * 64;
     printf("%-30s %s\n", "instruction", "SIMD cycles per wave64 instruction at 1 / 2 / 4 / 8 waves per SIMD");
     for (auto& e : ks) {
         printf("%-30s", e.name);
+        long long bits = 0;
         for (int wps : {1, 2, 4, 8}) {
             const int blocks = cus * 4 * wps; /* single-wave workgroups: wps waves on every SIMD */
             hipMemset(d, 0, sizeof(long long) * (1 + blocks));
@@ -172,7 +204,10 @@ int main()
             for (int i = 0; i < blocks; i++) sum += (double)h[1 + i];
             /* a wave's span holds the instructions of the wps waves sharing its SIMD */
             printf(" %7.2f", sum / blocks / (double)(n_ins * wps));
+            bits = h[0];
         }
+        /* the denormal rows leave lane 0's result: zero there would mean the device flushed */
+        if (e.k == k_mul_dres || e.k == k_mul_din || e.k == k_fma_den) printf("   result bits 0x%08llx", bits);
         printf("\n");
     }
     hipFree(d);
