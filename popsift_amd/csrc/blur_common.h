@@ -3,14 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "wave_dev.h"
+
 namespace popsift_hip {
 
 constexpr int BLUR_TW = 128; /* tile / strip width (outputs) */
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 /* One axis of a CUDA linear-filter fetch at normalised coordinate r
  * (s_image.cu:140-169: normalised coords, clamp, linear, 1.8 fixed-point weight). */

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "devfeatures.h"
+#include "ext_list.h"
 #include "kernels.h"
 #include "sift_types.h"
 #include "trace.h"
@@ -1159,7 +1160,7 @@ int finish(popsift_hip_ctx* c)
             ori_max = std::max(ori_max, h.ori_total);
             for (int q = 0; q < DET_SUBQ; q++) qmax = std::max(qmax, h.qcnt[q].n);
             long ext_sum = 0; /* ext_total is written by the scan, which may have run on a clipped list: recount */
-            for (int o = 0; o < c->pd.n_oct; o++) ext_sum += std::min(h.ext_ct[o], c->sc.max_extrema);
+            for (int o = 0; o < c->pd.n_oct; o++) ext_sum += ext_count(&h, c->sc.max_extrema, o);
             ext_max = std::max(ext_max, ext_sum);
         }
         const bool desc_short = ori_max > c->desc_cap;

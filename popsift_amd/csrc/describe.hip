@@ -9,6 +9,7 @@
  *   k_frame_out    after the descriptor kernel: k_scan_apply's feature records moved to caller order (invalid frames get
  *                  their own record), the descriptor -> feature map rewritten to caller indices
  *
+ * The rank of a frame among its wave's frames of the same octave and the wave sums come from wave_dev.h.
  * No atomics decide a position: the lists, the descriptor order and every output byte are the same from run to run.
  * The counterpart of vl_sift(I, 'frames', F[, 'orientations']) and of OpenCV's SIFT::compute; the reference has none.
  */
@@ -18,6 +19,7 @@
 
 #include "kernels.h"
 #include "sift_types.h"
+#include "wave_dev.h"
 
 namespace popsift_hip {
 namespace {
@@ -52,13 +54,6 @@ __device__ __forceinline__ int resolve(const popsift_hip_frame& f, const PyrDesc
     ie.sigma = s;
     ie.cell = 0;
     return o;
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
 }
 
 constexpr int FW = FRAME_CHUNK / 64; /* waves per workgroup */
@@ -137,14 +132,10 @@ __global__ __launch_bounds__(FRAME_CHUNK) void k_frame_place(const PyrDesc* __re
     InitExt   ie;
     const int o = i < n ? resolve(frames[i], pdp, sc, given, ie) : -1;
     int       rank = 0;
-    for (unsigned long long todo = __ballot(o >= 0); todo;) {
-        const int                first = __ffsll((long long)todo) - 1;
-        const int                oo = __shfl(o, first);
-        const unsigned long long m = __ballot(o == oo);
+    wave_each_key(o, o >= 0, [&](int oo, unsigned long long m, int first) {
         if (o == oo) rank = __popcll(m & ((1ull << lane) - 1ull));
         if (lane == first) s_wc[wave][oo] = __popcll(m);
-        todo &= ~m;
-    }
+    });
     __syncthreads();
     if (chunk == 0 && (int)threadIdx.x < PS_MAX_OCT) ct->ext_ct[threadIdx.x] = (int)threadIdx.x < n_oct ? s_total[threadIdx.x] : 0;
     if (o >= 0) {

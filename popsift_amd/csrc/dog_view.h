@@ -4,9 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace popsift_hip {
+#include "wave_dev.h"
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+namespace popsift_hip {
 
 /* The float at byte offset `b` behind a wave-uniform `base`.  With an UNSIGNED 32-bit offset the load takes the
  * scalar-base + vector-offset form and costs no vector instruction; with a 64-bit offset every load pays a 64-bit

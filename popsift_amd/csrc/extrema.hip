@@ -11,7 +11,8 @@
  * a 64-bit __ballot into a per-wave LDS queue + one atomicAdd per strip into one
  * of 64 sub-queues (the reference's 32-bit lane masks are wrong on wave64, and a
  * single hot counter saturates), and the per-octave counter is clamped to
- * max_extrema by its consumers instead of by a "last block" epilogue.
+ * max_extrema by its consumers (ext_count, ext_list.h) instead of by a "last block" epilogue; k_refine's step scan and
+ * its per-octave append are wave_dev.h's wave_incl_scan and wave_each_key.
  * The refinement arithmetic follows the reference expression by expression
  * (compiled with -ffp-contract=off) so that, given identical DoG planes, the
  * accepted set and the (x, y, level) values equal the CPU oracle's bit for bit.
@@ -21,13 +22,10 @@
 #include "dog_view.h"
 #include "kernels.h"
 #include "sift_types.h"
+#include "wave_dev.h"
 
 namespace popsift_hip {
 namespace {
-
-
-/* a value every lane of the wave holds identically, moved to scalar registers */
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 /* s_solve.h:24-85 */
 __device__ __forceinline__ bool solve3(float i[3][3], float b[3])
@@ -564,14 +562,7 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
     const int      seg = cand_cap / DET_SUBQ;
     if (threadIdx.x < 64) {
         const int tot = min(ct->qcnt[lane].n, seg);
-        const int steps = (tot + 255) >> 8;
-        int       incl = steps;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int v = __shfl_up(incl, s);
-            if (lane >= s) incl += v;
-        }
-        s_pref[lane + 1] = incl;
+        s_pref[lane + 1] = wave_incl_scan((tot + 255) >> 8); /* steps */
         s_tot[lane] = tot;
         if (lane == 0) s_pref[0] = 0;
     } else if ((int)threadIdx.x - 64 < n_oct) {
@@ -614,18 +605,14 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
                 dog.nl = L - 1;
                 found = refine<MODE, FLY>(dog, sc, x, y, level, L - 1, ec);
             }
-            /* wave64 compaction per octave (replaces extrema_count, s_extrema.cu:22-44), wave -> workgroup in LDS */
-            unsigned long long todo = __ballot(found);
-            while (todo) {
-                const int                leader = __ffsll((long long)todo) - 1;
-                const int                lo = __shfl(o, leader);
-                const unsigned long long mask = __ballot(found && o == lo);
-                int                      wbase = 0;
+            /* wave64 compaction per octave (replaces extrema_count, s_extrema.cu:22-44), wave -> workgroup in LDS: one
+             * returning LDS atomic per octave of the wave, a survivor's rank is its place among the octave's lanes */
+            wave_each_key(o, found, [&](int lo, unsigned long long mask, int leader) {
+                int wbase = 0;
                 if (lane == leader) wbase = atomicAdd(&s_cnt[lo], __popcll(mask));
-                wbase = __shfl(wbase, leader);
+                wbase = __builtin_amdgcn_readlane(wbase, leader);
                 if (found && o == lo) slot = wbase + __popcll(mask & ((1ull << lane) - 1ull));
-                todo &= ~mask;
-            }
+            });
             __syncthreads();
             if ((int)threadIdx.x < n_oct && s_cnt[threadIdx.x] > 0)
                 s_base[threadIdx.x] = atomicAdd(&ct->ext_ct[threadIdx.x], s_cnt[threadIdx.x]);

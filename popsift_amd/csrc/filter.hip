@@ -22,13 +22,16 @@
  *   k_filter_commit  new per-octave counts replace the old ones
  * All launches are sized by capacities; the real counts stay in device memory (no host sync, the
  * reference blocks on readDescCountersFromDevice here).  When the 10 % test fails the same kernels run
- * with every limit = count, i.e. they copy the list unchanged.
+ * with every limit = count, i.e. they copy the list unchanged.  The list rules (count, prefix, flat index -> octave, chunk
+ * of an octave) come from ext_list.h, the scans and the per-key histogram add from wave_dev.h.
  *
  * Order: "original index" is the position in this build's per-octave lists (octave-major), which like
  * the reference's atomicAdd arrival order carries no meaning; RandomScale therefore agrees with the
  * reference (and the oracle) in the NUMBER kept per cell, the two scale orders agree in the members.
  */
+#include "ext_list.h"
 #include "kernels.h"
+#include "wave_dev.h"
 
 namespace popsift_hip {
 namespace {
@@ -38,11 +41,6 @@ constexpr int FILTER_KEY_BITS = 31 + FILTER_IDX_BITS; /* 56 = 7 digits of 8 bits
 constexpr int FILTER_PASSES = 7;
 constexpr int COMPACT_ITEMS = 8; /* candidates per lane in k_filter_compact */
 constexpr int COMPACT_CHUNK = 256 * COMPACT_ITEMS;
-
-__device__ __forceinline__ int oct_count(const Counters* ct, const SiftConsts& sc, int o)
-{
-    return min(ct->ext_ct[o], sc.max_extrema);
-}
 
 /* s_filtergrid.cu:56-70 FunctionExtractCell + the two comparators (:34-53), as one integer key whose
  * DEScending order is the reference's sorted order */
@@ -60,33 +58,9 @@ __device__ __forceinline__ unsigned long long filter_key(const InitExt& e, int o
 /* one atomicAdd per distinct `slot` value in the wave instead of one per lane */
 __device__ __forceinline__ void wave_agg_inc(int* base, int slot, bool active)
 {
-    unsigned long long todo = __ballot(active);
-    while (todo) {
-        const int                leader = __ffsll((long long)todo) - 1;
-        const int                s = __shfl(slot, leader);
-        const unsigned long long same = __ballot(active && slot == s) & todo;
+    wave_each_key(slot, active, [&](int s, unsigned long long same, int leader) {
         if ((int)(threadIdx.x & 63) == leader) atomicAdd(base + s, __popcll(same));
-        todo &= ~same;
-    }
-}
-
-/* flattened index g over the per-octave lists -> (octave, position) */
-struct Locator {
-    int ps[PS_MAX_OCT + 1];
-    int n_oct;
-};
-
-__device__ __forceinline__ void locator_init(int* s_ps, const Counters* ct, const SiftConsts& sc, int n_oct)
-{
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int o = 0; o < n_oct; o++) {
-            s_ps[o] = acc;
-            acc += oct_count(ct, sc, o);
-        }
-        s_ps[n_oct] = acc;
-    }
-    __syncthreads();
+    });
 }
 
 /* per-cell member counts: LDS histogram per workgroup (NC <= FILTER_MAX_CELLS ints), then one global atomic per
@@ -100,16 +74,14 @@ __global__ __launch_bounds__(256) void k_filter_count(int n_oct, SiftConsts sc, 
     __shared__ int s_hist[FILTER_MAX_CELLS];
     const int      ncell = sc.grid_size * sc.grid_size;
     for (int c = threadIdx.x; c < ncell; c += 256) s_hist[c] = 0;
-    locator_init(s_ps, ct, sc, n_oct); /* ends with a barrier */
-    const int total = s_ps[n_oct];
+    const int total = ext_prefix(s_ps, ct, sc.max_extrema, n_oct); /* ends with a barrier */
     const int span = gridDim.x * 256;
     for (int g0 = blockIdx.x * 256; g0 < total; g0 += span) {
         const int  g = g0 + threadIdx.x;
         const bool act = g < total;
         int        cell = 0;
         if (act) {
-            int o = 0;
-            while (o + 1 < n_oct && g >= s_ps[o + 1]) o++;
+            const int o = ext_octave(s_ps, n_oct, g);
             cell = iext[(size_t)o * sc.max_extrema + (g - s_ps[o])].cell;
             cell = min(max(cell, 0), ncell - 1);
         }
@@ -136,7 +108,7 @@ __global__ __launch_bounds__(256) void k_filter_limit(int n_oct, SiftConsts sc, 
 
     if (tid == 0) {
         int acc = 0;
-        for (int o = 0; o < n_oct; o++) acc += oct_count(ct, sc, o);
+        for (int o = 0; o < n_oct; o++) acc += ext_count(ct, sc.max_extrema, o);
         s_total = acc;
         s_ct = 0;
         /* s_orientation.cu:362: int(filter_max * 1.1) with the double constant */
@@ -212,8 +184,7 @@ __global__ __launch_bounds__(256) void k_filter_hist(int pass, int n_oct, SiftCo
     const FilterState* __restrict__ fs = bd.s[blockIdx.y].fstate;
     int* __restrict__               hist = bd.s[blockIdx.y].fhist;
     __shared__ int s_ps[PS_MAX_OCT + 1];
-    locator_init(s_ps, ct, sc, n_oct);
-    const int total = s_ps[n_oct];
+    const int total = ext_prefix(s_ps, ct, sc.max_extrema, n_oct);
     const int ncell = sc.grid_size * sc.grid_size;
     const int span = gridDim.x * 256;
     const int shift = FILTER_KEY_BITS - 8 * (pass + 1); /* position of this pass's digit */
@@ -222,8 +193,7 @@ __global__ __launch_bounds__(256) void k_filter_hist(int pass, int n_oct, SiftCo
         bool      act = g < total;
         int       slot = 0;
         if (act) {
-            int o = 0;
-            while (o + 1 < n_oct && g >= s_ps[o + 1]) o++;
+            const int     o = ext_octave(s_ps, n_oct, g);
             const InitExt e = iext[(size_t)o * sc.max_extrema + (g - s_ps[o])];
             const int     cell = min(max(e.cell, 0), ncell - 1);
             if (fs->cell_mode[cell] != 0) {
@@ -244,23 +214,15 @@ __global__ __launch_bounds__(256) void k_filter_pick(BatchDesc bd)
 {
     FilterState* __restrict__ fs = bd.s[blockIdx.y].fstate;
     int* __restrict__         hist = bd.s[blockIdx.y].fhist;
-    __shared__ int s_above[256];
+    __shared__ int s_wsum[4];
     const int      cell = blockIdx.x, d = threadIdx.x;
     const int      mine = hist[cell * 256 + d];
     hist[cell * 256 + d] = 0; /* ready for the next pass */
-    if (fs->cell_mode[cell] != 0) return;
-    s_above[d] = mine;
-    __syncthreads();
-    /* suffix sums: above[d] = number of candidates with a larger digit */
-    for (int s = 1; s < 256; s <<= 1) {
-        const int v = (d + s < 256) ? s_above[d + s] : 0;
-        __syncthreads();
-        s_above[d] += v;
-        __syncthreads();
-    }
-    const int incl = s_above[d], above = incl - mine;
-    const int rem = fs->remaining[cell];
-    __syncthreads();
+    if (fs->cell_mode[cell] != 0) return; /* whole workgroup */
+    const int rem = fs->remaining[cell]; /* read by all before the scan's barrier, rewritten by one lane after it */
+    /* suffix sums: above = number of candidates with a larger digit = all of them - those up to this digit */
+    const WgScan scan = wg_scan<4>(mine, s_wsum);
+    const int    incl = scan.total - scan.excl, above = incl - mine;
     if (above < rem && rem <= incl) { /* exactly one digit satisfies this */
         fs->prefix[cell] = (fs->prefix[cell] << 8) | (unsigned long long)d;
         fs->remaining[cell] = rem - above;
@@ -276,12 +238,11 @@ __global__ __launch_bounds__(256) void k_filter_compact(int chunks_per_oct, Sift
     __shared__ int s_ps[PS_MAX_OCT + 1];
     __shared__ int s_wsum[4];
     __shared__ int s_base;
-    locator_init(s_ps, ct, sc, n_oct);
-    const int o = blockIdx.x / chunks_per_oct, chunk = blockIdx.x % chunks_per_oct;
-    const int cnt = s_ps[o + 1] - s_ps[o];
-    const int i0 = chunk * COMPACT_CHUNK;
-    if (i0 >= cnt) return; /* whole workgroup */
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    ext_prefix(s_ps, ct, sc.max_extrema, n_oct);
+    ExtChunk c(chunks_per_oct, COMPACT_CHUNK);
+    if (!c.within(s_ps[c.o + 1] - s_ps[c.o])) return; /* whole workgroup */
+    const int o = c.o, i0 = c.i0, cnt = c.n;
+    const int tid = threadIdx.x;
     const int ncell = sc.grid_size * sc.grid_size;
 
     InitExt e[COMPACT_ITEMS];
@@ -299,19 +260,10 @@ __global__ __launch_bounds__(256) void k_filter_compact(int chunks_per_oct, Sift
         }
         self += keep[k] ? 1 : 0;
     }
-    int incl = self;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int v = __shfl_up(incl, s);
-        if (lane >= s) incl += v;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
+    const WgScan scan = wg_scan<4>(self, s_wsum);
+    if (tid == 0) s_base = atomicAdd(&fs->new_ct[o], scan.total);
     __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_wsum[w];
-    if (tid == 255) s_base = atomicAdd(&fs->new_ct[o], woff + incl);
-    __syncthreads();
-    int pos = s_base + woff + incl - self;
+    int pos = s_base + scan.excl;
 #pragma unroll
     for (int k = 0; k < COMPACT_ITEMS; k++)
         if (keep[k]) out[(size_t)o * sc.max_extrema + pos++] = e[k];

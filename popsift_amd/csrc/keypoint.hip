@@ -1,8 +1,9 @@
 /*
  * keypoint.hip -- orientation assignment, orientation prefix sum, the 128-D loop descriptor + normalisation, Feature
  * assembly: the kernels of every benchmark step.  The descriptors of the other DescModes (grid, notile / igrid,
- * iloop) are in desc_modes.hip, the device helpers both files use (wave sums, wave-uniform values, the work
- * distribution KP_CHUNK, atan2_acc) in keypoint_dev.h.  All kernels size themselves
+ * iloop) are in desc_modes.hip, the device helpers both files use (the float wave sum, the work distribution KP_CHUNK,
+ * atan2_acc) in keypoint_dev.h, the rules of the lists the kernels walk in ext_list.h, the wave and workgroup scans in
+ * wave_dev.h.  All kernels size themselves
  * from the device-resident counters (grid-stride), so the host never has to
  * read a count back between stages (the reference blocks on the counters twice
  * per image: s_orientation.cu:351, sift_desc.cu:60-61).
@@ -17,6 +18,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include "ext_list.h"
 #include "kernels.h"
 #include "keypoint_dev.h"
 #include "sift_types.h"
@@ -25,19 +27,6 @@ namespace popsift_hip {
 namespace {
 
 constexpr float ORI_WINFACTOR = 1.5f; /* sift_constants.h:22-29 */
-
-/* Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1, 2, 4, 8 inside the rows of 16, then row_bcast:15
- * and row_bcast:31 carry the row totals across), register to register -- no LDS round trips as with six shuffles. */
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true); /* row_shr:1, out-of-row lanes read 0 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false); /* row_bcast:15 into rows 1 and 3 */
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); /* row_bcast:31 into rows 2 and 3 */
-    return v;
-}
 
 /* The four gradient taps around plane element `off` (>= pitch + 1, so every tap is in the plane).  `layer` and
  * `pitch` are wave-uniform: with an UNSIGNED 32-bit byte offset the loads take the scalar-base + vector-offset
@@ -61,17 +50,6 @@ struct Taps {
 };
 
 /* ISA: end */
-/* clamped extrema counts -> exclusive prefix (uniform, <= 20 entries) */
-__device__ __forceinline__ int ext_prefix(const Counters* ct, const SiftConsts& sc, int n_oct, int* ps)
-{
-    int acc = 0;
-    for (int o = 0; o < n_oct; o++) {
-        ps[o] = acc;
-        acc += min(ct->ext_ct[o], sc.max_extrema);
-    }
-    ps[n_oct] = acc;
-    return acc;
-}
 
 /* ------------------------------------------------------------ orientation */
 
@@ -186,16 +164,12 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
     fix64*           hist = s_hist[wave][lane & (ORI_COPIES - 1)];
 
     __shared__ int ps[PS_MAX_OCT + 1];
-    if (threadIdx.x == 0) ext_prefix(ct, sc, n_oct, ps);
-    __syncthreads();
-    const int total = min(ps[n_oct], hist_cap);
+    const int total = min(ext_prefix(ps, ct, sc.max_extrema, n_oct), hist_cap);
 
     for (XcdSlice sl = xcd_slice<KP_NW>(); sl.more(total); sl.s += sl.step) {
         const int g = sl.index();
         if (g >= total) continue;
-        int o = 0;
-        while (o + 1 < n_oct && g >= ps[o + 1]) o++;
-        o = uniform(o); /* the octave record and the list entry are then fetched through the scalar cache */
+        const int o = uniform(ext_octave(ps, n_oct, g)); /* the octave record and the list entry are then fetched through the scalar cache */
         const InitExt  ie = iext[(size_t)o * sc.max_extrema + (g - uniform(ps[o]))];
         const OctDesc* od = &pdp->o[o];
         const int      w = uniform(od->w), h = uniform(od->h), pitch = uniform(od->pitch);
@@ -493,10 +467,8 @@ __global__ __launch_bounds__(SCAN_LT) void k_scan_local(const PyrDesc* __restric
     __shared__ int s_wsum[SCAN_LT / 64];
     __shared__ int s_ps[PS_MAX_OCT + 1];
     const int      n_oct = pdp->n_oct;
-    if (threadIdx.x == 0) ext_prefix(ct, sc, n_oct, s_ps);
-    __syncthreads();
-    const int total = s_ps[n_oct];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int total = ext_prefix(s_ps, ct, sc.max_extrema, n_oct);
+    const int tid = threadIdx.x;
     const int j = tid & 3;
     /* the launch is sized for the device, not for the capacity of the lists: workgroups stride over the chunks */
     for (int chunk = blockIdx.x; chunk * SCAN_LCHUNK < total; chunk += gridDim.x) {
@@ -505,8 +477,7 @@ __global__ __launch_bounds__(SCAN_LT) void k_scan_local(const PyrDesc* __restric
     const bool valid = g < total;
     const int  gc = min(g, total - 1); /* lanes beyond the list compute along (the quad exchanges need them) */
     /* the second half of ori_par for extremum g, then its Extremum record (sift_extremum.h:40-51) */
-    int o = 0;
-    while (o + 1 < n_oct && gc >= s_ps[o + 1]) o++;
+    const int     o = ext_octave(s_ps, n_oct, gc);
     const InitExt ie = iext[(size_t)o * sc.max_extrema + (gc - s_ps[o])];
     Ext           e;
     e.xpos = ie.xpos;
@@ -523,16 +494,12 @@ __global__ __launch_bounds__(SCAN_LT) void k_scan_local(const PyrDesc* __restric
         for (int q = 0; q < POPSIFT_HIP_ORI_MAX; q++) e.orientation[q] = 0.0f;
     const int self = (valid && j == 0) ? e.num_ori : 0;
 
-    const int incl = wave_incl_scan(self);
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_wsum[w];
+    const WgScan scan = wg_scan<SCAN_LT / 64>(self, s_wsum);
     if (valid && j == 0) {
-        e.idx_ori = woff + incl - self; /* chunk-local for now */
+        e.idx_ori = scan.excl; /* chunk-local for now */
         ext[g] = e;
     }
-    if (tid == SCAN_LT - 1) partial[chunk] = woff + incl;
+    if (tid == SCAN_LT - 1) partial[chunk] = scan.excl + self;
     __syncthreads(); /* s_wsum is reused by the next chunk */
     }
 }
@@ -551,16 +518,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
     __shared__ int s_ps[PS_MAX_OCT + 1];
     const int      n_oct = pdp->n_oct;
     const int      tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) {
-        int acc = 0;
-        for (int o = 0; o < PS_MAX_OCT; o++) {
-            s_ps[o] = acc;
-            acc += (o < n_oct) ? min(ct->ext_ct[o], sc.max_extrema) : 0;
-        }
-        s_ps[PS_MAX_OCT] = acc;
-    }
-    __syncthreads();
-    const int total = s_ps[PS_MAX_OCT];
+    const int total = ext_prefix(s_ps, ct, sc.max_extrema, n_oct);
     const int nb = (total + SCAN_CHUNK - 1) / SCAN_CHUNK;
     if (nb == 0 && blockIdx.x == 0 && tid == 0) { /* no extrema at all: the counters still have to be written */
         ct->ori_total = 0;
@@ -577,8 +535,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
     /* offset of this chunk = sum of the partials of all preceding chunks (SCAN_SUB local chunks per chunk here) */
     int acc = 0;
     for (int b = tid; b < chunk * SCAN_SUB; b += 256) acc += partial[b];
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) acc += __shfl_xor(acc, s);
+    acc = wave_sum(acc);
     if (lane == 0) s_red[wave] = acc;
     __syncthreads();
     const int chunk_offset = s_red[0] + s_red[1] + s_red[2] + s_red[3];
@@ -631,7 +588,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
         ct->ext_total = total;
         for (int o = 0; o < PS_MAX_OCT; o++) {
             /* the reference clamps with atomicMin in the extrema kernel, s_extrema.cu:558 */
-            ct->ext_ct[o] = (o < n_oct) ? min(ct->ext_ct[o], sc.max_extrema) : 0;
+            ct->ext_ct[o] = (o < n_oct) ? ext_count(ct, sc.max_extrema, o) : 0;
             ct->ext_ps[o] = s_ps[o];
         }
     }

@@ -1,10 +1,13 @@
 /*
  * keypoint_dev.h -- device helpers shared by the orientation / scan / loop-descriptor kernels (keypoint.hip) and the
- * other descriptor modes (desc_modes.hip): fixed-point histogram words, wave-wide sums, wave-uniform values, the
- * distribution of keypoints over workgroups (KP_CHUNK), the accurate arctangent.
+ * other descriptor modes (desc_modes.hip): fixed-point histogram words, the float sum over a wave, the distribution of
+ * keypoints over workgroups (KP_CHUNK), the accurate arctangent.  Wave-uniform values and the integer wave primitives
+ * are in wave_dev.h.
  */
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "wave_dev.h"
 
 namespace popsift_hip {
 
@@ -47,16 +50,6 @@ __device__ __forceinline__ float wave_allsum(float v)
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return (r0 + r1) + (r2 + r3);
-}
-
-/* a value every lane of the wave holds identically, moved to scalar registers */
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float uniformf(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ __forceinline__ long long uniform64(long long v)
-{
-    const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)(v & 0xffffffffll));
-    const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
 /* element `idx` >= 0 of a wave-uniform plane through an unsigned 32-bit byte offset (scalar base + vector offset) */

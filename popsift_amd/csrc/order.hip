@@ -4,7 +4,7 @@
  * the grid filter's tie-break) is a function of (image, params) alone.
  *
  * The lists arrive in the order in which k_refine's / k_filter_compact's workgroups won their returning atomics.  Per
- * (image, octave) list of n = min(ext_ct[o], max_extrema) records, ascending in the tuple
+ * (image, octave) list of n = ext_count() records (ext_list.h), ascending in the tuple
  *     ( iy, ix, lpos, bits(ypos), bits(xpos), bits(sigma) )
  * by a bucket pass and a ranking pass:
  *   k_order_clear    zero the row counters of every octave
@@ -25,13 +25,15 @@
  *
  * The row counters sit on thousands of addresses; the one-hot-counter limit of Counters (sift_types.h) does not bite.
  * All launches are sized by capacities (max_extrema), the counts are read on the device, nothing synchronises with the
- * host.  Scratch (one InitExt list and the row counters per slot) exists only in a context created with
- * feature_order = POPSIFT_HIP_ORDER_RASTER.
+ * host (the count and the chunk of an octave: ext_list.h; the row scan: wave_dev.h).  Scratch (one InitExt list and the
+ * row counters per slot) exists only in a context created with feature_order = POPSIFT_HIP_ORDER_RASTER.
  */
 #include <hip/hip_runtime.h>
 
+#include "ext_list.h"
 #include "kernels.h"
 #include "sift_types.h"
+#include "wave_dev.h"
 
 namespace popsift_hip {
 namespace {
@@ -70,11 +72,6 @@ __device__ __forceinline__ int order_row(const OrderArgs& a, int o, const InitEx
     return a.row_base[o] + min(order_pix(e.ypos) >> a.coarse, a.rows[o] - 1);
 }
 
-__device__ __forceinline__ int order_count(const Counters* ct, const OrderArgs& a, int o)
-{
-    return min(max(ct->ext_ct[o], 0), a.max_extrema);
-}
-
 __global__ __launch_bounds__(256) void k_order_clear(OrderArgs a, OrderBatch ob)
 {
     int* __restrict__ rows = ob.s[blockIdx.y].rows;
@@ -89,10 +86,9 @@ __global__ __launch_bounds__(256) void k_order_bucket(OrderArgs a, OrderBatch ob
     const InitExt* __restrict__  list = ob.s[blockIdx.y].list;
     InitExt* __restrict__        tmp = ob.s[blockIdx.y].tmp;
     int* __restrict__            rows = ob.s[blockIdx.y].rows;
-    const int o = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
-    const int n = order_count(ct, a, o);
-    const int i0 = chunk * ORDER_CHUNK;
-    if (i0 >= n) return;
+    ExtChunk c(a.chunks, ORDER_CHUNK);
+    if (!c.within(ext_count(ct, a.max_extrema, c.o))) return;
+    const int o = c.o, i0 = c.i0, n = c.n;
     const size_t base = (size_t)o * a.max_extrema;
 #pragma unroll
     for (int k = 0; k < ORDER_ITEMS; k++) {
@@ -115,24 +111,14 @@ __global__ __launch_bounds__(256) void k_order_scan(OrderArgs a, OrderBatch ob)
     int* __restrict__ rows = ob.s[blockIdx.y].rows + a.row_base[blockIdx.x];
     const int         nr = a.rows[blockIdx.x];
     __shared__ int    s_wsum[4];
-    const int         tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int         tid = threadIdx.x;
     int               carry = 0;
     for (int r0 = 0; r0 < nr; r0 += 256) { /* workgroup-uniform trip count */
         const int r = r0 + tid;
         const int mine = r < nr ? rows[r] : 0;
-        int       incl = mine;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int v = __shfl_up(incl, s);
-            if (lane >= s) incl += v;
-        }
-        if (lane == 63) s_wsum[wave] = incl;
-        __syncthreads();
-        int woff = 0;
-        for (int w = 0; w < wave; w++) woff += s_wsum[w];
-        const int total = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
-        if (r < nr) rows[r] = carry + woff + incl - mine;
-        carry += total;
+        const WgScan scan = wg_scan<4>(mine, s_wsum);
+        if (r < nr) rows[r] = carry + scan.excl;
+        carry += scan.total;
         __syncthreads(); /* s_wsum is rewritten by the next step */
     }
 }
@@ -144,10 +130,9 @@ __global__ __launch_bounds__(256) void k_order_place(OrderArgs a, OrderBatch ob)
     InitExt* __restrict__        list = ob.s[blockIdx.y].list;
     const InitExt* __restrict__  tmp = ob.s[blockIdx.y].tmp;
     const int* __restrict__      rows = ob.s[blockIdx.y].rows;
-    const int o = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
-    const int n = order_count(ct, a, o);
-    const int i0 = chunk * ORDER_CHUNK;
-    if (i0 >= n) return;
+    ExtChunk c(a.chunks, ORDER_CHUNK);
+    if (!c.within(ext_count(ct, a.max_extrema, c.o))) return;
+    const int o = c.o, i0 = c.i0, n = c.n;
     const size_t base = (size_t)o * a.max_extrema;
 #pragma unroll 1
     for (int k = 0; k < ORDER_ITEMS; k++) {

@@ -18,13 +18,16 @@
  * stays, so the surviving set depends on the records alone, not on their order.
  *
  * All launches are sized by capacities (max_extrema); the counts are read on the device, nothing synchronises with the
- * host.  The buffers exist only in a context on which the setting was ever on.
+ * host.  The buffers exist only in a context on which the setting was ever on.  The list rules (count, prefix, chunk of an
+ * octave) come from ext_list.h, the scans and the per-digit histogram add from wave_dev.h.
  */
 #include <hip/hip_runtime.h>
 
 #include "dog_view.h"
+#include "ext_list.h"
 #include "kernels.h"
 #include "sift_types.h"
+#include "wave_dev.h"
 
 namespace popsift_hip {
 namespace {
@@ -39,25 +42,6 @@ static_assert(STRONG_CHUNK == SELECT_LANES, "k_strongest_select counts one chunk
 /* the header's key: responses are >= 0 or NaN, so the bit pattern orders them */
 __device__ __forceinline__ unsigned int strong_key(float r) { return r != r ? 0u : __float_as_uint(r); }
 
-__device__ __forceinline__ int strong_count(const Counters* ct, const StrongArgs& a, int o)
-{
-    return min(max(ct->ext_ct[o], 0), a.max_extrema);
-}
-
-/* exclusive prefix of the per-octave counts, as filter.hip's Locator; ends with a barrier */
-__device__ __forceinline__ void strong_locate(int* s_ps, const Counters* ct, const StrongArgs& a)
-{
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int o = 0; o < a.n_oct; o++) {
-            s_ps[o] = acc;
-            acc += strong_count(ct, a, o);
-        }
-        s_ps[a.n_oct] = acc;
-    }
-    __syncthreads();
-}
-
 template <bool FLY>
 __global__ __launch_bounds__(256) void k_strongest_response(const PyrDesc* __restrict__ pdp, StrongArgs a, StrongBatch sb)
 {
@@ -65,11 +49,10 @@ __global__ __launch_bounds__(256) void k_strongest_response(const PyrDesc* __res
     const InitExt* __restrict__  in = sb.s[blockIdx.y].in;
     float* __restrict__          resp = sb.s[blockIdx.y].resp_in;
     __shared__ int s_ps[PS_MAX_OCT + 1];
-    strong_locate(s_ps, ct, a);
-    const int o = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
-    const int n = s_ps[o + 1] - s_ps[o];
-    const int i0 = chunk * STRONG_CHUNK;
-    if (i0 >= n) return;
+    ext_prefix(s_ps, ct, a.max_extrema, a.n_oct);
+    ExtChunk c(a.chunks, STRONG_CHUNK);
+    if (!c.within(s_ps[c.o + 1] - s_ps[c.o])) return;
+    const int o = c.o, i0 = c.i0, n = c.n;
     const OctDesc* od = &pdp->o[o];
     DogView<FLY>   dog;
     dog.arena = (const char*)sb.s[blockIdx.y].arena;
@@ -103,16 +86,14 @@ __global__ __launch_bounds__(256) void k_strongest_response(const PyrDesc* __res
  * almost every key of an image shares its digit (responses of one order of magnitude share their exponent) */
 __device__ __forceinline__ void select_count(int* hist, int digit, bool act)
 {
-    unsigned long long todo = __ballot(act);
-    const int          lane = threadIdx.x & 63;
-    for (int round = 0; round < 2 && todo; round++) {
-        const int                leader = __ffsll((long long)todo) - 1;
-        const int                d = __builtin_amdgcn_readlane(digit, leader); /* leader is wave-uniform */
-        const unsigned long long same = __ballot(act && digit == d) & todo;
-        if (lane == leader) atomicAdd(&hist[d], __popcll(same));
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) atomicAdd(&hist[digit], 1);
+    const int                lane = threadIdx.x & 63;
+    const unsigned long long left = wave_each_key(
+        digit, act,
+        [&](int d, unsigned long long same, int leader) {
+            if (lane == leader) atomicAdd(&hist[d], __popcll(same));
+        },
+        2);
+    if ((left >> lane) & 1ull) atomicAdd(&hist[digit], 1);
 }
 
 __global__ __launch_bounds__(SELECT_LANES) void k_strongest_select(StrongArgs a, StrongBatch sb)
@@ -126,8 +107,7 @@ __global__ __launch_bounds__(SELECT_LANES) void k_strongest_select(StrongArgs a,
     __shared__ int s_new_ct[PS_MAX_OCT];
     __shared__ int s_digit, s_above;
     const int      tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    strong_locate(s_ps, ct, a);
-    const int total = s_ps[a.n_oct];
+    const int total = ext_prefix(s_ps, ct, a.max_extrema, a.n_oct);
 
     /* t = the keep-th largest key: digit by digit from the top, among the keys that share the digits chosen so far.
      * Everything below is workgroup-uniform but the lanes' own keys, so every barrier is reached by all waves */
@@ -160,13 +140,8 @@ __global__ __launch_bounds__(SELECT_LANES) void k_strongest_select(StrongArgs a,
                 int c[4], sum = 0;
 #pragma unroll
                 for (int b = 0; b < 4; b++) sum += c[b] = s_hist[4 * lane + b];
-                int incl = sum;
-#pragma unroll
-                for (int s = 1; s < 64; s <<= 1) {
-                    const int v = __shfl_down(incl, s);
-                    if (lane + s < 64) incl += v;
-                }
-                int above = incl - sum;
+                const int incl = wave_incl_scan(sum);
+                int       above = wave_scan_total(incl) - incl; /* the lanes above = all - those up to this one */
 #pragma unroll
                 for (int b = 3; b >= 0; b--) {
                     if (above < rem && rem <= above + c[b]) { /* exactly one digit satisfies this */
@@ -187,8 +162,8 @@ __global__ __launch_bounds__(SELECT_LANES) void k_strongest_select(StrongArgs a,
         st->total = total;
     }
     if (tid < PS_MAX_OCT) {
-        st->old_ct[tid] = tid < a.n_oct ? s_ps[tid + 1] - s_ps[tid] : 0;
-        st->old_ps[tid] = tid < a.n_oct ? s_ps[tid] : total;
+        st->old_ct[tid] = s_ps[tid + 1] - s_ps[tid]; /* from n_oct upward every entry is the total: counts of 0 */
+        st->old_ps[tid] = s_ps[tid];
     }
     /* survivors per chunk, a chunk per wave (no barrier inside: the trip counts are wave-uniform) ... */
     for (int o = 0; o < a.n_oct; o++) {
@@ -214,14 +189,9 @@ __global__ __launch_bounds__(SELECT_LANES) void k_strongest_select(StrongArgs a,
         for (int c0 = 0; c0 < n_chunks; c0 += 64) {
             const int c = c0 + lane;
             const int mine = c < n_chunks ? chunk_off[o * a.chunks + c] : 0;
-            int       incl = mine;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const int v = __shfl_up(incl, s);
-                if (lane >= s) incl += v;
-            }
+            const int incl = wave_incl_scan(mine);
             if (c < n_chunks) chunk_off[o * a.chunks + c] = run + incl - mine;
-            run += __shfl(incl, 63);
+            run += wave_scan_total(incl);
         }
         if (lane == 0) s_new_ct[o] = run;
     }
@@ -248,14 +218,13 @@ __global__ __launch_bounds__(256) void k_strongest_compact(StrongArgs a, StrongB
     const StrongState* __restrict__ st = sb.s[blockIdx.y].state;
     const int* __restrict__         chunk_off = sb.s[blockIdx.y].chunk_off;
     __shared__ int s_wsum[4];
-    const int      o = blockIdx.x / a.chunks, chunk = blockIdx.x % a.chunks;
-    const int      tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    ExtChunk       c(a.chunks, STRONG_CHUNK);
+    const int      o = c.o, i0 = c.i0, tid = threadIdx.x;
     /* the counts of before the pass come from the state: ext_ct[o] is rewritten here, by the octave's first chunk, which
      * exists for every octave whatever its count */
-    const int n = st->old_ct[o];
-    if (chunk == 0 && tid == 0) ct->ext_ct[o] = st->new_ct[o];
-    const int i0 = chunk * STRONG_CHUNK;
-    if (i0 >= n) return; /* whole workgroup */
+    if (c.chunk == 0 && tid == 0) ct->ext_ct[o] = st->new_ct[o];
+    if (!c.within(st->old_ct[o])) return; /* whole workgroup */
+    const int n = c.n;
     const unsigned int t = st->t;
     const int          src = st->old_ps[o], dst = st->new_ps[o], new_n = st->new_ct[o];
 
@@ -274,17 +243,7 @@ __global__ __launch_bounds__(256) void k_strongest_compact(StrongArgs a, StrongB
         }
         self += keep[k] ? 1 : 0;
     }
-    int incl = self;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int v = __shfl_up(incl, s);
-        if (lane >= s) incl += v;
-    }
-    if (lane == 63) s_wsum[wave] = incl;
-    __syncthreads();
-    int woff = 0;
-    for (int w = 0; w < wave; w++) woff += s_wsum[w];
-    int pos = chunk_off[o * a.chunks + chunk] + woff + incl - self;
+    int pos = chunk_off[o * a.chunks + c.chunk] + wg_scan<4>(self, s_wsum).excl;
 #pragma unroll
     for (int k = 0; k < STRONG_ITEMS; k++)
         if (keep[k]) {

@@ -12,8 +12,9 @@ import os
 import numpy as np
 import pytest
 
+import order_rule as R
 from popsift_amd.synth import synth
-from util import bits, capped_parity, sorted_features
+from util import _feature_frame, _keys, bits, capped_parity, sorted_features
 
 pytestmark = pytest.mark.gpu
 
@@ -109,6 +110,58 @@ def test_grid_filter_over_a_binding_cap(oracle_mod, gpu_hip, sorting):
     capped_parity(full_ext, 300, ctx, 1.0, orc=orc, full_dev=full_dev, filtered=True)
     assert 0 < ctx.report().ext_total < sum(min(c, 300) for c in counts)
     ctx.close()
+
+
+def test_raster_order_over_a_binding_cap(oracle_mod, gpu_hip):
+    """The ordering pass on lists that the cap cut: its kernels size every octave's list by min(ext_ct[o], cap) while
+    ext_ct[o] itself still holds the uncapped count.  The survivors pass capped_parity (counts equal min(count, cap)), and
+    the extrema and the fetched feature records are in the order tests/order_rule.py defines for that survivor list."""
+    full_ext, counts, full_dev = uncapped(oracle_mod, gpu_hip, DENSE, "dense")
+    ctx = gpu_hip.Context(gpu_hip.default_params(max_extrema=300, feature_order=gpu_hip.ORDER_RASTER))
+    ctx.submit(DENSE)
+    orc = oracle_mod.Oracle(oracle_mod.default_params(max_extrema=300), threads=THREADS).run(DENSE, keypoints=False)
+    capped_parity(full_ext, 300, ctx, 1.0, orc=orc, full_dev=full_dev)
+    ext, (feats, _) = ctx.extrema(), ctx.fetch()
+    ctx.close()
+    assert len(ext) == sum(min(c, 300) for c in counts)
+    assert ext.tobytes() == R.sort(ext).tobytes()
+    o, x, y, s = _feature_frame(ext, 1.0)
+    assert _keys(feats["debug_octave"], feats["xpos"], feats["ypos"], feats["sigma"]) == _keys(o, x, y, s)
+
+
+def _ekeys(ext):
+    return _keys(ext["octave"], ext["lpos"].view(np.float32), ext["xpos"], ext["ypos"], ext["sigma"])
+
+
+def test_keep_strongest_over_a_binding_cap(oracle_mod, gpu_hip):
+    """The keep-strongest pass on lists that the cap cut (n = 200 of the sum of min(count, 300) = 657 records): which
+    records the cap leaves is arrival order, so the kept set is not reproducible, but every kept record is bit for bit an
+    extremum of the uncapped run, none twice, with the response an uncapped run that keeps everything hands out for it; at
+    least n are kept and fewer than n lie strictly above the smallest kept response (the header's tie rule, which needs no
+    sight of the dropped records); no octave keeps more than min(count, cap)."""
+    from collections import Counter
+    full_ext, counts, _ = uncapped(oracle_mod, gpu_hip, DENSE, "dense")
+    n, cap = 200, 300
+    assert n < sum(min(c, cap) for c in counts) == 657
+    every = gpu_hip.Context(gpu_hip.default_params()).set_keep_strongest(2 ** 31 - 1).submit(DENSE)
+    ext_all, resp_all = every.extrema(), every.fetch_responses()
+    every.close()
+    assert Counter(_ekeys(ext_all)) == Counter(_ekeys(full_ext)) and np.isfinite(resp_all).all()
+    want = dict(zip(_ekeys(ext_all), bits(resp_all).tolist()))     # records with equal keys are byte-identical
+
+    ctx = gpu_hip.Context(gpu_hip.default_params(max_extrema=cap)).set_keep_strongest(n).submit(DENSE)
+    ext, resp, rep = ctx.extrema(), ctx.fetch_responses(), ctx.report()
+    ctx.close()
+    keys = _ekeys(ext)
+    full_count = Counter(_ekeys(full_ext))
+    bad = [k for k, m in Counter(keys).items() if m > full_count.get(k, 0)]
+    assert not bad, "kept records that are not uncapped extrema (or are repeated): %s" % bad[:10]
+    assert bits(resp).tolist() == [want[k] for k in keys]
+    assert len(ext) == len(resp) >= n
+    assert int((resp > resp.min()).sum()) < n
+    kept = np.bincount(ext["octave"], minlength=len(counts))
+    assert len(kept) == len(counts) and all(kept[o] <= min(counts[o], cap) for o in range(len(counts))), kept
+    assert list(rep.ext_ct[:len(counts)]) == kept.tolist() and rep.ext_total == len(ext)
 
 
 def test_binding_cap_through_the_slow_detection_pass(oracle_mod, gpu_hip):
