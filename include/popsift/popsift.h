@@ -44,14 +44,15 @@ class SiftJob {
     int            _w;
     int            _h;
     unsigned char* _imageData; /* this job's copy of the image, in a recycled block of the pinned pool (features.h) */
+    unsigned char* _mask = nullptr; /* ... and of its mask (PopSift::enqueueMasked), behind the image in the same block */
     bool           _is_float;
     bool           _pinned = false;
 
 public:
-    /** byte image, values 0..255 */
-    SiftJob(int w, int h, const unsigned char* imageData);
+    /** byte image, values 0..255; extension: mask, w * h bytes tightly packed (non-zero = visible) or null, copied too */
+    SiftJob(int w, int h, const unsigned char* imageData, const unsigned char* mask = nullptr);
     /** float image, values [0..1[ */
-    SiftJob(int w, int h, const float* imageData);
+    SiftJob(int w, int h, const float* imageData, const unsigned char* mask = nullptr);
     ~SiftJob();
 
     popsift::FeaturesHost* get();  // same as getHost()
@@ -68,6 +69,8 @@ public:
     const unsigned char* getImageData() const { return _imageData; }
     /** extension: the job's image copy is page-locked (the worker then uploads it without a staging copy) */
     bool                 isPinned() const { return _pinned; }
+    /** extension: the job's copy of its mask (PopSift::enqueueMasked), null for an unmasked job */
+    const unsigned char* getMask() const { return _mask; }
 
     /** extension: a describe job (PopSift::enqueue with frames) and its frames, copied at enqueue */
     void setFrames(const std::vector<popsift::Frame>& frames, bool computeOrientation)
@@ -126,6 +129,13 @@ public:
                      bool computeOrientation = true);
     SiftJob* enqueue(int w, int h, const float* imageData, const std::vector<popsift::Frame>& frames,
                      bool computeOrientation = true);
+
+    /** Extension (OpenCV detectAndCompute(image, mask, ..)): only keypoints on visible pixels are extracted; the rule is
+     *  written down in popsift_hip.h (popsift_hip_submit_batch_masked).  mask: w * h bytes, tightly packed, non-zero =
+     *  visible, copied before the call returns; mask == nullptr behaves like enqueue.  With POPSIFT_BATCH > 1 a worker
+     *  batches masked and unmasked extraction jobs of one size and type together. */
+    SiftJob* enqueueMasked(int w, int h, const unsigned char* imageData, const unsigned char* mask);
+    SiftJob* enqueueMasked(int w, int h, const float* imageData, const unsigned char* mask);
 
     /** deprecated blocking interface */
     inline void uninit(int /*pipe*/) { uninit(); }

@@ -279,6 +279,57 @@ int popsift_hip_fetch_begin_item(popsift_hip_ctx* ctx, int k, popsift_hip_featur
                                  size_t desc_cap);
 
 /*
+ * Extraction masks: keep only the keypoints on visible pixels (OpenCV's detectAndCompute(image, mask, ..), the per-image
+ * masks of COLMAP and AliceVision).  The mask acts inside refinement (k_refine, extrema.hip), so a hidden keypoint costs no
+ * list slot, no orientation and no descriptor, and max_extrema, keep-strongest and the grid filter are spent on the visible
+ * area only.
+ *
+ * A mask is a w x h array of uint8_t, the size of the input image, with a row pitch of its own in bytes (mask_pitch >= w).
+ *
+ * For a refined record of octave o at (xpos, ypos) in octave units:
+ *
+ *     x  = xpos * 2^(o - up),  y = ypos * 2^(o - up)     up = (int)upscale_factor
+ *          -- the floats popsift_hip_feature reports for it, bit for bit
+ *          -- (keypoint.hip, prep_features; a power-of-two product is exact)
+ *     mx = (int)fminf(fmaxf(floorf(x + 0.5f), 0.0f), (float)(w - 1))
+ *     my = (int)fminf(fmaxf(floorf(y + 0.5f), 0.0f), (float)(h - 1))
+ *     visible = mask[my * mask_pitch + mx] != 0
+ *
+ * - This is OpenCV's KeyPointsFilter::runByPixelsMask rule, (int)(pt + 0.5f).
+ * - The clamp is done on floats, as strongest.hip does, so every input has a defined pixel.  NaN goes to 0 and +inf to the
+ *   last column or row.
+ * - A caller can recompute the rule from the feature record alone.
+ * - A record that is not visible is dropped inside refinement, before it takes a list slot.
+ * - Counters::ext_ct[o] counts visible records only.  The max_extrema cap is spent on visible records only.
+ * - A NULL mask for an image means every pixel is visible.
+ *
+ * Consequences:
+ * 1. With POPSIFT_HIP_ORDER_RASTER, and no octave's count of ALL refined records reaching the cap, a masked run's results
+ *    are byte for byte those of the unmasked run with the hidden records removed and desc_idx renumbered.  That covers
+ *    extrema, features, descriptors, byte descriptors, responses and report counts.  It is the statement
+ *    popsift_hip_set_keep_strongest makes below.
+ * 2. With a cap the unmasked run hits, the masked run still returns every visible record, as long as the visible count of
+ *    each octave stays below the cap.
+ * 3. An all-non-zero mask returns the unmasked bytes.
+ * 4. An all-zero mask returns 0 features and POPSIFT_HIP_OK.
+ *
+ * popsift_hip_submit_batch_masked: imgs, n, kind, w, h, pitch as in popsift_hip_submit_batch.  masks[k] lies where kind says
+ * image k lies: pageable host memory, copied before return; pinned host memory, valid until the wait returns; device memory
+ * of the context's GPU, valid until the wait returns.  Any masks[k] may be NULL.  ERR_INVALID, before any GPU call:
+ * masks == NULL (use popsift_hip_submit_batch), mask_pitch < w while any mask is non-null, and everything the plain submit
+ * refuses.  State rules and all result calls are those of popsift_hip_submit_batch.
+ *
+ * Each slot keeps its own device copy of the mask, w * h bytes packed to pitch w, grown on first use; the copies are made
+ * on the context's stream next to the image upload.  A context that never sees a mask allocates and launches nothing more,
+ * and a batch in which no image has a mask launches exactly what popsift_hip_submit_batch launches.
+ * popsift_hip_rerun_keypoint_stages and the grow-and-rerun paths of popsift_hip_wait apply the masks of the last submit
+ * again.  A later plain submit, or a popsift_hip_describe_batch, clears them.  Describe takes no mask: frames are the
+ * caller's own.  popsift_hip_plan_arena is unchanged.  Detection is not masked: a candidate can move during refinement.
+ */
+int popsift_hip_submit_batch_masked(popsift_hip_ctx* ctx, const void* const* imgs, const uint8_t* const* masks, int n, int kind,
+                                    int w, int h, int pitch, int mask_pitch);
+
+/*
  * Keep the n strongest keypoints of every image (OpenCV's nfeatures, KeyPointsFilter::retainBest) and hand out every
  * feature's strength (OpenCV's KeyPoint::response).  A setting of the context, off by default; the pass (strongest.hip)
  * runs on the GPU between refinement and orientation, so orientation and the descriptors see the thinned lists only.

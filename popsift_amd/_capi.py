@@ -159,6 +159,8 @@ SYMBOLS = [
     ("popsift_hip_submit_pinned_u8", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_pinned_f32", C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_submit_batch", C.c_int, [_vp, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("popsift_hip_submit_batch_masked", C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_describe_batch", C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int,
                                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("popsift_hip_wait_batch", C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -809,7 +811,10 @@ class Context:
         self._chk(get(self._h, f.ctypes.data, s.ctypes.data, g.ctypes.data, C.byref(n)), "get_gauss_table")
         return f, s, g
 
-    def submit(self, img):
+    def submit(self, img, mask=None):
+        """one host image; mask: a uint8 (H, W) array, non-zero = visible (popsift_hip_submit_batch_masked), or None"""
+        if mask is not None:
+            return self.submit_batch([img], [mask])
         img = np.ascontiguousarray(img)
         if img.ndim != 2:
             raise ValueError("grayscale (H, W) image expected")
@@ -834,9 +839,12 @@ class Context:
         self._chk(fn(self._h, ptr, w, h, pitch), "popsift_hip_submit_dev")
         return self
 
-    def submit_batch(self, imgs):
-        """popsift_hip_submit_batch: several host images of one size and dtype, extracted together"""
+    def submit_batch(self, imgs, masks=None):
+        """popsift_hip_submit_batch: several host images of one size and dtype, extracted together.  masks: a list with a
+        uint8 (H, W) array (non-zero = visible) or None per image (popsift_hip_submit_batch_masked)"""
         imgs = [np.ascontiguousarray(im) for im in imgs]
+        if any(im.ndim != 2 for im in imgs):
+            raise ValueError("grayscale (H, W) images expected")
         h, w = imgs[0].shape
         if any(im.shape != (h, w) or im.dtype != imgs[0].dtype for im in imgs):
             raise ValueError("the images of a batch share one size and dtype")
@@ -847,14 +855,33 @@ class Context:
         else:
             raise TypeError("uint8 or float32 images expected, got %s" % imgs[0].dtype)
         arr = (C.c_void_p * len(imgs))(*[im.ctypes.data for im in imgs])
-        self._chk(lib().popsift_hip_submit_batch(self._h, arr, len(imgs), kind, w, h, w), "popsift_hip_submit_batch")
+        if masks is None:
+            self._chk(lib().popsift_hip_submit_batch(self._h, arr, len(imgs), kind, w, h, w), "popsift_hip_submit_batch")
+            return self
+        if len(masks) != len(imgs):
+            raise ValueError("one mask (or None) per image")
+        masks = [None if m is None else np.ascontiguousarray(m) for m in masks]
+        if any(m is not None and (m.shape != (h, w) or m.dtype != np.uint8) for m in masks):
+            raise ValueError("a mask is a uint8 array of the image's size")
+        marr = (C.c_void_p * len(imgs))(*[None if m is None else m.ctypes.data for m in masks])
+        self._chk(lib().popsift_hip_submit_batch_masked(self._h, arr, marr, len(imgs), kind, w, h, w, w),
+                  "popsift_hip_submit_batch_masked")
         return self
 
-    def submit_batch_dev(self, ptrs, w, h, pitch, is_f32=False):
-        """the same for images resident in this device's memory (ptrs: device addresses)"""
+    def submit_batch_dev(self, ptrs, w, h, pitch, is_f32=False, masks=None, mask_pitch=None):
+        """the same for images resident in this device's memory (ptrs: device addresses); masks: device addresses of the
+        masks (or None entries) with rows mask_pitch bytes apart (default w)"""
         arr = (C.c_void_p * len(ptrs))(*ptrs)
-        self._chk(lib().popsift_hip_submit_batch(self._h, arr, len(ptrs), IMG_DEV_F32 if is_f32 else IMG_DEV_U8, w, h, pitch),
-                  "popsift_hip_submit_batch")
+        kind = IMG_DEV_F32 if is_f32 else IMG_DEV_U8
+        if masks is None:
+            self._chk(lib().popsift_hip_submit_batch(self._h, arr, len(ptrs), kind, w, h, pitch), "popsift_hip_submit_batch")
+            return self
+        if len(masks) != len(ptrs):
+            raise ValueError("one mask (or None) per image")
+        marr = (C.c_void_p * len(ptrs))(*masks)
+        self._chk(lib().popsift_hip_submit_batch_masked(self._h, arr, marr, len(ptrs), kind, w, h, pitch,
+                                                         w if mask_pitch is None else mask_pitch),
+                  "popsift_hip_submit_batch_masked")
         return self
 
     def describe_batch_async(self, imgs, frame_lists, orientation="compute"):

@@ -119,6 +119,11 @@ struct ImageSlot {
     DevBuf<int>                 fcounts, perm, inv;
     DevBuf<popsift_hip_feature> lfeats;
     int n_frames = 0; /* frames of the described image */
+    /* extraction masks (popsift_hip_submit_batch_masked) only, grown on the first mask this slot sees: the packed w x h
+     * device copy k_refine reads and the pinned staging of a pageable mask */
+    DevBuf<uint8_t> mask;
+    void*           h_mask = nullptr;
+    size_t          h_mask_cap = 0;
 
     /* the descriptor group's capacity: 0 after a failed grow of any of its buffers */
     size_t desc_cap() const { return std::min({desc.cap, map.cap, rot.cap, drec.cap}); }
@@ -128,8 +133,9 @@ struct ImageSlot {
     {
         auto each = [](auto&... b) { ((void)b.release(), ...); };
         each(input, arena, iext, iext2, fstate, fhist, otmp, orows, sresp_in, sresp, sstate, schunk, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
-             alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats);
+             alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats, mask);
         if (h_input) (void)hipHostFree(h_input);
+        if (h_mask) (void)hipHostFree(h_mask);
         if (h_frames) (void)hipHostFree(h_frames);
     }
 };
@@ -159,6 +165,8 @@ struct popsift_hip_ctx {
     bool describe = false;  /* the batch in the context is a describe (popsift_hip_describe_batch), not an extraction */
     int  ori_given = 0;     /* ... with POPSIFT_HIP_ORI_GIVEN */
     int  frames_max = 0;    /* ... and the most frames of one of its images */
+    bool masked = false;    /* an image of the batch in the context has a mask (popsift_hip_submit_batch_masked): re-runs apply */
+    MaskArgs ma{};          /* ... these again; a plain submit or a describe clears them */
 
     /* one slot per image of a batch; a plain submit uses slot 0 */
     ImageSlot slot[PS_MAX_BATCH];
@@ -978,7 +986,7 @@ int enqueue_keypoint_stages(popsift_hip_ctx* c, bool counters_cleared = false)
     if (!counters_cleared) HIP_TRY(c, hipMemsetAsync(c->d_ct, 0, sizeof(Counters) * (size_t)c->nb, c->stream));
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DETECT)); /* = end of the pyramid stage */
     HIP_TRY(c, launch_extrema(c->pd, c->d_pd, c->bd, c->nb, c->sc, c->cand_cap, filtered, c->stream,
-                              stages ? c->ev_stage[POPSIFT_HIP_STAGE_REFINE] : nullptr));
+                              stages ? c->ev_stage[POPSIFT_HIP_STAGE_REFINE] : nullptr, c->masked ? &c->ma : nullptr));
     SYNC_CHK(c, "k_detect / k_refine");
     const bool raster = c->p.feature_order == POPSIFT_HIP_ORDER_RASTER;
     if (raster) {
@@ -1055,9 +1063,54 @@ int prepare_frames(popsift_hip_ctx* c, ImageSlot& s)
     return 0;
 }
 
+/* the masks of an extraction (popsift_hip_submit_batch_masked), lying where the images lie; null for a plain submit */
+struct MaskSubmit {
+    const uint8_t* const* masks;
+    int                   pitch; /* bytes */
+};
+
+/* The masks of the batch into their slots, packed to pitch w, on the context's stream next to the image upload and by the
+ * same route as the images: a pageable mask through pinned staging (copied before submit returns), a pinned or device
+ * mask from where it lies.  A batch without a mask leaves the context unmasked and touches nothing. */
+int upload_masks(popsift_hip_ctx* c, const MaskSubmit& ms, int nb, int where, int w, int h)
+{
+    const size_t bytes = (size_t)w * h;
+    MaskArgs     ma{};
+    bool         any = false;
+    for (int k = 0; k < nb; k++) {
+        const uint8_t* src = ms.masks[k];
+        if (!src) continue;
+        ImageSlot& s = c->slot[k];
+        if (int rc = grow(c, s.mask, bytes)) return rc;
+        if (where == 0) {
+            if (bytes > s.h_mask_cap) {
+                if (s.h_mask) HIP_TRY(c, hipHostFree(s.h_mask));
+                s.h_mask = nullptr;
+                s.h_mask_cap = 0;
+                HIP_TRY(c, hipHostMalloc(&s.h_mask, bytes, hipHostMallocDefault));
+                s.h_mask_cap = bytes;
+            }
+            for (int y = 0; y < h; y++) memcpy((char*)s.h_mask + (size_t)y * w, src + (size_t)y * ms.pitch, (size_t)w);
+            HIP_TRY(c, hipMemcpyAsync(s.mask.p, s.h_mask, bytes, hipMemcpyHostToDevice, c->stream));
+        } else {
+            HIP_TRY(c, hipMemcpy2DAsync(s.mask.p, (size_t)w, src, (size_t)ms.pitch, (size_t)w, (size_t)h,
+                                        where == 1 ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        }
+        ma.m[k] = s.mask.p;
+        any = true;
+    }
+    ma.w = w;
+    ma.h = h;
+    ma.pitch = w;
+    ma.up = c->sc.up_fac_int;
+    c->ma = ma;
+    c->masked = any;
+    return 0;
+}
+
 /* where the images of a batch lie: kind = POPSIFT_HIP_IMG_* */
 int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind, int w, int h, int pitch,
-                  const DescribeArgs* da = nullptr)
+                  const DescribeArgs* da = nullptr, const MaskSubmit* ms = nullptr)
 {
     if (!c) return POPSIFT_HIP_ERR_INVALID;
     POPSIFT_RANGE("popsift_hip: submit");
@@ -1065,6 +1118,8 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
         return fail(c, POPSIFT_HIP_ERR_INVALID, "bad image arguments");
     for (int k = 0; k < nb; k++)
         if (!imgs[k]) return fail(c, POPSIFT_HIP_ERR_INVALID, "bad image arguments");
+    for (int k = 0; k < nb && ms; k++)
+        if (ms->masks[k] && ms->pitch < w) return fail(c, POPSIFT_HIP_ERR_INVALID, "mask_pitch %d below the width %d", ms->pitch, w);
     const int is_f32 = kind & 1, where = kind >> 1; /* 0 host, 1 device, 2 pinned host */
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->have_image && !c->finished) {
@@ -1076,6 +1131,7 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
      * wait / fetch with the previous batch's counts for slots whose kernels never ran */
     c->batch_ok = false;
     c->finished = false;
+    c->masked = false; /* a plain submit and a describe clear the masks of the submit before */
     if (int rc = prepare_geometry(c, w, h, nb)) return rc;
     c->nb = nb;
     refresh_caps(c);
@@ -1114,6 +1170,8 @@ int submit_common(popsift_hip_ctx* c, const void* const* imgs, int nb, int kind,
         dpitch = w;
     }
     if (where != 1) aligned4 = (dpitch & 3) == 0; /* hipMalloc'd buffers are aligned */
+    if (ms)
+        if (int rc = upload_masks(c, *ms, nb, where, w, h)) return rc;
     c->describe = da != nullptr;
     c->ori_given = da && da->ori_mode == POPSIFT_HIP_ORI_GIVEN;
     c->frames_max = 0;
@@ -1647,6 +1705,15 @@ int popsift_hip_submit_dev_f32(popsift_hip_ctx* c, const void* d_img, int w, int
 int popsift_hip_submit_batch(popsift_hip_ctx* c, const void* const* imgs, int n, int kind, int w, int h, int pitch)
 {
     return submit_common(c, imgs, n, kind, w, h, pitch);
+}
+
+int popsift_hip_submit_batch_masked(popsift_hip_ctx* c, const void* const* imgs, const uint8_t* const* masks, int n, int kind,
+                                    int w, int h, int pitch, int mask_pitch)
+{
+    if (!c) return POPSIFT_HIP_ERR_INVALID;
+    if (!masks) return fail(c, POPSIFT_HIP_ERR_INVALID, "null mask list: use popsift_hip_submit_batch");
+    const MaskSubmit ms{masks, mask_pitch};
+    return submit_common(c, imgs, n, kind, w, h, pitch, nullptr, &ms);
 }
 
 int popsift_hip_describe_batch(popsift_hip_ctx* c, const void* const* imgs, const popsift_hip_frame* const* frames,

@@ -535,14 +535,20 @@ __global__ __launch_bounds__(256) void k_detect(const PyrDesc* __restrict__ pdp,
     }
 }
 
+__device__ __forceinline__ const MaskArgs& only(const MaskArgs& ma) { return ma; }
+
 /*
  * Refinement of the candidates: one lane per candidate in dense waves.  Survivors are appended
  * to their octave's list with ONE returning global atomic per workgroup, octave and step (LDS counters
  * gather the four waves first) -- the same hot-counter limit as in the detection kernel.
  */
-template <int MODE, bool FLY>
-__global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc, int cand_cap)
+/* MASK: nothing, or one MaskArgs (popsift_hip_submit_batch_masked) -- the masked instantiation, launched only for a batch in
+ * which an image has a mask.  It drops a refined record that lies on a hidden pixel (mask_visible, sift_types.h) before the
+ * record is counted anywhere, at the price of one more dependent round trip, a byte load per refined survivor. */
+template <int MODE, bool FLY, class... MASK>
+__global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc, int cand_cap, MASK... mask)
 {
+    static_assert(sizeof...(MASK) <= 1, "no mask, or one MaskArgs");
     const float* __restrict__ arena = bd.s[blockIdx.y].arena;
     Counters* __restrict__    ct = bd.s[blockIdx.y].ct;
     const int2* __restrict__  cand = bd.s[blockIdx.y].cand;
@@ -604,6 +610,12 @@ __global__ __launch_bounds__(256) void k_refine(const PyrDesc* __restrict__ pdp,
                 dog.pitch = s_pitch[o];
                 dog.nl = L - 1;
                 found = refine<MODE, FLY>(dog, sc, x, y, level, L - 1, ec);
+                if constexpr (sizeof...(MASK) == 1) {
+                    /* the slot's mask pointer is wave-uniform; a hidden record takes part in neither the LDS counts nor
+                     * the global atomicAdd below */
+                    const MaskArgs& ma = only(mask...);
+                    if (found) found = mask_visible(ma.m[blockIdx.y], ma.w, ma.h, ma.pitch, ma.up, o, ec.xpos, ec.ypos);
+                }
             }
             /* wave64 compaction per octave (replaces extrema_count, s_extrema.cu:22-44), wave -> workgroup in LDS: one
              * returning LDS atomic per octave of the wave, a survivor's rank is its place among the octave's lanes */
@@ -655,39 +667,48 @@ static void launch_detect(const PyrDesc& pd, const PyrDesc* d_pd, const BatchDes
     }
 }
 
+/* ma: the masks of the batch, or null: then exactly the unmasked instantiation is launched */
+template <int MODE>
+static void launch_refine(const PyrDesc& pd, const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int cand_cap,
+                          const MaskArgs* ma, hipStream_t s)
+{
+    const dim3 block(256), rgrid(1024, nb);
+    if (ma) {
+        if (pd.dog_fly)
+            hipLaunchKernelGGL((k_refine<MODE, true, MaskArgs>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap, *ma);
+        else
+            hipLaunchKernelGGL((k_refine<MODE, false, MaskArgs>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap, *ma);
+    } else {
+        if (pd.dog_fly)
+            hipLaunchKernelGGL((k_refine<MODE, true>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
+        else
+            hipLaunchKernelGGL((k_refine<MODE, false>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
+    }
+}
+
 hipError_t launch_extrema(const PyrDesc& pd, const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int cand_cap,
-                          bool /*filtered*/, hipStream_t s, hipEvent_t mid)
+                          bool /*filtered*/, hipStream_t s, hipEvent_t mid, const MaskArgs* ma)
 {
     if (pd.total_tiles <= 0) {
         if (mid) (void)hipEventRecord(mid, s); /* the stage boundary exists even when there is nothing to detect */
         return hipSuccess;
     }
     if (pd.levels < 2 || pd.levels > 9) return hipErrorInvalidValue;
-    const dim3 block(256), rgrid(1024, nb);
     switch (sc.sift_mode) {
     case POPSIFT_HIP_SIFT_OPENCV:
         launch_detect<POPSIFT_HIP_SIFT_OPENCV>(pd, d_pd, bd, nb, sc, cand_cap, s);
         if (mid) (void)hipEventRecord(mid, s);
-        if (pd.dog_fly)
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_OPENCV, true>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
-        else
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_OPENCV, false>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
+        launch_refine<POPSIFT_HIP_SIFT_OPENCV>(pd, d_pd, bd, nb, sc, cand_cap, ma, s);
         break;
     case POPSIFT_HIP_SIFT_VLFEAT:
         launch_detect<POPSIFT_HIP_SIFT_VLFEAT>(pd, d_pd, bd, nb, sc, cand_cap, s);
         if (mid) (void)hipEventRecord(mid, s);
-        if (pd.dog_fly)
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_VLFEAT, true>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
-        else
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_VLFEAT, false>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
+        launch_refine<POPSIFT_HIP_SIFT_VLFEAT>(pd, d_pd, bd, nb, sc, cand_cap, ma, s);
         break;
     default:
         launch_detect<POPSIFT_HIP_SIFT_POPSIFT>(pd, d_pd, bd, nb, sc, cand_cap, s);
         if (mid) (void)hipEventRecord(mid, s);
-        if (pd.dog_fly)
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_POPSIFT, true>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
-        else
-            hipLaunchKernelGGL((k_refine<POPSIFT_HIP_SIFT_POPSIFT, false>), rgrid, block, 0, s, d_pd, bd, sc, cand_cap);
+        launch_refine<POPSIFT_HIP_SIFT_POPSIFT>(pd, d_pd, bd, nb, sc, cand_cap, ma, s);
         break;
     }
     return hipGetLastError();

@@ -109,9 +109,10 @@ int        scale_tile_h(); /* rows of the tiles of the three launches above */
 hipError_t launch_dog_plane(float* dog, const float* upper, const float* lower, size_t n, hipStream_t s); /* debug / test downloads */
 int        extrema_units(int w, int h); /* wave-sized work units of the detection kernel */
 /* Every launcher below takes the slot table `bd` (passed to the kernels by value) and the number of images nb = gridDim.y. */
-/* mid: event recorded between detection and refinement (stage timing), or null */
+/* mid: event recorded between detection and refinement (stage timing), or null; ma: the masks of the batch
+ * (popsift_hip_submit_batch_masked), or null when no image has one */
 hipError_t launch_extrema(const PyrDesc& pd, const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int cand_cap,
-                          bool filtered, hipStream_t s, hipEvent_t mid);
+                          bool filtered, hipStream_t s, hipEvent_t mid, const MaskArgs* ma);
 
 /* keypoint.hip */
 /* ohist: 36 floats per extremum (the raw orientation histogram), hist_cap extrema */

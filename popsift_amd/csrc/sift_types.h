@@ -217,6 +217,28 @@ struct StrongArgs {
     int levels; /* DoG search levels */
 };
 
+/* Extraction masks (popsift_hip_submit_batch_masked).  A kernel argument of its own, handed to the masked instantiation of
+ * k_refine only, so that BatchDesc and the argument block of every other launch keep their size: each slot's packed device
+ * copy of its mask (null: every pixel of that image is visible), the size of the input image, the row pitch of the copies
+ * in bytes and up = (int)upscale_factor. */
+struct MaskArgs {
+    const uint8_t* m[PS_MAX_BATCH];
+    int            w, h, pitch, up;
+};
+
+/* The mask rule of popsift_hip.h, the one text of it: is the refined record (xpos, ypos in octave units) of octave o on a
+ * visible pixel?  x and y are the floats popsift_hip_feature reports (k_scan_apply multiplies by the same power of two,
+ * which is exact); the clamp is done on floats so that every input has a pixel (fmaxf drops a NaN: pixel 0). */
+__host__ __device__ inline bool mask_visible(const uint8_t* mask, int w, int h, int mask_pitch, int up, int o, float xpos, float ypos)
+{
+    if (!mask) return true;
+    const float scl = ldexpf(1.0f, o - up);
+    const float x = xpos * scl, y = ypos * scl;
+    const int   mx = (int)fminf(fmaxf(floorf(x + 0.5f), 0.0f), (float)(w - 1));
+    const int   my = (int)fminf(fmaxf(floorf(y + 0.5f), 0.0f), (float)(h - 1));
+    return mask[(size_t)my * (size_t)mask_pitch + (size_t)mx] != 0;
+}
+
 struct OrderArgs {
     int n_oct, coarse, max_extrema;
     int chunks;     /* workgroups per octave = ceil(max_extrema / POPSIFT_HIP_ORDER_CHUNK) */

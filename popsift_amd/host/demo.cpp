@@ -43,6 +43,7 @@ static bool   pgmread_loading = false;
 static bool   float_mode = false;
 static string output_file = "output-features.txt";
 static string responses_file = ""; /* --write-responses */
+static string mask_file = "";      /* --mask */
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& inputFile)
 {
@@ -151,6 +152,11 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& in
         "With --keep-strongest: write every feature's response to this file, one %.9g per line, in feature order",
         [&](const string& s) { responses_file = s; });
 
+    val("mask", 0, "Extensions",
+        "Binary PGM (P5, maxval 255) of each input's size: keypoints are extracted on its non-zero pixels only, the hidden\n"
+        "ones dropped on the GPU before orientation.  Applied to every input image",
+        [&](const string& s) { mask_file = s; });
+
     opts.parse(argc, argv);
     if (!responses_file.empty() && config.getKeepStrongest() <= 0)
         opts.error("option '--write-responses' needs '--keep-strongest'");
@@ -167,19 +173,38 @@ static void collectFilenames(list<string>& inputFiles, const filesystem::path& i
     }
 }
 
-static SiftJob* process_image(const string& inputFile, PopSift& sift)
+/* --mask: the file is a P5 of maxval 255, read by the demo's own reader; null after a message otherwise */
+static unsigned char* read_mask(const string& file, int& w, int& h)
+{
+    char          head[2] = {0, 0};
+    std::ifstream in(file.c_str(), std::ios::binary);
+    if (!in.read(head, 2) || head[0] != 'P' || head[1] != '5') {
+        cerr << "--mask: " << file << " is not a readable binary PGM (P5)" << endl;
+        return 0;
+    }
+    in.close();
+    return readPGMfile(file, w, h);
+}
+
+/* mask: w * h bytes or null (enqueueMasked then behaves like enqueue) */
+static SiftJob* process_image(const string& inputFile, PopSift& sift, const unsigned char* mask, int mask_w, int mask_h)
 {
     /* main.cpp:168-247, pgmread branch */
     int            w, h;
     unsigned char* image_data = readPGMfile(inputFile, w, h);
     if (image_data == 0) exit(-1);
+    if (mask && (w != mask_w || h != mask_h)) {
+        /* main() has checked every input before the first extraction: the file changed in between */
+        cerr << "--mask: " << inputFile << " is " << w << " x " << h << ", the mask " << mask_w << " x " << mask_h << endl;
+        exit(-1);
+    }
     SiftJob* job;
     if (!float_mode) {
-        job = sift.enqueue(w, h, image_data);
+        job = sift.enqueueMasked(w, h, image_data, mask);
     } else {
         float* f_image_data = new float[(size_t)w * h];
         for (size_t i = 0; i < (size_t)w * h; i++) f_image_data[i] = float(image_data[i]) / 256.0f;
-        job = sift.enqueue(w, h, f_image_data);
+        job = sift.enqueueMasked(w, h, f_image_data, mask);
         delete[] f_image_data;
     }
     delete[] image_data;
@@ -235,6 +260,24 @@ int main(int argc, char** argv)
         }
     }
 
+    /* --mask: an unreadable mask or an input of another size ends the run before any extraction */
+    unsigned char* mask = 0;
+    int            mask_w = 0, mask_h = 0;
+    if (!mask_file.empty()) {
+        mask = read_mask(mask_file, mask_w, mask_h);
+        if (mask == 0) exit(-1);
+        for (const string& name : inputFiles) {
+            int            w, h;
+            unsigned char* img = readPGMfile(name, w, h);
+            if (img == 0) exit(-1);
+            delete[] img;
+            if (w != mask_w || h != mask_h) {
+                cerr << "--mask: " << name << " is " << w << " x " << h << ", the mask " << mask_w << " x " << mask_h << endl;
+                exit(-1);
+            }
+        }
+    }
+
     popsift::cuda::device_prop_t deviceInfo;
     deviceInfo.set(0, print_dev_info);
     if (print_dev_info) deviceInfo.print();
@@ -243,7 +286,8 @@ int main(int argc, char** argv)
 
     const auto           t0 = chrono::steady_clock::now();
     std::queue<SiftJob*> jobs;
-    for (const string& name : inputFiles) jobs.push(process_image(name, sift));
+    for (const string& name : inputFiles) jobs.push(process_image(name, sift, mask, mask_w, mask_h));
+    delete[] mask; /* every job holds its own copy */
 
     while (!jobs.empty()) {
         SiftJob* job = jobs.front();

@@ -217,20 +217,30 @@ int contexts_per_device()
 /* The job's copy of the caller's image (the caller may free or reuse its buffer as soon as enqueue() returns,
  * popsift.cpp:245-247) goes into a recycled block of the pinned pool: no malloc -- a 2 MB malloc is an mmap and 512 page
  * faults every time -- and no second copy, the worker uploads straight from the block (popsift_hip_submit_pinned_*). */
-SiftJob::SiftJob(int w, int h, const unsigned char* imageData) : _w(w), _h(h), _is_float(false)
+SiftJob::SiftJob(int w, int h, const unsigned char* imageData, const unsigned char* mask) : _w(w), _h(h), _is_float(false)
 {
     _f = _p.get_future();
-    _imageData = (unsigned char*)popsift::pinnedBlockGet((size_t)w * h, &_pinned);
+    const size_t bytes = (size_t)w * h;
+    _imageData = (unsigned char*)popsift::pinnedBlockGet(bytes + (mask ? bytes : 0), &_pinned);
     if (_imageData == 0) DIE("Memory limitation: failed to allocate memory for SiftJob");
-    memcpy(_imageData, imageData, (size_t)w * h);
+    memcpy(_imageData, imageData, bytes);
+    if (mask) {
+        _mask = _imageData + bytes;
+        memcpy(_mask, mask, bytes);
+    }
 }
 
-SiftJob::SiftJob(int w, int h, const float* imageData) : _w(w), _h(h), _is_float(true)
+SiftJob::SiftJob(int w, int h, const float* imageData, const unsigned char* mask) : _w(w), _h(h), _is_float(true)
 {
     _f = _p.get_future();
-    _imageData = (unsigned char*)popsift::pinnedBlockGet((size_t)w * h * sizeof(float), &_pinned);
+    const size_t bytes = (size_t)w * h * sizeof(float);
+    _imageData = (unsigned char*)popsift::pinnedBlockGet(bytes + (mask ? (size_t)w * h : 0), &_pinned);
     if (_imageData == 0) DIE("Memory limitation: failed to allocate memory for SiftJob");
-    memcpy(_imageData, imageData, (size_t)w * h * sizeof(float));
+    memcpy(_imageData, imageData, bytes);
+    if (mask) {
+        _mask = _imageData + bytes;
+        memcpy(_mask, mask, (size_t)w * h);
+    }
 }
 
 SiftJob::~SiftJob() { popsift::pinnedBlockPut(_imageData); }
@@ -492,7 +502,17 @@ void PopSift::worker_loop(Worker* me)
                 rc = popsift_hip_describe_batch(me->ctx, imgs, frs, nfr, (int)jobs.size(), kind, job->getWidth(), job->getHeight(),
                                                 job->getWidth(), job->computesOrientation() ? POPSIFT_HIP_ORI_COMPUTE : POPSIFT_HIP_ORI_GIVEN);
             } else {
-                rc = popsift_hip_submit_batch(me->ctx, imgs, (int)jobs.size(), kind, job->getWidth(), job->getHeight(), job->getWidth());
+                /* masked and unmasked jobs share a submit: an unmasked job carries a null entry */
+                const uint8_t* masks[POPSIFT_HIP_MAX_BATCH];
+                bool           masked = false;
+                for (size_t k = 0; k < jobs.size(); k++) {
+                    masks[k] = jobs[k]->getMask();
+                    masked = masked || masks[k];
+                }
+                rc = masked ? popsift_hip_submit_batch_masked(me->ctx, imgs, masks, (int)jobs.size(), kind, job->getWidth(),
+                                                              job->getHeight(), job->getWidth(), job->getWidth())
+                            : popsift_hip_submit_batch(me->ctx, imgs, (int)jobs.size(), kind, job->getWidth(), job->getHeight(),
+                                                       job->getWidth());
             }
             if (rc != POPSIFT_HIP_OK) DIE(string("extraction failed: ") + popsift_hip_last_error(me->ctx));
             complete_pending(); /* the previous jobs' downloads and conversion, under this batch's kernels */
@@ -535,6 +555,13 @@ void PopSift::worker_loop(Worker* me)
                                             : (job->isPinned() ? POPSIFT_HIP_IMG_PINNED_U8 : POPSIFT_HIP_IMG_HOST_U8);
             rc = popsift_hip_describe_batch(me->ctx, &img, &frs, &nfr, 1, kind, job->getWidth(), job->getHeight(), job->getWidth(),
                                             job->computesOrientation() ? POPSIFT_HIP_ORI_COMPUTE : POPSIFT_HIP_ORI_GIVEN);
+        } else if (job->getMask()) {
+            const void*    img = job->getImageData();
+            const uint8_t* mask = job->getMask();
+            const int kind = job->isFloat() ? (job->isPinned() ? POPSIFT_HIP_IMG_PINNED_F32 : POPSIFT_HIP_IMG_HOST_F32)
+                                            : (job->isPinned() ? POPSIFT_HIP_IMG_PINNED_U8 : POPSIFT_HIP_IMG_HOST_U8);
+            rc = popsift_hip_submit_batch_masked(me->ctx, &img, &mask, 1, kind, job->getWidth(), job->getHeight(), job->getWidth(),
+                                                 job->getWidth());
         } else if (job->isFloat())
             rc = (job->isPinned() ? popsift_hip_submit_pinned_f32 : popsift_hip_submit_f32)(
                 me->ctx, (const float*)job->getImageData(), job->getWidth(), job->getHeight(), job->getWidth());
@@ -643,6 +670,20 @@ SiftJob* PopSift::enqueue(int w, int h, const float* imageData, const std::vecto
     SiftJob* job = new SiftJob(w, h, imageData);
     job->setFrames(frames, computeOrientation);
     return push(job, w, h);
+}
+
+SiftJob* PopSift::enqueueMasked(int w, int h, const unsigned char* imageData, const unsigned char* mask)
+{
+    if (_image_mode != ByteImages)
+        DIE("Image mode error: cannot load byte images into a PopSift pipeline configured for float images");
+    return push(new SiftJob(w, h, imageData, mask), w, h);
+}
+
+SiftJob* PopSift::enqueueMasked(int w, int h, const float* imageData, const unsigned char* mask)
+{
+    if (_image_mode != FloatImages)
+        DIE("Image mode error: cannot load float images into a PopSift pipeline configured for byte images");
+    return push(new SiftJob(w, h, imageData, mask), w, h);
 }
 
 SiftJob* PopSift::push(SiftJob* job, int w, int h)
