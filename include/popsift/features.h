@@ -16,6 +16,7 @@
 
 struct popsift_hip_devfeatures;
 struct popsift_hip_bytefeatures;
+struct popsift_hip_gallery;
 
 namespace popsift {
 
@@ -236,6 +237,38 @@ public:
     std::vector<Match> matchAndGet(FeaturesDevBytes* other);
     std::vector<Pair>  matchPairs(FeaturesDevBytes* other, const MatchOptions& opts);
     std::vector<Pair>  matchPairs(FeaturesDevBytes* other) { return matchPairs(other, MatchOptions()); }
+};
+
+/*
+ * Extension: byte sets end to end on one GPU (popsift_hip_gallery), matched against one query set in one pass: what
+ * query->matchPairs(member) returns for every member, from a fixed number of kernel launches and one download instead of
+ * a loop of calls.  add() copies the set's bytes on the device; the set may be deleted afterwards.  Pair indices are
+ * those of the sets the members came from.  One call at a time per gallery; the query is only read.
+ */
+class Gallery {
+    popsift_hip_gallery* _gallery;
+
+    Gallery(const Gallery&);
+    Gallery& operator=(const Gallery&);
+
+public:
+    typedef FeaturesDev::MatchOptions MatchOptions;
+    typedef FeaturesDev::Pair         Pair;
+
+    explicit Gallery(int device = 0);
+    ~Gallery();
+
+    /* the new member's index: 0, 1, ... */
+    int add(FeaturesDevBytes* member);
+    /* members */
+    int size() const;
+    popsift_hip_gallery* getHandle() { return _gallery; }
+
+    /* one pair list per member, each as FeaturesDevBytes::matchPairs(member, opts) returns it */
+    std::vector<std::vector<Pair>> matchPairs(FeaturesDevBytes* query, const MatchOptions& opts);
+    std::vector<std::vector<Pair>> matchPairs(FeaturesDevBytes* query) { return matchPairs(query, MatchOptions()); }
+    /* the lengths of those lists alone: no pair is downloaded */
+    std::vector<int> counts(FeaturesDevBytes* query, const MatchOptions& opts);
 };
 
 }  // namespace popsift

@@ -619,6 +619,62 @@ int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsi
                                   const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap, int* n_pairs);
 
 /*
+ * One byte set against many: a popsift_hip_gallery is a device-resident concatenation of byte sets ("members") on one
+ * GPU -- the members' bytes end to end, their norms (formed once, when a member is added), the member table first[m],
+ * count[m], and a stream and grow-only match scratch of its own.  Byte sets only.
+ *   add / add_host    a new member from a byte set (copied device to device, between GPUs with a peer copy; f is not
+ *                     referenced afterwards and may be freed) or from n_descriptors x 128 host bytes.  *member (may be
+ *                     NULL) receives its index 0, 1, ...  An empty set is a valid member.  The buffers grow
+ *                     geometrically; indices and results of earlier members do not change.  A gallery holds no positions
+ *                     and no maps: pair indices are descriptor indices of the sets the members came from.
+ *   info / member     device, members, descriptors in all; first descriptor and count of member m
+ *   download          member m's bytes, count x 128
+ * ERR_INVALID, before any GPU call: a NULL gallery, set or out; n_descriptors < 0; desc NULL with n_descriptors > 0; m out
+ * of range; an add that would take the gallery past 2^30 descriptors or 2^20 members.  A bad device: as
+ * popsift_hip_bytefeatures_from_host.  A failed allocation: ERR_OOM, and the gallery is as it was before the call.
+ * One call at a time per gallery (as for a verifier): an add must not run while a match on the gallery is in flight.
+ *
+ * The two matchers define nothing new; they are stated through the per-pair calls.
+ * popsift_hip_match_gallery writes n_members x l_len rows, member-major: out[m * l_len + i] is, bit for bit, row i of
+ * popsift_hip_match_bytes(l, member m), with member-local best / second (an empty member: {0, 0, 0, +INFINITY, +INFINITY}
+ * rows).  cap_rows < n_members x l_len: ERR_TOO_SMALL and nothing is written.  l empty or no members: OK, nothing written.
+ * popsift_hip_match_pairs_gallery returns the pairs in CSR form: those of member m are pairs[offsets[m] .. offsets[m + 1]),
+ * offsets[0] = 0, and they are exactly the array popsift_hip_match_pairs_bytes(l, member m, opts, ..) returns (conditions 1
+ * to 4, ascending l, member-local r).  *n_pairs = offsets[n_members]; offsets (n_members + 1 ints) is always written in
+ * full; the first min(*n_pairs, cap) pairs in that flat order are written, more than cap is ERR_TOO_SMALL with count and
+ * offsets valid; n_members x l_len is always a sufficient cap; cap = 0 with pairs = NULL asks for the counts alone (which
+ * images match, and how strongly).  An empty l or a gallery without members: all offsets 0, OK.
+ * ERR_INVALID, before any GPU call: the checks of popsift_hip_match_pairs_bytes on opts, pairs and n_pairs; a NULL l, g or
+ * offsets (out with rows to write); n_members x l_len > INT32_MAX.
+ * The results are a function of the bytes, the member order and the options: the same bytes on every run;
+ * popsift_hip_match_set_path does not apply.
+ *
+ * All scratch of the two calls belongs to the gallery (one call at a time per gallery).  l is only read -- its norms are
+ * formed in the gallery's scratch on every call -- so l may at the same time be the left or the right set of another
+ * thread's call.  With l on another GPU its bytes are copied to the gallery's GPU once per call.
+ *
+ * The members are walked in groups of max(1, POPSIFT_HIP_GALLERY_GROUP_ROWS / l_len) consecutive members, so that the
+ * scratch follows the group and not the gallery; a group costs a fixed number of launches whatever its size
+ * (match_gallery.hip).  The define is stated here for the tests of its edges; results do not depend on it.
+ * popsift_hip_gallery_debug_set_group_rows replaces it for one gallery from the next call on (0 = the default; < 0:
+ * ERR_INVALID).
+ */
+#define POPSIFT_HIP_GALLERY_GROUP_ROWS (1 << 22)
+typedef struct popsift_hip_gallery popsift_hip_gallery;
+int popsift_hip_gallery_create(int device, popsift_hip_gallery** out);
+int popsift_hip_gallery_free(popsift_hip_gallery* g); /* NULL: OK */
+int popsift_hip_gallery_add(popsift_hip_gallery* g, const popsift_hip_bytefeatures* f, int* member);
+int popsift_hip_gallery_add_host(popsift_hip_gallery* g, const uint8_t* desc, int n_descriptors, int* member);
+int popsift_hip_gallery_info(const popsift_hip_gallery* g, int* device, int* n_members, int64_t* n_descriptors);
+int popsift_hip_gallery_member(const popsift_hip_gallery* g, int m, int64_t* first, int* count);
+int popsift_hip_gallery_download(const popsift_hip_gallery* g, int m, uint8_t* desc);
+int popsift_hip_gallery_debug_set_group_rows(popsift_hip_gallery* g, int rows);
+int popsift_hip_match_gallery(const popsift_hip_bytefeatures* l, popsift_hip_gallery* g, popsift_hip_match* out, size_t cap_rows);
+int popsift_hip_match_pairs_gallery(const popsift_hip_bytefeatures* l, popsift_hip_gallery* g,
+                                    const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap,
+                                    int32_t* offsets /* n_members + 1 */, int* n_pairs);
+
+/*
  * Geometric verification: RANSAC over point pairs (OpenCV's findHomography(.., RANSAC), CudaSift's FindHomography).  Given
  * n pairs (x, y) -> (x', y') the verifier returns the model with the most inliers among T sampled hypotheses, its inlier
  * count and a per-pair inlier mask.  The result is a function of (points, options) alone: the same bytes on every run.

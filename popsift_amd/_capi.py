@@ -203,6 +203,16 @@ SYMBOLS = [
     ("popsift_hip_bytefeatures_download", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_bytes", C.c_int, [_vp, _vp, _vp]),
     ("popsift_hip_match_pairs_bytes", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _ip]),
+    ("popsift_hip_gallery_create", C.c_int, [C.c_int, C.POINTER(_vp)]),
+    ("popsift_hip_gallery_free", C.c_int, [_vp]),
+    ("popsift_hip_gallery_add", C.c_int, [_vp, _vp, _ip]),
+    ("popsift_hip_gallery_add_host", C.c_int, [_vp, _vp, C.c_int, _ip]),
+    ("popsift_hip_gallery_info", C.c_int, [_vp, _ip, _ip, C.POINTER(C.c_int64)]),
+    ("popsift_hip_gallery_member", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _ip]),
+    ("popsift_hip_gallery_download", C.c_int, [_vp, C.c_int, _vp]),
+    ("popsift_hip_gallery_debug_set_group_rows", C.c_int, [_vp, C.c_int]),
+    ("popsift_hip_match_gallery", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
+    ("popsift_hip_match_pairs_gallery", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _vp, _ip]),
     ("popsift_hip_verifier_create", C.c_int, [C.c_int, C.POINTER(_vp)]),
     ("popsift_hip_verifier_free", C.c_int, [_vp]),
     ("popsift_hip_default_ransac_opts", None, [C.POINTER(RansacOpts)]),
@@ -512,6 +522,104 @@ class ByteFeatures:
     def close(self):
         if self._h:
             lib().popsift_hip_bytefeatures_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+GALLERY_GROUP_ROWS = 1 << 22  # POPSIFT_HIP_GALLERY_GROUP_ROWS
+
+
+class Gallery:
+    """popsift_hip_gallery: byte sets end to end on one GPU, matched against one query set in one pass."""
+
+    def __init__(self, device=0):
+        h = _vp()
+        rc = lib().popsift_hip_gallery_create(device, C.byref(h))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_create")
+        self._h = h
+
+    def add(self, member):
+        """a ByteFeatures set (copied on the device) or an (n, 128) uint8 array; returns the member's index"""
+        m = C.c_int(-1)
+        if isinstance(member, ByteFeatures):
+            rc, where = lib().popsift_hip_gallery_add(self._h, member._h, C.byref(m)), "popsift_hip_gallery_add"
+        else:
+            desc = np.ascontiguousarray(member, np.uint8).reshape(-1, 128)
+            rc = lib().popsift_hip_gallery_add_host(self._h, desc.ctypes.data if len(desc) else None, len(desc), C.byref(m))
+            where = "popsift_hip_gallery_add_host"
+        if rc != OK:
+            raise PopsiftHipError(rc, where)
+        return m.value
+
+    def info(self):
+        """(device, n_members, n_descriptors)"""
+        d, nm, nd = C.c_int(), C.c_int(), C.c_int64()
+        lib().popsift_hip_gallery_info(self._h, C.byref(d), C.byref(nm), C.byref(nd))
+        return d.value, nm.value, nd.value
+
+    def member(self, m):
+        """(first descriptor, count) of member m"""
+        first, count = C.c_int64(), C.c_int()
+        rc = lib().popsift_hip_gallery_member(self._h, m, C.byref(first), C.byref(count))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_member")
+        return first.value, count.value
+
+    def download(self, m):
+        """member m's bytes (count, 128)"""
+        desc = np.zeros((self.member(m)[1], 128), np.uint8)
+        rc = lib().popsift_hip_gallery_download(self._h, m, desc.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_download")
+        return desc
+
+    def match(self, query):
+        """popsift_hip_match_gallery: (n_members, l_len) MATCH_DTYPE rows, row [m, i] = query.match(member m)[i]"""
+        nm, nl = self.info()[1], query.info()[1]
+        out = np.zeros((nm, nl), MATCH_DTYPE)
+        rc = lib().popsift_hip_match_gallery(query._h, self._h, out.ctypes.data, nm * nl)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_gallery")
+        return out
+
+    def match_pairs(self, query, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """popsift_hip_match_pairs_gallery: (pairs, offsets); pairs[offsets[m]:offsets[m + 1]] = query.match_pairs(member m)"""
+        nm, nl = self.info()[1], query.info()[1]
+        out = np.zeros(nm * nl, PAIR_DTYPE)
+        offsets = np.zeros(nm + 1, np.int32)
+        opts = MatchOpts(ratio, max_dist2, 1 if cross_check else 0, 0)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs_gallery(query._h, self._h, C.byref(opts), out.ctypes.data if len(out) else None,
+                                                   len(out), offsets.ctypes.data, C.byref(n))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_gallery")
+        return out[:n.value], offsets
+
+    def counts(self, query, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """pairs per member, without the pairs (cap = 0): which members match the query, and how strongly"""
+        offsets = np.zeros(self.info()[1] + 1, np.int32)
+        opts = MatchOpts(ratio, max_dist2, 1 if cross_check else 0, 0)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs_gallery(query._h, self._h, C.byref(opts), None, 0, offsets.ctypes.data, C.byref(n))
+        if rc not in (OK, ERR_TOO_SMALL):                              # more pairs than cap = 0: the count is the answer
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_gallery")
+        return np.diff(offsets)
+
+    def set_group_rows(self, n):
+        """popsift_hip_gallery_debug_set_group_rows: rows of a group from the next call on; 0 = the default"""
+        rc = lib().popsift_hip_gallery_debug_set_group_rows(self._h, n)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_debug_set_group_rows")
+
+    def close(self):
+        if self._h:
+            lib().popsift_hip_gallery_free(self._h)
             self._h = None
 
     def __del__(self):

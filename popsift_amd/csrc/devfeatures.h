@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 
@@ -91,6 +92,56 @@ struct popsift_hip_bytefeatures : MatchScratch {
     int*     d_norm = nullptr; /* |x - 128|^2 per descriptor, computed on first use by a match */
 
     ~popsift_hip_bytefeatures() { free_bufs({d_desc, d_rev, d_norm}); }
+};
+
+/* A gallery of byte sets (popsift_hip_gallery): the members' bytes end to end with their norms, the member table on the
+ * host, and the scratch of the two gallery matchers (match_gallery.hip), which belongs to the gallery and not to the query.
+ * Plain pointers and counts only: a zero-filled block reads as a gallery without members.  sets.hip makes and fills it,
+ * the destructor here frees everything. */
+struct popsift_hip_gallery {
+    int      device = 0;
+    int      n_members = 0;
+    int64_t  n_desc = 0;
+    uint8_t* d_desc = nullptr;  /* cap * 128 */
+    int*     d_norm = nullptr;  /* cap: |x - 128|^2, computed when the member is added */
+    size_t   cap = 0;           /* descriptors the two buffers hold */
+    int64_t* first = nullptr;   /* host, tab_cap: first descriptor of member m */
+    int*     count = nullptr;   /* host, tab_cap */
+    size_t   tab_cap = 0;
+    int      group_rows = 0;    /* popsift_hip_gallery_debug_set_group_rows; 0 = POPSIFT_HIP_GALLERY_GROUP_ROWS */
+    void*    stream = nullptr;  /* hipStream_t */
+    /* scratch of a match, grow-only */
+    void*  w_dev = nullptr;     /* a group's member table and work items ... */
+    void*  w_host = nullptr;    /* ... and the pinned block they are built in */
+    size_t w_cap = 0;           /* bytes */
+    void*  w_event = nullptr;   /* hipEvent_t: the upload of w_host has been read */
+    int*   lnorm = nullptr;     /* the query's norms */
+    size_t lnorm_cap = 0;       /* ints */
+    void*  partial = nullptr;   /* the sweeps' per-split candidates */
+    size_t partial_cap = 0;     /* bytes */
+    void*  rows = nullptr;      /* popsift_hip_match of one group, member-major */
+    size_t rows_cap = 0;        /* rows */
+    void*  rows_host = nullptr; /* pinned: all rows of popsift_hip_match_gallery */
+    size_t rows_host_cap = 0;   /* rows */
+    void*  res = nullptr;       /* offsets, the running pair count, |J|; then the pairs */
+    void*  res_host = nullptr;  /* pinned twin */
+    size_t res_cap = 0;         /* bytes */
+    int*   idx = nullptr;       /* over a group's gallery rows: flags, ranks, the list J; and the compactions' block counts */
+    size_t idx_cap = 0;         /* ints */
+    void*  back = nullptr;      /* of J: gathered descriptors, the reverse sweep's rows, norms */
+    size_t back_cap = 0;        /* rows */
+
+    popsift_hip_gallery() = default;
+    popsift_hip_gallery(const popsift_hip_gallery&) = delete;
+    popsift_hip_gallery& operator=(const popsift_hip_gallery&) = delete;
+    ~popsift_hip_gallery()
+    {
+        if (w_event) (void)hipEventDestroy((hipEvent_t)w_event);
+        if (stream) (void)hipStreamDestroy((hipStream_t)stream);
+        free_bufs({d_desc, d_norm, w_dev, lnorm, partial, rows, res, idx, back}, {w_host, rows_host, res_host});
+        free(first);
+        free(count);
+    }
 };
 
 namespace popsift_hip {

@@ -244,3 +244,157 @@ int popsift_hip_bytefeatures_download(const popsift_hip_bytefeatures* f, uint8_t
 }
 
 } /* extern "C" */
+
+/* ---- galleries of byte sets */
+
+namespace {
+
+constexpr int64_t GALLERY_MAX_DESC = (int64_t)1 << 30;
+constexpr int     GALLERY_MAX_MEMBERS = 1 << 20;
+
+/* Room for n more descriptors and one more member.  New buffers are filled device to device and swapped in only when
+ * every allocation has succeeded: a failure leaves the gallery as it was. */
+int gallery_reserve(popsift_hip_gallery* g, int n, hipStream_t s)
+{
+    if ((size_t)g->n_members + 1 > g->tab_cap) {
+        const size_t   cap = std::max<size_t>(2 * g->tab_cap, 64);
+        int64_t* const first = (int64_t*)malloc(sizeof(int64_t) * cap);
+        int* const     count = (int*)malloc(sizeof(int) * cap);
+        if (!first || !count) {
+            free(first);
+            free(count);
+            return POPSIFT_HIP_ERR_OOM;
+        }
+        if (g->n_members > 0) {
+            memcpy(first, g->first, sizeof(int64_t) * (size_t)g->n_members);
+            memcpy(count, g->count, sizeof(int) * (size_t)g->n_members);
+        }
+        free(g->first);
+        free(g->count);
+        g->first = first;
+        g->count = count;
+        g->tab_cap = cap;
+    }
+    const size_t need = (size_t)g->n_desc + (size_t)n;
+    if (need <= g->cap) return POPSIFT_HIP_OK;
+    const size_t cap = std::max(need, std::max<size_t>(2 * g->cap, 1024));
+    uint8_t*     desc = nullptr;
+    int*         norm = nullptr;
+    Status       ok;
+    if (ok(hipMalloc((void**)&desc, 128 * cap)) && ok(hipMalloc((void**)&norm, sizeof(int) * cap)) && g->n_desc > 0)
+        ok(hipMemcpyAsync(desc, g->d_desc, 128 * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s)) &&
+            ok(hipMemcpyAsync(norm, g->d_norm, sizeof(int) * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s)) &&
+            ok(hipStreamSynchronize(s));
+    if (!ok.good()) {
+        free_bufs({desc, norm});
+        return ok.rc;
+    }
+    free_bufs({g->d_desc, g->d_norm});
+    g->d_desc = desc;
+    g->d_norm = norm;
+    g->cap = cap;
+    return POPSIFT_HIP_OK;
+}
+
+/* a new member of n descriptors from `src` (device memory of src_device, or host memory with src_device < 0) */
+int gallery_append(popsift_hip_gallery* g, const uint8_t* src, int src_device, int n, int* member)
+{
+    if (g->n_desc + n > GALLERY_MAX_DESC || g->n_members + 1 > GALLERY_MAX_MEMBERS) return POPSIFT_HIP_ERR_INVALID;
+    if (hipSetDevice(g->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    hipStream_t const s = (hipStream_t)g->stream;
+    if (int rc = gallery_reserve(g, n, s)) return rc;
+    if (n > 0) {
+        uint8_t* const dst = g->d_desc + 128 * (size_t)g->n_desc;
+        const size_t   bytes = 128 * (size_t)n;
+        Status         ok;
+        if (src_device < 0) ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+        else if (src_device == g->device) ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
+        else ok(hipMemcpyPeer(dst, g->device, src, src_device, bytes));
+        if (ok.good()) ok(launch_norms_u8(dst, n, g->d_norm + g->n_desc, s));
+        if (ok.good()) ok(hipStreamSynchronize(s));
+        if (!ok.good()) return ok.rc;
+    }
+    g->first[g->n_members] = g->n_desc;
+    g->count[g->n_members] = n;
+    if (member) *member = g->n_members;
+    g->n_members += 1;
+    g->n_desc += n;
+    return POPSIFT_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int popsift_hip_gallery_create(int device, popsift_hip_gallery** out)
+{
+    if (!out) return POPSIFT_HIP_ERR_INVALID;
+    *out = nullptr;
+    if (int rc = check_device(device)) return rc;
+    if (hipSetDevice(device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    popsift_hip_gallery* g = new (std::nothrow) popsift_hip_gallery();
+    if (!g) return POPSIFT_HIP_ERR_OOM;
+    g->device = device;
+    Status      ok;
+    hipStream_t s = nullptr;
+    hipEvent_t  e = nullptr;
+    if (ok(hipStreamCreateWithFlags(&s, hipStreamNonBlocking))) g->stream = s;
+    if (ok.good() && ok(hipEventCreateWithFlags(&e, hipEventDisableTiming))) g->w_event = e;
+    return hand_over(ok.rc, g, out);
+}
+
+int popsift_hip_gallery_free(popsift_hip_gallery* g)
+{
+    if (!g) return POPSIFT_HIP_OK;
+    (void)hipSetDevice(g->device);
+    delete g;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_gallery_add(popsift_hip_gallery* g, const popsift_hip_bytefeatures* f, int* member)
+{
+    if (!g || !f) return POPSIFT_HIP_ERR_INVALID;
+    return gallery_append(g, f->d_desc, f->device, f->n_desc, member);
+}
+
+int popsift_hip_gallery_add_host(popsift_hip_gallery* g, const uint8_t* desc, int n_descriptors, int* member)
+{
+    if (!g || n_descriptors < 0 || (n_descriptors > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
+    return gallery_append(g, desc, -1, n_descriptors, member);
+}
+
+int popsift_hip_gallery_info(const popsift_hip_gallery* g, int* device, int* n_members, int64_t* n_descriptors)
+{
+    if (!g) return POPSIFT_HIP_ERR_INVALID;
+    if (device) *device = g->device;
+    if (n_members) *n_members = g->n_members;
+    if (n_descriptors) *n_descriptors = g->n_desc;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_gallery_member(const popsift_hip_gallery* g, int m, int64_t* first, int* count)
+{
+    if (!g || m < 0 || m >= g->n_members) return POPSIFT_HIP_ERR_INVALID;
+    if (first) *first = g->first[m];
+    if (count) *count = g->count[m];
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_gallery_download(const popsift_hip_gallery* g, int m, uint8_t* desc)
+{
+    if (!g || m < 0 || m >= g->n_members || (g->count[m] > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
+    if (g->count[m] == 0) return POPSIFT_HIP_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status ok;
+    ok(hipMemcpy(desc, g->d_desc + 128 * (size_t)g->first[m], 128 * (size_t)g->count[m], hipMemcpyDeviceToHost));
+    return ok.rc;
+}
+
+int popsift_hip_gallery_debug_set_group_rows(popsift_hip_gallery* g, int rows)
+{
+    if (!g || rows < 0) return POPSIFT_HIP_ERR_INVALID;
+    g->group_rows = rows;
+    return POPSIFT_HIP_OK;
+}
+
+} /* extern "C" */

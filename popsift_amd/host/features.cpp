@@ -461,6 +461,72 @@ std::vector<FeaturesDevBytes::Pair> FeaturesDevBytes::matchPairs(FeaturesDevByte
     return match_pairs(_set, other ? other->_set : 0, getDescriptorCount(), opts, popsift_hip_match_pairs_bytes);
 }
 
+/* ------------------------------------------------------------------------ Gallery */
+
+Gallery::Gallery(int device) : _gallery(0)
+{
+    const int rc = popsift_hip_gallery_create(device, &_gallery);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot create the gallery", rc);
+}
+
+Gallery::~Gallery() { popsift_hip_gallery_free(_gallery); }
+
+int Gallery::add(FeaturesDevBytes* member)
+{
+    int       m = -1;
+    const int rc = popsift_hip_gallery_add(_gallery, member ? member->getHandle() : 0, &m);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot add to the gallery", rc);
+    return m;
+}
+
+int Gallery::size() const
+{
+    int n = 0;
+    popsift_hip_gallery_info(_gallery, 0, &n, 0);
+    return n;
+}
+
+namespace {
+/* offsets (size() + 1) and, with room, the pairs of popsift_hip_match_pairs_gallery */
+std::vector<int32_t> gallery_pairs(popsift_hip_gallery* g, FeaturesDevBytes* query, const FeaturesDev::MatchOptions& opts,
+                                   int n_members, std::vector<FeaturesDev::Pair>* flat)
+{
+    static_assert(sizeof(FeaturesDev::Pair) == sizeof(popsift_hip_pair), "Pair is popsift_hip_pair");
+    std::vector<int32_t> offsets((size_t)n_members + 1, 0);
+    if (!query) return offsets;
+    popsift_hip_match_opts o;
+    popsift_hip_default_match_opts(&o);
+    o.ratio = opts.ratio;
+    o.max_dist2 = opts.maxDist2;
+    o.cross_check = opts.crossCheck ? 1 : 0;
+    if (flat) flat->resize((size_t)n_members * (size_t)query->getDescriptorCount()); /* always enough */
+    int       n = 0;
+    const int rc = popsift_hip_match_pairs_gallery(query->getHandle(), g, &o, flat && !flat->empty() ? (popsift_hip_pair*)flat->data() : 0,
+                                                   flat ? flat->size() : 0, offsets.data(), &n);
+    if (rc != POPSIFT_HIP_OK && !(rc == POPSIFT_HIP_ERR_TOO_SMALL && !flat)) dev_fatal("matching failed", rc);
+    return offsets;
+}
+}  // namespace
+
+std::vector<std::vector<Gallery::Pair>> Gallery::matchPairs(FeaturesDevBytes* query, const MatchOptions& opts)
+{
+    const int                      n = size();
+    std::vector<Pair>              flat;
+    const std::vector<int32_t>     offsets = gallery_pairs(_gallery, query, opts, n, &flat);
+    std::vector<std::vector<Pair>> res((size_t)n);
+    for (int m = 0; m < n; m++) res[(size_t)m].assign(flat.begin() + offsets[(size_t)m], flat.begin() + offsets[(size_t)m + 1]);
+    return res;
+}
+
+std::vector<int> Gallery::counts(FeaturesDevBytes* query, const MatchOptions& opts)
+{
+    const int                  n = size();
+    const std::vector<int32_t> offsets = gallery_pairs(_gallery, query, opts, n, 0);
+    std::vector<int>           res((size_t)n);
+    for (int m = 0; m < n; m++) res[(size_t)m] = offsets[(size_t)m + 1] - offsets[(size_t)m];
+    return res;
+}
+
 /* FeaturesDev::match + show_distance (features.cu:222-300): the reference prints from the device */
 void FeaturesDev::match(FeaturesDev* other)
 {

@@ -11,6 +11,8 @@
  * and prints those pairs after the model block.
  * Extension: --refit [--refit-rounds N] with --verify refits the model RANSAC found to all its inliers by least squares
  * (Verifier::refit) and prints the refitted model under the RANSAC block; with --guided the refitted model is the guide.
+ * Extension: --gallery FILE (repeatable, instead of -r; implies --bytes --pairs) matches the left image against every
+ * gallery image in one pass (popsift::Gallery) and prints, per gallery image in the order given, its pair count and pairs.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -49,6 +51,7 @@ static bool guided_pairs = false;
 static float guided_err = 0.0f; /* 0: --max-err */
 static bool refit_model = false;
 static int refit_rounds = 4;
+static vector<string> gallery_files;
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -58,7 +61,7 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.flag("verbose", 'v', "Options", "", [&] { config.setVerbose(); });
     o.flag("log", 0, "Options", "Write debugging files", [&] { config.setLogMode(popsift::Config::All); });
     o.val("left", 'l', "Options", "\"Left\"  input file", [&](const string& v) { lFile = v; }, true);
-    o.val("right", 'r', "Options", "\"Right\" input file", [&](const string& v) { rFile = v; }, true);
+    o.val("right", 'r', "Options", "\"Right\" input file (required without --gallery)", [&](const string& v) { rFile = v; });
     /* match.cpp:61-73 */
     o.ival("octaves", "Parameters", "Number of octaves", [&](int v) { config.octaves = v; });
     o.ival("levels", "Parameters", "Number of levels per octave", [&](int v) { config.levels = v; });
@@ -138,6 +141,11 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
            "RANSAC lines; --guided then matches under the refitted model",
            [&] { refit_model = true; });
     o.ival("refit-rounds", "Matching", "With --refit: the most rounds, 1 .. 16 (default 4)", [&](int v) { refit_rounds = v; });
+    o.val("gallery", 0, "Matching",
+          "Match the left image against this image too; repeatable, replaces --right and implies --bytes --pairs.  All\n"
+          "gallery images are matched in one pass on the GPU; prints per image, in the order given, a line\n"
+          "'gallery <k> <file>: <n> pairs' and its pair lines, then the total.  Not with --verify or --guided",
+          [&](const string& v) { gallery_files.push_back(v); });
     o.val("feature-order", 0, "Extensions",
           "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
           "pixel column, level: the same bytes on every run)",
@@ -154,6 +162,18 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
                config.setKeepStrongest(n);
            });
     o.parse(argc, argv);
+    if (gallery_files.empty() && rFile.empty()) o.error("the option '--right' is required but missing");
+    if (!gallery_files.empty()) {
+        if (!rFile.empty()) {
+            cerr << "--gallery replaces --right: give one or the other" << endl;
+            exit(-1);
+        }
+        if (verify_pairs || guided_pairs) {
+            cerr << "--gallery matches byte sets, which hold no positions: no --verify or --guided over a gallery" << endl;
+            exit(-1);
+        }
+        match_bytes = print_pairs = true;
+    }
     if (verify_pairs && !print_pairs) {
         cerr << "--verify works on the pairs: add --pairs" << endl;
         exit(-1);
@@ -261,6 +281,47 @@ static void print_byte_matches(popsift::FeaturesDevBytes* l, popsift::FeaturesDe
                r_fem[(size_t)m[i].second], m[i].second, m[i].dist_best, m[i].dist_second);
 }
 
+static SiftJob* process_image(const string& inputFile, PopSift& sift);
+
+/* --gallery: the left image against all gallery images in one pass */
+static int match_gallery_files(const string& lFile, PopSift& sift)
+{
+    SiftJob*              lJob = process_image(lFile, sift);
+    popsift::FeaturesDev* lFeatures = lJob->getDev();
+    cout << "Number of features:    " << lFeatures->getFeatureCount() << endl;
+    cout << "Number of descriptors: " << lFeatures->getDescriptorCount() << endl;
+    popsift::FeaturesDevBytes* lBytes = lFeatures->toBytes();
+    const vector<int>          l_fem = reverse_map(lBytes);
+    popsift::Gallery           gallery(lFeatures->getDevice());
+    vector<vector<int>>        r_fem;
+    for (const string& f : gallery_files) {
+        SiftJob*              job = process_image(f, sift);
+        popsift::FeaturesDev* feat = job->getDev();
+        cout << "Number of features:    " << feat->getFeatureCount() << endl;
+        cout << "Number of descriptors: " << feat->getDescriptorCount() << endl;
+        popsift::FeaturesDevBytes* bytes = feat->toBytes();
+        r_fem.push_back(reverse_map(bytes));
+        gallery.add(bytes); /* copied: the set can go */
+        delete bytes;
+        delete feat;
+        delete job;
+    }
+    const vector<vector<popsift::Gallery::Pair>> all = gallery.matchPairs(lBytes, pair_opts);
+    size_t                                       total = 0;
+    for (size_t k = 0; k < all.size(); k++) {
+        printf("gallery %zu %s: %zu pairs\n", k, gallery_files[k].c_str(), all[k].size());
+        for (const popsift::Gallery::Pair& p : all[k])
+            printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[k][(size_t)p.r], p.r,
+                   sqrtf(p.distBest));
+        total += all[k].size();
+    }
+    printf("Number of pairs:       %zu\n", total);
+    delete lBytes;
+    delete lFeatures;
+    delete lJob;
+    return 0;
+}
+
 static SiftJob* process_image(const string& inputFile, PopSift& sift)
 {
     int            w, h;
@@ -278,9 +339,16 @@ int main(int argc, char** argv)
     string          rFile = "";
 
     parseargs(argc, argv, config, lFile, rFile);
-    std::cout << lFile << " <-> " << rFile << std::endl;
+    vector<string> inputs = {lFile};
+    if (gallery_files.empty()) {
+        std::cout << lFile << " <-> " << rFile << std::endl;
+        inputs.push_back(rFile);
+    } else {
+        std::cout << lFile << " <-> " << gallery_files.size() << " gallery images" << std::endl;
+        inputs.insert(inputs.end(), gallery_files.begin(), gallery_files.end());
+    }
 
-    for (const string& f : {lFile, rFile}) {
+    for (const string& f : inputs) {
         if (filesystem::exists(f) && !filesystem::is_regular_file(f)) {
             cout << "Input file " << f << " is not a regular file, nothing to do" << endl;
             exit(-1);
@@ -292,6 +360,12 @@ int main(int argc, char** argv)
     if (print_dev_info) deviceInfo.print();
 
     PopSift sift(config, popsift::Config::MatchingMode);
+
+    if (!gallery_files.empty()) {
+        const int rc = match_gallery_files(lFile, sift);
+        sift.uninit();
+        return rc;
+    }
 
     SiftJob* lJob = process_image(lFile, sift);
     SiftJob* rJob = process_image(rFile, sift);
