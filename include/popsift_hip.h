@@ -1030,7 +1030,9 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * plane-to-plane levels: 0 by plane size (default), 1 the one-tile-per-workgroup kernels only, 2 the strip-march kernels
  * wherever they apply, also on small planes (results do not depend on it: every path is bit-identical; the tests run
  * their small images through 2); BLUR_SEG = rows per segment of the march kernels (a multiple of 32; 0 = chosen from the
- * plane and the batch); PYR_TAIL = 0: the smallest octaves -- from the first whose plane fits one workgroup's LDS -- are
+ * plane and the batch); BLUR_TILE_H = rows per tile of the one-tile-per-workgroup kernels: 0 by plane size (default: 64
+ * from about 4.2 Mpx on, else 32), 32 or 64 for every plane, anything else is POPSIFT_HIP_ERR_INVALID (results do not
+ * depend on it: every height is bit-identical; the tests run their small images through 64); PYR_TAIL = 0: the smallest octaves -- from the first whose plane fits one workgroup's LDS -- are
  * built by one launch (default), 1: by level launches like the others (results do not depend on it); DIRECT_PATH (Gauss
  * mode vlfeat-direct only) = 0: octave 0's levels by one fused launch (default), 1: by one level-0 launch per level
  * (results do not depend on it); SCALE_PATH (ScaleDirect only) = 0: level 0 of every octave by one launch and each
@@ -1046,7 +1048,7 @@ enum { POPSIFT_HIP_DEBUG_DET_QCAP = 1, POPSIFT_HIP_DEBUG_CAND_CAP = 2, POPSIFT_H
        POPSIFT_HIP_DEBUG_KP_WAVES = 7, POPSIFT_HIP_DEBUG_BLUR_PATH = 8, POPSIFT_HIP_DEBUG_BLUR_SEG = 9,
        POPSIFT_HIP_DEBUG_PYR_TAIL = 10, POPSIFT_HIP_DEBUG_DIRECT_PATH = 11,
        POPSIFT_HIP_DEBUG_DESC_CAP = 12, POPSIFT_HIP_DEBUG_SCALE_PATH = 13, POPSIFT_HIP_DEBUG_ORDER_COARSE = 14,
-       POPSIFT_HIP_DEBUG_DESC_LIST = 15 };
+       POPSIFT_HIP_DEBUG_DESC_LIST = 15, POPSIFT_HIP_DEBUG_BLUR_TILE_H = 16 };
 int popsift_hip_debug_set(popsift_hip_ctx* ctx, int what, int value);
 
 #ifdef __cplusplus

@@ -242,7 +242,7 @@ MATCH_AUTO, MATCH_EXACT, MATCH_SCREEN = 0, 1, 2
 STAGES = ("pyramid", "detect", "refine", "orientation", "scan", "descriptor")
 DEBUG_DET_QCAP, DEBUG_CAND_CAP, DEBUG_OHIST_CAP, DEBUG_FAIL_ALLOC, DEBUG_DESC_ROWS, DEBUG_KP_WAVES = 1, 2, 3, 4, 5, 7  # 6: retired
 DEBUG_BLUR_PATH, DEBUG_BLUR_SEG, DEBUG_PYR_TAIL, DEBUG_DIRECT_PATH, DEBUG_DESC_CAP = 8, 9, 10, 11, 12
-DEBUG_SCALE_PATH, DEBUG_ORDER_COARSE, DEBUG_DESC_LIST = 13, 14, 15
+DEBUG_SCALE_PATH, DEBUG_ORDER_COARSE, DEBUG_DESC_LIST, DEBUG_BLUR_TILE_H = 13, 14, 15, 16
 MAX_BATCH = 16
 IMG_HOST_U8, IMG_HOST_F32, IMG_DEV_U8, IMG_DEV_F32, IMG_PINNED_U8, IMG_PINNED_F32 = range(6)
 

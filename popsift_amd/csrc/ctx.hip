@@ -176,7 +176,7 @@ struct popsift_hip_ctx {
     int       det_qcap = 1 << 30;  /* popsift_hip_debug_set hooks, see popsift_hip.h */
     int       desc_rows = 1 << 30;
     int       desc_list = 1 << 30;
-    BlurTune  blur_tune{0, 0}; /* BLUR_PATH / BLUR_SEG debug switches */
+    BlurTune  blur_tune{0, 0, 0}; /* BLUR_PATH / BLUR_SEG / BLUR_TILE_H debug switches */
     int       keep_strongest = 0; /* popsift_hip_set_keep_strongest: 0 off, n: the next enqueue keeps the n strongest */
     int       batch_keep = 0;     /* ... and what the keypoint stages of the batch in the context were enqueued with */
     int       order_coarse = 0; /* ORDER_COARSE: row bits the ordering pass drops from its bucket key */
@@ -604,6 +604,13 @@ int timed_launch(popsift_hip_ctx* c, double alg_bytes, const char* what, F launc
     return 0;
 }
 
+/* Rows per tile of the launches on a w x h plane: blur_tile_h's choice by plane size, or the BLUR_TILE_H test switch's for
+ * every plane.  The one place the switch applies: the tile grid (set_plane), the kernel (launch_blur) and the pairing
+ * into k_blur_duo all take the height from here.  Nothing else depends on it -- a plane's pitch (rows padded to 64
+ * floats) and stride come from its size alone (prepare), the kernels clamp their loads to the plane and store only
+ * pixels inside it -- so a forced height moves no buffer and changes no value. */
+int tile_rows(const popsift_hip_ctx* c, int w, int h) { return c->blur_tune.tile_h ? c->blur_tune.tile_h : blur_tile_h(w, h); }
+
 int blur_launch(popsift_hip_ctx* c, const BlurArgs& a, int mode, int span, int tile_h, double alg_bytes)
 {
     return timed_launch(
@@ -628,7 +635,7 @@ BlurArgs level_args(const popsift_hip_ctx* c, int o, int level)
     const PyrDesc& pd = c->pd;
     const OctDesc& od = pd.o[o];
     BlurArgs       a{};
-    set_plane(a, od, blur_tile_h(od.w, od.h));
+    set_plane(a, od, tile_rows(c, od.w, od.h));
     memcpy(a.taps.g, &c->tab.filter[level * PS_GA], sizeof(a.taps.g));
     a.dst_off = od.data_off + level * od.plane_stride;
     a.src_off = od.data_off + (level - 1) * od.plane_stride;
@@ -706,7 +713,7 @@ int enqueue_direct_octave0(popsift_hip_ctx* c, int is_f32, int pitch, bool align
         const double bytes = in_bytes + 4.0 * px * (L + (pd.dog_fly ? 0 : L - 1)) + (next0_off >= 0 ? px : 0.0);
         return timed_launch(c, bytes, "k_pyr_direct", [&] { return launch_pyr_direct(a, c->bd, c->nb, is_f32, c->stream); });
     }
-    const int thd = blur_tile_h(od.w, od.h);
+    const int thd = tile_rows(c, od.w, od.h);
     for (int l = 0; l < L; l++) {
         BlurArgs a = input_args(c, 0, thd, is_f32, pitch, aligned4);
         memcpy(a.taps.g, &c->abs0.filter[l * PS_GA], sizeof(a.taps.g));
@@ -792,7 +799,7 @@ int enqueue_scale_direct(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned
         for (int l = 1; l < L; l++) {
             BlurArgs a = level_args(c, o, l);
             a.next0_off = -1;
-            if (int rc = blur_launch(c, a, 0, c->tab.span[l], blur_tile_h(pd.o[o].w, pd.o[o].h), lvl_bpp * pd.o[o].w * pd.o[o].h))
+            if (int rc = blur_launch(c, a, 0, c->tab.span[l], tile_rows(c, pd.o[o].w, pd.o[o].h), lvl_bpp * pd.o[o].w * pd.o[o].h))
                 return rc;
         }
     return 0;
@@ -817,14 +824,14 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
         const BlurArgs a = level_args(c, o, level);
         const double   px = (double)pd.o[o].w * pd.o[o].h;
         /* read plane l-1 once, write plane l (and DoG l-1 when it is stored) once: 8 (12) B / pixel */
-        return blur_launch(c, a, 0, c->tab.span[level], blur_tile_h(pd.o[o].w, pd.o[o].h), (pd.dog_fly ? 8.0 : 12.0) * px);
+        return blur_launch(c, a, 0, c->tab.span[level], tile_rows(c, pd.o[o].w, pd.o[o].h), (pd.dog_fly ? 8.0 : 12.0) * px);
     };
     const bool direct = c->p.gauss_mode == POPSIFT_HIP_GAUSS_VLFEAT_RELATIVE_ALL;
     if (direct) {
         if (int rc = enqueue_direct_octave0(c, is_f32, pitch, aligned4)) return rc;
     } else {
         const OctDesc& od = pd.o[0];
-        const int      thd = blur_tile_h(od.w, od.h);
+        const int      thd = tile_rows(c, od.w, od.h);
         BlurArgs       a = input_args(c, 0, thd, is_f32, pitch, aligned4);
         memcpy(a.taps.g, &c->tab.filter[0], sizeof(a.taps.g));
         const double bytes = (double)c->in_w * c->in_h * (is_f32 ? 4 : 1) + 4.0 * (double)od.w * od.h;
@@ -862,8 +869,8 @@ int enqueue_pyramid(popsift_hip_ctx* c, int is_f32, int pitch, bool aligned4)
     for (int o = 1; o < n_front; o++) {
         /* per-launch profiling keeps one kernel per event pair; BLUR_PATH = 2 sends every plane-to-plane level through
          * the march kernels, so no level of it is paired into k_blur_duo */
-        const bool pair = c->profile != 1 && c->blur_tune.path != 2 && o >= 2 && blur_tile_h(pd.o[o].w, pd.o[o].h) == 32 &&
-                          blur_tile_h(pd.o[o - 1].w, pd.o[o - 1].h) == 32;
+        const bool pair = c->profile != 1 && c->blur_tune.path != 2 && o >= 2 && tile_rows(c, pd.o[o].w, pd.o[o].h) == 32 &&
+                          tile_rows(c, pd.o[o - 1].w, pd.o[o - 1].h) == 32;
         for (int level = 1; level <= L - 3; level++) {
             const int trail = L - 3 + level; /* L-2, L-1 of the octave before */
             if (pair && level <= 2) {
@@ -2047,6 +2054,10 @@ int popsift_hip_debug_set(popsift_hip_ctx* c, int what, int value)
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_BLUR_SEG:
         c->blur_tune.seg_rows = std::max(value, 0);
+        return POPSIFT_HIP_OK;
+    case POPSIFT_HIP_DEBUG_BLUR_TILE_H:
+        if (value != 0 && value != 32 && value != 64) return fail(c, POPSIFT_HIP_ERR_INVALID, "BLUR_TILE_H: 0, 32 or 64");
+        c->blur_tune.tile_h = value;
         return POPSIFT_HIP_OK;
     case POPSIFT_HIP_DEBUG_PYR_TAIL:
         c->pyr_tail = value;

@@ -36,16 +36,18 @@ struct BlurArgs {
     int     seg_rows;
 };
 
-/* how launch_blur picks the kernel of a plane-to-plane level launch (popsift_hip_debug_set BLUR_PATH / BLUR_SEG) */
+/* how launch_blur picks the kernel of a plane-to-plane level launch (popsift_hip_debug_set BLUR_PATH / BLUR_SEG), and the
+ * rows per tile of every launch that would take them from blur_tile_h (BLUR_TILE_H) */
 struct BlurTune {
     int path;     /* 0: by plane size, 1: tile kernels only (pyramid.hip), 2: march kernels wherever they apply */
     int seg_rows; /* 0: chosen from the plane and the batch, else rows per segment (rounded to a multiple of 32) */
+    int tile_h;   /* 0: blur_tile_h(w, h), else 32 or 64 rows for every plane */
 };
 
 int        blur_tile_w();
 int        blur_tile_h(int w, int h); /* 32 or 64 rows, by plane size */
 hipError_t launch_blur(const BlurArgs& a, const BatchDesc& bd, int nb, int mode, int span, int tile_h, hipStream_t s,
-                       BlurTune tune = BlurTune{0, 0});
+                       BlurTune tune = BlurTune{0, 0, 0});
 /* blur_march.hip: level l >= 1 of a large plane, strips of 128 columns marched down 32 rows a step */
 bool       blur_march_supported(const BlurArgs& a, int halo);
 int        blur_march_seg_rows(int w, int h, int nb, int want_wgs);

@@ -748,6 +748,8 @@ static hipError_t launch_blur_small(const BlurArgs& a, const BatchDesc& bd, int 
     return hipErrorInvalidValue;
 }
 
+/* Which instance a tile launch takes -- family, HALO bucket, lanes -- is restated by tile_instance() in tests/blur_cases.py,
+ * whose coverage check (tests/test_blur_cases.py) holds the test images to every 64-row instance: change both together. */
 hipError_t launch_blur(const BlurArgs& a, const BatchDesc& bd, int nb, int mode, int span, int tile_h, hipStream_t s, BlurTune tune)
 {
     const int halo = span - 1;

@@ -112,16 +112,18 @@ def test_planes_bit_identical_to_restatement(gpu_hip, ref, name, kw, shape, kind
 @pytest.mark.parametrize("name,kw,shape,kind", EDGE_CASES, ids=[c[0] for c in EDGE_CASES])
 def test_per_level_path_at_the_range_edges(gpu_hip, ref, name, kw, shape, kind):
     """DIRECT_PATH = 1 (one level-0 launch per level of octave 0) at L = 10 and 12 and at sigma 0.5: the restatement's
-    planes too, and the fused launch's results bit for bit"""
+    planes too, and the fused launch's results bit for bit; the per-level path again with 64-row tiles (BLUR_TILE_H)"""
     img = synth(90 + len(name), *shape)
     res = []
-    for path in (0, 1):
-        ctx = _ctx(gpu_hip, path=path, **kw).submit(img)
+    for path, tile_h in ((0, 0), (1, 0), (1, 64)):
+        ctx = _ctx(gpu_hip, path=path, **kw)
+        ctx.debug_set(gpu_hip.DEBUG_BLUR_TILE_H, tile_h)
+        ctx.submit(img)
         ctx.wait()
-        _check_pyramid(ctx, ref, img, ctx.params, "%s DIRECT_PATH %d" % (name, path))
+        _check_pyramid(ctx, ref, img, ctx.params, "%s DIRECT_PATH %d tile_h %d" % (name, path, tile_h))
         res.append(_canon(*ctx.fetch()))
         ctx.close()
-    assert _same(res[0], res[1]), name
+    assert _same(res[0], res[1]) and _same(res[0], res[2]), name
 
 
 @pytest.mark.gpu

@@ -148,11 +148,18 @@ def test_planes_large(gpu_hip, ref, shape, n_oct):
 def test_fused_equals_yardstick_path(gpu_hip, kw, shape):
     img = synth(11, *shape)
     res = []
-    for path in (0, 1):
-        ctx = _ctx(gpu_hip, path, **kw).submit(img)
+    # the yardstick's level launches of the stored-DoG and the wide-filter rows again with 64-row tiles (BLUR_TILE_H)
+    again_64 = bool(kw.get("store_dog")) or kw.get("initial_blur") == 4.0
+    for path, tile_h in ((0, 0), (1, 0)) + (((1, 64),) if again_64 else ()):
+        ctx = _ctx(gpu_hip, path, **kw)
+        ctx.debug_set(gpu_hip.DEBUG_BLUR_TILE_H, tile_h)
+        ctx.submit(img)
         res.append((_canon(*ctx.fetch()), _planes(ctx)))
         ctx.close()
-    (fa, pa), (fb, pb) = res
+    (fa, pa), (fb, pb) = res[:2]
+    for fc, pc in res[2:]:
+        assert len(pa) == len(pc) and all(np.array_equal(bits(a), bits(b)) for a, b in zip(pa, pc)), "tile_h 64"
+        assert _same(fa, fc), "tile_h 64"
     assert len(pa) == len(pb) and all(np.array_equal(bits(a), bits(b)) for a, b in zip(pa, pb))
     # (an assumed blur of 4 leaves few or no extrema: the planes carry that case)
     assert (len(fa[0]) > 50 or kw.get("initial_blur", 0.5) > 2) and _same(fa, fb)
