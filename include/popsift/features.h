@@ -243,7 +243,9 @@ public:
  * Extension: byte sets end to end on one GPU (popsift_hip_gallery), matched against one query set in one pass: what
  * query->matchPairs(member) returns for every member, from a fixed number of kernel launches and one download instead of
  * a loop of calls.  add() copies the set's bytes on the device; the set may be deleted afterwards.  Pair indices are
- * those of the sets the members came from.  One call at a time per gallery; the query is only read.
+ * those of the sets the members came from.  One call at a time per gallery; the query is only read.  A member added as a
+ * FeaturesDev brings the positions of its features along, and pairPoints() turns the pair lists into the points of
+ * Verifier::ransacMany (popsift/verify.h): every gallery image verified in one call.
  */
 class Gallery {
     popsift_hip_gallery* _gallery;
@@ -260,6 +262,9 @@ public:
 
     /* the new member's index: 0, 1, ... */
     int add(FeaturesDevBytes* member);
+    /* a member from a float set (popsift_hip_gallery_add_set): the bytes of member->toBytes() and, for pairPoints, the
+     * positions of the features behind its descriptors */
+    int add(FeaturesDev* member);
     /* members */
     int size() const;
     popsift_hip_gallery* getHandle() { return _gallery; }
@@ -269,6 +274,11 @@ public:
     std::vector<std::vector<Pair>> matchPairs(FeaturesDevBytes* query) { return matchPairs(query, MatchOptions()); }
     /* the lengths of those lists alone: no pair is downloaded */
     std::vector<int> counts(FeaturesDevBytes* query, const MatchOptions& opts);
+
+    /* (x, y, x', y') of every pair of matchPairs' lists, list after list, and the lists' offsets (size() + 1, from 0)
+     * into them (popsift_hip_gallery_pair_points): the input of Verifier::ransacMany.  query is the float set the query
+     * bytes came from; every member with a pair was added as a FeaturesDev. */
+    std::vector<float> pairPoints(FeaturesDev* query, const std::vector<std::vector<Pair>>& pairs, std::vector<int>& offsets);
 };
 
 }  // namespace popsift

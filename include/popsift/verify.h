@@ -34,6 +34,16 @@ struct EpipolarOptions {
     unsigned seed = 0;
 };
 
+/* Many pair lists in one call (popsift_hip_ransac_many): the lists of a gallery, each verified as ransac() / epipolar()
+ * verifies it alone, with the same hypotheses, maxErr and seed for every list. */
+struct ManyOptions {
+    enum Kind { Homography = 0, Affine = 1, Epipolar = 2 };
+    Kind     kind = Homography;
+    int      hypotheses = 2048; /* 1 .. 65536 */
+    float    maxErr = 2.0f;     /* the kind's inlier limit in pixels */
+    unsigned seed = 0;
+};
+
 struct RansacResult {
     /* row major, right ~ H * left; from Verifier::epipolar the fundamental matrix F, [x' y' 1] F [x y 1]^T = 0; zeros
      * without a winner */
@@ -90,6 +100,10 @@ public:
     RansacResult epipolar(const std::vector<float>& pts) { return epipolar(pts, EpipolarOptions()); }
     /* the same points and the model to start from */
     RefitResult refit(const std::vector<float>& pts, const RefitOptions& opts);
+    /* list m is the pairs offsets[m] .. offsets[m + 1] of pts, as Gallery::pairPoints returns both; result m is what
+     * ransac() / epipolar() returns for list m alone, from one upload, one download and a number of launches that does
+     * not depend on the number of lists */
+    std::vector<RansacResult> ransacMany(const std::vector<float>& pts, const std::vector<int>& offsets, const ManyOptions& opts);
 };
 
 }  // namespace popsift

@@ -625,8 +625,9 @@ int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsi
  *   add / add_host    a new member from a byte set (copied device to device, between GPUs with a peer copy; f is not
  *                     referenced afterwards and may be freed) or from n_descriptors x 128 host bytes.  *member (may be
  *                     NULL) receives its index 0, 1, ...  An empty set is a valid member.  The buffers grow
- *                     geometrically; indices and results of earlier members do not change.  A gallery holds no positions
- *                     and no maps: pair indices are descriptor indices of the sets the members came from.
+ *                     geometrically; indices and results of earlier members do not change.  A gallery holds no maps,
+ *                     and positions only of the members of add_set (below): pair indices are descriptor indices of the
+ *                     sets the members came from.
  *   info / member     device, members, descriptors in all; first descriptor and count of member m
  *   download          member m's bytes, count x 128
  * ERR_INVALID, before any GPU call: a NULL gallery, set or out; n_descriptors < 0; desc NULL with n_descriptors > 0; m out
@@ -653,6 +654,21 @@ int popsift_hip_match_pairs_bytes(const popsift_hip_bytefeatures* l, const popsi
  * formed in the gallery's scratch on every call -- so l may at the same time be the left or the right set of another
  * thread's call.  With l on another GPU its bytes are copied to the gallery's GPU once per call.
  *
+ * Positions.  popsift_hip_gallery_add_set adds a member from a float set: its bytes are
+ * popsift_hip_bytefeatures_from_set(f)'s, and with them the gallery keeps per descriptor the (xpos, ypos) of the feature
+ * its map names -- the floats popsift_hip_pair_points gathers -- 8 bytes per descriptor next to the 128 of the descriptor,
+ * in an array that is allocated with the first such member and grows with the gallery; a gallery that never sees add_set
+ * allocates and launches nothing more.  Members added by add / add_host have no positions.  ERR_INVALID also when f's map
+ * names no feature for a descriptor; the gallery is then as it was.  Indices, bytes and results of earlier members, and
+ * everything popsift_hip_match*_gallery returns, do not change.
+ * popsift_hip_gallery_pair_points turns the CSR (pairs, offsets) of popsift_hip_match_pairs_gallery into the points of the
+ * verifier (popsift_hip_ransac_many): pts[i] = (x, y of descriptor pairs[i].l of l, x', y' of descriptor pairs[i].r of the
+ * member i lies in); l is the float set the query bytes came from.  ERR_INVALID, checked on the host before any GPU call:
+ * a NULL l, g or offsets; offsets[0] != 0 or a decreasing offset; pairs or pts NULL with pairs present; a pair index
+ * outside l or outside its member; a non-empty list for a member without positions; and, found on the GPU, l's map naming
+ * no feature for a descriptor (as popsift_hip_pair_points).  On an error nothing is written.  The gather runs on the
+ * gallery's GPU in the gallery's scratch; l on another GPU is copied once per call.
+ *
  * The members are walked in groups of max(1, POPSIFT_HIP_GALLERY_GROUP_ROWS / l_len) consecutive members, so that the
  * scratch follows the group and not the gallery; a group costs a fixed number of launches whatever its size
  * (match_gallery.hip).  The define is stated here for the tests of its edges; results do not depend on it.
@@ -665,6 +681,9 @@ int popsift_hip_gallery_create(int device, popsift_hip_gallery** out);
 int popsift_hip_gallery_free(popsift_hip_gallery* g); /* NULL: OK */
 int popsift_hip_gallery_add(popsift_hip_gallery* g, const popsift_hip_bytefeatures* f, int* member);
 int popsift_hip_gallery_add_host(popsift_hip_gallery* g, const uint8_t* desc, int n_descriptors, int* member);
+int popsift_hip_gallery_add_set(popsift_hip_gallery* g, const popsift_hip_devfeatures* f, int* member);
+int popsift_hip_gallery_pair_points(const popsift_hip_devfeatures* l, popsift_hip_gallery* g, const popsift_hip_pair* pairs,
+                                    const int32_t* offsets /* n_members + 1 */, float* pts);
 int popsift_hip_gallery_info(const popsift_hip_gallery* g, int* device, int* n_members, int64_t* n_descriptors);
 int popsift_hip_gallery_member(const popsift_hip_gallery* g, int m, int64_t* first, int* count);
 int popsift_hip_gallery_download(const popsift_hip_gallery* g, int m, uint8_t* desc);
@@ -914,6 +933,56 @@ int  popsift_hip_refit(popsift_hip_verifier* v, const float* pts, int n, const p
 int  popsift_hip_refit_trace(popsift_hip_verifier* v, const float* pts, int n, const popsift_hip_refit_opts* o,
                              popsift_hip_refit_result* res, uint8_t* inlier, double* sums, float* models, int32_t* counts,
                              int32_t* accepted);
+
+/*
+ * Many pair lists in one call: the grouped form of the sampler, for the CSR pair lists of a gallery
+ * (popsift_hip_match_pairs_gallery, popsift_hip_gallery_pair_points).  It defines no new numerics; it is stated entirely
+ * through the per-list calls.
+ *
+ * The rule.  res[m], inlier[offsets[m] .. offsets[m+1]) and list m's slice of the trace are, byte for byte, what the
+ * per-list call writes for the points pts + 4 * offsets[m] with n = offsets[m+1] - offsets[m] and the same hypotheses,
+ * max_err and seed.  The per-list call is popsift_hip_ransac for kinds 0 and 1, and popsift_hip_epipolar for kind 2.
+ * This includes a list shorter than the kind's sample: hypothesis -1, zeros, and a trace of -1 / 0 / -1.
+ *
+ * The per-list calls keep their bytes, their options and their records.  Calls of all kinds may alternate on one verifier,
+ * and each returns what a fresh verifier returns.
+ *
+ * ERR_INVALID, before any GPU call: a NULL verifier, opts, offsets or res (res is not required for the trace); n_lists < 0
+ * or > 2^20; offsets[0] != 0, or a decreasing offset; offsets[n_lists] > 2^24; pts NULL with pairs present; an unknown
+ * kind; hypotheses outside 1 .. 65536; max_err not finite or <= 0; reserved != 0.  n_lists == 0 returns OK and writes
+ * nothing.
+ *
+ * A call is one upload of all points with the offsets, a number of launches that does not depend on the number of lists
+ * within a group (ransac.hip), one download of all records, plus the masks when asked for, and one synchronisation.
+ * Scratch is grow-only and belongs to the verifier.  Models, samples and counts cost 36 + 16..32 + 4 bytes per (list,
+ * hypothesis), so the lists are walked in groups of consecutive lists, each holding at most POPSIFT_HIP_RANSAC_MANY_GROUP
+ * (list, hypothesis) records and always at least one list.  The scoring kernel walks a list in segments of
+ * POPSIFT_HIP_RANSAC_MANY_SEGMENT pairs.  The two defines are stated here for the tests of their edges; results do not
+ * depend on them.  popsift_hip_verifier_debug_set_group replaces the first for one verifier from the next call on (0 =
+ * the default; < 0: ERR_INVALID).
+ *
+ * popsift_hip_ransac_many_trace is the parity hook: the same call, returning list-major the samples (n_lists x T x 4 ints,
+ * x 8 for the epipolar kind), the models (n_lists x T x 9) and the counts (n_lists x T); any of the three, res and inlier
+ * may be NULL.
+ */
+#define POPSIFT_HIP_RANSAC_MANY_GROUP (1 << 20)
+#define POPSIFT_HIP_RANSAC_MANY_SEGMENT 256
+typedef struct popsift_hip_ransac_many_opts {   /* 32 bytes */
+    int32_t  kind;         /* POPSIFT_HIP_REFIT_HOMOGRAPHY / _AFFINE / _EPIPOLAR: the one numbering of the kinds */
+    int32_t  hypotheses;   /* T, 1 .. 65536, the same for every list                                             */
+    float    max_err;      /* the kind's inlier limit (px)                                                       */
+    uint32_t seed;         /* the same for every list: a sample depends on (seed, t, n, kind) alone              */
+    int32_t  reserved[4];  /* must be 0 */
+} popsift_hip_ransac_many_opts;
+void popsift_hip_default_ransac_many_opts(popsift_hip_ransac_many_opts* o);   /* {HOMOGRAPHY, 2048, 2.0f, 0, {0, 0, 0, 0}} */
+/* pts: offsets[n_lists] x 4 floats; offsets: n_lists + 1 ints, offsets[0] = 0, non-decreasing (the CSR of
+ * popsift_hip_match_pairs_gallery); res: n_lists records; inlier: offsets[n_lists] bytes or NULL */
+int  popsift_hip_ransac_many(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists,
+                             const popsift_hip_ransac_many_opts* o, popsift_hip_ransac_result* res, uint8_t* inlier);
+int  popsift_hip_ransac_many_trace(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists,
+                                   const popsift_hip_ransac_many_opts* o, popsift_hip_ransac_result* res, uint8_t* inlier,
+                                   int32_t* samples, float* models, int32_t* counts);
+int  popsift_hip_verifier_debug_set_group(popsift_hip_verifier* v, int records);
 
 /*
  * Guided matching: nearest neighbours under a known model (the expectation SiftGPU's GetGuidedSiftMatch(.., H, F, distmax,

@@ -95,6 +95,12 @@ class RefitOpts(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class RansacManyOpts(C.Structure):
+    """popsift_hip_ransac_many_opts"""
+    _fields_ = [("kind", C.c_int32), ("hypotheses", C.c_int32), ("max_err", C.c_float), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 4)]
+
+
 FEATURE_DTYPE = np.dtype([
     ("debug_octave", np.int32), ("xpos", np.float32), ("ypos", np.float32),
     ("sigma", np.float32), ("num_ori", np.int32),
@@ -116,6 +122,8 @@ REFITS = {"homography": REFIT_HOMOGRAPHY, "affine": REFIT_AFFINE, "epipolar": RE
 REFIT_STOP_ROUNDS, REFIT_STOP_CONVERGED, REFIT_STOP_NOT_BETTER, REFIT_STOP_NO_FIT, REFIT_STOP_NO_SUPPORT = range(5)
 # POPSIFT_HIP_REFIT_*: pairs per workgroup of the accumulating kernel, the most rounds, sums per round of the trace
 REFIT_CHUNK, REFIT_MAX_ROUNDS, REFIT_SLOTS = 1024, 16, 45
+# POPSIFT_HIP_RANSAC_MANY_*: (list, hypothesis) records of a group of Verifier.ransac_many, pairs of a scoring segment
+RANSAC_MANY_GROUP, RANSAC_MANY_SEGMENT = 1 << 20, 256
 MODEL_HOMOGRAPHY, MODEL_AFFINE = 0, 1
 MODELS = {"homography": MODEL_HOMOGRAPHY, "affine": MODEL_AFFINE}
 RANSAC_CHUNK, RANSAC_HYP_BLOCK = 1024, 64  # POPSIFT_HIP_RANSAC_*: pairs / hypotheses per workgroup of the scoring kernel
@@ -207,6 +215,8 @@ SYMBOLS = [
     ("popsift_hip_gallery_free", C.c_int, [_vp]),
     ("popsift_hip_gallery_add", C.c_int, [_vp, _vp, _ip]),
     ("popsift_hip_gallery_add_host", C.c_int, [_vp, _vp, C.c_int, _ip]),
+    ("popsift_hip_gallery_add_set", C.c_int, [_vp, _vp, _ip]),
+    ("popsift_hip_gallery_pair_points", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("popsift_hip_gallery_info", C.c_int, [_vp, _ip, _ip, C.POINTER(C.c_int64)]),
     ("popsift_hip_gallery_member", C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _ip]),
     ("popsift_hip_gallery_download", C.c_int, [_vp, C.c_int, _vp]),
@@ -225,6 +235,10 @@ SYMBOLS = [
     ("popsift_hip_default_refit_opts", None, [C.POINTER(RefitOpts)]),
     ("popsift_hip_refit", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RefitOpts), _vp, _vp]),
     ("popsift_hip_refit_trace", C.c_int, [_vp, _vp, C.c_int, C.POINTER(RefitOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("popsift_hip_default_ransac_many_opts", None, [C.POINTER(RansacManyOpts)]),
+    ("popsift_hip_ransac_many", C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(RansacManyOpts), _vp, _vp]),
+    ("popsift_hip_ransac_many_trace", C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(RansacManyOpts), _vp, _vp, _vp, _vp, _vp]),
+    ("popsift_hip_verifier_debug_set_group", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_default_guided_opts", None, [C.POINTER(GuidedOpts)]),
     ("popsift_hip_match_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp]),
     ("popsift_hip_match_pairs_guided", C.c_int, [_vp, _vp, C.POINTER(GuidedOpts), _vp, C.c_size_t, _ip]),
@@ -557,6 +571,30 @@ class Gallery:
             raise PopsiftHipError(rc, where)
         return m.value
 
+    def add_set(self, features):
+        """popsift_hip_gallery_add_set: a member from a DevFeatures set -- the bytes of ByteFeatures.from_set(features) and
+        the positions behind its descriptors, for pair_points(); returns the member's index"""
+        m = C.c_int(-1)
+        rc = lib().popsift_hip_gallery_add_set(self._h, features._h, C.byref(m))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_add_set")
+        return m.value
+
+    def pair_points(self, query_set, pairs, offsets):
+        """popsift_hip_gallery_pair_points: (n, 4) float32 rows (x, y, x', y') of the CSR (pairs, offsets) of match_pairs();
+        query_set is the DevFeatures set the query bytes came from.  With the same offsets, the input of
+        Verifier.ransac_many"""
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(offsets) != self.info()[1] + 1 or offsets[-1] != len(pairs):
+            raise ValueError("offsets: n_members + 1 ints, offsets[-1] = len(pairs)")
+        pts = np.zeros((len(pairs), 4), np.float32)
+        rc = lib().popsift_hip_gallery_pair_points(query_set._h, self._h, pairs.ctypes.data if len(pairs) else None,
+                                                   offsets.ctypes.data, pts.ctypes.data if len(pairs) else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_pair_points")
+        return pts
+
     def info(self):
         """(device, n_members, n_descriptors)"""
         d, nm, nd = C.c_int(), C.c_int(), C.c_int64()
@@ -690,6 +728,20 @@ def refit_opts(model="homography", M=None, max_err=None, rounds=None):
     return o
 
 
+def ransac_many_opts(kind="homography", hypotheses=None, max_err=None, seed=None):
+    """popsift_hip_ransac_many_opts: the library's defaults with the given fields replaced; kind by name or number"""
+    o = RansacManyOpts()
+    lib().popsift_hip_default_ransac_many_opts(C.byref(o))
+    o.kind = REFITS.get(kind, kind)
+    if hypotheses is not None:
+        o.hypotheses = hypotheses
+    if max_err is not None:
+        o.max_err = max_err
+    if seed is not None:
+        o.seed = seed
+    return o
+
+
 class Verifier:
     """popsift_hip_verifier: RANSAC over point pairs on one GPU (a stream and grow-only scratch; one call at a time)."""
 
@@ -795,6 +847,52 @@ class Verifier:
         if rc != OK:
             raise PopsiftHipError(rc, "popsift_hip_refit_trace")
         return res[0], mask, sums, models, counts, accepted
+
+    @staticmethod
+    def _offsets(offsets, pts):
+        offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(offsets) < 1 or offsets[-1] != len(pts):
+            raise ValueError("offsets: n_lists + 1 ints, offsets[0] = 0, offsets[-1] = len(pts)")
+        return offsets
+
+    def ransac_many(self, pts, offsets, kind="homography", hypotheses=None, max_err=None, seed=None, want_mask=True):
+        """popsift_hip_ransac_many -> (results, mask): list m is pts[offsets[m]:offsets[m + 1]] (the CSR of
+        Gallery.match_pairs / Gallery.pair_points); results (n_lists,) RANSAC_RESULT_DTYPE records, mask len(pts) bytes
+        (None with want_mask=False), each list's what ransac() / epipolar() returns for it alone"""
+        pts = self._points(pts)
+        offsets = self._offsets(offsets, pts)
+        nl, n = len(offsets) - 1, len(pts)
+        res = np.zeros(nl, RANSAC_RESULT_DTYPE)
+        mask = np.zeros(n, np.uint8) if want_mask else None
+        o = ransac_many_opts(kind, hypotheses, max_err, seed)
+        rc = lib().popsift_hip_ransac_many(self._h, pts.ctypes.data if n else None, offsets.ctypes.data, nl, C.byref(o),
+                                           res.ctypes.data, mask.ctypes.data if want_mask and n else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_ransac_many")
+        return res, mask
+
+    def ransac_many_trace(self, pts, offsets, kind="homography", hypotheses=None, max_err=None, seed=None):
+        """popsift_hip_ransac_many_trace -> (samples (n_lists, T, 4 | 8) int32, models (n_lists, T, 9) float32, counts
+        (n_lists, T) int32)"""
+        pts = self._points(pts)
+        offsets = self._offsets(offsets, pts)
+        nl, n = len(offsets) - 1, len(pts)
+        o = ransac_many_opts(kind, hypotheses, max_err, seed)
+        T = max(int(o.hypotheses), 0)
+        row = EPIPOLAR_SAMPLE if o.kind == REFIT_EPIPOLAR else 4
+        samples, models, counts = np.zeros((nl, T, row), np.int32), np.zeros((nl, T, 9), np.float32), np.zeros((nl, T), np.int32)
+        rc = lib().popsift_hip_ransac_many_trace(self._h, pts.ctypes.data if n else None, offsets.ctypes.data, nl, C.byref(o),
+                                                 None, None, samples.ctypes.data, models.ctypes.data, counts.ctypes.data)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_ransac_many_trace")
+        return samples, models, counts
+
+    def set_group(self, records):
+        """popsift_hip_verifier_debug_set_group: (list, hypothesis) records of a group of ransac_many from the next call
+        on; 0 = the default"""
+        rc = lib().popsift_hip_verifier_debug_set_group(self._h, records)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_verifier_debug_set_group")
 
     def close(self):
         if self._h:

@@ -107,7 +107,12 @@ struct popsift_hip_gallery {
     size_t   cap = 0;           /* descriptors the two buffers hold */
     int64_t* first = nullptr;   /* host, tab_cap: first descriptor of member m */
     int*     count = nullptr;   /* host, tab_cap */
+    uint8_t* has_xy = nullptr;  /* host, tab_cap: 1 = the member came from a float set and has positions */
     size_t   tab_cap = 0;
+    float*   d_xy = nullptr;    /* cap * 2: (xpos, ypos) per descriptor; allocated with the first member that has positions */
+    void*    xy_dev = nullptr;  /* scratch of popsift_hip_gallery_pair_points: a flag, the (l, gallery row) items, the points */
+    void*    xy_host = nullptr; /* pinned twin */
+    size_t   xy_cap = 0;        /* bytes */
     int      group_rows = 0;    /* popsift_hip_gallery_debug_set_group_rows; 0 = POPSIFT_HIP_GALLERY_GROUP_ROWS */
     void*    stream = nullptr;  /* hipStream_t */
     /* scratch of a match, grow-only */
@@ -138,9 +143,11 @@ struct popsift_hip_gallery {
     {
         if (w_event) (void)hipEventDestroy((hipEvent_t)w_event);
         if (stream) (void)hipStreamDestroy((hipStream_t)stream);
-        free_bufs({d_desc, d_norm, w_dev, lnorm, partial, rows, res, idx, back}, {w_host, rows_host, res_host});
+        free_bufs({d_desc, d_norm, d_xy, xy_dev, w_dev, lnorm, partial, rows, res, idx, back},
+                  {xy_host, w_host, rows_host, res_host});
         free(first);
         free(count);
+        free(has_xy);
     }
 };
 

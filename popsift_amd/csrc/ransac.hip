@@ -19,6 +19,17 @@
  *   k_ransac_mask     the winner's inlier bytes, four pairs per lane
  *   k_pair_points     (x, y, x', y') of descriptor pairs through the sets' descriptor -> feature maps
  *
+ * popsift_hip_ransac_many runs the same five steps over many pair lists at once, through the same device functions
+ * (transfer_hypothesis, epipolar_hypothesis, the two inlier rules, select_winner), so a list's bytes are those of the
+ * per-list call:
+ *
+ *   k_many_bounds     the eight keys of every list, one workgroup per segment of a list
+ *   k_many_models     one lane per (list, hypothesis)
+ *   k_many_score      one lane per hypothesis, its model and its count in registers, over a segment's pairs, each pair a
+ *                     wave-uniform 16-byte load: no ballot, no LDS, and a short list costs its own pairs only
+ *   k_many_select     one workgroup per list
+ *   k_many_mask       one lane and one byte per pair of a segment
+ *
  * popsift_hip_refit, the least-squares refit of such a model on its inliers (tests/refit_ref.c), enqueues all its rounds up
  * front; a state record on the device carries the current model and a `done` flag between them:
  *
@@ -40,6 +51,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <memory>
 #include <new>
 
 #include "devfeatures.h"
@@ -275,15 +287,15 @@ __device__ __forceinline__ bool round_model(const double (&h)[9], float (&M)[9])
     return ok;
 }
 
+/* hypothesis t of n >= m pairs under a list's bounds: its sample, its model and its count (0, or -1 for none) into row
+ * `rec` of the three arrays.  One text for a homography and an affine map, used by the per-list and the grouped kernel */
 template <int MODEL>
-__global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
-                                                      const uint32_t* __restrict__ bounds, float* __restrict__ models,
-                                                      int* __restrict__ samples, int* __restrict__ counts)
+__device__ __forceinline__ void transfer_hypothesis(const v4f* __restrict__ pts, int n, int t, uint32_t seed,
+                                                    const uint32_t* __restrict__ bounds, size_t rec, float* __restrict__ models,
+                                                    int* __restrict__ samples, int* __restrict__ counts)
 {
     constexpr int M = Kind<MODEL>::m, ROW = Kind<MODEL>::row;
-    const int     t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= T) return;
-    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    const Norm    L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
     int        idx[ROW];
     bool       ok = sample<M>(seed, t, n, idx);
     Pair       q[M];
@@ -330,10 +342,20 @@ __global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pt
     denormalise_transfer(g, L, Rn, h);
     ok = round_model(h, H) && ok;
 #pragma unroll
-    for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? H[i] : 0.0f;
+    for (int i = 0; i < 9; i++) models[9 * rec + i] = ok ? H[i] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < ROW; i++) samples[ROW * (size_t)t + i] = idx[i];
-    counts[t] = ok ? 0 : -1;
+    for (int i = 0; i < ROW; i++) samples[ROW * rec + i] = idx[i];
+    counts[rec] = ok ? 0 : -1;
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_ransac_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
+                                                      const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                      int* __restrict__ samples, int* __restrict__ counts)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= T) return;
+    transfer_hypothesis<MODEL>(pts, n, t, seed, bounds, (size_t)t, models, samples, counts);
 }
 
 /* ---- popsift_hip_epipolar, rules 3 to 5: one fundamental matrix per lane.  As above every index is a compile-time
@@ -507,14 +529,13 @@ __device__ __forceinline__ bool denormalise_fundamental(const double (&f)[9], co
     return !(d == 0.0);
 }
 
-__global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
-                                                        const uint32_t* __restrict__ bounds, float* __restrict__ models,
-                                                        int* __restrict__ samples, int* __restrict__ counts)
+/* the same for a fundamental matrix */
+__device__ __forceinline__ void epipolar_hypothesis(const v4f* __restrict__ pts, int n, int t, uint32_t seed,
+                                                    const uint32_t* __restrict__ bounds, size_t rec, float* __restrict__ models,
+                                                    int* __restrict__ samples, int* __restrict__ counts)
 {
     constexpr int M = Kind<FIT_EPIPOLAR>::m;
-    const int     t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= T) return;
-    const Norm L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
+    const Norm    L = normaliser(bounds, 0), Rn = normaliser(bounds, 2);
     int        idx[M];
     bool       ok = sample<M>(seed, t, n, idx);
     double     a[M][9], f[9], h[9];
@@ -531,10 +552,19 @@ __global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ 
     float F[9];
     ok = round_model(h, F) && ok;
 #pragma unroll
-    for (int i = 0; i < 9; i++) models[9 * (size_t)t + i] = ok ? F[i] : 0.0f;
+    for (int i = 0; i < 9; i++) models[9 * rec + i] = ok ? F[i] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < M; i++) samples[M * (size_t)t + i] = idx[i];
-    counts[t] = ok ? 0 : -1;
+    for (int i = 0; i < M; i++) samples[M * rec + i] = idx[i];
+    counts[rec] = ok ? 0 : -1;
+}
+
+__global__ __launch_bounds__(64) void k_epipolar_models(const v4f* __restrict__ pts, int n, int T, uint32_t seed,
+                                                        const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                        int* __restrict__ samples, int* __restrict__ counts)
+{
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= T) return;
+    epipolar_hypothesis(pts, n, t, seed, bounds, (size_t)t, models, samples, counts);
 }
 
 /* ---- rule 4: score */
@@ -608,8 +638,8 @@ __global__ __launch_bounds__(S_BLOCK) void k_ransac_score(const v4f* __restrict_
 
 /* ---- rule 5: select.  One workgroup; key = (count, ~t): the largest count, then the lowest t */
 
-__global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ counts, const float* __restrict__ models, int T,
-                                                       int min_count, popsift_hip_ransac_result* __restrict__ res)
+__device__ __forceinline__ void select_winner(const int* __restrict__ counts, const float* __restrict__ models, int T,
+                                              int min_count, popsift_hip_ransac_result* __restrict__ res)
 {
     __shared__ long long s_key[4];
     __shared__ int       s_valid[4];
@@ -647,6 +677,12 @@ __global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ c
     res->reserved = 0;
 }
 
+__global__ __launch_bounds__(256) void k_ransac_select(const int* __restrict__ counts, const float* __restrict__ models, int T,
+                                                       int min_count, popsift_hip_ransac_result* __restrict__ res)
+{
+    select_winner(counts, models, T, min_count, res);
+}
+
 /* four pairs and four mask bytes per lane; mask has room for n rounded up to a multiple of 4 */
 template <class Rule>
 __global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts, int n,
@@ -666,6 +702,123 @@ __global__ __launch_bounds__(256) void k_ransac_mask(const v4f* __restrict__ pts
         if (won && i < n && Rule::inlier(H, pts[i], max_err2)) word |= 1u << (8 * r);
     }
     mask[q] = word;
+}
+
+/* ---- popsift_hip_ransac_many: the five kernels above over many lists.  The host cuts every list into segments of at most
+ * G_SEG consecutive pairs (an empty list has none); a segment is the unit of work of the kernels that walk pairs. */
+
+constexpr int G_SEG = POPSIFT_HIP_RANSAC_MANY_SEGMENT; /* pairs of a segment */
+constexpr int G_BLOCK = 256;                           /* lanes of the grouped kernels: hypotheses of a score workgroup */
+static_assert(G_SEG == G_BLOCK, "k_many_bounds and k_many_mask give a segment one lane per pair");
+
+struct Segment {
+    int list;   /* index in the call */
+    int first;  /* flat index of its first pair */
+    int count;  /* 1 .. G_SEG */
+    int whole;  /* 1: the segment is its whole list */
+};
+static_assert(sizeof(Segment) == 16, "one 16-byte load");
+
+/* grid (segments).  bounds: 8 keys per list, zeroed before */
+__global__ __launch_bounds__(G_BLOCK) void k_many_bounds(const v4f* __restrict__ pts, const Segment* __restrict__ segs,
+                                                         uint32_t* __restrict__ bounds)
+{
+    const Segment sg = segs[blockIdx.x];
+    uint32_t      m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((int)threadIdx.x < sg.count) {
+        const v4f p = pts[(size_t)sg.first + threadIdx.x];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const float f = p[c];
+            if (isfinite(f)) {
+                const uint32_t k = order_key(f);
+                m[c] = k;
+                m[4 + c] = ~k;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m[c] = max(m[c], (uint32_t)__shfl_xor((int)m[c], d));
+        if ((threadIdx.x & 63) == 0 && m[c] != 0) atomicMax(&bounds[8 * (size_t)sg.list + c], m[c]);
+    }
+}
+
+/* grid (lists of the group, blocks of 64 hypotheses): one lane per (list, hypothesis).  A list shorter than a sample has
+ * the rows of a per-list call that never reached the GPU: -1, zeros, -1 */
+template <int KIND>
+__global__ __launch_bounds__(64) void k_many_models(const v4f* __restrict__ pts, const int* __restrict__ offsets, int list0, int T,
+                                                    uint32_t seed, const uint32_t* __restrict__ bounds, float* __restrict__ models,
+                                                    int* __restrict__ samples, int* __restrict__ counts)
+{
+    constexpr int M = Kind<KIND>::m, ROW = Kind<KIND>::row;
+    const int     t = blockIdx.y * 64 + threadIdx.x;
+    if (t >= T) return;
+    const int    list = list0 + blockIdx.x;
+    const int    base = offsets[list], n = offsets[list + 1] - base;
+    const size_t rec = (size_t)blockIdx.x * T + t;
+    if (n < M) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) models[9 * rec + i] = 0.0f;
+#pragma unroll
+        for (int i = 0; i < ROW; i++) samples[ROW * rec + i] = -1;
+        counts[rec] = -1;
+        return;
+    }
+    const uint32_t* __restrict__ b = bounds + 8 * (size_t)list;
+    if constexpr (KIND == FIT_EPIPOLAR) epipolar_hypothesis(pts + base, n, t, seed, b, rec, models, samples, counts);
+    else transfer_hypothesis<KIND>(pts + base, n, t, seed, b, rec, models, samples, counts);
+}
+
+/* grid (segments of the group, blocks of G_BLOCK hypotheses).  A lane keeps one hypothesis' nine coefficients and its
+ * count in registers and walks the segment's pairs; a pair is the same 16 bytes in every lane (a scalar load).  No
+ * ballot, no LDS: a short list costs its own pairs and nothing more.  A list of one segment stores its counts; a longer
+ * one adds them, one integer atomic per (segment, hypothesis).  A slot without a model is all zeros, counts nothing and
+ * keeps its -1 */
+template <class Rule>
+__global__ __launch_bounds__(G_BLOCK) void k_many_score(const v4f* __restrict__ pts, const Segment* __restrict__ segs, int list0,
+                                                        const float* __restrict__ models, int T, float max_err2,
+                                                        int* __restrict__ counts)
+{
+    const Segment sg = segs[blockIdx.x];
+    const int     t = blockIdx.y * G_BLOCK + threadIdx.x;
+    if (t >= T) return;
+    const size_t rec = (size_t)(sg.list - list0) * T + t;
+    float        H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) H[i] = models[9 * rec + i];
+    const v4f* __restrict__ p = pts + sg.first;
+    int                     c = 0;
+#pragma unroll 4
+    for (int i = 0; i < sg.count; i++) c += Rule::inlier(H, p[i], max_err2) ? 1 : 0;
+    if (c == 0) return;
+    if (sg.whole) counts[rec] = c;
+    else atomicAdd(&counts[rec], c);
+}
+
+/* grid (lists of the group) */
+__global__ __launch_bounds__(256) void k_many_select(const int* __restrict__ counts, const float* __restrict__ models, int T,
+                                                     int min_count, popsift_hip_ransac_result* __restrict__ res)
+{
+    const size_t r0 = (size_t)blockIdx.x * T;
+    select_winner(counts + r0, models + 9 * r0, T, min_count, res + blockIdx.x);
+}
+
+/* grid (segments): one lane and one byte per pair, at the pair's flat index -- a list starts at any byte of the mask */
+template <class Rule>
+__global__ __launch_bounds__(G_BLOCK) void k_many_mask(const v4f* __restrict__ pts, const Segment* __restrict__ segs,
+                                                       const popsift_hip_ransac_result* __restrict__ res, float max_err2,
+                                                       uint8_t* __restrict__ mask)
+{
+    const Segment sg = segs[blockIdx.x];
+    if ((int)threadIdx.x >= sg.count) return;
+    const popsift_hip_ransac_result* __restrict__ r = res + sg.list;
+    float H[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) H[i] = r->H[i];
+    const size_t i = (size_t)sg.first + threadIdx.x;
+    mask[i] = r->hypothesis >= 0 && Rule::inlier(H, pts[i], max_err2) ? 1 : 0;
 }
 
 /* ---- popsift_hip_refit: least squares on the inliers, every round enqueued up front.  The state record starts like a
@@ -1005,6 +1158,7 @@ struct popsift_hip_verifier {
     size_t      d_cap = 0;
     char*       h_buf = nullptr; /* pinned: the points going up; the result record, the mask and the trace coming down */
     size_t      h_cap = 0;
+    int         many_group = 0; /* popsift_hip_verifier_debug_set_group; 0: POPSIFT_HIP_RANSAC_MANY_GROUP */
 };
 
 namespace {
@@ -1182,6 +1336,130 @@ int run_epipolar(popsift_hip_verifier* v, const float* pts, int n, const popsift
 {
     if (!epipolar_opts_valid(o)) return POPSIFT_HIP_ERR_INVALID;
     return run<FIT_EPIPOLAR>(v, pts, n, Fit{o->hypotheses, o->max_err, o->seed}, res, inlier, trace, samples, models, counts);
+}
+
+/* ---- popsift_hip_ransac_many */
+
+constexpr int MAX_LISTS = 1 << 20;
+
+bool many_opts_valid(const popsift_hip_ransac_many_opts* o)
+{
+    return o && o->kind >= FIT_HOMOGRAPHY && o->kind <= FIT_EPIPOLAR && o->hypotheses >= 1 && o->hypotheses <= MAX_HYP &&
+           std::isfinite(o->max_err) && o->max_err > 0.0f && o->reserved[0] == 0 && o->reserved[1] == 0 && o->reserved[2] == 0 &&
+           o->reserved[3] == 0;
+}
+
+bool many_args_valid(const popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists)
+{
+    if (!v || !offsets || n_lists < 0 || n_lists > MAX_LISTS || offsets[0] != 0) return false;
+    for (int m = 0; m < n_lists; m++)
+        if (offsets[m + 1] < offsets[m]) return false;
+    return offsets[n_lists] <= MAX_PAIRS && (offsets[n_lists] == 0 || pts);
+}
+
+/* One upload (points, offsets, segments), the bounds of every list, then per group of consecutive lists the models, the
+ * scores and the winners in that group's scratch, the masks of all lists, one download (records, masks) and one
+ * synchronisation.  A trace brings each group's three arrays down before the next group overwrites them.
+ * device: [bounds 32 / list][records][mask][points][offsets][segments][models][samples][counts], the last three for the
+ * largest group; pinned: [points][offsets][segments][records][mask][the trace's models][samples][counts].  As in run()
+ * the layout is a function of the arguments and every byte a call reads it has written before. */
+template <int KIND>
+int run_many(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists, const Fit& fit,
+             popsift_hip_ransac_result* res, uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+{
+    typedef Kind<KIND>        K;
+    typedef typename K::Rule Rule;
+    const int    T = fit.hypotheses;
+    const size_t P = (size_t)offsets[n_lists];
+    const int    group = v->many_group > 0 ? v->many_group : POPSIFT_HIP_RANSAC_MANY_GROUP;
+    const int    per_group = std::min(std::max(1, group / T), n_lists); /* lists of a group: at least one */
+    const int    n_groups = (n_lists + per_group - 1) / per_group;
+    size_t       n_seg = 0;
+    for (int m = 0; m < n_lists; m++) n_seg += ((size_t)(offsets[m + 1] - offsets[m]) + G_SEG - 1) / G_SEG;
+
+    const size_t recs = (size_t)per_group * T, all = (size_t)n_lists * T;
+    const size_t b_bounds = 32 * (size_t)n_lists, b_res = round16(sizeof(popsift_hip_ransac_result) * (size_t)n_lists),
+                 b_mask = round16(P), b_pts = sizeof(float) * 4 * P, b_off = round16(sizeof(int32_t) * ((size_t)n_lists + 1)),
+                 b_segs = sizeof(Segment) * n_seg, b_up = b_pts + b_off + b_segs;
+    const size_t o_res = b_bounds, o_mask = o_res + b_res, o_pts = o_mask + b_mask, o_off = o_pts + b_pts, o_segs = o_off + b_off,
+                 o_models = o_segs + b_segs, o_samples = o_models + round16(sizeof(float) * 9 * recs),
+                 o_counts = o_samples + sizeof(int) * K::row * recs, d_need = o_counts + round16(sizeof(int) * recs);
+    const size_t h_res = b_up, h_models = h_res + b_res + b_mask, h_samples = h_models + round16(sizeof(float) * 9 * all),
+                 h_counts = h_samples + sizeof(int) * K::row * all, h_need = trace ? h_counts + sizeof(int) * all : h_models;
+    if (hipSetDevice(v->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status ok;
+    if (!grow(ok, v, d_need, h_need)) return ok.rc;
+    hipStream_t const s = v->stream;
+    char* const       d = v->d_buf;
+    char* const       h = v->h_buf;
+    auto* const       d_bounds = (uint32_t*)d;
+    auto* const       d_res = (popsift_hip_ransac_result*)(d + o_res);
+    auto* const       d_mask = (uint8_t*)(d + o_mask);
+    auto* const       d_pts = (const v4f*)(d + o_pts);
+    auto* const       d_off = (const int*)(d + o_off);
+    auto* const       d_segs = (const Segment*)(d + o_segs);
+    auto* const       d_models = (float*)(d + o_models);
+    auto* const       d_samples = (int*)(d + o_samples);
+    auto* const       d_counts = (int*)(d + o_counts);
+    const float       max_err2 = fit.max_err * fit.max_err;
+
+    /* the pinned block going up; seg0[g]: the first segment of group g */
+    std::unique_ptr<size_t[]> seg0(new (std::nothrow) size_t[(size_t)n_groups + 1]);
+    if (!seg0) return POPSIFT_HIP_ERR_OOM;
+    if (b_pts) memcpy(h, pts, b_pts);
+    memset(h + b_pts, 0, b_off);
+    memcpy(h + b_pts, offsets, sizeof(int32_t) * ((size_t)n_lists + 1));
+    Segment* sg = (Segment*)(h + b_pts + b_off);
+    size_t   k = 0;
+    for (int m = 0; m < n_lists; m++) {
+        if (m % per_group == 0) seg0[m / per_group] = k;
+        const int n = offsets[m + 1] - offsets[m];
+        for (int i = 0; i < n; i += G_SEG) sg[k++] = Segment{m, offsets[m] + i, std::min(G_SEG, n - i), n <= G_SEG ? 1 : 0};
+    }
+    seg0[n_groups] = k;
+
+    if (ok(hipMemcpyAsync(d + o_pts, h, b_up, hipMemcpyHostToDevice, s)) && ok(hipMemsetAsync(d_bounds, 0, b_bounds, s))) {
+        if (n_seg) hipLaunchKernelGGL(k_many_bounds, dim3((unsigned)n_seg), dim3(G_BLOCK), 0, s, d_pts, d_segs, d_bounds);
+        for (int g = 0; g < n_groups && ok.good(); g++) {
+            const int    list0 = g * per_group, L = std::min(per_group, n_lists - list0);
+            const size_t ns = seg0[g + 1] - seg0[g], r0 = (size_t)list0 * T, nr = (size_t)L * T;
+            hipLaunchKernelGGL(k_many_models<KIND>, dim3(L, (T + 63) / 64), dim3(64), 0, s, d_pts, d_off, list0, T, fit.seed, d_bounds,
+                               d_models, d_samples, d_counts);
+            if (ns)
+                hipLaunchKernelGGL(k_many_score<Rule>, dim3((unsigned)ns, (T + G_BLOCK - 1) / G_BLOCK), dim3(G_BLOCK), 0, s, d_pts,
+                                   d_segs + seg0[g], list0, d_models, T, max_err2, d_counts);
+            hipLaunchKernelGGL(k_many_select, dim3(L), dim3(256), 0, s, d_counts, d_models, T, K::m, d_res + list0);
+            if (trace)
+                ok(hipMemcpyAsync(h + h_models + sizeof(float) * 9 * r0, d_models, sizeof(float) * 9 * nr, hipMemcpyDeviceToHost, s)) &&
+                    ok(hipMemcpyAsync(h + h_samples + sizeof(int) * K::row * r0, d_samples, sizeof(int) * K::row * nr,
+                                      hipMemcpyDeviceToHost, s)) &&
+                    ok(hipMemcpyAsync(h + h_counts + sizeof(int) * r0, d_counts, sizeof(int) * nr, hipMemcpyDeviceToHost, s));
+        }
+        if (n_seg && inlier)
+            hipLaunchKernelGGL(k_many_mask<Rule>, dim3((unsigned)n_seg), dim3(G_BLOCK), 0, s, d_pts, d_segs, d_res, max_err2, d_mask);
+        ok(hipGetLastError());
+    }
+    /* the records and, for a caller that takes them, the masks behind them */
+    if (ok.good() && ok(hipMemcpyAsync(h + h_res, d + o_res, b_res + (inlier ? P : 0), hipMemcpyDeviceToHost, s)) &&
+        ok(hipStreamSynchronize(s))) {
+        if (res) memcpy(res, h + h_res, sizeof *res * (size_t)n_lists);
+        if (inlier && P) memcpy(inlier, h + h_res + b_res, P);
+        if (models) memcpy(models, h + h_models, sizeof(float) * 9 * all);
+        if (samples) memcpy(samples, h + h_samples, sizeof(int) * K::row * all);
+        if (counts) memcpy(counts, h + h_counts, sizeof(int) * all);
+    }
+    return ok.rc;
+}
+
+int ransac_many(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists, const popsift_hip_ransac_many_opts* o,
+                popsift_hip_ransac_result* res, uint8_t* inlier, bool trace, int32_t* samples, float* models, int32_t* counts)
+{
+    if (!many_opts_valid(o) || !many_args_valid(v, pts, offsets, n_lists) || (!trace && !res)) return POPSIFT_HIP_ERR_INVALID;
+    if (n_lists == 0) return POPSIFT_HIP_OK;
+    const Fit fit{o->hypotheses, o->max_err, o->seed};
+    return o->kind == FIT_HOMOGRAPHY ? run_many<FIT_HOMOGRAPHY>(v, pts, offsets, n_lists, fit, res, inlier, trace, samples, models, counts)
+           : o->kind == FIT_AFFINE   ? run_many<FIT_AFFINE>(v, pts, offsets, n_lists, fit, res, inlier, trace, samples, models, counts)
+                                     : run_many<FIT_EPIPOLAR>(v, pts, offsets, n_lists, fit, res, inlier, trace, samples, models, counts);
 }
 
 bool refit_opts_valid(const popsift_hip_refit_opts* o)
@@ -1379,7 +1657,36 @@ int popsift_hip_epipolar_trace(popsift_hip_verifier* v, const float* pts, int n,
     return run_epipolar(v, pts, n, o, nullptr, nullptr, true, samples, models, counts);
 }
 
-int popsift_hip_pair_points(const popsift_hip_devfeatures* lc, const popsift_hip_devfeatures* r, const popsift_hip_pair* pairs,
+void popsift_hip_default_ransac_many_opts(popsift_hip_ransac_many_opts* o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->kind = POPSIFT_HIP_REFIT_HOMOGRAPHY;
+    o->hypotheses = 2048;
+    o->max_err = 2.0f;
+}
+
+int popsift_hip_ransac_many(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists,
+                            const popsift_hip_ransac_many_opts* o, popsift_hip_ransac_result* res, uint8_t* inlier)
+{
+    return ransac_many(v, pts, offsets, n_lists, o, res, inlier, false, nullptr, nullptr, nullptr);
+}
+
+int popsift_hip_ransac_many_trace(popsift_hip_verifier* v, const float* pts, const int32_t* offsets, int n_lists,
+                                  const popsift_hip_ransac_many_opts* o, popsift_hip_ransac_result* res, uint8_t* inlier,
+                                  int32_t* samples, float* models, int32_t* counts)
+{
+    return ransac_many(v, pts, offsets, n_lists, o, res, inlier, true, samples, models, counts);
+}
+
+int popsift_hip_verifier_debug_set_group(popsift_hip_verifier* v, int records)
+{
+    if (!v || records < 0) return POPSIFT_HIP_ERR_INVALID;
+    v->many_group = records;
+    return POPSIFT_HIP_OK;
+}
+
+int popsift_hip_pair_points(const popsift_hip_devfeatures* lc,const popsift_hip_devfeatures* r, const popsift_hip_pair* pairs,
                             int n, float* pts)
 {
     if (!lc || !r || n < 0 || (n > 0 && (!pairs || !pts))) return POPSIFT_HIP_ERR_INVALID;

@@ -254,55 +254,73 @@ constexpr int     GALLERY_MAX_MEMBERS = 1 << 20;
 
 /* Room for n more descriptors and one more member.  New buffers are filled device to device and swapped in only when
  * every allocation has succeeded: a failure leaves the gallery as it was. */
-int gallery_reserve(popsift_hip_gallery* g, int n, hipStream_t s)
+int gallery_reserve(popsift_hip_gallery* g, int n, bool with_xy, hipStream_t s)
 {
     if ((size_t)g->n_members + 1 > g->tab_cap) {
         const size_t   cap = std::max<size_t>(2 * g->tab_cap, 64);
         int64_t* const first = (int64_t*)malloc(sizeof(int64_t) * cap);
         int* const     count = (int*)malloc(sizeof(int) * cap);
-        if (!first || !count) {
+        uint8_t* const has_xy = (uint8_t*)malloc(cap);
+        if (!first || !count || !has_xy) {
             free(first);
             free(count);
+            free(has_xy);
             return POPSIFT_HIP_ERR_OOM;
         }
         if (g->n_members > 0) {
             memcpy(first, g->first, sizeof(int64_t) * (size_t)g->n_members);
             memcpy(count, g->count, sizeof(int) * (size_t)g->n_members);
+            memcpy(has_xy, g->has_xy, (size_t)g->n_members);
         }
         free(g->first);
         free(g->count);
+        free(g->has_xy);
         g->first = first;
         g->count = count;
+        g->has_xy = has_xy;
         g->tab_cap = cap;
     }
+    /* the positions exist from the first member that brings some, and are as long as the descriptors from then on */
+    const bool   xy = with_xy || g->d_xy;
     const size_t need = (size_t)g->n_desc + (size_t)n;
-    if (need <= g->cap) return POPSIFT_HIP_OK;
-    const size_t cap = std::max(need, std::max<size_t>(2 * g->cap, 1024));
+    if (need <= g->cap && (!xy || g->d_xy)) return POPSIFT_HIP_OK;
+    const bool   more = need > g->cap;
+    const size_t cap = more ? std::max(need, std::max<size_t>(2 * g->cap, 1024)) : g->cap;
     uint8_t*     desc = nullptr;
     int*         norm = nullptr;
+    float*       pos = nullptr;
     Status       ok;
-    if (ok(hipMalloc((void**)&desc, 128 * cap)) && ok(hipMalloc((void**)&norm, sizeof(int) * cap)) && g->n_desc > 0)
+    if (more && ok(hipMalloc((void**)&desc, 128 * cap)) && ok(hipMalloc((void**)&norm, sizeof(int) * cap)) && g->n_desc > 0)
         ok(hipMemcpyAsync(desc, g->d_desc, 128 * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s)) &&
-            ok(hipMemcpyAsync(norm, g->d_norm, sizeof(int) * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s)) &&
-            ok(hipStreamSynchronize(s));
+            ok(hipMemcpyAsync(norm, g->d_norm, sizeof(int) * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s));
+    if (xy && ok.good() && ok(hipMalloc((void**)&pos, sizeof(float) * 2 * std::max<size_t>(cap, 1))) && g->d_xy && g->n_desc > 0)
+        ok(hipMemcpyAsync(pos, g->d_xy, sizeof(float) * 2 * (size_t)g->n_desc, hipMemcpyDeviceToDevice, s));
+    if (ok.good()) ok(hipStreamSynchronize(s));
     if (!ok.good()) {
-        free_bufs({desc, norm});
+        free_bufs({desc, norm, pos});
         return ok.rc;
     }
-    free_bufs({g->d_desc, g->d_norm});
-    g->d_desc = desc;
-    g->d_norm = norm;
-    g->cap = cap;
+    if (more) {
+        free_bufs({g->d_desc, g->d_norm});
+        g->d_desc = desc;
+        g->d_norm = norm;
+        g->cap = cap;
+    }
+    if (xy) {
+        free_bufs({g->d_xy});
+        g->d_xy = pos;
+    }
     return POPSIFT_HIP_OK;
 }
 
-/* a new member of n descriptors from `src` (device memory of src_device, or host memory with src_device < 0) */
-int gallery_append(popsift_hip_gallery* g, const uint8_t* src, int src_device, int n, int* member)
+/* a new member of n descriptors from `src` (device memory of src_device, or host memory with src_device < 0); xy: its
+ * n x 2 positions in device memory of src_device, or NULL for a member without positions */
+int gallery_append(popsift_hip_gallery* g, const uint8_t* src, int src_device, int n, const float* xy, int* member)
 {
     if (g->n_desc + n > GALLERY_MAX_DESC || g->n_members + 1 > GALLERY_MAX_MEMBERS) return POPSIFT_HIP_ERR_INVALID;
     if (hipSetDevice(g->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
     hipStream_t const s = (hipStream_t)g->stream;
-    if (int rc = gallery_reserve(g, n, s)) return rc;
+    if (int rc = gallery_reserve(g, n, xy != nullptr, s)) return rc;
     if (n > 0) {
         uint8_t* const dst = g->d_desc + 128 * (size_t)g->n_desc;
         const size_t   bytes = 128 * (size_t)n;
@@ -310,21 +328,137 @@ int gallery_append(popsift_hip_gallery* g, const uint8_t* src, int src_device, i
         if (src_device < 0) ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
         else if (src_device == g->device) ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s));
         else ok(hipMemcpyPeer(dst, g->device, src, src_device, bytes));
+        if (ok.good() && xy) {
+            float* const pos = g->d_xy + 2 * (size_t)g->n_desc;
+            if (src_device == g->device) ok(hipMemcpyAsync(pos, xy, sizeof(float) * 2 * (size_t)n, hipMemcpyDeviceToDevice, s));
+            else ok(hipMemcpyPeer(pos, g->device, xy, src_device, sizeof(float) * 2 * (size_t)n));
+        }
         if (ok.good()) ok(launch_norms_u8(dst, n, g->d_norm + g->n_desc, s));
         if (ok.good()) ok(hipStreamSynchronize(s));
         if (!ok.good()) return ok.rc;
     }
     g->first[g->n_members] = g->n_desc;
     g->count[g->n_members] = n;
+    g->has_xy[g->n_members] = xy != nullptr;
     if (member) *member = g->n_members;
     g->n_members += 1;
     g->n_desc += n;
     return POPSIFT_HIP_OK;
 }
 
+/* (xpos, ypos) of the feature behind each of a set's n descriptors; *bad = 1 when a map entry names no feature */
+__global__ __launch_bounds__(256) void k_member_xy(const DevFeature* __restrict__ feat, const int* __restrict__ rev, int n_feat,
+                                                   int n, float2* __restrict__ xy, int* __restrict__ bad)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int f = rev[i];
+    if (f < 0 || f >= n_feat) {
+        *bad = 1;
+        xy[i] = make_float2(0.0f, 0.0f);
+        return;
+    }
+    xy[i] = make_float2(feat[f].xpos, feat[f].ypos);
+}
+
+/* item = (descriptor of l, row of the gallery): the point pair (x, y of the feature behind l's descriptor, the gallery's
+ * position of the row); *bad = 1 when l's map names no feature */
+__global__ __launch_bounds__(256) void k_gallery_points(const int2* __restrict__ items, int n, const DevFeature* __restrict__ lf,
+                                                        const int* __restrict__ lrev, int l_nfeat, const float2* __restrict__ xy,
+                                                        float4* __restrict__ out, int* __restrict__ bad)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int2 it = items[i];
+    const int  f = lrev[it.x];
+    if (f < 0 || f >= l_nfeat) {
+        *bad = 1;
+        out[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float2 r = xy[it.y];
+    out[i] = make_float4(lf[f].xpos, lf[f].ypos, r.x, r.y);
+}
+
 }  // namespace
 
 extern "C" {
+
+int popsift_hip_gallery_add_set(popsift_hip_gallery* g, const popsift_hip_devfeatures* f, int* member)
+{
+    if (!g || !f) return POPSIFT_HIP_ERR_INVALID;
+    /* on the set's GPU: its bytes (those of popsift_hip_bytefeatures_from_set) and, behind a flag, its positions */
+    popsift_hip_bytefeatures* b = nullptr;
+    if (int rc = popsift_hip_bytefeatures_from_set(f, &b)) return rc;
+    const int n = f->n_desc;
+    char*     d_xy = nullptr;
+    int       bad = 0;
+    Status    ok;
+    if (ok(hipMalloc((void**)&d_xy, 16 + sizeof(float2) * (size_t)std::max(n, 1))) && ok(hipMemsetAsync(d_xy, 0, 16, nullptr)) &&
+        n > 0) {
+        hipLaunchKernelGGL(k_member_xy, dim3((n + 255) / 256), dim3(256), 0, nullptr, f->d_feat, f->d_rev, f->n_feat, n,
+                           (float2*)(d_xy + 16), (int*)d_xy);
+        ok(hipGetLastError());
+    }
+    if (ok.good()) ok(hipMemcpy(&bad, d_xy, sizeof bad, hipMemcpyDeviceToHost));
+    if (ok.good() && bad) ok.rc = POPSIFT_HIP_ERR_INVALID;
+    if (ok.good()) ok.rc = gallery_append(g, b->d_desc, b->device, n, (const float*)(d_xy + 16), member);
+    (void)hipSetDevice(f->device);
+    if (d_xy) (void)hipFree(d_xy);
+    (void)popsift_hip_bytefeatures_free(b);
+    return ok.rc;
+}
+
+int popsift_hip_gallery_pair_points(const popsift_hip_devfeatures* l, popsift_hip_gallery* g, const popsift_hip_pair* pairs,
+                                    const int32_t* offsets, float* pts)
+{
+    if (!l || !g || !offsets || offsets[0] != 0) return POPSIFT_HIP_ERR_INVALID;
+    for (int m = 0; m < g->n_members; m++)
+        if (offsets[m + 1] < offsets[m]) return POPSIFT_HIP_ERR_INVALID;
+    const int n = offsets[g->n_members];
+    if (n > 0 && (!pairs || !pts)) return POPSIFT_HIP_ERR_INVALID;
+    for (int m = 0; m < g->n_members; m++) {
+        if (offsets[m + 1] > offsets[m] && !g->has_xy[m]) return POPSIFT_HIP_ERR_INVALID;
+        for (int i = offsets[m]; i < offsets[m + 1]; i++)
+            if (pairs[i].l < 0 || pairs[i].l >= l->n_desc || pairs[i].r < 0 || pairs[i].r >= g->count[m]) return POPSIFT_HIP_ERR_INVALID;
+    }
+    if (n == 0) return POPSIFT_HIP_OK;
+    if (hipSetDevice(g->device) != hipSuccess) return POPSIFT_HIP_ERR_DEVICE;
+    Status            ok;
+    hipStream_t const s = (hipStream_t)g->stream;
+    /* device block and its pinned twin: a flag, the items, the points */
+    const size_t b_items = round16(sizeof(int2) * (size_t)n), b_pts = sizeof(float) * 4 * (size_t)n;
+    grow_twin(ok, g->xy_dev, g->xy_host, g->xy_cap, 16 + b_items + b_pts);
+    /* a query set on another GPU: its feature records and its map come over for the call */
+    const DevFeature* lf = l->d_feat;
+    const int*        lrev = l->d_rev;
+    PeerCopy          peer;
+    if (peer.fetch(ok, g->device, l->device,
+                   {{l->d_feat, sizeof(DevFeature) * (size_t)std::max(l->n_feat, 1)}, {l->d_rev, sizeof(int) * (size_t)l->n_desc}})) {
+        lf = (const DevFeature*)peer.at[0];
+        lrev = (const int*)peer.at[1];
+    }
+    if (ok.good()) {
+        char* const d = (char*)g->xy_dev;
+        char* const h = (char*)g->xy_host;
+        memset(h, 0, 16);
+        int2* const items = (int2*)(h + 16);
+        for (int m = 0; m < g->n_members; m++)
+            for (int i = offsets[m]; i < offsets[m + 1]; i++) items[i] = make_int2(pairs[i].l, (int)(g->first[m] + pairs[i].r));
+        if (ok(hipMemcpyAsync(d, h, 16 + b_items, hipMemcpyHostToDevice, s))) {
+            hipLaunchKernelGGL(k_gallery_points, dim3((n + 255) / 256), dim3(256), 0, s, (const int2*)(d + 16), n, lf, lrev, l->n_feat,
+                               (const float2*)g->d_xy, (float4*)(d + 16 + b_items), (int*)d);
+            ok(hipGetLastError());
+        }
+        /* the flag and the points come down; the items in between stay */
+        if (ok.good() && ok(hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, s)) &&
+            ok(hipMemcpyAsync(h + 16 + b_items, d + 16 + b_items, b_pts, hipMemcpyDeviceToHost, s)) && ok(hipStreamSynchronize(s))) {
+            if (*(const int*)h != 0) ok.rc = POPSIFT_HIP_ERR_INVALID;
+            else memcpy(pts, h + 16 + b_items, b_pts);
+        }
+    }
+    return ok.rc;
+}
 
 int popsift_hip_gallery_create(int device, popsift_hip_gallery** out)
 {
@@ -354,13 +488,13 @@ int popsift_hip_gallery_free(popsift_hip_gallery* g)
 int popsift_hip_gallery_add(popsift_hip_gallery* g, const popsift_hip_bytefeatures* f, int* member)
 {
     if (!g || !f) return POPSIFT_HIP_ERR_INVALID;
-    return gallery_append(g, f->d_desc, f->device, f->n_desc, member);
+    return gallery_append(g, f->d_desc, f->device, f->n_desc, nullptr, member);
 }
 
 int popsift_hip_gallery_add_host(popsift_hip_gallery* g, const uint8_t* desc, int n_descriptors, int* member)
 {
     if (!g || n_descriptors < 0 || (n_descriptors > 0 && !desc)) return POPSIFT_HIP_ERR_INVALID;
-    return gallery_append(g, desc, -1, n_descriptors, member);
+    return gallery_append(g, desc, -1, n_descriptors, nullptr, member);
 }
 
 int popsift_hip_gallery_info(const popsift_hip_gallery* g, int* device, int* n_members, int64_t* n_descriptors)

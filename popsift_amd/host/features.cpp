@@ -479,6 +479,31 @@ int Gallery::add(FeaturesDevBytes* member)
     return m;
 }
 
+int Gallery::add(FeaturesDev* member)
+{
+    int       m = -1;
+    const int rc = popsift_hip_gallery_add_set(_gallery, member ? member->getHandle() : 0, &m);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot add the set to the gallery", rc);
+    return m;
+}
+
+std::vector<float> Gallery::pairPoints(FeaturesDev* query, const std::vector<std::vector<Pair>>& pairs, std::vector<int>& offsets)
+{
+    static_assert(sizeof(Pair) == sizeof(popsift_hip_pair) && sizeof(int) == sizeof(int32_t), "Pair is popsift_hip_pair");
+    if ((int)pairs.size() != size()) dev_fatal("one pair list per member", POPSIFT_HIP_ERR_INVALID);
+    offsets.assign(pairs.size() + 1, 0);
+    std::vector<Pair> flat;
+    for (size_t m = 0; m < pairs.size(); m++) {
+        flat.insert(flat.end(), pairs[m].begin(), pairs[m].end());
+        offsets[m + 1] = (int)flat.size();
+    }
+    std::vector<float> pts(4 * flat.size());
+    const int rc = popsift_hip_gallery_pair_points(query ? query->getHandle() : 0, _gallery, flat.empty() ? 0 : (const popsift_hip_pair*)flat.data(),
+                                                   offsets.data(), flat.empty() ? 0 : pts.data());
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot gather the gallery's points", rc);
+    return pts;
+}
+
 int Gallery::size() const
 {
     int n = 0;

@@ -13,6 +13,9 @@
  * (Verifier::refit) and prints the refitted model under the RANSAC block; with --guided the refitted model is the guide.
  * Extension: --gallery FILE (repeatable, instead of -r; implies --bytes --pairs) matches the left image against every
  * gallery image in one pass (popsift::Gallery) and prints, per gallery image in the order given, its pair count and pairs.
+ * Extension: --gallery-verify homography|affine|epipolar [--hypotheses T] [--max-err E] [--seed S] with --gallery fits the
+ * model to every gallery image's pairs in one call (Gallery::pairPoints, Verifier::ransacMany) and prints it with its inlier
+ * count under the image's pair lines, then, after the total, the gallery images ranked by their inliers.
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -22,6 +25,7 @@
 
 #include <popsift_hip.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,6 +56,7 @@ static float guided_err = 0.0f; /* 0: --max-err */
 static bool refit_model = false;
 static int refit_rounds = 4;
 static vector<string> gallery_files;
+static string gallery_verify; /* empty: off */
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -144,8 +149,20 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.val("gallery", 0, "Matching",
           "Match the left image against this image too; repeatable, replaces --right and implies --bytes --pairs.  All\n"
           "gallery images are matched in one pass on the GPU; prints per image, in the order given, a line\n"
-          "'gallery <k> <file>: <n> pairs' and its pair lines, then the total.  Not with --verify or --guided",
+          "'gallery <k> <file>: <n> pairs' and its pair lines, then the total.  Not with --verify or --guided (see\n"
+          "--gallery-verify)",
           [&](const string& v) { gallery_files.push_back(v); });
+    o.val("gallery-verify", 0, "Matching",
+          "With --gallery: fit a model (homography, affine or epipolar) to every gallery image's pairs by RANSAC, all\n"
+          "images in one call on the GPU, with --hypotheses, --max-err and --seed as for --verify; prints the model and\n"
+          "the number of inliers under each image's pair lines and, after the total, the images ranked by inliers",
+          [&](const string& v) {
+              if (v != "homography" && v != "affine" && v != "epipolar") {
+                  cerr << "--gallery-verify: homography, affine or epipolar, not " << v << endl;
+                  exit(-1);
+              }
+              gallery_verify = v;
+          });
     o.val("feature-order", 0, "Extensions",
           "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
           "pixel column, level: the same bytes on every run)",
@@ -173,6 +190,10 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
             exit(-1);
         }
         match_bytes = print_pairs = true;
+    }
+    if (!gallery_verify.empty() && gallery_files.empty()) {
+        cerr << "--gallery-verify verifies the images of a gallery: add --gallery" << endl;
+        exit(-1);
     }
     if (verify_pairs && !print_pairs) {
         cerr << "--verify works on the pairs: add --pairs" << endl;
@@ -301,21 +322,50 @@ static int match_gallery_files(const string& lFile, PopSift& sift)
         cout << "Number of descriptors: " << feat->getDescriptorCount() << endl;
         popsift::FeaturesDevBytes* bytes = feat->toBytes();
         r_fem.push_back(reverse_map(bytes));
-        gallery.add(bytes); /* copied: the set can go */
+        /* copied: the set can go.  For --gallery-verify the float set, whose positions the gallery keeps with the bytes */
+        if (gallery_verify.empty()) gallery.add(bytes);
+        else gallery.add(feat);
         delete bytes;
         delete feat;
         delete job;
     }
     const vector<vector<popsift::Gallery::Pair>> all = gallery.matchPairs(lBytes, pair_opts);
     size_t                                       total = 0;
+    vector<popsift::RansacResult>                fits;
+    if (!gallery_verify.empty()) {
+        popsift::Verifier    verifier(lFeatures->getDevice());
+        popsift::ManyOptions mo;
+        mo.kind = gallery_verify == "epipolar" ? popsift::ManyOptions::Epipolar
+                  : gallery_verify == "affine" ? popsift::ManyOptions::Affine
+                                               : popsift::ManyOptions::Homography;
+        mo.hypotheses = verify_opts.hypotheses;
+        mo.maxErr = verify_opts.maxErr;
+        mo.seed = verify_opts.seed;
+        vector<int>         offsets;
+        const vector<float> pts = gallery.pairPoints(lFeatures, all, offsets);
+        fits = verifier.ransacMany(pts, offsets, mo);
+    }
     for (size_t k = 0; k < all.size(); k++) {
         printf("gallery %zu %s: %zu pairs\n", k, gallery_files[k].c_str(), all[k].size());
         for (const popsift::Gallery::Pair& p : all[k])
             printf("pair feat %4d [%4d] matches feat %4d [%4d] dist %.3f\n", l_fem[(size_t)p.l], p.l, r_fem[k][(size_t)p.r], p.r,
                    sqrtf(p.distBest));
         total += all[k].size();
+        if (fits.empty()) continue;
+        printf("Model (%s):\n", gallery_verify.c_str());
+        for (int i = 0; i < 3; i++) printf("  %.9g %.9g %.9g\n", fits[k].H[3 * i], fits[k].H[3 * i + 1], fits[k].H[3 * i + 2]);
+        printf("Number of inliers:     %d of %zu\n", fits[k].inliers, all[k].size());
     }
     printf("Number of pairs:       %zu\n", total);
+    if (!fits.empty()) {
+        /* most inliers first, the order given on a tie */
+        vector<size_t> rank(fits.size());
+        for (size_t k = 0; k < rank.size(); k++) rank[k] = k;
+        stable_sort(rank.begin(), rank.end(), [&](size_t a, size_t b) { return fits[a].inliers > fits[b].inliers; });
+        printf("Ranking by inliers:   ");
+        for (size_t k : rank) printf(" %zu (%d)", k, fits[k].inliers);
+        printf("\n");
+    }
     delete lBytes;
     delete lFeatures;
     delete lJob;

@@ -68,6 +68,32 @@ RansacResult Verifier::epipolar(const std::vector<float>& pts, const EpipolarOpt
     return out;
 }
 
+std::vector<RansacResult> Verifier::ransacMany(const std::vector<float>& pts, const std::vector<int>& offsets,
+                                               const ManyOptions& opts)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "offsets are int32_t");
+    const int                              n_lists = offsets.empty() ? 0 : (int)offsets.size() - 1;
+    std::vector<RansacResult>              out((size_t)n_lists);
+    std::vector<popsift_hip_ransac_result> res((size_t)n_lists);
+    std::vector<unsigned char>             mask(pts.size() / 4);
+    popsift_hip_ransac_many_opts           o;
+    popsift_hip_default_ransac_many_opts(&o);
+    o.kind = (int)opts.kind;
+    o.hypotheses = opts.hypotheses;
+    o.max_err = opts.maxErr;
+    o.seed = opts.seed;
+    if (n_lists == 0) return out;
+    if (offsets.back() < 0 || (size_t)offsets.back() != mask.size()) verify_fatal("the offsets do not end at the last pair", POPSIFT_HIP_ERR_INVALID);
+    const int rc = popsift_hip_ransac_many(_v, pts.empty() ? 0 : pts.data(), offsets.data(), n_lists, &o, res.data(),
+                                           mask.empty() ? 0 : mask.data());
+    if (rc != POPSIFT_HIP_OK) verify_fatal("verification of the lists failed", rc);
+    for (int m = 0; m < n_lists; m++) {
+        take(out[(size_t)m], res[(size_t)m]);
+        out[(size_t)m].mask.assign(mask.begin() + offsets[(size_t)m], mask.begin() + offsets[(size_t)m + 1]);
+    }
+    return out;
+}
+
 RefitResult Verifier::refit(const std::vector<float>& pts, const RefitOptions& opts)
 {
     RefitResult              out;
