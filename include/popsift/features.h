@@ -279,6 +279,23 @@ public:
      * into them (popsift_hip_gallery_pair_points): the input of Verifier::ransacMany.  query is the float set the query
      * bytes came from; every member with a pair was added as a FeaturesDev. */
     std::vector<float> pairPoints(FeaturesDev* query, const std::vector<std::vector<Pair>>& pairs, std::vector<int>& offsets);
+
+    /* Members against members (popsift_hip_match_pairs_links): a link is an ordered pair of member indices, left image a
+     * and right image b; any list of them, a == b and repeats included. */
+    struct Link {
+        int a, b;
+    };
+    /* every a < b of n members, a-major: exhaustive matching */
+    static std::vector<Link> allLinks(int n);
+    /* (a, a + 1 .. a + k) for every member a of a sequence of n */
+    static std::vector<Link> sequentialLinks(int n, int k);
+    /* one pair list per link, each as memberA->matchPairs(memberB, opts) returns it for the sets the members came from */
+    std::vector<std::vector<Pair>> matchPairs(const std::vector<Link>& links, const MatchOptions& opts);
+    std::vector<std::vector<Pair>> matchPairs(const std::vector<Link>& links) { return matchPairs(links, MatchOptions()); }
+    /* (x, y, x', y') of every pair of those lists, list after list, and the lists' offsets (links.size() + 1, from 0)
+     * into them (popsift_hip_gallery_link_points): the input of Verifier::ransacMany.  Both positions are the members'
+     * own: every member of a link with a pair was added as a FeaturesDev. */
+    std::vector<float> pairPoints(const std::vector<Link>& links, const std::vector<std::vector<Pair>>& pairs, std::vector<int>& offsets);
 };
 
 }  // namespace popsift

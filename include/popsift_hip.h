@@ -694,6 +694,52 @@ int popsift_hip_match_pairs_gallery(const popsift_hip_bytefeatures* l, popsift_h
                                     int32_t* offsets /* n_members + 1 */, int* n_pairs);
 
 /*
+ * Members against members: which images of a collection show the same thing as each other (the exhaustive and sequential
+ * matching of structure from motion and stitching).  A link is an ordered pair (a, b) of member indices of one gallery:
+ * left image a, right image b.  The caller supplies any list of links -- all a < b, (a, a + 1 .. a + k) for a sequence,
+ * a retrieval shortlist; a == b and repeated links are allowed and answered like any other link.
+ *
+ * The three calls define nothing new; they are stated through the per-pair calls.  A_e and B_e are the byte sets
+ * popsift_hip_bytefeatures_from_host makes of popsift_hip_gallery_download(g, a_e) and (g, b_e).
+ * popsift_hip_match_links writes the rows of every link, link after link: those of link e start at
+ * R[e] = sum over e' < e of count[a_e'], and out[R[e] + i] is, bit for bit, row i of popsift_hip_match_bytes(A_e, B_e).
+ * An empty B_e gives {0, 0, 0, +INFINITY, +INFINITY} rows, an empty A_e no rows.  cap_rows < R[n_links]: ERR_TOO_SMALL
+ * and nothing is written.
+ * popsift_hip_match_pairs_links returns the pairs in CSR form: pairs[offsets[e] .. offsets[e + 1]) is exactly the array
+ * popsift_hip_match_pairs_bytes(A_e, B_e, opts, ..) returns (conditions 1 to 4, ascending l, l local to a_e, r local to
+ * b_e).  offsets[0] = 0 and *n_pairs = offsets[n_links]; offsets (n_links + 1 ints) is always written in full; the first
+ * min(*n_pairs, cap) pairs are written, more than cap is ERR_TOO_SMALL with the count and the offsets valid; R[n_links] is
+ * always a sufficient cap; cap = 0 with pairs = NULL asks for the counts alone (the edge weights of the view graph).
+ * popsift_hip_gallery_link_points turns that CSR into the points popsift_hip_ransac_many takes, unchanged:
+ * pts[i] = (x, y of descriptor pairs[i].l of member a_e, x', y' of descriptor pairs[i].r of member b_e), e the link i
+ * lies in.  Both positions come from the gallery's position array (popsift_hip_gallery_add_set members): the floats
+ * popsift_hip_pair_points gathers from the sets the members came from.
+ * The results are a function of the gallery's bytes, the link list and the options: the same bytes on every run.
+ *
+ * ERR_INVALID, before any GPU call and with nothing written: a NULL gallery, opts, offsets or n_pairs; links NULL with
+ * n_links > 0; n_links < 0 or > 2^20 (popsift_hip_ransac_many's limit); an a or b outside 0 .. n_members - 1;
+ * R[n_links] > INT32_MAX; pairs (cap > 0) or out (rows to write) NULL; the opts checks of popsift_hip_match_pairs_bytes.
+ * popsift_hip_gallery_link_points also: offsets[0] != 0 or a decreasing offset; pairs or pts NULL with pairs present; a
+ * pair index outside its member; a non-empty list on a link with a member that has no positions.
+ * n_links == 0: OK, *n_pairs = 0 and offsets[0] = 0.
+ *
+ * One call at a time per gallery, as above; everything lives on the gallery's GPU.  The links are walked in groups of
+ * consecutive links holding at most POPSIFT_HIP_GALLERY_GROUP_ROWS left rows (popsift_hip_gallery_debug_set_group_rows
+ * applies), always at least one link; a group costs a fixed number of launches and at most one read-back whatever the
+ * number of its links (match_links.hip), and results do not depend on the grouping.
+ */
+typedef struct popsift_hip_link {
+    int32_t a, b;
+} popsift_hip_link; /* 8 bytes */
+int popsift_hip_match_links(popsift_hip_gallery* g, const popsift_hip_link* links, int n_links, popsift_hip_match* out,
+                            size_t cap_rows);
+int popsift_hip_match_pairs_links(popsift_hip_gallery* g, const popsift_hip_link* links, int n_links,
+                                  const popsift_hip_match_opts* opts, popsift_hip_pair* pairs, size_t cap,
+                                  int32_t* offsets /* n_links + 1 */, int* n_pairs);
+int popsift_hip_gallery_link_points(popsift_hip_gallery* g, const popsift_hip_link* links, int n_links,
+                                    const popsift_hip_pair* pairs, const int32_t* offsets /* n_links + 1 */, float* pts);
+
+/*
  * Geometric verification: RANSAC over point pairs (OpenCV's findHomography(.., RANSAC), CudaSift's FindHomography).  Given
  * n pairs (x, y) -> (x', y') the verifier returns the model with the most inliers among T sampled hypotheses, its inlier
  * count and a per-pair inlier mask.  The result is a function of (points, options) alone: the same bytes on every run.

@@ -223,6 +223,9 @@ SYMBOLS = [
     ("popsift_hip_gallery_debug_set_group_rows", C.c_int, [_vp, C.c_int]),
     ("popsift_hip_match_gallery", C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     ("popsift_hip_match_pairs_gallery", C.c_int, [_vp, _vp, C.POINTER(MatchOpts), _vp, C.c_size_t, _vp, _ip]),
+    ("popsift_hip_match_links", C.c_int, [_vp, _vp, C.c_int, _vp, C.c_size_t]),
+    ("popsift_hip_match_pairs_links", C.c_int, [_vp, _vp, C.c_int, C.POINTER(MatchOpts), _vp, C.c_size_t, _vp, _ip]),
+    ("popsift_hip_gallery_link_points", C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
     ("popsift_hip_verifier_create", C.c_int, [C.c_int, C.POINTER(_vp)]),
     ("popsift_hip_verifier_free", C.c_int, [_vp]),
     ("popsift_hip_default_ransac_opts", None, [C.POINTER(RansacOpts)]),
@@ -546,6 +549,26 @@ class ByteFeatures:
 
 
 GALLERY_GROUP_ROWS = 1 << 22  # POPSIFT_HIP_GALLERY_GROUP_ROWS
+# popsift_hip_link: an ordered pair of member indices of one gallery, left image a and right image b
+LINK_DTYPE = np.dtype([("a", np.int32), ("b", np.int32)])
+
+
+def as_links(links):
+    """a LINK_DTYPE array of anything that holds (a, b) pairs"""
+    if isinstance(links, np.ndarray) and links.dtype == LINK_DTYPE:
+        return np.ascontiguousarray(links).reshape(-1)
+    return np.ascontiguousarray(np.asarray(links, np.int32).reshape(-1, 2)).view(LINK_DTYPE).reshape(-1)
+
+
+def all_links(n):
+    """every a < b of n members, a-major: exhaustive matching"""
+    a, b = np.triu_indices(n, 1)
+    return as_links(np.stack([a, b], axis=1))
+
+
+def sequential_links(n, k):
+    """(a, a + 1 .. a + k) for every member a of a sequence of n"""
+    return as_links([(a, b) for a in range(n) for b in range(a + 1, min(a + k, n - 1) + 1)])
 
 
 class Gallery:
@@ -648,6 +671,65 @@ class Gallery:
         if rc not in (OK, ERR_TOO_SMALL):                              # more pairs than cap = 0: the count is the answer
             raise PopsiftHipError(rc, "popsift_hip_match_pairs_gallery")
         return np.diff(offsets)
+
+    def _left_rows(self, links):
+        """R[n_links]: the rows of match_links(), and a cap that always suffices for the pairs.  A left member out of range
+        raises here as it would in the call."""
+        counts = {int(a): self.member(int(a))[1] for a in np.unique(links["a"])}
+        return sum(counts[int(a)] for a in links["a"])
+
+    def match_links(self, links):
+        """popsift_hip_match_links: the MATCH_DTYPE rows of every link, link after link; those of link e are member a_e
+        matched against member b_e"""
+        links = as_links(links)
+        out = np.zeros(self._left_rows(links), MATCH_DTYPE)
+        rc = lib().popsift_hip_match_links(self._h, links.ctypes.data if len(links) else None, len(links),
+                                           out.ctypes.data if len(out) else None, len(out))
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_links")
+        return out
+
+    def _pairs_links(self, links, cap, ratio, max_dist2, cross_check):
+        out = np.empty(cap, PAIR_DTYPE)                                # the first n are written; untouched pages cost nothing
+        offsets = np.zeros(len(links) + 1, np.int32)
+        opts = MatchOpts(ratio, max_dist2, 1 if cross_check else 0, 0)
+        n = C.c_int(0)
+        rc = lib().popsift_hip_match_pairs_links(self._h, links.ctypes.data if len(links) else None, len(links), C.byref(opts),
+                                                 out.ctypes.data if cap else None, cap, offsets.ctypes.data, C.byref(n))
+        return rc, n.value, out, offsets
+
+    def match_pairs_links(self, links, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """popsift_hip_match_pairs_links: (pairs, offsets); pairs[offsets[e]:offsets[e + 1]] is what the per-pair call returns
+        for member a_e on the left and member b_e on the right"""
+        links = as_links(links)
+        rc, n, out, offsets = self._pairs_links(links, self._left_rows(links), ratio, max_dist2, cross_check)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_links")
+        return out[:n].copy(), offsets
+
+    def link_counts(self, links, ratio=0.8, max_dist2=np.inf, cross_check=False):
+        """pairs per link, without the pairs (cap = 0): the edge weights of the view graph"""
+        rc, _, _, offsets = self._pairs_links(as_links(links), 0, ratio, max_dist2, cross_check)
+        if rc not in (OK, ERR_TOO_SMALL):                              # more pairs than cap = 0: the count is the answer
+            raise PopsiftHipError(rc, "popsift_hip_match_pairs_links")
+        return np.diff(offsets)
+
+    def link_points(self, links, pairs, offsets):
+        """popsift_hip_gallery_link_points: (n, 4) float32 rows (x, y, x', y') of the CSR (pairs, offsets) of
+        match_pairs_links(), both positions from the members' own (add_set members).  With the same offsets, the input of
+        Verifier.ransac_many"""
+        links = as_links(links)
+        pairs = np.ascontiguousarray(pairs, PAIR_DTYPE)
+        offsets = np.ascontiguousarray(offsets, np.int32).reshape(-1)
+        if len(offsets) != len(links) + 1 or offsets[-1] != len(pairs):
+            raise ValueError("offsets: n_links + 1 ints, offsets[-1] = len(pairs)")
+        pts = np.zeros((len(pairs), 4), np.float32)
+        rc = lib().popsift_hip_gallery_link_points(self._h, links.ctypes.data if len(links) else None, len(links),
+                                                   pairs.ctypes.data if len(pairs) else None, offsets.ctypes.data,
+                                                   pts.ctypes.data if len(pairs) else None)
+        if rc != OK:
+            raise PopsiftHipError(rc, "popsift_hip_gallery_link_points")
+        return pts
 
     def set_group_rows(self, n):
         """popsift_hip_gallery_debug_set_group_rows: rows of a group from the next call on; 0 = the default"""

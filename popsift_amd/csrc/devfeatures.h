@@ -135,6 +135,14 @@ struct popsift_hip_gallery {
     size_t idx_cap = 0;         /* ints */
     void*  back = nullptr;      /* of J: gathered descriptors, the reverse sweep's rows, norms */
     size_t back_cap = 0;        /* rows */
+    /* of the link matchers (match_links.hip), which share w_*, partial, rows, rows_host, idx, back and xy_* with the above */
+    void*  lk_rev = nullptr;      /* a group's link table and work items of the reverse sweep ... */
+    void*  lk_rev_host = nullptr; /* ... and the pinned block they are built in */
+    size_t lk_rev_cap = 0;        /* bytes */
+    void*  lk_res = nullptr;      /* the running pair count, the links' offsets; then the pairs */
+    size_t lk_res_cap = 0;        /* bytes */
+    void*  lk_host = nullptr;     /* pinned: J's segment starts of a group; the head of lk_res; the pairs found */
+    size_t lk_host_cap = 0;       /* bytes */
 
     popsift_hip_gallery() = default;
     popsift_hip_gallery(const popsift_hip_gallery&) = delete;
@@ -143,8 +151,8 @@ struct popsift_hip_gallery {
     {
         if (w_event) (void)hipEventDestroy((hipEvent_t)w_event);
         if (stream) (void)hipStreamDestroy((hipStream_t)stream);
-        free_bufs({d_desc, d_norm, d_xy, xy_dev, w_dev, lnorm, partial, rows, res, idx, back},
-                  {xy_host, w_host, rows_host, res_host});
+        free_bufs({d_desc, d_norm, d_xy, xy_dev, w_dev, lnorm, partial, rows, res, idx, back, lk_rev, lk_res},
+                  {xy_host, w_host, rows_host, res_host, lk_rev_host, lk_host});
         free(first);
         free(count);
         free(has_xy);

@@ -200,6 +200,9 @@ hipError_t launch_match_u8(const uint8_t* ldesc, int l_len, const int* lnorm, co
 /* match_gallery.hip (one byte set against a gallery of byte sets) launches its own kernels -- the grouped k_match_u8 over
  * a work list, its segmented finish and the pair stage -- from its two entry points; of the launchers above it uses
  * launch_norms_u8, launch_gather_rows and launch_match_u8 (the reverse sweep of the cross-check), U_LB / U_RB / U_GROUPS. */
+/* match_links.hip (any list of member pairs of one gallery) likewise launches its own kernels -- k_match_gallery with a left
+ * side per work item, a finish and a pair stage that find a row's link in a table -- and uses launch_norms_u8 and
+ * launch_gather_rows (the reverse sweep of the cross-check), U_LB / U_RB / U_GROUPS. */
 /* Feature records (72-byte popsift::Feature layout) with device descriptor pointers for a cloned set */
 hipError_t launch_clone_features(const popsift_hip_feature* feats, int n_feat, float* desc_base, void* out, hipStream_t s);
 

@@ -552,6 +552,66 @@ std::vector<int> Gallery::counts(FeaturesDevBytes* query, const MatchOptions& op
     return res;
 }
 
+std::vector<Gallery::Link> Gallery::allLinks(int n)
+{
+    std::vector<Link> links;
+    for (int a = 0; a < n; a++)
+        for (int b = a + 1; b < n; b++) links.push_back(Link{a, b});
+    return links;
+}
+
+std::vector<Gallery::Link> Gallery::sequentialLinks(int n, int k)
+{
+    std::vector<Link> links;
+    for (int a = 0; a < n; a++)
+        for (int b = a + 1; b < n && b <= a + k; b++) links.push_back(Link{a, b});
+    return links;
+}
+
+std::vector<std::vector<Gallery::Pair>> Gallery::matchPairs(const std::vector<Link>& links, const MatchOptions& opts)
+{
+    static_assert(sizeof(Link) == sizeof(popsift_hip_link) && sizeof(Pair) == sizeof(popsift_hip_pair), "Link is popsift_hip_link");
+    const int n_members = size();
+    size_t    rows = 0; /* the links' left rows: always enough room for the pairs */
+    for (const Link& l : links) {
+        int count = 0;
+        if (l.a < 0 || l.a >= n_members || l.b < 0 || l.b >= n_members) dev_fatal("a link names no member", POPSIFT_HIP_ERR_INVALID);
+        popsift_hip_gallery_member(_gallery, l.a, 0, &count);
+        rows += (size_t)count;
+    }
+    popsift_hip_match_opts o;
+    popsift_hip_default_match_opts(&o);
+    o.ratio = opts.ratio;
+    o.max_dist2 = opts.maxDist2;
+    o.cross_check = opts.crossCheck ? 1 : 0;
+    std::vector<Pair>    flat(rows);
+    std::vector<int32_t> offsets(links.size() + 1, 0);
+    int                  n = 0;
+    const int rc = popsift_hip_match_pairs_links(_gallery, links.empty() ? 0 : (const popsift_hip_link*)links.data(), (int)links.size(), &o,
+                                                 flat.empty() ? 0 : (popsift_hip_pair*)flat.data(), flat.size(), offsets.data(), &n);
+    if (rc != POPSIFT_HIP_OK) dev_fatal("matching the links failed", rc);
+    std::vector<std::vector<Pair>> res(links.size());
+    for (size_t e = 0; e < links.size(); e++) res[e].assign(flat.begin() + offsets[e], flat.begin() + offsets[e + 1]);
+    return res;
+}
+
+std::vector<float> Gallery::pairPoints(const std::vector<Link>& links, const std::vector<std::vector<Pair>>& pairs, std::vector<int>& offsets)
+{
+    if (pairs.size() != links.size()) dev_fatal("one pair list per link", POPSIFT_HIP_ERR_INVALID);
+    offsets.assign(pairs.size() + 1, 0);
+    std::vector<Pair> flat;
+    for (size_t e = 0; e < pairs.size(); e++) {
+        flat.insert(flat.end(), pairs[e].begin(), pairs[e].end());
+        offsets[e + 1] = (int)flat.size();
+    }
+    std::vector<float> pts(4 * flat.size());
+    const int rc = popsift_hip_gallery_link_points(_gallery, links.empty() ? 0 : (const popsift_hip_link*)links.data(), (int)links.size(),
+                                                   flat.empty() ? 0 : (const popsift_hip_pair*)flat.data(), offsets.data(),
+                                                   flat.empty() ? 0 : pts.data());
+    if (rc != POPSIFT_HIP_OK) dev_fatal("cannot gather the links' points", rc);
+    return pts;
+}
+
 /* FeaturesDev::match + show_distance (features.cu:222-300): the reference prints from the device */
 void FeaturesDev::match(FeaturesDev* other)
 {

@@ -16,6 +16,10 @@
  * Extension: --gallery-verify homography|affine|epipolar [--hypotheses T] [--max-err E] [--seed S] with --gallery fits the
  * model to every gallery image's pairs in one call (Gallery::pairPoints, Verifier::ransacMany) and prints it with its inlier
  * count under the image's pair lines, then, after the total, the gallery images ranked by their inliers.
+ * Extension: --all-pairs or --sequential K with --gallery (and without -l) matches the gallery images with each other in one
+ * pass -- every a < b, or every image with its K successors (Gallery::matchPairs over links) -- and prints one line per link:
+ * its pair count and, with --gallery-verify, its inlier count and model (Gallery::pairPoints over links,
+ * Verifier::ransacMany).
  */
 #include <popsift/common/device_prop.h>
 #include <popsift/features.h>
@@ -57,6 +61,8 @@ static bool refit_model = false;
 static int refit_rounds = 4;
 static vector<string> gallery_files;
 static string gallery_verify; /* empty: off */
+static bool all_pairs = false;
+static int sequential_k = 0; /* 0: off */
 
 static void parseargs(int argc, char** argv, popsift::Config& config, string& lFile, string& rFile)
 {
@@ -65,7 +71,7 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
     o.flag("help", 'h', "Options", "Print usage", [] {});
     o.flag("verbose", 'v', "Options", "", [&] { config.setVerbose(); });
     o.flag("log", 0, "Options", "Write debugging files", [&] { config.setLogMode(popsift::Config::All); });
-    o.val("left", 'l', "Options", "\"Left\"  input file", [&](const string& v) { lFile = v; }, true);
+    o.val("left", 'l', "Options", "\"Left\"  input file", [&](const string& v) { lFile = v; });
     o.val("right", 'r', "Options", "\"Right\" input file (required without --gallery)", [&](const string& v) { rFile = v; });
     /* match.cpp:61-73 */
     o.ival("octaves", "Parameters", "Number of octaves", [&](int v) { config.octaves = v; });
@@ -163,6 +169,15 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
               }
               gallery_verify = v;
           });
+    o.flag("all-pairs", 0, "Matching",
+           "With --gallery and without --left: match the gallery images with each other, every a < b, in one pass on the\n"
+           "GPU; prints one line per link, 'link <a> <b>: <n> pairs', with --gallery-verify followed by its inliers and\n"
+           "its model, then the total",
+           [&] { all_pairs = true; });
+    o.ival("sequential", "Matching", "As --all-pairs, but every gallery image with its K successors only", [&](int k) {
+        if (k < 1) o.error("the argument ('" + to_string(k) + "') for option '--sequential' is invalid");
+        sequential_k = k;
+    });
     o.val("feature-order", 0, "Extensions",
           "Order of the features of an image: arrival (default; differs from run to run) or raster (by octave, pixel row,\n"
           "pixel column, level: the same bytes on every run)",
@@ -179,6 +194,16 @@ static void parseargs(int argc, char** argv, popsift::Config& config, string& lF
                config.setKeepStrongest(n);
            });
     o.parse(argc, argv);
+    const bool links = all_pairs || sequential_k > 0;
+    if (links && (all_pairs && sequential_k > 0)) {
+        cerr << "--all-pairs or --sequential: give one or the other" << endl;
+        exit(-1);
+    }
+    if (links && (gallery_files.empty() || !lFile.empty())) {
+        cerr << "--all-pairs and --sequential match the --gallery images with each other: give them, and no --left" << endl;
+        exit(-1);
+    }
+    if (!links && lFile.empty()) o.error("the option '--left' is required but missing");
     if (gallery_files.empty() && rFile.empty()) o.error("the option '--right' is required but missing");
     if (!gallery_files.empty()) {
         if (!rFile.empty()) {
@@ -372,6 +397,53 @@ static int match_gallery_files(const string& lFile, PopSift& sift)
     return 0;
 }
 
+/* --all-pairs / --sequential: the gallery images with each other in one pass */
+static int match_gallery_links(PopSift& sift)
+{
+    popsift::Gallery gallery(0);
+    for (const string& f : gallery_files) {
+        SiftJob*              job = process_image(f, sift);
+        popsift::FeaturesDev* feat = job->getDev();
+        cout << "Number of features:    " << feat->getFeatureCount() << endl;
+        cout << "Number of descriptors: " << feat->getDescriptorCount() << endl;
+        /* copied with its positions: the set can go */
+        gallery.add(feat);
+        delete feat;
+        delete job;
+    }
+    const int                                    n = (int)gallery_files.size();
+    const vector<popsift::Gallery::Link>         links = all_pairs ? popsift::Gallery::allLinks(n)
+                                                                   : popsift::Gallery::sequentialLinks(n, sequential_k);
+    const vector<vector<popsift::Gallery::Pair>> all = gallery.matchPairs(links, pair_opts);
+    vector<popsift::RansacResult>                fits;
+    if (!gallery_verify.empty()) {
+        popsift::Verifier    verifier(0);
+        popsift::ManyOptions mo;
+        mo.kind = gallery_verify == "epipolar" ? popsift::ManyOptions::Epipolar
+                  : gallery_verify == "affine" ? popsift::ManyOptions::Affine
+                                               : popsift::ManyOptions::Homography;
+        mo.hypotheses = verify_opts.hypotheses;
+        mo.maxErr = verify_opts.maxErr;
+        mo.seed = verify_opts.seed;
+        vector<int>         offsets;
+        const vector<float> pts = gallery.pairPoints(links, all, offsets);
+        fits = verifier.ransacMany(pts, offsets, mo);
+    }
+    size_t total = 0;
+    for (size_t e = 0; e < links.size(); e++) {
+        printf("link %d %d: %zu pairs", links[e].a, links[e].b, all[e].size());
+        if (!fits.empty()) {
+            printf(", %d inliers, %s", fits[e].inliers, gallery_verify.c_str());
+            for (int i = 0; i < 9; i++) printf(" %.9g", fits[e].H[i]);
+        }
+        printf("\n");
+        total += all[e].size();
+    }
+    printf("Number of links:       %zu\n", links.size());
+    printf("Number of pairs:       %zu\n", total);
+    return 0;
+}
+
 static SiftJob* process_image(const string& inputFile, PopSift& sift)
 {
     int            w, h;
@@ -389,8 +461,12 @@ int main(int argc, char** argv)
     string          rFile = "";
 
     parseargs(argc, argv, config, lFile, rFile);
+    const bool     links = all_pairs || sequential_k > 0;
     vector<string> inputs = {lFile};
-    if (gallery_files.empty()) {
+    if (links) {
+        std::cout << gallery_files.size() << " gallery images <-> each other" << std::endl;
+        inputs = gallery_files;
+    } else if (gallery_files.empty()) {
         std::cout << lFile << " <-> " << rFile << std::endl;
         inputs.push_back(rFile);
     } else {
@@ -412,7 +488,7 @@ int main(int argc, char** argv)
     PopSift sift(config, popsift::Config::MatchingMode);
 
     if (!gallery_files.empty()) {
-        const int rc = match_gallery_files(lFile, sift);
+        const int rc = links ? match_gallery_links(sift) : match_gallery_files(lFile, sift);
         sift.uninit();
         return rc;
     }
