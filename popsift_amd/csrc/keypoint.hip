@@ -169,6 +169,7 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
     for (XcdSlice sl = xcd_slice<KP_NW>(); sl.more(total); sl.s += sl.step) {
         const int g = sl.index();
         if (g >= total) continue;
+        /* ISA: record */
         const int o = uniform(ext_octave(ps, n_oct, g)); /* the octave record and the list entry are then fetched through the scalar cache */
         const InitExt  ie = iext[(size_t)o * sc.max_extrema + (g - uniform(ps[o]))];
         const OctDesc* od = &pdp->o[o];
@@ -176,8 +177,10 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
         const int      lvl = uniform(min(max(ie.lpos, 0), L - 1));
         const float*   layer = arena + uniform64(od->data_off + lvl * od->plane_stride);
 
+        /* ISA: clear */
         for (int k = lane; k < ORI_COPIES * NB; k += 64) hall[k] = 0ull;
         wave_lds_sync();
+        /* ISA: set-up */
 
         const float x = uniformf(ie.xpos), y = uniformf(ie.ypos), sig = uniformf(ie.sigma);
         const float sigw = ORI_WINFACTOR * sig;
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
          * and the byte offset of the taps are formed in floats (exact small integers): one conversion, one floor and FMAs
          * instead of two conversions, two 24-bit multiplies and a shift-add -- half-rate instructions on gfx950
          * (tools/ubench/valu_rate.hip).  (fx, fy) = the pixel, as the floats the reference converts its ints to. */
-        auto coord = [&](int i, float& fx, float& fy, unsigned int& off) {
+        auto coord = [&](int i, float& fx, float& fy, unsigned int& off) { /* ISA: coordinates */
             const float fi = (float)i;
             const float frow = floorf((fi + 0.5f) * inv_wx);
             const float fcol = fmaf(-frow, wxf, fi);
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
             off = (unsigned int)fmaf(frow, pitch4f, fcol * 4.0f);
         };
         /* one sample: pixel (fx, fy) with gradient (gdx, gdy) -> at most one fixed-point LDS atomic */
-        auto bin = [&](float fx, float fy, float gdx, float gdy, bool live) {
+        auto bin = [&](float fx, float fy, float gdx, float gdy, bool live) { /* ISA: bin */
             const float dx = fx - x;
             const float dy = fy - y;
             /* int truncation, s_orientation.cu:123 -- as a float (the values are far below 2^24, so truncf, the
@@ -241,26 +244,43 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
                 atomicAdd(&hist[bidx], (fix64)(unsigned int)wfix);
             }
         };
+        /* ISA: control */
         /* two register sets take turns as "being binned" and "in flight", as in k_descriptor (unrolled by two, so no
          * value is copied from one role to the other) */
         float        xa = 0.0f, ya = 0.0f, xb = 0.0f, yb = 0.0f;
         unsigned int oa = 0, ob = 0;
         float        a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f, b0 = 0.0f, b1 = 0.0f, b2 = 0.0f, b3 = 0.0f;
         const Taps   taps(corner, pitch);
-        if (loops > 0) {
+        /* steps of 64 window positions, exactly (wave-uniform): the last one may be partial, none is empty */
+        const int steps = (loops + 63) >> 6;
+        if (steps > 0) {
             coord(min(lane, loops - 1), xa, ya, oa);
             taps.load_b(oa, a0, a1, a2, a3);
         }
-        for (int i = lane; i < loops; i += 128) {
-            coord(min(i + 64, loops - 1), xb, yb, ob);
+        /* double steps while a further step follows them, as in k_descriptor: only then is the set requested at the end
+         * ever binned.  Neither step of the pair is the window's last, so both are full (no lane beyond the window);
+         * the step after them may be the last one, so its index is held inside the window. */
+        int t = steps, i = lane;
+        for (; t > 2; t -= 2, i += 128) {
+            coord(i + 64, xb, yb, ob);
             taps.load_b(ob, b0, b1, b2, b3);
             bin(xa, ya, a0 - a1, a2 - a3, true);
             coord(min(i + 128, loops - 1), xa, ya, oa);
             taps.load_b(oa, a0, a1, a2, a3);
-            bin(xb, yb, b0 - b1, b2 - b3, i + 64 < loops);
+            bin(xb, yb, b0 - b1, b2 - b3, true);
         }
+        /* the last one or two steps (wave-uniform branches): nothing is requested beyond the window's last step.  With
+         * a double step to the end, every window with an odd number of steps (half of them, at about nine steps per
+         * keypoint) walked a whole dead half-step: coordinates, four tap loads, the distance test. */
+        if (t == 2) {
+            coord(min(i + 64, loops - 1), xb, yb, ob);
+            taps.load_b(ob, b0, b1, b2, b3);
+        }
+        if (t > 0) bin(xa, ya, a0 - a1, a2 - a3, i < loops);
+        if (t == 2) bin(xb, yb, b0 - b1, b2 - b3, i + 64 < loops);
         wave_lds_sync();
 
+        /* ISA: read-out */
         if (lane < PS_ORI_NBINS) {
             fix64 acc = 0ull;
 #pragma unroll
@@ -268,7 +288,7 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
                 acc += hall[k * NB + lane] + (lane < NB - PS_ORI_NBINS ? hall[k * NB + PS_ORI_NBINS + lane] : 0ull);
             ohist[(size_t)g * PS_ORI_NBINS + lane] = from_fix(acc);
         }
-        wave_lds_sync();
+        wave_lds_sync(); /* ISA: end */
     }
 }
 
@@ -689,24 +709,30 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
     const int     maxlist = min(max(sc.desc_list, 64), DESC_LISTCAP);
 
     for (XcdSlice sl = xcd_slice<KP_NW>(); sl.more(total); sl.s += sl.step) {
-        const int d = sl.index();
+        /* one descriptor per wave: its number is wave-uniform, and said to be, so that the record below is fetched
+         * through the scalar cache */
+        const int d = uniform(sl.index());
         if (d >= total) continue;
+        /* ISA: record */
         /* everything about the descriptor is wave-uniform and was worked out by k_scan_apply (DescRec): three 16-byte
-         * loads of one address, moved to scalar registers (the taps become scalar-base + 32-bit-offset loads) */
+         * SCALAR loads (the taps become scalar-base + 32-bit-offset loads).  As vector loads of one address in all 64
+         * lanes every word of the record cost a v_readfirstlane on its way to a scalar register, a dozen per descriptor
+         * and a 64-bit vector address. */
         typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        const u4*          rp = reinterpret_cast<const u4*>(drec + d);
+        typedef __attribute__((address_space(4))) const u4 const_u4; /* written by an earlier kernel, never by this one */
+        const_u4*          rp = (const_u4*)(size_t)(drec + d);
         const u4           q0 = rp[0], q1 = rp[1], q2 = rp[2];
-        const float        x = uniformf(__uint_as_float(q0.x)), y = uniformf(__uint_as_float(q0.y));
-        const float        crsbp = uniformf(__uint_as_float(q0.z)), srsbp = uniformf(__uint_as_float(q0.w));
+        const float        x = __uint_as_float(q0.x), y = __uint_as_float(q0.y);
+        const float        crsbp = __uint_as_float(q0.z), srsbp = __uint_as_float(q0.w);
         /* the keypoint orientation in bins enters the angle's last FMA as 2 - ang_bins (half_angle_bins) */
-        const float        ang_k0 = 2.0f - uniformf(__uint_as_float(q1.x));
-        const float        inv_c = uniformf(__uint_as_float(q1.y)), inv_s = uniformf(__uint_as_float(q2.w));
-        const int          pmin = uniform((int)q1.z), pmax = uniform((int)q1.w);
-        const unsigned int misc = (unsigned int)uniform((int)q2.z);
+        const float        ang_k0 = 2.0f - __uint_as_float(q1.x);
+        const float        inv_c = __uint_as_float(q1.y), inv_s = __uint_as_float(q2.w);
+        const int          pmin = (int)q1.z, pmax = (int)q1.w;
+        const unsigned int misc = q2.z;
         const int          pitch = (int)(misc & 0xffffu), fbits = (int)((misc >> 16) & 0xffu);
-        const float*       layer = arena + uniform64((long long)(((unsigned long long)q2.y << 32) | q2.x));
+        const float*       layer = arena + (long long)(((unsigned long long)q2.y << 32) | q2.x);
 
-        {
+        { /* ISA: clear */
             /* the zeros are made here, every time: left to itself the compiler keeps them alive across the whole sample
              * loop, which is the 65th vector register and up (a spill, and with it scratch set-up for every wave).
              * 16-byte stores (the histograms start on a 16-byte boundary, ROW_WORDS): five per lane where 8-byte stores
@@ -722,6 +748,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                 if (lane + 64 * k < CLEAR16) h16[lane + 64 * k] = zero;
         }
 
+        /* ISA: set-up */
         if (misc & (1u << 24)) { /* DESC_MAGNIFY * sigma != 0 */
             const int   xmin = (int)(short)(pmin & 0xffff), ymin0 = pmin >> 16;
             const int   xmax = (int)(short)(pmax & 0xffff), ymax = pmax >> 16;
@@ -738,10 +765,12 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
             for (int rb = 0, skip = 0; rb < hy_all && wx > 0;) {
             const int   ymin = ymin0 + rb;
             const int   hy = min(hy_all - rb, maxrows);
+            /* ISA: clear */
             /* the row-end bits of the previous pass go (the first pass clears what the previous descriptor left) */
             if (lane < DESC_TAB64) ((unsigned long long*)tab)[lane] = 0ull;
             wave_lds_sync();
 
+            /* ISA: spans */
             /* Row spans.  The samples that count lie in the square |u|,|v| < 2.5 (cell units, rotated
              * by ang), which fills only 1/(|cos|+|sin|)^2 = 50..100 % of its bounding box.  Per patch
              * row the square cuts out ONE column interval; the rows' intervals are laid end to end
@@ -837,6 +866,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
             }
             wave_lds_sync();
 
+            /* ISA: set-up */
             /* steps of 64 list positions, exactly: the last one may be partial (what lies beyond the list's end drops out by
              * itself, above), none is empty */
 #ifdef DESC_PROBE_NOLOOP
@@ -895,6 +925,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
                  * v_cvt_rpi_i32_f32 in k_orientation */
                 asm("v_cvt_u32_f32 %0, %1" : "=v"(off) : "v"(fmaf(fr, pitch4f, fc * 4.0f)));
             };
+            /* ISA: control */
             /* one sample: gradient (gx, gy) at cell-unit position (u, v) -> up to four 64-bit LDS atomics */
             unsigned int probe_acc = 0u; /* DESC_PROBE_NOATOMIC only */
             auto bin = [&](float u, float v, float gx, float gy) {
@@ -1021,23 +1052,39 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
         }
         wave_lds_sync();
 
+        /* ISA: read-out */
         /* bin b of cell (iy, ix) = low half of that cell's word for b + high half of its word for b-1 (mod 8),
-         * summed over the copies; word positions as in the header comment */
-        fix64 a0 = 0ull, a1 = 0ull;
+         * summed over the copies; word positions as in the header comment.  The eight halves of a bin are read as 32-bit
+         * words and summed in 32 bits: the samples behind the low halves (lower bin b) and behind the high halves (lower
+         * bin b-1) are different samples of the same cell, each adds at most its weight plus the half unit of its
+         * rounding, and all the samples of a cell together weigh at most 361 * cell_px * 2^fbits <= 2^31 (make_desc_rec,
+         * the bound that keeps a low half from carrying), so a bin is below 2^31 + cell_px / 2 < 2^32.  One v_cvt_f32_u32
+         * then rounds the same integer to the same float as the 64-bit sum's conversion did, which took two carry adds
+         * per term and a normalise-and-round sequence of nineteen instructions per descriptor. */
+        unsigned int a0 = 0u, a1 = 0u;
         {
-            const int b = lane & 7, ix = (lane >> 3) & 3, iyl = lane >> 5; /* element lane: cell row iyl, lane+64: iyl+2 */
+            /* element lane: bin b of cell (iyl, ix), element lane + 64: of cell (iyl + 2, ix).  Copy k keeps the bin in slot
+             * (t + k) & 7 and the bin below it in the slot before: five slot addresses in all, everything else -- the copy,
+             * the two cell rows, the high half -- is an immediate offset of the read */
+            const int          b = lane & 7, ix = (lane >> 3) & 3, iyl = lane >> 5;
+            const int          t = b + ((ix & 1) << 2);
+            const unsigned int cell = (unsigned int)(size_t)(lds_fix64*)hall + 8u * (unsigned int)(iyl * DESC_RS + ix * 8);
+            unsigned int       slot[DESC_COPIES + 1];
+#pragma unroll
+            for (int j = 0; j <= DESC_COPIES; j++) slot[j] = cell + 8u * (unsigned int)((t + j + 7) & 7);
 #pragma unroll
             for (int k = 0; k < DESC_COPIES; k++) {
-                const int sl = (b + k + ((ix & 1) << 2)) & 7, sh = (b + 7 + k + ((ix & 1) << 2)) & 7;
-                const int c0 = k * DESC_CS + iyl * DESC_RS + ix * 8;
-                const int c1 = k * DESC_CS + (iyl + 2) * DESC_RS + ix * 8;
-                a0 += (hall[c0 + sl] & 0xffffffffull) + (hall[c0 + sh] >> 32);
-                a1 += (hall[c1 + sl] & 0xffffffffull) + (hall[c1 + sh] >> 32);
+                constexpr unsigned int ROW2 = 2u * DESC_RS * 8u;
+                const unsigned int     cp = (unsigned int)k * DESC_CS * 8u;
+                a0 += *(lds_u32*)(size_t)(slot[k + 1] + cp) + *(lds_u32*)(size_t)(slot[k] + cp + 4u);
+                a1 += *(lds_u32*)(size_t)(slot[k + 1] + cp + ROW2) + *(lds_u32*)(size_t)(slot[k] + cp + ROW2 + 4u);
             }
         }
+        /* ISA: u32 to f32 */
         const float inv_scale = scalbnf(1.0f, -fbits);
         float       v0 = (float)a0 * inv_scale, v1 = (float)a1 * inv_scale;
 
+        /* ISA: normalise + store */
         /* normalisation (s_desc_norm_rs.h:44-79, s_desc_norm_l2.h:87-134), whole wave.  The reference's RootSift is
          * __fsqrt_rn(__fdividef(v, sum)) and its L2 norms are __fsqrt_rn / __frsqrt_rn: an approximate quotient under
          * correctly rounded roots.  Here the quotient is the hardware reciprocal (1 ulp, like __fdividef's 2 ulp) and the
@@ -1065,7 +1112,7 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
         }
         desc[(size_t)d * 128 + lane] = v0;
         desc[(size_t)d * 128 + 64 + lane] = v1;
-        wave_lds_sync();
+        wave_lds_sync(); /* ISA: end */
     }
 }
 

@@ -93,7 +93,9 @@ __device__ __forceinline__ XcdSlice xcd_slice()
 {
     XcdSlice sl;
     sl.x = blockIdx.x & 7;
-    sl.s = (int)(blockIdx.x >> 3) * NW + (int)(threadIdx.x >> 6);
+    /* the wave's number in its workgroup is wave-uniform, and said to be: position, list index and the loop over them
+     * then stay in scalar registers (seven vector instructions per keypoint otherwise) */
+    sl.s = (int)(blockIdx.x >> 3) * NW + uniform((int)(threadIdx.x >> 6));
     sl.step = (int)(gridDim.x >> 3) * NW;
     return sl;
 }

@@ -73,7 +73,7 @@ struct Ext {
 
 /* Everything about one (extremum, orientation) that the loop-descriptor kernel would otherwise derive, wave-uniformly and
  * once per descriptor, from the extremum, its octave and its rotation: written by k_scan_apply with one LANE per extremum
- * (same expressions, same values), read by k_descriptor as three 16-byte loads.  48 bytes. */
+ * (same expressions, same values), read by k_descriptor as three 16-byte scalar loads.  48 bytes. */
 struct DescRec {
     float        x, y;         /* position in the octave */
     float        crsbp, srsbp; /* cos, sin of the orientation / (DESC_MAGNIFY * sigma): pixel -> cell units */

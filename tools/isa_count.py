@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction budget of a kernel's hot loop from the compiler's own ISA (no GPU needed).
 
-    tools/isa_count.py [--src FILE.hip] [--kernel k_descriptor] [--marker ds_add_u64] [--samples 2] [--most] [extra hipcc flags ...]
+    tools/isa_count.py [--src FILE.hip] [--kernel k_descriptor] [--marker ds_add_u64] [--samples 2] [--most] [--whole] [extra hipcc flags ...]
 
 Compiles popsift_amd/csrc/keypoint.hip, the benchmarked kernels (or --src FILE.hip: desc_modes.hip for the other descriptor
 modes, extrema.hip), for gfx950 with the Makefile's flags plus -gline-tables-only, takes the
@@ -15,6 +15,8 @@ innermost-but-one loop of <kernel> that contains <marker>, and counts its instru
   named by its arguments: k_detectILi0ELi3ELb0ELb1E is k_detect<0, 3, false, true>.
 --most: of the loops that contain <marker>, take the one whose own blocks hold most of them (default: the first in
   program order).
+--whole: count every block of the kernel once, not one loop (static counts by source group: the work around a loop, e.g. of
+  a -DDESC_PROBE_NOLOOP build; how often a block runs is for the reader to weigh).
 The 64-bit vector address arithmetic of the loop (v_lshl_add_u64, v_mad_i64_i32, v_mad_u64_u32, v_add_co_u32 /
 v_addc_co_u32 pairs) is counted on a line of its own: a load with a wave-uniform base and a 32-bit lane offset needs none.
 
@@ -54,7 +56,7 @@ def source_groups():
 def main():
     a = sys.argv[1:]
     global SRC
-    kernel, marker, samples, most = "k_descriptor", "ds_add_u64", 2, False
+    kernel, marker, samples, most, whole = "k_descriptor", "ds_add_u64", 2, False, False
     extra = []
     i = 0
     while i < len(a):
@@ -66,6 +68,8 @@ def main():
             SRC = os.path.abspath(a[i + 1]); i += 2
         elif a[i] == "--most":
             most = True; i += 1
+        elif a[i] == "--whole":
+            whole = True; samples = 1; i += 1
         elif a[i] == "--samples":
             samples = int(a[i + 1]); i += 2
         else:
@@ -111,9 +115,11 @@ def main():
             return name, int(m.group(1))
         return None, 0
     marked = [n for n, b in blocks.items() if any(marker in x for x in b["ins"])]
+    if whole:
+        marked = list(blocks)[:1]
     if not marked:
         sys.exit("marker %s not found in %s" % (marker, kernel))
-    looped = [n for n in marked if header_of(n, blocks[n])[1] > 0]
+    looped = [n for n in marked if header_of(n, blocks[n])[1] > 0] or (marked if whole else [])
     if not looped:
         sys.exit("marker %s is in no loop of %s" % (marker, kernel))
     hits = collections.Counter()
@@ -121,11 +127,13 @@ def main():
         hits[header_of(n, blocks[n])[0]] += sum(marker in x for x in blocks[n]["ins"])
     pick = max(looped, key=lambda n: hits[header_of(n, blocks[n])[0]]) if most else looped[0]
     hdr, depth = header_of(pick, blocks[pick])
+    if whole:
+        hdr, depth = "(whole kernel)", 0
     # all blocks of that loop (including deeper child loops whose parent chain mentions the header)
     member = []
     for n, b in blocks.items():
         h, dp = header_of(n, b)
-        if h == hdr or ("Parent Loop BB%s " % hdr[4:]) in b["note"] or n == hdr:
+        if whole or h == hdr or ("Parent Loop BB%s " % hdr[4:]) in b["note"] or n == hdr:
             member.append(n)
     groups = source_groups()
     kp_files = set()
