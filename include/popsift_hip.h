@@ -167,7 +167,7 @@ enum { POPSIFT_HIP_STAGE_PYRAMID = 0,     /* every k_blur_tile launch           
        POPSIFT_HIP_STAGE_DETECT = 1,      /* k_detect (both passes)                                */
        POPSIFT_HIP_STAGE_REFINE = 2,      /* k_refine (+ grid filter / keep-strongest pass when on) */
        POPSIFT_HIP_STAGE_ORIENTATION = 3, /* k_orientation                                         */
-       POPSIFT_HIP_STAGE_SCAN = 4,        /* k_scan_local + k_scan_apply                           */
+       POPSIFT_HIP_STAGE_SCAN = 4,        /* k_scan_apply                                          */
        POPSIFT_HIP_STAGE_DESCRIPTOR = 5,  /* the descriptor kernel                                 */
        POPSIFT_HIP_STAGE_COUNT = 6 };
 
@@ -1131,8 +1131,8 @@ int popsift_hip_download_extrema(popsift_hip_ctx* ctx, popsift_hip_extremum* out
 int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
 /* Test switches of one context (no environment variables are read by this library).  Set them before the first
  * submit: DET_QCAP = candidate-queue entries the fast detection pass may use (small values force strips into the
- * slow pass); CAND_CAP / OHIST_CAP = initial capacity of the candidate buffer / of the orientation-histogram buffer
- * (small values exercise the grow-and-rerun path of popsift_hip_wait); FAIL_ALLOC = n: the n-th device allocation
+ * slow pass); CAND_CAP / OHIST_CAP = initial capacity of the candidate buffer / initial number of extrema the orientation
+ * stage serves in one pass (small values exercise the grow-and-rerun path of popsift_hip_wait); FAIL_ALLOC = n: the n-th device allocation
  * of this context from now on fails with POPSIFT_HIP_ERR_OOM (0 = off); DESC_ROWS = patch rows the loop descriptor
  * walks per pass (4 .. 96, default 96: small values make ordinary patches take the several passes that otherwise only
  * the largest patches take; results do not depend on it); DESC_LIST = list positions (samples of the patch's rows laid
@@ -1140,7 +1140,8 @@ int popsift_hip_rerun_keypoint_stages(popsift_hip_ctx* ctx);
  * default: patches of the coarsest levels have up to 5200 and take two passes; a pass that fills up ends inside a row
  * and the next one takes the rest of that row; results do not depend on it);
  * KP_WAVES = waves per image in the launches of
- * the orientation and descriptor kernels (a multiple of 32; default 8 per wave slot of the device; results do not
+ * the orientation and descriptor kernels (a multiple of 32; default 8 per wave slot of the device; the orientation
+ * kernel, whose waves take 16 keypoints at a time, launches an eighth of them, at least 8; results do not
  * depend on it; tools/kp_waves_sweep.sh: 8192 .. 131072 within 1.5 %); BLUR_PATH = which kernels build the pyramid's
  * plane-to-plane levels: 0 by plane size (default), 1 the one-tile-per-workgroup kernels only, 2 the strip-march kernels
  * wherever they apply, also on small planes (results do not depend on it: every path is bit-identical; the tests run

@@ -92,7 +92,6 @@ struct ImageSlot {
     DevBuf<StrongState> sstate;
     DevBuf<int>         schunk;
     DevBuf<Ext>         ext;
-    DevBuf<float, PS_ORI_NBINS> ohist; /* raw orientation histograms, one per extremum (k_orientation -> k_scan_local) */
     DevBuf<popsift_hip_feature> feats;
     /* the descriptor group, grown as one (slot_desc_cap): desc_cap() descriptors */
     DevBuf<float, 128> desc;
@@ -132,7 +131,7 @@ struct ImageSlot {
     void release()
     {
         auto each = [](auto&... b) { ((void)b.release(), ...); };
-        each(input, arena, iext, iext2, fstate, fhist, otmp, orows, sresp_in, sresp, sstate, schunk, ext, ohist, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
+        each(input, arena, iext, iext2, fstate, fhist, otmp, orows, sresp_in, sresp, sstate, schunk, ext, feats, desc, map, rot, drec, cand, partial, ovf, alt_feats,
              alt_desc, desc_u8, frames, fcounts, perm, inv, lfeats, mask);
         if (h_input) (void)hipHostFree(h_input);
         if (h_mask) (void)hipHostFree(h_mask);
@@ -188,6 +187,8 @@ struct popsift_hip_ctx {
     size_t    ext_cap = 0; /* entries every one of iext/ext/feats(/iext2) of the sized slots holds */
     /* capacities the kernels are told: the smallest over the slots of the batch (refresh_caps) */
     int       cand_cap = 0, desc_cap = 0;
+    /* extrema k_orientation gives orientations to in one pass: no buffer (a group's histograms stay in its wave's LDS), a
+     * bound the host keeps, grow-only like the buffers; finish() raises it and re-runs when an image has more */
     size_t    ohist_cap = 0;
     hipStream_t copy_stream = nullptr;
     hipEvent_t  ev_u8 = nullptr;    /* the byte pass of a fetch_begin*_u8 on `stream` -> its copies on copy_stream */
@@ -434,12 +435,11 @@ int grow(popsift_hip_ctx* c, DevBuf<T, PER>& b, size_t need)
 /* the capacities the kernels are told = the smallest over the slots of the batch, and the kernels' slot table */
 void refresh_caps(popsift_hip_ctx* c)
 {
-    size_t cand = 1 << 30, desc = 1 << 30, hist = (size_t)1 << 40;
+    size_t cand = 1 << 30, desc = 1 << 30;
     for (int k = 0; k < c->nb; k++) {
         const ImageSlot& s = c->slot[k];
         cand = std::min(cand, s.cand.cap);
         desc = std::min(desc, s.desc_cap());
-        hist = std::min(hist, s.ohist.cap);
         Slot& v = c->bd.s[k];
         v.arena = s.arena.p;
         v.ct = c->d_ct + k;
@@ -449,7 +449,6 @@ void refresh_caps(popsift_hip_ctx* c)
         v.iext2 = s.iext2.p;
         v.fstate = s.fstate.p;
         v.fhist = s.fhist.p;
-        v.ohist = s.ohist.p;
         v.ext = s.ext.p;
         v.partial = s.partial.p;
         v.map = s.map.p;
@@ -460,7 +459,6 @@ void refresh_caps(popsift_hip_ctx* c)
     }
     c->cand_cap = (int)cand;
     c->desc_cap = (int)desc;
-    c->ohist_cap = hist;
 }
 
 /* the descriptor group: all four buffers are freed, then allocated in order, so that a failure anywhere leaves
@@ -519,6 +517,10 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
                            : (size_t)last.dog_off + (size_t)last.plane_stride * (size_t)(c->L - 1);
     }
     const size_t need_ext = (size_t)pd.n_oct * (size_t)c->sc.max_extrema;
+    /* orientations: 2 * max_extrema extrema to start with (all octaves together seldom exceed one octave's cap); finish()
+     * raises the bound and re-runs the keypoint stages when an image has more */
+    c->ohist_cap = std::max(c->ohist_cap, c->ohist_cap_init > 0 ? (size_t)c->ohist_cap_init
+                                                                 : std::min(need_ext, (size_t)2 * c->sc.max_extrema));
     for (int k = 0; k < nb; k++) {
         ImageSlot& s = c->slot[k];
         if (s.sized) continue;
@@ -550,12 +552,6 @@ int prepare_geometry(popsift_hip_ctx* c, int w, int h, int nb)
             cand0 = std::max(cand0, (int)std::min(px / 8.0, 64.0 * 1024 * 1024));
         }
         if (int rc = grow(c, s.cand, std::max(cand0, c->cand_cap))) return rc;
-        /* orientation histograms: 2 * max_extrema extrema to start with (all octaves together seldom exceed one octave's
-         * cap); finish() grows the buffer and re-runs the keypoint stages when an image has more */
-        if (int rc = grow(c, s.ohist, std::max(c->ohist_cap_init > 0 ? (size_t)c->ohist_cap_init
-                                                                      : std::min(need_ext, (size_t)2 * c->sc.max_extrema),
-                                               c->slot[0].sized ? c->ohist_cap : (size_t)0)))
-            return rc;
         if (int rc = grow(c, s.ovf, (size_t)pd.total_tiles + 1)) return rc;
         s.sized = true;
     }
@@ -948,7 +944,7 @@ hipError_t enqueue_strongest(popsift_hip_ctx* c)
 }
 
 /* What extraction and describe end with: orientation -> scan -> descriptors -> the counters to the host, with their stage
- * marks.  lb: the slot table the scan writes its records through; with_ori: k_orientation and k_scan_local run (otherwise
+ * marks.  lb: the slot table the scan writes its records through; with_ori: k_orientation runs (otherwise
  * the Ext records and the partial sums are there already, k_frame_place); fb: the frames of a describe, whose records
  * k_frame_out moves to caller order after the descriptor kernel, or null. */
 int enqueue_descriptor_stages(popsift_hip_ctx* c, const BatchDesc& lb, bool filtered, bool with_ori, const FrameBatch* fb)
@@ -962,11 +958,8 @@ int enqueue_descriptor_stages(popsift_hip_ctx* c, const BatchDesc& lb, bool filt
     }
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_SCAN));
     const int n_chunks = std::max((int)(((size_t)c->pd.n_oct * c->sc.max_extrema + scan_chunk() - 1) / scan_chunk()), 1);
-    if (with_ori)
-        HIP_TRY(c, launch_scan(c->d_pd, lb, c->nb, c->sc, filtered, (int)c->ohist_cap, n_chunks, c->desc_cap, c->stream));
-    else
-        HIP_TRY(c, launch_scan_apply(c->d_pd, lb, c->nb, c->sc, n_chunks, c->desc_cap, c->stream));
-    SYNC_CHK(c, "k_scan_local / k_scan_apply");
+    HIP_TRY(c, launch_scan_apply(c->d_pd, lb, c->nb, c->sc, n_chunks, c->desc_cap, c->stream));
+    SYNC_CHK(c, "k_scan_apply");
     HIP_TRY(c, mark(POPSIFT_HIP_STAGE_DESCRIPTOR));
     HIP_TRY(c, launch_descriptors(c->d_pd, c->bd, c->nb, c->sc, c->desc_cap, c->kp_waves, c->stream));
     SYNC_CHK(c, "descriptor kernel");
@@ -1243,10 +1236,7 @@ int finish(popsift_hip_ctx* c)
         if (cand_short)
             if (int rc = ensure_cap(c, [&](ImageSlot& s) { return grow(c, s.cand, DET_SUBQ * (qmax + qmax / 8 + 64)); }))
                 return rc;
-        if (hist_short) {
-            const size_t need = (size_t)ext_max + (size_t)ext_max / 8 + 1024;
-            if (int rc = ensure_cap(c, [&](ImageSlot& s) { return grow(c, s.ohist, need); })) return rc;
-        }
+        if (hist_short) c->ohist_cap = std::max(c->ohist_cap, (size_t)ext_max + (size_t)ext_max / 8 + 1024);
         if (int rc = c->describe ? enqueue_describe_stages(c) : enqueue_keypoint_stages(c)) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_end, c->stream));
         rerun = true;

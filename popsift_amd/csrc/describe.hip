@@ -4,7 +4,7 @@
  *
  *   k_frame_count  resolves every frame to (octave, level) and counts the valid ones per (octave, chunk of FRAME_CHUNK)
  *   k_frame_place  stable partition by octave: the InitExt lists in caller order within an octave, ext_ct, the list
- *                  position <-> frame maps; with given orientations also the Ext records and k_scan_local's partial sums,
+ *                  position <-> frame maps; with given orientations also the Ext records and k_orientation's partial sums,
  *                  so that k_scan_apply alone finishes the scan
  *   k_frame_out    after the descriptor kernel: k_scan_apply's feature records moved to caller order (invalid frames get
  *                  their own record), the descriptor -> feature map rewritten to caller indices
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(FRAME_CHUNK) void k_frame_place(const PyrDesc* __re
         perm[g] = i;
         inv[i] = g;
         if (given) {
-            /* what k_scan_local would leave for an extremum with this one orientation: idx_ori local to its chunk of
+            /* what k_orientation would leave for an extremum with this one orientation: idx_ori local to its group of
              * lchunk list entries, one partial sum per such chunk (every entry has one descriptor) */
             Ext e;
             e.xpos = ie.xpos;

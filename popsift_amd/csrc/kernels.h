@@ -117,13 +117,13 @@ hipError_t launch_extrema(const PyrDesc& pd, const PyrDesc* d_pd, const BatchDes
                           bool filtered, hipStream_t s, hipEvent_t mid, const MaskArgs* ma);
 
 /* keypoint.hip */
-/* ohist: 36 floats per extremum (the raw orientation histogram), hist_cap extrema */
+/* k_orientation: histograms, peaks, the Ext record of EVERY extremum of the lists and one partial sum per group of
+ * scan_chunk() / scan_partials_per_chunk() extrema; hist_cap: extrema from that list position on get no orientation;
+ * blocks: the launch size of the one-entry-per-wave keypoint kernels, in waves (the launch takes its share of it) */
 hipError_t launch_orientation(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, bool filtered, int hist_cap,
                               int blocks, hipStream_t s);
 int        scan_chunk(); /* extrema per k_scan_apply workgroup */
-int        scan_partials_per_chunk(); /* partial sums k_scan_local leaves per scan_chunk() extrema */
-hipError_t launch_scan(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, bool filtered, int hist_cap,
-                       int n_chunks, int desc_cap, hipStream_t s);
+int        scan_partials_per_chunk(); /* partial sums k_orientation leaves per scan_chunk() extrema */
 hipError_t launch_descriptors(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
                               hipStream_t s);
 
@@ -131,13 +131,13 @@ hipError_t launch_descriptors(const PyrDesc* d_pd, const BatchDesc& bd, int nb, 
 hipError_t launch_desc_modes(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int desc_cap, int blocks,
                              hipStream_t s);
 
-/* k_scan_apply alone, for lists whose Ext records and local partial sums were written elsewhere (k_frame_place) */
+/* k_scan_apply: the lists' Ext records and group partial sums are there (k_orientation, or k_frame_place for given angles) */
 hipError_t launch_scan_apply(const PyrDesc* d_pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
                              hipStream_t s);
 
 /* describe.hip: caller-supplied frames (popsift_hip_describe_batch).  n_max: the most frames of an image of the batch.
  * frame_count + frame_place resolve each frame to (octave, level) and partition the frames stably by octave into the
- * InitExt lists (ext_ct, perm / inv; with `given` also the Ext records and k_scan_local's partial sums); frame_out, after
+ * InitExt lists (ext_ct, perm / inv; with `given` also the Ext records and k_orientation's partial sums); frame_out, after
  * the descriptor kernel, moves the feature records to caller order and rewrites the descriptor -> feature map. */
 constexpr int FRAME_CHUNK = 256;
 int        frame_chunks(int n_max);

@@ -9,8 +9,8 @@
  * per image: s_orientation.cu:351, sift_desc.cu:60-61).
  *
  * Replaces:
- *   ori_par               s_orientation.cu:60-242   -> k_orientation (1 wave / extremum)
- *   ori_prefix_sum        s_orientation.cu:303-345  -> k_scan_local + k_scan_apply (256 extrema / workgroup)
+ *   ori_par               s_orientation.cu:60-242   -> k_orientation (1 wave / group of 16 extrema)
+ *   ori_prefix_sum        s_orientation.cu:303-345  -> the epilogue of k_orientation (16 extrema / wave) + k_scan_apply (256 / workgroup)
  *   ext_desc_loop(+_sub)  s_desc_loop.cu:19-161     -> k_descriptor (1 wave / descriptor)
  *   normalize_histogram   s_desc_normalize.h:14-33, s_desc_norm_rs.h, s_desc_norm_l2.h
  *                                                   -> fused into k_descriptor
@@ -129,30 +129,161 @@ __device__ __forceinline__ float half_angle_bins(float y, float x, float mod, fl
 
 typedef __attribute__((address_space(3))) fix64 lds_fix64;
 typedef __attribute__((address_space(3))) unsigned int lds_u32;
+typedef __attribute__((address_space(3))) float lds_f32;
 typedef __attribute__((address_space(3))) short lds_i16;
 typedef __attribute__((address_space(3))) unsigned long long lds_u64;
 
 /* ISA: end */
 #ifndef KP_NW
-#define KP_NW 1 /* waves per workgroup of k_orientation / k_descriptor: the waves are independent (one keypoint each) */
+#define KP_NW 1 /* waves per workgroup of k_orientation / k_descriptor: the waves are independent (a group / one descriptor each) */
 #endif
 constexpr int ORI_COPIES = 4; /* private histogram copies by lane: neighbouring pixels often share a bin */
 
+/* ISA: peaks */
 /*
- * ori_par, first half (s_orientation.cu:60-139): the weighted 36-bin gradient-orientation histogram of one
- * extremum, one wave per extremum.  The second half -- smoothing, peak interpolation, the four best peaks --
- * is serial per extremum and runs with one LANE per extremum in k_scan_local (as a wave-wide epilogue here it
- * was ~350 of the kernel's ~1250 vector instructions per extremum, 62 of them dependent cross-lane shuffles).
- * The raw histogram crosses in `ohist` (36 floats per extremum).
+ * x / 3.0f, correctly rounded for normal x (Markstein: q = x * RN(1/3), one FMA residual, one FMA correction; checked
+ * against IEEE division for every float of six binades, tools/check_div3.py) instead of the ten-instruction division
  */
-__global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc,
-                                                     int filtered, int hist_cap)
+__device__ __forceinline__ float div3(float x)
+{
+    const float r = 0.333333343267440796f; /* RN(1/3) */
+    const float q = x * r;
+    return fmaf(fmaf(-3.0f, q, x), r, q);
+}
+
+/*
+ * ori_par, second half (s_orientation.cu:142-240), FOUR lanes per extremum, nine of the 36 bins each: six circular
+ * box-filter passes, parabolic peak interpolation, the (at most four) best peaks within 80 % of the best.  The lanes of
+ * a quad exchange their edge bins and their candidates with DPP quad permutes (register-to-register, no LDS);
+ * BitonicSort::Warp32::sort64 (common/warp_bitonic_sort.h:35-78) becomes four selection rounds, ties to the lower
+ * bin.  Everything is indexed statically, so the bins live in registers.  (One LANE per extremum -- 36 bins in
+ * registers, no exchange at all -- needs only 1200 waves for a 1080p image: 24 us at barely one wave per SIMD.)
+ * All four lanes of a quad must be active; all return the same result.  hsrc: the raw histogram, in LDS.
+ */
+__device__ __forceinline__ float quad_from_prev(float v) /* lane j of a quad reads lane (j + 3) & 3 */
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x93, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float quad_from_next(float v) /* lane j reads lane (j + 1) & 3 */
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x39, 0xf, 0xf, false));
+}
+template <int CTRL> /* 0xB1: lane ^ 1, 0x4E: lane ^ 2 */
+__device__ __forceinline__ int quad_xchg(int v)
+{
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+
+__device__ __forceinline__ int ori_peaks_quad(const lds_f32* __restrict__ hsrc, int j, bool have, float* angle_out)
+{
+    constexpr int N = PS_ORI_NBINS, M = N / 4; /* 9 bins per lane: 9j .. 9j+8 */
+    float         h[M], t[M];
+#pragma unroll
+    for (int b = 0; b < M; b++) h[b] = have ? hsrc[M * j + b] : 0.0f;
+#pragma unroll
+    for (int pass = 0; pass < 3; pass++) {
+        {
+            const float lft = quad_from_prev(h[M - 1]), rgt = quad_from_next(h[0]);
+#pragma unroll
+            for (int b = 0; b < M; b++) t[b] = div3(((b == 0 ? lft : h[b - 1]) + h[b]) + (b == M - 1 ? rgt : h[b + 1]));
+        }
+        {
+            const float lft = quad_from_prev(t[M - 1]), rgt = quad_from_next(t[0]);
+#pragma unroll
+            for (int b = 0; b < M; b++) h[b] = div3(((b == 0 ? lft : t[b - 1]) + t[b]) + (b == M - 1 ? rgt : t[b + 1]));
+        }
+    }
+    float refined[M], yval[M];
+    {
+        const float lft = quad_from_prev(h[M - 1]), rgt = quad_from_next(h[0]);
+#pragma unroll
+        for (int b = 0; b < M; b++) {
+            const int   bin = M * j + b;
+            const int   prev = (bin == 0) ? N - 1 : bin - 1;
+            const float hp = (b == 0) ? lft : h[b - 1], hv = h[b], hn = (b == M - 1) ? rgt : h[b + 1];
+            bool        predicate = hv > fmaxf(hp, hn);
+            const float num = predicate ? 3.0f * hp - 4.0f * hv + 1.0f * hn : 0.0f;
+            const float denB = predicate ? 2.0f * (hp - 2.0f * hv + hn) : 1.0f;
+            const float newbin = num / denB;
+            predicate = (predicate && newbin >= 0.0f && newbin <= 2.0f);
+            refined[b] = predicate ? prev + newbin : -1.0f;
+            yval[b] = predicate ? -(num * num) / (4.0f * denB) + hp : -INFINITY;
+        }
+    }
+    unsigned int used = 0u; /* of this lane's nine bins */
+    float        best0 = 0.0f;
+    int          angles = 0;
+#pragma unroll
+    for (int k = 0; k < POPSIFT_HIP_ORI_MAX; k++) {
+        /* best unused bin of this lane: largest value, lowest bin on ties (every lane has unused bins: 9 > 4) */
+        float bv = 0.0f, br = -1.0f;
+        int   bi = -1;
+#pragma unroll
+        for (int b = 0; b < M; b++) {
+            const bool take = !((used >> b) & 1u) && (bi < 0 || yval[b] > bv);
+            bv = take ? yval[b] : bv;
+            br = take ? refined[b] : br;
+            bi = take ? M * j + b : bi;
+        }
+        /* ... of the quad */
+        {
+            const float ov = __int_as_float(quad_xchg<0xB1>(__float_as_int(bv))), orf = __int_as_float(quad_xchg<0xB1>(__float_as_int(br)));
+            const int   oi = quad_xchg<0xB1>(bi);
+            const bool  take = ov > bv || (ov == bv && oi < bi);
+            bv = take ? ov : bv;
+            br = take ? orf : br;
+            bi = take ? oi : bi;
+        }
+        {
+            const float ov = __int_as_float(quad_xchg<0x4E>(__float_as_int(bv))), orf = __int_as_float(quad_xchg<0x4E>(__float_as_int(br)));
+            const int   oi = quad_xchg<0x4E>(bi);
+            const bool  take = ov > bv || (ov == bv && oi < bi);
+            bv = take ? ov : bv;
+            br = take ? orf : br;
+            bi = take ? oi : bi;
+        }
+        const int mine = bi - M * j;
+        if (mine >= 0 && mine < M) used |= 1u << mine;
+        if (k == 0) best0 = bv;
+        /* the candidates come in descending order, so the accepted ones are a prefix */
+        if (bv >= 0.8f * best0) {
+            float chosen_bin = br;
+            if (chosen_bin >= N) chosen_bin -= N;
+            angle_out[k] = fmaf(F_PI2 * chosen_bin, 1.0f / N, -F_PI);
+            angles = k + 1;
+        } else {
+            angle_out[k] = 0.0f;
+        }
+    }
+    return angles;
+}
+/* ISA: end */
+
+/* The scan's granularity: k_orientation leaves idx_ori local to its group of SCAN_LCHUNK list entries and one partial sum
+ * per group; k_scan_apply (SCAN_CHUNK entries per workgroup, SCAN_SUB groups) adds what precedes. */
+constexpr int SCAN_LCHUNK = KP_GROUP;
+
+/*
+ * ori_par (s_orientation.cu:60-242), a wave per group of KP_GROUP = 16 consecutive list entries.  First half, the whole
+ * wave on one extremum after the other: its weighted 36-bin gradient-orientation histogram, whose 36 floats stay in the
+ * wave's LDS (s_stage).  Second half -- smoothing, peak interpolation, the four best peaks -- is serial per extremum and
+ * runs once per group, FOUR lanes per extremum (ori_peaks_quad): as a wave-wide epilogue per extremum it was ~350 of the
+ * kernel's ~1250 vector instructions per extremum, as a launch of its own (k_scan_local, until the groups) it read the
+ * histograms back from device memory, 144 bytes per extremum written and read for nothing.  The quad's first lane then
+ * writes the extremum's Ext record with idx_ori local to the group, and the group's number of orientations goes to
+ * partial[group] for k_scan_apply.
+ * Every extremum of the list gets its record; those from hist_cap on (the host's capacity for this pass: it raises it and
+ * runs the stages again, ctx.hip finish) get no histogram and no orientation.
+ */
+__global__ __launch_bounds__(64 * KP_NW, 8) void k_orientation(const PyrDesc* __restrict__ pdp, BatchDesc bd, SiftConsts sc,
+                                                        int filtered, int hist_cap)
 {
     /* this image's planes and lists (the slot of blockIdx.y) */
     const float* __restrict__   arena = bd.s[blockIdx.y].arena;
     Counters* __restrict__      ct = bd.s[blockIdx.y].ct;
     const InitExt* __restrict__ iext = filtered ? bd.s[blockIdx.y].iext2 : bd.s[blockIdx.y].iext;
-    float* __restrict__         ohist = bd.s[blockIdx.y].ohist;
+    Ext* __restrict__           ext = bd.s[blockIdx.y].ext;
+    int* __restrict__           partial = bd.s[blockIdx.y].partial;
     const int n_oct = pdp->n_oct, L = pdp->L;
     /* The histogram is circular and the loop's bin coordinate runs from 9 to 45 (half_angle_bins: the angle in [-pi/2,
      * 3pi/2]; next to a bin edge from 0 to 36, atan2_acc): bin b + 36 is bin b.  A sample is added where it falls and
@@ -163,12 +294,20 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
     fix64*           hall = &s_hist[wave][0][0];
     fix64*           hist = s_hist[wave][lane & (ORI_COPIES - 1)];
 
-    __shared__ int ps[PS_MAX_OCT + 1];
-    const int total = min(ext_prefix(ps, ct, sc.max_extrema, n_oct), hist_cap);
+    /* the group's raw histograms, for the peak search after the group's last extremum */
+    __shared__ float s_stage[KP_NW][KP_GROUP][PS_ORI_NBINS];
+    static_assert(KP_GROUP * 4 == 64, "four lanes per extremum of a group");
+    static_assert(sizeof(s_hist) / KP_NW + sizeof(s_stage) / KP_NW + 64 <= 5120, "32 waves per CU share 160 KiB");
 
-    for (XcdSlice sl = xcd_slice<KP_NW>(); sl.more(total); sl.s += sl.step) {
-        const int g = sl.index();
-        if (g >= total) continue;
+    __shared__ int ps[PS_MAX_OCT + 1];
+    const int total = ext_prefix(ps, ct, sc.max_extrema, n_oct);
+
+    for (XcdSliceOf<KP_GROUP> sl = xcd_slice<KP_NW, KP_GROUP>(); sl.more(total); sl.s += sl.step) {
+        const int g0 = uniform(sl.index());
+        if (g0 >= total) continue;
+        /* the histograms of the group's extrema below the list's end and below the capacity of this pass */
+        const int g_end = min(min(g0 + KP_GROUP, total), hist_cap);
+        for (int g = g0; g < g_end; g++) {
         /* ISA: record */
         const int o = uniform(ext_octave(ps, n_oct, g)); /* the octave record and the list entry are then fetched through the scalar cache */
         const InitExt  ie = iext[(size_t)o * sc.max_extrema + (g - uniform(ps[o]))];
@@ -286,125 +425,44 @@ __global__ __launch_bounds__(64 * KP_NW) void k_orientation(const PyrDesc* __res
 #pragma unroll
             for (int k = 0; k < ORI_COPIES; k++)
                 acc += hall[k * NB + lane] + (lane < NB - PS_ORI_NBINS ? hall[k * NB + PS_ORI_NBINS + lane] : 0ull);
-            ohist[(size_t)g * PS_ORI_NBINS + lane] = from_fix(acc);
+            s_stage[wave][g - g0][lane] = from_fix(acc);
         }
         wave_lds_sync(); /* ISA: end */
-    }
-}
+        } /* the group's extrema */
 
-/*
- * ori_par, second half (s_orientation.cu:142-240), FOUR lanes per extremum, nine of the 36 bins each: six circular
- * box-filter passes, parabolic peak interpolation, the (at most four) best peaks within 80 % of the best.  The lanes of
- * a quad exchange their edge bins and their candidates with DPP quad permutes (register-to-register, no LDS);
- * BitonicSort::Warp32::sort64 (common/warp_bitonic_sort.h:35-78) becomes four selection rounds, ties to the lower
- * bin.  Everything is indexed statically, so the bins live in registers.  (One LANE per extremum -- 36 bins in
- * registers, no exchange at all -- needs only 1200 waves for a 1080p image: 24 us at barely one wave per SIMD.)
- * All four lanes of a quad must be active; all return the same result.
- */
-__device__ __forceinline__ float quad_from_prev(float v) /* lane j of a quad reads lane (j + 3) & 3 */
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x93, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float quad_from_next(float v) /* lane j reads lane (j + 1) & 3 */
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x39, 0xf, 0xf, false));
-}
-template <int CTRL> /* 0xB1: lane ^ 1, 0x4E: lane ^ 2 */
-__device__ __forceinline__ int quad_xchg(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-/* x / 3.0f, correctly rounded for normal x (Markstein: q = x * RN(1/3), one FMA residual, one FMA correction; checked
- * against IEEE division for every float of six binades, tools/check_div3.py) instead of the ten-instruction division */
-__device__ __forceinline__ float div3(float x)
-{
-    const float r = 0.333333343267440796f; /* RN(1/3) */
-    const float q = x * r;
-    return fmaf(fmaf(-3.0f, q, x), r, q);
-}
-
-__device__ __forceinline__ int ori_peaks_quad(const float* __restrict__ hsrc, int j, bool have, float* angle_out)
-{
-    constexpr int N = PS_ORI_NBINS, M = N / 4; /* 9 bins per lane: 9j .. 9j+8 */
-    float         h[M], t[M];
-#pragma unroll
-    for (int b = 0; b < M; b++) h[b] = have ? hsrc[M * j + b] : 0.0f;
-#pragma unroll
-    for (int pass = 0; pass < 3; pass++) {
+        /* ISA: peaks */
+        /* The second half for the whole group: lane 4k + j is lane j of the quad of extremum g0 + k.  Quads beyond the
+         * list's end compute along on its last entry (the quad exchanges need every lane) and write nothing. */
         {
-            const float lft = quad_from_prev(h[M - 1]), rgt = quad_from_next(h[0]);
-#pragma unroll
-            for (int b = 0; b < M; b++) t[b] = div3(((b == 0 ? lft : h[b - 1]) + h[b]) + (b == M - 1 ? rgt : h[b + 1]));
+            const int  j = lane & 3;
+            const int  g = g0 + (lane >> 2);
+            const bool valid = g < total;
+            const int  gc = min(g, total - 1);
+            /* the extremum's record (sift_extremum.h:40-51) */
+            const int     o = ext_octave(ps, n_oct, gc);
+            const InitExt ie = iext[(size_t)o * sc.max_extrema + (gc - ps[o])];
+            Ext           e;
+            e.xpos = ie.xpos;
+            e.ypos = ie.ypos;
+            e.lpos = ie.lpos;
+            e.sigma = ie.sigma;
+            e.octave = o;
+            /* beyond the capacity of this pass (the host raises it and re-runs the stages): no orientation */
+            const bool have = gc < hist_cap;
+            const int  n = ori_peaks_quad((const lds_f32*)&s_stage[wave][gc - g0][0], j, have, e.orientation);
+            e.num_ori = have ? n : 0;
+            if (!have)
+                for (int q = 0; q < POPSIFT_HIP_ORI_MAX; q++) e.orientation[q] = 0.0f;
+            const int self = (valid && j == 0) ? e.num_ori : 0;
+            const int incl = wave_incl_scan(self);
+            if (valid && j == 0) {
+                e.idx_ori = incl - self; /* local to the group for now */
+                ext[g] = e;
+            }
+            if (lane == 63) partial[g0 / SCAN_LCHUNK] = incl;
         }
-        {
-            const float lft = quad_from_prev(t[M - 1]), rgt = quad_from_next(t[0]);
-#pragma unroll
-            for (int b = 0; b < M; b++) h[b] = div3(((b == 0 ? lft : t[b - 1]) + t[b]) + (b == M - 1 ? rgt : t[b + 1]));
-        }
+        wave_lds_sync(); /* the next group's histograms go where these were read */ /* ISA: end */
     }
-    float refined[M], yval[M];
-    {
-        const float lft = quad_from_prev(h[M - 1]), rgt = quad_from_next(h[0]);
-#pragma unroll
-        for (int b = 0; b < M; b++) {
-            const int   bin = M * j + b;
-            const int   prev = (bin == 0) ? N - 1 : bin - 1;
-            const float hp = (b == 0) ? lft : h[b - 1], hv = h[b], hn = (b == M - 1) ? rgt : h[b + 1];
-            bool        predicate = hv > fmaxf(hp, hn);
-            const float num = predicate ? 3.0f * hp - 4.0f * hv + 1.0f * hn : 0.0f;
-            const float denB = predicate ? 2.0f * (hp - 2.0f * hv + hn) : 1.0f;
-            const float newbin = num / denB;
-            predicate = (predicate && newbin >= 0.0f && newbin <= 2.0f);
-            refined[b] = predicate ? prev + newbin : -1.0f;
-            yval[b] = predicate ? -(num * num) / (4.0f * denB) + hp : -INFINITY;
-        }
-    }
-    unsigned int used = 0u; /* of this lane's nine bins */
-    float        best0 = 0.0f;
-    int          angles = 0;
-#pragma unroll
-    for (int k = 0; k < POPSIFT_HIP_ORI_MAX; k++) {
-        /* best unused bin of this lane: largest value, lowest bin on ties (every lane has unused bins: 9 > 4) */
-        float bv = 0.0f, br = -1.0f;
-        int   bi = -1;
-#pragma unroll
-        for (int b = 0; b < M; b++) {
-            const bool take = !((used >> b) & 1u) && (bi < 0 || yval[b] > bv);
-            bv = take ? yval[b] : bv;
-            br = take ? refined[b] : br;
-            bi = take ? M * j + b : bi;
-        }
-        /* ... of the quad */
-        {
-            const float ov = __int_as_float(quad_xchg<0xB1>(__float_as_int(bv))), orf = __int_as_float(quad_xchg<0xB1>(__float_as_int(br)));
-            const int   oi = quad_xchg<0xB1>(bi);
-            const bool  take = ov > bv || (ov == bv && oi < bi);
-            bv = take ? ov : bv;
-            br = take ? orf : br;
-            bi = take ? oi : bi;
-        }
-        {
-            const float ov = __int_as_float(quad_xchg<0x4E>(__float_as_int(bv))), orf = __int_as_float(quad_xchg<0x4E>(__float_as_int(br)));
-            const int   oi = quad_xchg<0x4E>(bi);
-            const bool  take = ov > bv || (ov == bv && oi < bi);
-            bv = take ? ov : bv;
-            br = take ? orf : br;
-            bi = take ? oi : bi;
-        }
-        const int mine = bi - M * j;
-        if (mine >= 0 && mine < M) used |= 1u << mine;
-        if (k == 0) best0 = bv;
-        /* the candidates come in descending order, so the accepted ones are a prefix */
-        if (bv >= 0.8f * best0) {
-            float chosen_bin = br;
-            if (chosen_bin >= N) chosen_bin -= N;
-            angle_out[k] = fmaf(F_PI2 * chosen_bin, 1.0f / N, -F_PI);
-            angles = k + 1;
-        } else {
-            angle_out[k] = 0.0f;
-        }
-    }
-    return angles;
 }
 
 /* The per-descriptor constants of the loop descriptor (k_descriptor), computed where one lane serves one extremum.
@@ -458,71 +516,19 @@ __device__ __forceinline__ DescRec make_desc_rec(const PyrDesc* __restrict__ pdp
 /*
  * Exclusive prefix sum of num_ori over all extrema -> idx_ori, the reverse map
  * descriptor -> extremum, and the totals (replaces ori_prefix_sum's single
- * 32x32 block looping over everything, s_orientation.cu:303-345).  Two launches:
- * k_scan_local scans 64-extrema chunks and leaves one partial per chunk;
- * k_scan_apply (256 extrema per workgroup) adds the sum of the preceding partials
- * (<= 14 100 values for the default 9 x 100000 capacity, ~1 200 for a 1080p image,
- * summed redundantly per workgroup) and writes the map and the counters.
+ * 32x32 block looping over everything, s_orientation.cu:303-345).  k_orientation
+ * scans each group of 16 extrema and leaves one partial per group (on the describe
+ * path with given angles: k_frame_place); k_scan_apply (256 extrema per workgroup)
+ * adds the sum of the preceding partials (<= 56 300 values for the default 9 x 100000
+ * capacity, ~4 800 for a 1080p image, summed redundantly per workgroup) and writes
+ * the map and the counters.
  */
 /* extrema per lane: 1 -- the per-extremum work of k_scan_apply (feature record, double-precision cos / sin)
  * is serial per lane, so wide beats deep (8 per lane: 22.8 us, 2: 10.2 us, 1: 7.5 us) */
 constexpr int SCAN_ITEMS = 1;
 constexpr int SCAN_CHUNK = 256 * SCAN_ITEMS;
-/* k_scan_local: lanes per workgroup (four per extremum) and the extrema it scans; SCAN_SUB local chunks per apply chunk.
- * The kernel is a latency chain per workgroup (record, histogram, peaks, scan, store), so many small workgroups beat
- * few large ones: 128 / 256 / 512 / 1024 lanes -> 14.0 / 13.2 / 14.3 / 19.9 us for the 77 000 extrema of a 1080p image */
-constexpr int SCAN_LT = 256;
-constexpr int SCAN_LCHUNK = SCAN_LT / 4;
 constexpr int SCAN_SUB = SCAN_CHUNK / SCAN_LCHUNK;
-
-__global__ __launch_bounds__(SCAN_LT) void k_scan_local(const PyrDesc* __restrict__ pdp, SiftConsts sc, BatchDesc bd,
-                                                     int filtered, int hist_cap)
-{
-    const Counters* __restrict__ ct = bd.s[blockIdx.y].ct;
-    const InitExt* __restrict__  iext = filtered ? bd.s[blockIdx.y].iext2 : bd.s[blockIdx.y].iext;
-    const float* __restrict__    ohist = bd.s[blockIdx.y].ohist;
-    Ext* __restrict__            ext = bd.s[blockIdx.y].ext;
-    int* __restrict__            partial = bd.s[blockIdx.y].partial;
-    static_assert(SCAN_CHUNK % SCAN_LCHUNK == 0 && SCAN_LT % 64 == 0, "four lanes per extremum, whole waves");
-    __shared__ int s_wsum[SCAN_LT / 64];
-    __shared__ int s_ps[PS_MAX_OCT + 1];
-    const int      n_oct = pdp->n_oct;
-    const int total = ext_prefix(s_ps, ct, sc.max_extrema, n_oct);
-    const int tid = threadIdx.x;
-    const int j = tid & 3;
-    /* the launch is sized for the device, not for the capacity of the lists: workgroups stride over the chunks */
-    for (int chunk = blockIdx.x; chunk * SCAN_LCHUNK < total; chunk += gridDim.x) {
-    const int  base = chunk * SCAN_LCHUNK;
-    const int  g = base + (tid >> 2);
-    const bool valid = g < total;
-    const int  gc = min(g, total - 1); /* lanes beyond the list compute along (the quad exchanges need them) */
-    /* the second half of ori_par for extremum g, then its Extremum record (sift_extremum.h:40-51) */
-    const int     o = ext_octave(s_ps, n_oct, gc);
-    const InitExt ie = iext[(size_t)o * sc.max_extrema + (gc - s_ps[o])];
-    Ext           e;
-    e.xpos = ie.xpos;
-    e.ypos = ie.ypos;
-    e.lpos = ie.lpos;
-    e.sigma = ie.sigma;
-    e.octave = o;
-    e.idx_ori = 0;
-    /* beyond the histogram buffer (the host grows it and re-runs the stages): no orientation */
-    const bool have = gc < hist_cap;
-    const int  n = ori_peaks_quad(ohist + (size_t)min(gc, max(hist_cap - 1, 0)) * PS_ORI_NBINS, j, have, e.orientation);
-    e.num_ori = have ? n : 0;
-    if (!have)
-        for (int q = 0; q < POPSIFT_HIP_ORI_MAX; q++) e.orientation[q] = 0.0f;
-    const int self = (valid && j == 0) ? e.num_ori : 0;
-
-    const WgScan scan = wg_scan<SCAN_LT / 64>(self, s_wsum);
-    if (valid && j == 0) {
-        e.idx_ori = scan.excl; /* chunk-local for now */
-        ext[g] = e;
-    }
-    if (tid == SCAN_LT - 1) partial[chunk] = scan.excl + self;
-    __syncthreads(); /* s_wsum is reused by the next chunk */
-    }
-}
+static_assert(SCAN_CHUNK % SCAN_LCHUNK == 0 && SCAN_SUB <= 64, "whole groups per chunk, one lane of a wave per group");
 
 __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ pdp, SiftConsts sc, BatchDesc bd,
                                                     int with_drec, int desc_cap)
@@ -535,6 +541,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
     DescRec* __restrict__             drec = with_drec ? bd.s[blockIdx.y].drec : nullptr;
     popsift_hip_feature* __restrict__ feats = bd.s[blockIdx.y].feats;
     __shared__ int s_red[4];
+    __shared__ int s_sub[SCAN_SUB];
     __shared__ int s_ps[PS_MAX_OCT + 1];
     const int      n_oct = pdp->n_oct;
     const int      tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -552,16 +559,27 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
     for (int chunk = blockIdx.x; chunk < nb; chunk += gridDim.x) {
     const int base = chunk * SCAN_CHUNK;
 
-    /* offset of this chunk = sum of the partials of all preceding chunks (SCAN_SUB local chunks per chunk here) */
+    /* offset of this chunk = sum of the partials of all preceding chunks (SCAN_SUB groups per chunk here) */
+    /* four partials per load (whole chunks: a multiple of four of them): the loop is a chain of dependent round trips, and
+     * with a partial per 16 extrema instead of per 64 it would be four times as long */
+    static_assert(SCAN_SUB % 4 == 0, "16-byte loads of the partials");
     int acc = 0;
-    for (int b = tid; b < chunk * SCAN_SUB; b += 256) acc += partial[b];
+    for (int b = tid; b < chunk * (SCAN_SUB / 4); b += 256) {
+        const int4 v = reinterpret_cast<const int4*>(partial)[b];
+        acc += (v.x + v.y) + (v.z + v.w);
+    }
     acc = wave_sum(acc);
     if (lane == 0) s_red[wave] = acc;
+    /* ... plus the groups of this chunk that precede the lane's own: their exclusive prefix, one lane of the first wave per
+     * group (a group beyond the list's end has no partial; what is read there reaches only groups beyond it) */
+    if (wave == 0) {
+        const int v = (lane < SCAN_SUB) ? partial[chunk * SCAN_SUB + lane] : 0;
+        const int incl = wave_incl_scan(v);
+        if (lane < SCAN_SUB) s_sub[lane] = incl - v;
+    }
     __syncthreads();
     const int chunk_offset = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-    /* ... plus the local chunks of this chunk that precede the lane's own */
-    int offset = chunk_offset;
-    for (int k = 0; k < (tid * SCAN_ITEMS) / SCAN_LCHUNK; k++) offset += partial[chunk * SCAN_SUB + k];
+    const int offset = chunk_offset + s_sub[(tid * SCAN_ITEMS) / SCAN_LCHUNK];
 
     const int g0 = base + tid * SCAN_ITEMS;
 #pragma unroll
@@ -612,7 +630,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(const PyrDesc* __restrict__ 
             ct->ext_ps[o] = s_ps[o];
         }
     }
-    __syncthreads(); /* s_red is reused by the next chunk */
+    __syncthreads(); /* s_red and s_sub are reused by the next chunk */
     }
 }
 
@@ -1121,22 +1139,17 @@ __global__ __launch_bounds__(64 * KP_NW, 8) void k_descriptor(BatchDesc bd, Sift
 hipError_t launch_orientation(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, bool filtered, int hist_cap,
                               int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_orientation, dim3(blocks / KP_NW, nb), dim3(64 * KP_NW), 0, s, pd, bd, sc, filtered ? 1 : 0, hist_cap);
+    /* `blocks` waves are eight per wave slot of the device, sized for kernels that take one list entry per position; a
+     * position here is a group of KP_GROUP entries, so an eighth of them (one per slot, a multiple of 8 for the XCDs) */
+    const int waves = std::max(blocks / 8 / (8 * KP_NW) * (8 * KP_NW), 8 * KP_NW);
+    hipLaunchKernelGGL(k_orientation, dim3(waves / KP_NW, nb), dim3(64 * KP_NW), 0, s, pd, bd, sc, filtered ? 1 : 0, hist_cap);
     return hipGetLastError();
-}
-
-hipError_t launch_scan(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, bool filtered, int hist_cap,
-                       int n_chunks, int desc_cap, hipStream_t s)
-{
-    /* n_chunks is the capacity of the lists; a 1080p image fills ~300 chunks */
-    hipLaunchKernelGGL(k_scan_local, dim3(std::min(n_chunks * SCAN_SUB, 512 * SCAN_SUB), nb), dim3(SCAN_LT), 0, s, pd, sc, bd,
-                       filtered ? 1 : 0, hist_cap);
-    return launch_scan_apply(pd, bd, nb, sc, n_chunks, desc_cap, s);
 }
 
 hipError_t launch_scan_apply(const PyrDesc* pd, const BatchDesc& bd, int nb, const SiftConsts& sc, int n_chunks, int desc_cap,
                              hipStream_t s)
 {
+    /* n_chunks is the capacity of the lists; a 1080p image fills ~300 chunks */
     hipLaunchKernelGGL(k_scan_apply, dim3(std::min(n_chunks, 1024), nb), dim3(256), 0, s, pd, sc, bd,
                        sc.desc_mode == POPSIFT_HIP_DESC_LOOP ? 1 : 0, desc_cap);
     return hipGetLastError();

@@ -82,16 +82,25 @@ __device__ __forceinline__ float plane_at(const float* pl, int idx)
 #ifndef KP_CHUNK
 #define KP_CHUNK 256
 #endif
-struct XcdSlice {
+/* k_orientation hands a wave KP_GROUP consecutive list entries at a time (it finds the peaks of their histograms together,
+ * four lanes each): a position is then a GROUP of UNIT entries, a chunk holds KP_CHUNK / UNIT of them, and index() is the
+ * group's first entry -- a multiple of UNIT inside the same chunk of the same XCD as with single entries, so what the
+ * waves in flight on an XCD share stays what it was.  UNIT = 1: the descriptor kernels' one entry per position. */
+constexpr int KP_GROUP = 16;
+template <int UNIT>
+struct XcdSliceOf {
+    static constexpr int PER_CHUNK = KP_CHUNK / UNIT;
+    static_assert(KP_CHUNK % UNIT == 0, "whole groups per chunk");
     int x, s, step;
-    __device__ __forceinline__ int index() const { return ((s / KP_CHUNK) * 8 + x) * KP_CHUNK + (s % KP_CHUNK); }
+    __device__ __forceinline__ int index() const { return ((s / PER_CHUNK) * 8 + x) * KP_CHUNK + (s % PER_CHUNK) * UNIT; }
     /* positions whose element lies beyond the list are skipped: later chunks of the same XCD may still be inside */
-    __device__ __forceinline__ bool more(int total) const { return (s / KP_CHUNK) * 8 * KP_CHUNK < total; }
+    __device__ __forceinline__ bool more(int total) const { return (s / PER_CHUNK) * 8 * KP_CHUNK < total; }
 };
-template <int NW>
-__device__ __forceinline__ XcdSlice xcd_slice()
+typedef XcdSliceOf<1> XcdSlice;
+template <int NW, int UNIT = 1>
+__device__ __forceinline__ XcdSliceOf<UNIT> xcd_slice()
 {
-    XcdSlice sl;
+    XcdSliceOf<UNIT> sl;
     sl.x = blockIdx.x & 7;
     /* the wave's number in its workgroup is wave-uniform, and said to be: position, list index and the loop over them
      * then stay in scalar registers (seven vector instructions per keypoint otherwise) */

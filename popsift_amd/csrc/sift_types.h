@@ -133,7 +133,6 @@ struct Slot {
     InitExt*             iext2; /* grid filter output (filter enabled only) */
     FilterState*         fstate;
     int*                 fhist;
-    float*               ohist;
     Ext*                 ext;
     int*                 partial;
     int*                 map;

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/quick_ab
 rm -rf $OUT; mkdir -p $OUT
-PAT=${1:-k_descriptor|k_orientation|k_scan_local|k_order}
+PAT=${1:-k_descriptor|k_orientation|k_scan_apply|k_order}
 cd /tmp && export TMPDIR=/tmp
 run_one() {
   n=$1
